@@ -14,9 +14,10 @@ single-pass RGB-D render -> fused loss -> backward), the flat [N,14] fp32 gradie
 fused Adam on its 1/N row block and the updated rows are all-gathered (activesplat_amd/parallel.py).  `value` = keyframes rendered +
 back-propagated per second by the whole job (strong scaling: the batch is fixed); rank 0 also times the same 64-keyframe step alone
 (`single_gpu_same_workload_fps`; the N = 1 line carries the same figure as `configs3_single_gpu`).
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  N = 1: `ms_per_step` = milliseconds of one timed step; --dump-outputs DIR writes what the last timed step returned
+(colour, radii, depth, opacity and the input gradients; per-Gaussian arrays at a fixed, seeded sample of rows) as DIR/<name>.npy.
 
-Extra legs (rank 0, N = 1 only, after the timed region):
+Extra legs (rank 0, N = 1 only, after the timed region, only with --full; a plain run sets up, warms up, times the K steps and prints the line):
   roofline      : per-stage hipEvent timing through the C ABI's gs_profile_* hooks over a second pass of the same K steps; the
                   dominant stage's algorithmic bytes / its average duration against the 8 TB/s HBM peak; the whole
                   frame's algorithmic bytes / the sequential frame time (`frame_frac_sequential`, the north star's figure).
@@ -102,6 +103,25 @@ def frame_bytes(P, D, npix, sh=False):
     return P * (832 if sh else 292) + D * 160 + npix * 48
 
 
+DUMP_ROWS = 65536            # --dump-outputs: per-Gaussian arrays are written for this fixed, seeded sample of rows (all rows below it)
+
+
+def dump_outputs(d, wl, outs, grads):
+    """--dump-outputs DIR: what the timed render step returned to its caller in its last step, as float32 .npy files -- the image-sized
+    forward outputs whole, the per-Gaussian ones (radii and every input gradient) at DUMP_ROWS rows drawn with seed 2 (sorted), so that
+    two builds can be compared output for output (about 23 MB at 2 M Gaussians with SH degree 3)."""
+    os.makedirs(d, exist_ok=True)
+    N = wl.N
+    rows = torch.arange(N) if N <= DUMP_ROWS else torch.randperm(N, generator=torch.Generator().manual_seed(2))[:DUMP_ROWS].sort().values
+    rows = rows.to(outs[0].device)
+    arrays = {"color": outs[0], "radii": outs[1].index_select(0, rows), "depth": outs[2], "opacity": outs[3]}
+    for k, g in zip(wl.keys + ["means2D"], grads):
+        arrays["grad_" + k] = g.index_select(0, rows)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v.detach().to(torch.float32).cpu().numpy())
+    return sorted(arrays)
+
+
 def c4_roofline(n_gauss, D, npix, sh, world, KF, step_s, exchange_ms, exchange_bytes, single_fps=None):
     """The `roofline` block of a configs[3] line.  Per GPU: the keyframes one rank renders per step x SURVEY 8(d)'s algorithmic bytes of a
     forward + backward frame (N b_g + D b_i + px b_p: the metric's figure -- the loss kernels' and the depth/silhouette channels' extra
@@ -149,13 +169,15 @@ class RenderWorkload:
         # other inputs it is resident before the timed region -- a fresh torch.zeros(N, 3) per frame is a 24 MB fill at 2 M Gaussians
         self.m2d = torch.zeros(N, 3, device=dev, requires_grad=True)
 
-    def step(self):
+    def step(self, outputs=False):
+        """-> the input gradients (self.keys, then means2D); outputs=True: (forward outputs (color, radii, depth, opacity), the gradients)"""
         from activesplat_amd import GaussianRasterizer
-        color = GaussianRasterizer(raster_settings=self.cam)(means2D=self.m2d, **self.rv)[0]
+        out = GaussianRasterizer(raster_settings=self.cam)(means2D=self.m2d, **self.rv)
         # (the backward on the calling thread instead of autograd's device thread: no thread hand-over per frame -- at 2 M Gaussians the frame is GPU-bound
         # either way; at the reference's 256 x 256 frames the hand-over is what made the host the bound in the slow thread placement: INTEGRATION.md 3b)
         with torch.autograd.set_multithreading_enabled(False):
-            return torch.autograd.grad(color, [self.rv[k] for k in self.keys] + [self.m2d], self.dL)
+            grads = torch.autograd.grad(out[0], [self.rv[k] for k in self.keys] + [self.m2d], self.dL)
+        return (out, grads) if outputs else grads
 
     def sequential(self, steps, warmup):
         for _ in range(warmup):
@@ -652,7 +674,12 @@ def main():
     ap.add_argument("--streams", type=int, default=1,
                     help="configs[3]: HIP streams a rank's keyframes are issued on in turn (1: with the chained backward blend a 640x480 keyframe fills the chip "
                          "by itself -- 1371-1442 keyframes/s on one stream against 1276-1278 on two at 2 M Gaussians)")
-    ap.add_argument("--no-extras", action="store_true", help="skip every leg but the timed region")
+    ap.add_argument("--full", action="store_true", help="N = 1: after the timed region, run every other leg too (roofline, CPU baseline, configs[0]/[1]/[2]/[3], "
+                    "operating points, mapping iteration); without it the run times the steps and prints the line, nothing else")
+    ap.add_argument("--no-extras", action="store_true", help="skip every leg but the timed region (N = 1: the default without --full; N > 1: skip "
+                    "rank 0's one-GPU reference)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="N = 1 render workload: write what the last timed step returned (forward outputs, a fixed "
+                    "sample of the per-Gaussian gradients) as DIR/<name>.npy, float32")
     ap.add_argument("--prep-seconds", type=float, default=0.5, help="untimed preparation in front of the warm-up steps (clock ramp, allocator)")
     ap.add_argument("--cpu-threads", type=int, default=64, help="upper bound on the host threads of the cpu_baseline leg")
     ap.add_argument("--c4-gaussians", type=int, default=2_000_000, help="configs[3]: Gaussians of the replicated map")
@@ -672,6 +699,8 @@ def main():
                     "reduced mean-2D gradient statistic, so that an event clones / splits ~0.5 %% of the map and the workload stays configs[3]'s")
     ap.add_argument("--workload", choices=("auto", "c4"), default="auto", help="auto: configs[2]'s render on one GPU, configs[3] on several")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # development knobs for exercising the N > 1 code path on a 1-GPU box: all ranks on device 0, gloo instead of RCCL
     same_dev = bool(os.environ.get("BENCH_SAME_DEVICE"))
@@ -717,6 +746,8 @@ def main():
     if os.environ.get("GS_CHAIN_OFF"):                      # development knob (A/B): one backward walker per quadrant, no chained pieces
         _lib.check(lib.gs_set_backward_chain(1, -1))
     if dist_on or args.workload == "c4":
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs is implemented for the N = 1 render workload only")
         out = run_c4(args, dev, rank, world, ranks_info=ranks_info)
         if args.c4_sh_degree < 0 and not args.c4_one_map:
             # the second exchange SURVEY 8(d)/(e) names for configs[3]: the map's colour as 16-coefficient SH rows (configs[2]'s map), G = 59 floats
@@ -754,7 +785,8 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        wl.step()
+        last = None                                         # (only the last step's results are kept: none held across a step)
+        last = wl.step(outputs=True)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     D = int(R.last_stats["num_rendered"])
@@ -772,7 +804,10 @@ def main():
                    "parallelism": "single GPU"},
     }
 
-    if not args.no_extras:
+    if args.dump_outputs:
+        note(f"outputs of the last timed step -> {args.dump_outputs}: {', '.join(dump_outputs(args.dump_outputs, wl, *last))}")
+    del last
+    if args.full and not args.no_extras:
         note(f"timed region done: {fps:.1f} frames/s; roofline leg")
         # ---- roofline leg: per-stage hipEvents over a second pass of the same K steps ----
         stages, sb, _ = wl.stages(lib, args.steps)

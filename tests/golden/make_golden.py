@@ -20,6 +20,9 @@ What is pinned:
   pointcloud.npz get_pointcloud, initialize_params, initialize_new_params, add_new_gaussians
                                                      (splatam.py:25-115,304-379)
   keyframe.npz   keyframe_selection_overlap          (keyframe_selection.py:40-95)
+  dropin.npz     the reference's own caller code on this repository's drop-in (host-emulated kernels):
+                 get_pointcloud -> initialize_params -> get_loss -> backward -> Adam step, and render()
+                                                     (splatam.py:25-124,172-301,413-468; written by `make_golden.py dropin`)
 """
 import importlib
 import os
@@ -427,5 +430,67 @@ def main():
     print("golden vectors written to", HERE)
 
 
+def main_dropin():
+    """dropin.npz: the reference's OWN caller code (get_pointcloud -> initialize_params -> initialize_optimizer -> get_loss -> backward ->
+    optimizer.step, and the no-grad render()) run unmodified against THIS repository's `diff_gaussian_rasterization` on the host-emulated
+    kernels (tests/hipemu) -- what tests/test_reference_dropin.py checks the host-side mirrors against.  A process of its own: main() puts a
+    stub renderer where the drop-in lives."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(HERE))
+    sys.path.insert(0, root)
+    subprocess.check_call(["make", "-C", os.path.join(root, "tests", "hipemu"), "-j8"], stdout=subprocess.DEVNULL)
+    from tests import util
+    util.use_emulated_kernels(os.path.join(root, "tests", "hipemu", "libgsplat_emu.so"))
+    for name, p in [("mapper", R + "/mapper"), ("mapper.splatam", R + "/mapper/splatam"),
+                    ("mapper.splatam.utils", R + "/mapper/splatam/utils")]:
+        m = types.ModuleType(name)
+        m.__path__ = [p]
+        sys.modules[name] = m
+    sys.modules["cv2"] = types.ModuleType("cv2")
+    import diff_gaussian_rasterization  # noqa: F401  -- this repository's drop-in
+    from activesplat_amd import synthetic as syn
+    torch.Tensor.cuda = lambda self, *a, **k: self
+    out = {}
+    with CudaToCpu():
+        sp = importlib.import_module("mapper.splatam.splatam")
+        from mapper.splatam.utils.recon_helpers import setup_camera as ref_setup_camera
+        # ---------------- get_loss -> backward -> Adam step ----------------
+        H, W = 48, 64
+        g = torch.Generator().manual_seed(0)
+        color = torch.rand(3, H, W, generator=g)
+        depth = torch.rand(1, H, W, generator=g) * 2 + 1.0
+        K = torch.tensor(syn.intrinsics(W, H), dtype=torch.float32)
+        w2c = torch.eye(4)
+        pc, msd = sp.get_pointcloud(color, depth, K, w2c, compute_mean_sq_dist=True, mean_sq_dist_method="projective")
+        params, variables = sp.initialize_params(pc, 2, msd, "anisotropic")
+        lrs = dict(means3D=1e-4, rgb_colors=2.5e-3, unnorm_rotations=1e-3, logit_opacities=0.05, log_scales=1e-3, cam_unnorm_rots=0.0, cam_trans=0.0)
+        opt = sp.initialize_optimizer(params, lrs, tracking=False)
+        cam = ref_setup_camera(W, H, K.numpy(), np.eye(4))
+        gt_im = torch.rand(3, H, W, generator=g)
+        gt = dict(cam=cam, im=gt_im, depth=depth * 1.05, id=0, intrinsics=K, w2c=w2c)
+        loss, variables, _ = sp.get_loss(params, gt, variables, 0, dict(im=0.5, depth=1.0), True, 0.99, True, False, mapping=True)
+        loss.backward()
+        out.update(color=n(color), depth=n(depth), K=n(K), w2c=n(w2c), gt_im=n(gt_im), gt_depth=n(gt["depth"]), pc=n(pc),
+                   loss=n(loss), seen=n(variables["seen"]), m2d_grad=n(variables["means2D"].grad))
+        out.update({f"grad_{k}": n(v.grad) for k, v in params.items() if v.grad is not None})
+        out.update(p0_means3D=n(params["means3D"]))
+        opt.step()
+        out.update(p1_means3D=n(params["means3D"]))
+        # ---------------- no-grad render ----------------
+        W, H, N = 80, 60, 1500
+        p = syn.make_params(N, W, H, seed=4)
+        params = dict(means3D=p["means3D"], rgb_colors=p["rgb_colors"], unnorm_rotations=p["unnorm_rotations"],
+                      logit_opacities=p["logit_opacities"], log_scales=p["log_scales"])
+        rv, dv = sp.get_rendervars(params, np.eye(4))
+        im, rdepth, opacity, sil = sp.render(np.eye(4), syn.intrinsics(W, H), rv, dv, dict(viz_w=W, viz_h=H, viz_near=0.01, viz_far=100.0))
+        out.update({f"render_{k}": n(v) for k, v in params.items()})
+        out.update(render_K=np.asarray(syn.intrinsics(W, H)), render_im=n(im), render_depth=n(rdepth), render_opacity=n(opacity), render_sil=n(sil))
+    np.savez_compressed(os.path.join(HERE, "dropin.npz"), **out)
+    print("golden vectors written to", os.path.join(HERE, "dropin.npz"))
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["dropin"]:
+        main_dropin()
+    else:
+        main()
