@@ -54,7 +54,7 @@ SORT_AUTO, SORT_TILE_LDS, SORT_RADIX = 0, 1, 2
 
 # every symbol include/gsplat_hip.h declares (tests check the library exports all of them)
 #: the GS_ABI_VERSION of include/gsplat_hip.h this binding was written against (checked when a library is bound)
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 SYMBOLS = ("gs_abi_version", "gs_geom_layout", "gs_image_layout", "gs_bin_layout", "gs_backward_scratch_bytes", "gs_last_error",
            "gs_version", "gs_set_sort_path", "gs_set_forward_segments", "gs_set_half_quadrants", "gs_set_backward_chain", "gs_set_backward_chain_tickets", "gs_set_backward_chain_polls", "gs_async_status_word", "gs_async_status_clear", "gs_recorded_cut", "gs_set_backward_segments", "gs_preprocess_forward", "gs_preprocess_forward_raw", "gs_render_forward", "gs_render_backward", "gs_render_backward_raw", "gs_render_backward_raw_adam", "gs_adam_step", "gs_adam_step_multi",
@@ -62,7 +62,8 @@ SYMBOLS = ("gs_abi_version", "gs_geom_layout", "gs_image_layout", "gs_bin_layout
            "gs_compact_scratch_bytes", "gs_compact_index", "gs_gather_rows", "gs_mapping_loss_scratch_bytes", "gs_mapping_loss", "gs_activate_forward", "gs_activate_backward", "gs_activate_backward_accumulate",
            "gs_grow_scratch_bytes", "gs_grow_gaussians", "gs_keyframe_overlap", "gs_visibility_stats", "gs_accumulate_grad2d",
            "gs_gather_rows_zero_tail", "gs_densify_classify", "gs_densify_children", "gs_atlas_layout",
-           "gs_pack_columns", "gs_adam_rows", "gs_unpack_columns", "gs_compact3_scratch_bytes", "gs_compact_index3")
+           "gs_pack_columns", "gs_adam_rows", "gs_unpack_columns", "gs_compact3_scratch_bytes", "gs_compact_index3",
+           "gs_pose_grad_scratch_bytes", "gs_render_backward_raw_pose", "gs_activate_backward_pose")
 
 
 def _bind(lib):
@@ -118,6 +119,12 @@ def _bind(lib):
     lib.gs_render_backward_raw_adam.argtypes = [C.POINTER(GsCamera), i32, i64] + [vp] * 6 + [vp, i32] + [vp] * 4 + [vp] * 2 + [vp] + [vp, i32, i32] + \
         [C.POINTER(GsAdamTensor), vp]
     lib.gs_render_backward_raw_adam.restype = C.c_int
+    # gs_render_backward_raw's arguments, then pose_only, dL_dpose7, pose_scratch, stream
+    lib.gs_render_backward_raw_pose.argtypes = [C.POINTER(GsCamera), i32, i64] + [vp] * 6 + [vp, i32, i32] + [vp] * 4 + [vp] * 2 + [vp] * 7 + \
+        [vp, i32, i32, i32, vp, vp, vp]
+    lib.gs_render_backward_raw_pose.restype = C.c_int
+    lib.gs_pose_grad_scratch_bytes.argtypes = [i32]
+    lib.gs_pose_grad_scratch_bytes.restype = C.c_uint64
     lib.gs_preprocess_forward_raw.restype = C.c_int
     lib.gs_render_backward_raw.restype = C.c_int
     lib.gs_adam_step.argtypes = [i64, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, i32, vp]
@@ -134,6 +141,9 @@ def _bind(lib):
     lib.gs_activate_backward.restype = C.c_int
     lib.gs_activate_backward_accumulate.argtypes = [i32, i32] + [vp] * 12 + [vp]
     lib.gs_activate_backward_accumulate.restype = C.c_int
+    # (P, isotropic, h_pose7, means3D, unnorm_rot, out_op, out_scales, 4 gradients in, 4 out, accumulate, pose_only, dL_dpose7, pose_scratch, stream)
+    lib.gs_activate_backward_pose.argtypes = [i32, i32] + [vp] * 13 + [i32, i32, vp, vp, vp]
+    lib.gs_activate_backward_pose.restype = C.c_int
     lib.gs_mapping_loss_scratch_bytes.argtypes = [i32, i32]
     lib.gs_mapping_loss_scratch_bytes.restype = C.c_uint64
     lib.gs_mapping_loss.argtypes = [i32, i32, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, i64, vp]

@@ -480,7 +480,8 @@ static int render_backward_impl(const GsCamera* cam, int32_t P, int64_t D, const
                                 const float* dL_ddepth, float* dL_dmeans2D, float* dL_dmeans3D, float* dL_dopacities, float* dL_dcolors_precomp,
                                 float* dL_dshs, float* dL_dscales, float* dL_drotations, float* dL_dcov3D, void* scratch,
                                 int32_t scratch_zeroed, int32_t have_sh_jacobian, gs_stream_t stream, const float* logit,
-                                const float* h_pose7, int32_t isotropic, int32_t accumulate, const GsAdamTensor* adam5 = nullptr)
+                                const float* h_pose7, int32_t isotropic, int32_t accumulate, const GsAdamTensor* adam5 = nullptr,
+                                int32_t pose_mode = 0, float* dL_dpose7 = nullptr, void* pose_scratch = nullptr)
 {
     gs::Cam k;
     if (!make_cam(cam, k)) return fail(GS_EINVAL, "gs_render_backward: invalid camera settings");
@@ -490,7 +491,16 @@ static int render_backward_impl(const GsCamera* cam, int32_t P, int64_t D, const
     if (k.V > 1) return fail(GS_EINVAL, "gs_render_backward: multi-view atlas renders are forward-only");
     if (P < 0 || D < 0 || !geom_state || !image_state || !dL_dcolor || !scratch)
         return fail(GS_EINVAL, "gs_render_backward: null pointer");
-    if (P == 0) return GS_OK;
+    if (pose_mode && (!k.act || adam5 || !dL_dpose7 || !pose_scratch))
+        return fail(GS_EINVAL, "gs_render_backward_raw_pose: raw-parameter mode with a pose-gradient output and its scratch only");
+    if (P == 0) {
+        if (pose_mode) {
+            const hipError_t e0 = hipMemsetAsync(dL_dpose7, 0, 7 * sizeof(float), (hipStream_t)stream);
+            if (e0 != hipSuccess) return fail(GS_ELAUNCH, "gs_render_backward_raw_pose: memset %s", hipGetErrorString(e0));
+        }
+        return GS_OK;
+    }
+    const bool pose_only = pose_mode == 2;
     gs::FusedAdam fa{};
     if (adam5) {
         // the optimiser step inside the per-Gaussian kernel: the five descriptors must describe the very tensors this call reads
@@ -509,6 +519,10 @@ static int render_backward_impl(const GsCamera* cam, int32_t P, int64_t D, const
             fa.c[t] = gs::adam_coef(a.lr, a.beta1, a.beta2, a.eps, a.step);
         }
         fa.fail = gs::chain_fail_word();
+    } else if (pose_only) {
+        // (tracking: no parameter gradient is formed; the colour / SH inputs are still read)
+        if (!means3D || !radii || !dL_dmeans2D || !scales || !rotations || (shs == nullptr) == (colors_precomp == nullptr))
+            return fail(GS_EINVAL, "gs_render_backward_raw_pose: null input/output pointer");
     } else {
         if (!means3D || !radii || !dL_dmeans2D || !dL_dmeans3D || !dL_dopacities)
             return fail(GS_EINVAL, "gs_render_backward: null input/output pointer");
@@ -535,9 +549,13 @@ static int render_backward_impl(const GsCamera* cam, int32_t P, int64_t D, const
         ScopedStage ps(ST_PREPROCESS_BWD, st);
         e = gs::launch_preprocess_backward(k, P, means3D, shs, scales, rotations, cov3D_precomp, radii, gp.clamped, (shs && have_sh_jacobian) ? gp.sh_jac : nullptr, grad2d,
                                            dL_dmeans2D, dL_dmeans3D, dL_dopacities, dL_dcolors_precomp, dL_dshs, dL_dscales,
-                                           dL_drotations, dL_dcov3D, logit, adam5 ? &fa : nullptr, st);
+                                           dL_drotations, dL_dcov3D, logit, adam5 ? &fa : nullptr, st, pose_mode, (float*)pose_scratch);
     }
     if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_backward: preprocess %s", hipGetErrorString(e));
+    if (pose_mode) {
+        e = gs::launch_pose_grad_finish(gs::pose_rows_count(P), h_pose7, (const float*)pose_scratch, dL_dpose7, st);
+        if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_backward_raw_pose: pose reduction %s", hipGetErrorString(e));
+    }
     return GS_OK;
 }
 
@@ -566,6 +584,24 @@ int gs_render_backward_raw(const GsCamera* cam, int32_t P, int64_t D, const floa
                                 image_state, dL_dcolor, dL_ddepth, dL_dmeans2D, dL_dmeans3D, dL_dlogit_opacities, dL_dcolors_precomp, dL_dshs,
                                 dL_dlog_scales, dL_dunnorm_rotations, nullptr, scratch, scratch_zeroed, have_sh_jacobian, stream,
                                 logit_opacities, h_pose7, isotropic, accumulate);
+}
+
+uint64_t gs_pose_grad_scratch_bytes(int32_t P) { return align_up((uint64_t)gs::pose_rows_count(P > 0 ? P : 1) * gs::kPoseAcc * 4); }
+
+int gs_render_backward_raw_pose(const GsCamera* cam, int32_t P, int64_t D, const float* means3D, const float* shs, const float* colors_precomp,
+                                const float* logit_opacities, const float* log_scales, const float* unnorm_rotations, const float* h_pose7,
+                                int32_t isotropic, int32_t accumulate, const int32_t* radii, const void* geom_state, const uint32_t* point_list,
+                                const void* image_state, const float* dL_dcolor, const float* dL_ddepth, float* dL_dmeans2D, float* dL_dmeans3D,
+                                float* dL_dlogit_opacities, float* dL_dcolors_precomp, float* dL_dshs, float* dL_dlog_scales,
+                                float* dL_dunnorm_rotations, void* scratch, int32_t scratch_zeroed, int32_t have_sh_jacobian, int32_t pose_only,
+                                float* dL_dpose7, void* pose_scratch, gs_stream_t stream)
+{
+    if (!h_pose7 || (P > 0 && !logit_opacities)) return fail(GS_EINVAL, "gs_render_backward_raw_pose: null pose / opacity parameters");
+    if (!dL_dpose7 || !pose_scratch) return fail(GS_EINVAL, "gs_render_backward_raw_pose: null pose-gradient output or scratch");
+    return render_backward_impl(cam, P, D, means3D, shs, colors_precomp, log_scales, unnorm_rotations, nullptr, radii, geom_state, point_list,
+                                image_state, dL_dcolor, dL_ddepth, dL_dmeans2D, dL_dmeans3D, dL_dlogit_opacities, dL_dcolors_precomp, dL_dshs,
+                                dL_dlog_scales, dL_dunnorm_rotations, nullptr, scratch, scratch_zeroed, have_sh_jacobian, stream,
+                                logit_opacities, h_pose7, isotropic, pose_only ? 0 : accumulate, nullptr, pose_only ? 2 : 1, dL_dpose7, pose_scratch);
 }
 
 int gs_render_backward_raw_adam(const GsCamera* cam, int32_t P, int64_t D, const float* means3D, const float* shs, const float* colors_precomp,
@@ -694,6 +730,30 @@ int gs_activate_backward_accumulate(int32_t P, int32_t isotropic, const float* h
                                                 g_opacities, g_scales, d_means3D, d_unnorm_rotations, d_logit_opacities, d_log_scales, 1,
                                                 (hipStream_t)stream);
     if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_activate_backward_accumulate: %s", hipGetErrorString(e));
+    return GS_OK;
+}
+
+int gs_activate_backward_pose(int32_t P, int32_t isotropic, const float* h_pose7, const float* means3D, const float* unnorm_rotations,
+                              const float* out_opacities, const float* out_scales, const float* g_means3D, const float* g_rotations,
+                              const float* g_opacities, const float* g_scales, float* d_means3D, float* d_unnorm_rotations,
+                              float* d_logit_opacities, float* d_log_scales, int32_t accumulate, int32_t pose_only, float* dL_dpose7,
+                              void* pose_scratch, gs_stream_t stream)
+{
+    if (P < 0 || !h_pose7 || !dL_dpose7 || !pose_scratch || (P > 0 && (!means3D || !unnorm_rotations)) ||
+        (P > 0 && !pose_only && (!out_opacities || !out_scales || !d_means3D || !d_unnorm_rotations || !d_logit_opacities || !d_log_scales)))
+        return fail(GS_EINVAL, "gs_activate_backward_pose: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    if (P == 0) {
+        const hipError_t e0 = hipMemsetAsync(dL_dpose7, 0, 7 * sizeof(float), st);
+        if (e0 != hipSuccess) return fail(GS_ELAUNCH, "gs_activate_backward_pose: memset %s", hipGetErrorString(e0));
+        return GS_OK;
+    }
+    hipError_t e = gs::launch_activate_backward_pose(P, isotropic, h_pose7, means3D, unnorm_rotations, out_opacities, out_scales, g_means3D,
+                                                     g_rotations, g_opacities, g_scales, d_means3D, d_unnorm_rotations, d_logit_opacities,
+                                                     d_log_scales, accumulate, pose_only ? 2 : 1, (float*)pose_scratch, st);
+    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_activate_backward_pose: %s", hipGetErrorString(e));
+    e = gs::launch_pose_grad_finish(gs::pose_rows_count(P), h_pose7, (const float*)pose_scratch, dL_dpose7, st);
+    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_activate_backward_pose: pose reduction %s", hipGetErrorString(e));
     return GS_OK;
 }
 

@@ -123,6 +123,42 @@ __device__ __forceinline__ void activate_rotation_bwd(const float* cam_q, int is
     for (int k = 0; k < 4; k++) dq[k] = (du[k] - u[k] * dotu) / nq;
 }
 
+// ---- camera-pose gradient (tracking / bundle adjustment; slam_helpers.py:252-304 with camera_grad=True) ----
+// da = R(b)^T dm  where m = a (x) b is linear in a (the counterpart of qmul_bwd_rhs)
+__device__ __forceinline__ void qmul_bwd_lhs(const float* b, const float* dm, float* da)
+{
+    da[0] = b[0] * dm[0] + b[1] * dm[1] + b[2] * dm[2] + b[3] * dm[3];
+    da[1] = -b[1] * dm[0] + b[0] * dm[1] - b[3] * dm[2] + b[2] * dm[3];
+    da[2] = -b[2] * dm[0] + b[3] * dm[1] + b[0] * dm[2] - b[1] * dm[3];
+    da[3] = -b[3] * dm[0] - b[2] * dm[1] + b[1] * dm[2] + b[0] * dm[3];
+}
+// Number of floats of one Gaussian's (and one workgroup's) pose-gradient record: dL/dt (3), dL/dR row-major (9), dL/dq_cam through the
+// rotation the rasteriser sees (4).  dL/dR becomes dL/dq_cam once, in the final pass (pose_grad_finish_kernel, activate.hip).
+constexpr int kPoseAcc = 16;
+// Adds one Gaussian's share to `acc`: w = its world mean, dmean = dL/d(its camera-frame mean), q = its unnormalised quaternion parameter,
+// g = dL/d(the rotation the rasteriser sees, activate_rotation's output).  means_cam = R(q_cam) w + t: dL/dt += dmean, dL/dR += dmean w^T;
+// anisotropic maps: rot = normalize(q_cam (x) normalize(q)) also depends on q_cam (isotropic maps keep q: no term).
+__device__ __forceinline__ void pose_grad_accumulate(const float* cam_q, int iso, const float* w, const float* dmean, const float* q,
+                                                     const float* g, float (&acc)[kPoseAcc])
+{
+    for (int a = 0; a < 3; a++) {
+        acc[a] += dmean[a];
+        for (int b = 0; b < 3; b++) acc[3 + 3 * a + b] += dmean[a] * w[b];
+    }
+    if (iso) return;
+    const float nq = fmaxf(sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]), 1e-12f);
+    const float u[4] = {q[0] / nq, q[1] / nq, q[2] / nq, q[3] / nq};
+    float m[4];
+    qmul(cam_q, u, m);
+    const float nm = fmaxf(sqrtf(m[0] * m[0] + m[1] * m[1] + m[2] * m[2] + m[3] * m[3]), 1e-12f);
+    const float r[4] = {m[0] / nm, m[1] / nm, m[2] / nm, m[3] / nm};
+    const float dot = r[0] * g[0] + r[1] * g[1] + r[2] * g[2] + r[3] * g[3];
+    float dm[4], da[4];
+    for (int k = 0; k < 4; k++) dm[k] = (g[k] - r[k] * dot) / nm;
+    qmul_bwd_lhs(u, dm, da);
+    for (int k = 0; k < 4; k++) acc[12 + k] += da[k];
+}
+
 // The optimiser step INSIDE the raw-parameter backward (gs_render_backward_raw_adam; single-keyframe steps -- the reference's loop,
 // src/mapper/splatam/__init__.py:470-480, and BASELINE configs[2]'s): the thread that forms a Gaussian's parameter gradient applies
 // Adam to the parameter and its two moments in place -- no gradient tensor is written and read back.  Tensor order: 0 means3D,
@@ -186,6 +222,23 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, int lane)
         if (lane >= d) v += o;
     }
     return v;
+}
+// Deterministic workgroup sum of every lane's record into row[0..kPoseAcc): butterfly within each wavefront, then the four wavefronts'
+// sums in a fixed order.  Every thread of the workgroup must call it.
+__device__ __forceinline__ void pose_grad_block_row(float (&acc)[kPoseAcc], float* __restrict__ row)
+{
+    __shared__ float s_red[kBlock / kWave][kPoseAcc];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    for (int k = 0; k < kPoseAcc; k++) {
+        const float v = wave_sum(acc[k]);
+        if (lane == 0) s_red[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < kPoseAcc) {
+        float s = 0.f;
+        for (int w = 0; w < kBlock / kWave; w++) s += s_red[w][threadIdx.x];
+        row[threadIdx.x] = s;
+    }
 }
 
 // Coalesced staging of `nrows` rows of K floats (array-of-structs in HBM) into LDS: the full-block
@@ -543,7 +596,8 @@ hipError_t launch_preprocess_backward(const Cam& cam, int P, const float* means3
                                       const float* scales, const float* rots, const float* cov3Dp,
                                       const int32_t* radii, const uint32_t* clamped, const float2* sh_jac, const float* grad2d,
                                       float* dmeans2D, float* dmeans3D, float* dopac, float* dcolors, float* dshs,
-                                      float* dscales, float* drots, float* dcov3D, const float* logit, const FusedAdam* adam, hipStream_t st);
+                                      float* dscales, float* drots, float* dcov3D, const float* logit, const FusedAdam* adam, hipStream_t st,
+                                      int pose_mode = 0, float* pose_rows = nullptr);
 hipError_t launch_tile_count(const Cam& cam, int P, GeomPtrs gp, uint32_t* tile_total, uint32_t* tile_base,
                              uint2* ranges, uint32_t* d_counts, uint32_t* host_counts, hipStream_t st);
 hipError_t launch_tile_scatter_sort(const Cam& cam, int P, GeomPtrs gp, uint32_t* tile_base, const uint2* ranges,
@@ -636,6 +690,14 @@ hipError_t launch_activate_forward(int P, int iso, const float* pose7, const flo
 hipError_t launch_activate_backward(int P, int iso, const float* pose7, const float* rots, const float* o_op, const float* o_scales,
                                     const float* g_means, const float* g_rots, const float* g_op, const float* g_scales, float* d_means,
                                     float* d_rots, float* d_logit, float* d_logs, int accumulate, hipStream_t st);
+// camera-pose gradient (pose_mode 1: with the four parameter gradients, 2: pose only -- the d_* may be null): one row of kPoseAcc partial sums
+// per 256-Gaussian workgroup into pose_rows, then pose_grad_finish reduces them into dpose7 = dL/d(qw,qx,qy,qz,tx,ty,tz)
+hipError_t launch_activate_backward_pose(int P, int iso, const float* pose7, const float* means3D, const float* rots, const float* o_op,
+                                         const float* o_scales, const float* g_means, const float* g_rots, const float* g_op,
+                                         const float* g_scales, float* d_means, float* d_rots, float* d_logit, float* d_logs, int accumulate,
+                                         int pose_mode, float* pose_rows, hipStream_t st);
+inline int64_t pose_rows_count(int64_t P) { return (P + kBlock - 1) / kBlock; }
+hipError_t launch_pose_grad_finish(int64_t nrows, const float* pose7, const float* pose_rows, float* dpose7, hipStream_t st);
 constexpr int kLossAccSlots = 256;          // 64-byte accumulator lines at the head of the mapping loss' scratch (loss.hip)
 hipError_t launch_mapping_loss(int W, int H, const float* im, const float* gt, const float* depth, const float* depth_sq,
                                const float* gt_depth, float w_im, float w_depth, float* losses, float* dL_dim,

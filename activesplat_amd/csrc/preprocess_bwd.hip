@@ -31,15 +31,27 @@ namespace gs {
 template <bool NOALIAS> struct ParamPtr { typedef const float* __restrict__ type; };
 template <> struct ParamPtr<false> { typedef const float* type; };
 
-template <int SH, bool ACT = false, bool ADAM = false>
+// POSE (raw-parameter mode, no ADAM; camera-pose gradient for tracking / bundle adjustment): 1 = every rendered Gaussian also adds its share of
+// the pose gradient (pose_grad_accumulate, gs_common.h) to a per-thread record, and every workgroup -- all of its threads, so a lane that is done
+// early jumps to the reduction instead of returning -- writes one row of kPoseAcc partial sums to pose_rows (no float atomics; reduced in a fixed
+// order by pose_grad_finish_kernel, activate.hip); 2 = the pose share ONLY: no parameter gradient row is written and the parameter-side chain that
+// only feeds those rows is skipped (dmeans2D is written as always).  POSE = 0: the instantiations of every other mode, unchanged.
+template <int SH, bool ACT = false, bool ADAM = false, int POSE = 0>
 __global__ __launch_bounds__(kBlock, (ACT && SH == 3) ? GS_PBWD_RAW_SH_WGS : 4) void preprocess_backward_kernel(
     Cam cam, int P, typename ParamPtr<!ADAM>::type means3D, typename ParamPtr<!ADAM>::type shs,
     typename ParamPtr<!ADAM>::type scales, typename ParamPtr<!ADAM>::type rots, const float* __restrict__ cov3Dp,
     const int32_t* __restrict__ radii, const uint32_t* __restrict__ clamped, const float2* __restrict__ sh_jac,
     const float* __restrict__ grad2d, float* __restrict__ dmeans2D, float* __restrict__ dmeans3D, float* __restrict__ dopac,
     float* __restrict__ dcolors, float* __restrict__ dshs, float* __restrict__ dscales,
-    float* __restrict__ drots, float* __restrict__ dcov3D, typename ParamPtr<!ADAM>::type logit, FusedAdam ad)
+    float* __restrict__ drots, float* __restrict__ dcov3D, typename ParamPtr<!ADAM>::type logit, FusedAdam ad, float* __restrict__ pose_rows)
 {
+    static_assert(POSE == 0 || (ACT && !ADAM && SH != 1), "the pose gradient is a raw-parameter mode without the optimiser step");
+    float pacc[kPoseAcc];
+    for (int k = 0; k < kPoseAcc; k++) pacc[k] = 0.f;
+#define GS_PBWD_LEAVE do { if (POSE != 0) goto pose_reduce; return; } while (0)
+    // NO BARE `return` INSIDE THIS BLOCK (outside the ADAM-only paths): leave through GS_PBWD_LEAVE.  Every thread of a POSE workgroup must reach
+    // the __syncthreads in pose_grad_block_row at the end; a plain return would skip it for the pose instantiations only.
+    {
     // per-wave slabs: 32 coefficient rows in, their gradients written back IN PLACE (each element is read before it is overwritten)
     constexpr bool HAS_SH = SH != 0;
     constexpr bool SLAB = SH == 1 || SH == 3;
@@ -53,7 +65,7 @@ __global__ __launch_bounds__(kBlock, (ACT && SH == 3) ? GS_PBWD_RAW_SH_WGS : 4) 
         if (in_range) { dmeans2D[3 * i] = 0.f; dmeans2D[3 * i + 1] = 0.f; dmeans2D[3 * i + 2] = 0.f; }
         return;
     }
-    if (!HAS_SH && !in_range) return;
+    if (!HAS_SH && !in_range) GS_PBWD_LEAVE;
     const int ic = in_range ? i : P - 1;                       // clamped index: out-of-range lanes only help with the SH slabs
     const bool live = in_range && radii[ic] > 0;
     const float4* gr4 = reinterpret_cast<const float4*>(grad2d + (size_t)ic * kGradStride);
@@ -69,7 +81,7 @@ __global__ __launch_bounds__(kBlock, (ACT && SH == 3) ? GS_PBWD_RAW_SH_WGS : 4) 
             // dL/dmeans2D is NOT accumulated: the header promises that every row is written, and the host hands the buffer out uninitialised
             // (torch.empty).  12 B per row against the 64-byte record read the gate saves.
             if (in_range) { dmeans2D[3 * i] = 0.f; dmeans2D[3 * i + 1] = 0.f; dmeans2D[3 * i + 2] = 0.f; }
-            return;
+            GS_PBWD_LEAVE;
         }
         const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
         ga = z4; gb = z4; gc = z4;
@@ -202,11 +214,11 @@ __global__ __launch_bounds__(kBlock, (ACT && SH == 3) ? GS_PBWD_RAW_SH_WGS : 4) 
                     adam_elem(pp.z, gs_[2], mm.z, vv.z, ad.c[4]); adam_elem(pp.w, gs_[3], mm.w, vv.w, ad.c[4]);
                     store_stream(&p4[q4], pp); store_stream(&m4[q4], mm); store_stream(&v4[q4], vv);
                 }
-            } else {
+            } else if (POSE != 2) {
                 sh_wave_rows_from_lds<KC>(slab, dshs, row0, nrows, K, lane);
             }
         }
-        if (!in_range) return;
+        if (!in_range) GS_PBWD_LEAVE;
     }
     if (live) {
         const float* m = cam.view;
@@ -339,8 +351,17 @@ __global__ __launch_bounds__(kBlock, (ACT && SH == 3) ? GS_PBWD_RAW_SH_WGS : 4) 
         // gradients w.r.t. the parameters (activate.hip's backward): means through the frame rotation, rotation through the normalisations and
         // the camera quaternion, opacity through the sigmoid, scales through the exponential
         for (int c = 0; c < 3; c++) dmeans2D[3 * i + c] = o_m2d[c];
+        if (POSE != 0) {
+            if (live) {
+                // (the world mean again: the registers that held it carry the camera-frame mean since the top; 12 bytes the kernel has just read)
+                const float w[3] = {means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]};
+                const float qr[4] = {rq_raw.x, rq_raw.y, rq_raw.z, rq_raw.w};
+                pose_grad_accumulate(cam.act_q, cam.act_iso, w, dmean, qr, o_rot, pacc);
+            }
+            if (POSE == 2) GS_PBWD_LEAVE;
+        }
         const bool acc = !ADAM && cam.act_accumulate != 0;
-        if (acc && !live) return;                                   // nothing to add
+        if (acc && !live) GS_PBWD_LEAVE;                            // nothing to add
         const float dm[3] = {actR[0][0] * dmean[0] + actR[1][0] * dmean[1] + actR[2][0] * dmean[2],
                              actR[0][1] * dmean[0] + actR[1][1] * dmean[1] + actR[2][1] * dmean[2],
                              actR[0][2] * dmean[0] + actR[1][2] * dmean[1] + actR[2][2] * dmean[2]};
@@ -403,7 +424,7 @@ __global__ __launch_bounds__(kBlock, (ACT && SH == 3) ? GS_PBWD_RAW_SH_WGS : 4) 
         float4 out = make_float4(dq[0], dq[1], dq[2], dq[3]);
         if (acc) { const float4 old = reinterpret_cast<const float4*>(drots)[i]; out.x += old.x; out.y += old.y; out.z += old.z; out.w += old.w; }
         reinterpret_cast<float4*>(drots)[i] = out;
-        return;
+        GS_PBWD_LEAVE;
     }
     for (int c = 0; c < 3; c++) { dmeans2D[3 * i + c] = o_m2d[c]; dmeans3D[3 * i + c] = dmean[c]; }
     dopac[i] = live ? gb.y : 0.f;
@@ -411,21 +432,34 @@ __global__ __launch_bounds__(kBlock, (ACT && SH == 3) ? GS_PBWD_RAW_SH_WGS : 4) 
     if (dscales) for (int c = 0; c < 3; c++) dscales[3 * i + c] = o_sc[c];
     if (drots) reinterpret_cast<float4*>(drots)[i] = make_float4(o_rot[0], o_rot[1], o_rot[2], o_rot[3]);
     if (dcov3D) for (int c = 0; c < 6; c++) dcov3D[6 * i + c] = o_cov[c];
+    }
+#undef GS_PBWD_LEAVE
+    return;
+pose_reduce:
+    if (POSE != 0) pose_grad_block_row(pacc, pose_rows + (size_t)blockIdx.x * kPoseAcc);
 }
 
 hipError_t launch_preprocess_backward(const Cam& cam, int P, const float* means3D, const float* shs,
                                       const float* scales, const float* rots, const float* cov3Dp,
                                       const int32_t* radii, const uint32_t* clamped, const float2* sh_jac, const float* grad2d,
                                       float* dmeans2D, float* dmeans3D, float* dopac, float* dcolors, float* dshs,
-                                      float* dscales, float* drots, float* dcov3D, const float* logit, const FusedAdam* adam, hipStream_t st)
+                                      float* dscales, float* drots, float* dcov3D, const float* logit, const FusedAdam* adam, hipStream_t st,
+                                      int pose_mode, float* pose_rows)
 {
     const int nb = (P + kBlock - 1) / kBlock;
-    if (cam.act && (cov3Dp || !logit || !scales || !rots || (!adam && (!dscales || !drots)) || (shs && cam.sh_coeffs != 16))) return hipErrorInvalidValue;
+    const bool pose_only = pose_mode == 2;
+    if (cam.act && (cov3Dp || !logit || !scales || !rots || (!adam && !pose_only && (!dscales || !drots)) || (shs && cam.sh_coeffs != 16))) return hipErrorInvalidValue;
     if (adam && (!cam.act || cam.act_accumulate)) return hipErrorInvalidValue;
+    if (pose_mode && (!cam.act || adam || !pose_rows || pose_mode > 2)) return hipErrorInvalidValue;
     const FusedAdam ad = adam ? *adam : FusedAdam{};
 #define GS_PBWD(...) hipLaunchKernelGGL((preprocess_backward_kernel<__VA_ARGS__>), dim3(nb), dim3(kBlock), 0, st, cam, P, means3D, shs, scales, rots, \
-                                        cov3Dp, radii, clamped, sh_jac, grad2d, dmeans2D, dmeans3D, dopac, dcolors, dshs, dscales, drots, dcov3D, logit, ad)
-    if (nb > 0 && shs && cam.sh_coeffs == 16) { if (adam) GS_PBWD(3, true, true); else if (cam.act) GS_PBWD(3, true); else GS_PBWD(3, false); }
+                                        cov3Dp, radii, clamped, sh_jac, grad2d, dmeans2D, dmeans3D, dopac, dcolors, dshs, dscales, drots, dcov3D, logit, ad, \
+                                        pose_rows)
+    if (nb > 0 && pose_mode) {
+        if (shs) { if (pose_only) GS_PBWD(3, true, false, 2); else GS_PBWD(3, true, false, 1); }
+        else { if (pose_only) GS_PBWD(0, true, false, 2); else GS_PBWD(0, true, false, 1); }
+    }
+    else if (nb > 0 && shs && cam.sh_coeffs == 16) { if (adam) GS_PBWD(3, true, true); else if (cam.act) GS_PBWD(3, true); else GS_PBWD(3, false); }
     else if (nb > 0 && shs) GS_PBWD(1, false);
     else if (nb > 0) { if (adam) GS_PBWD(0, true, true); else if (cam.act) GS_PBWD(0, true); else GS_PBWD(0, false); }
 #undef GS_PBWD

@@ -162,7 +162,8 @@ class _FusedRendervars(torch.autograd.Function):
     transformed_params2rendervar in one launch each way."""
 
     @staticmethod
-    def forward(ctx, means3D, unnorm_rotations, logit_opacities, log_scales, pose7, accumulate=False):
+    def forward(ctx, means3D, unnorm_rotations, logit_opacities, log_scales, pose7, accumulate=False, cam_rot=None, cam_trans=None,
+                gaussians_grad=True):
         import ctypes as C
         from . import _lib
         lib = _lib.get()
@@ -177,7 +178,11 @@ class _FusedRendervars(torch.autograd.Function):
         st = _lib.stream_ptr(dev)
         p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
         _lib.check(lib.gs_activate_forward(P, iso, pose, p(m), p(r), p(o), p(s), p(om), p(orr), p(oo), p(os_), st))
-        ctx.save_for_backward(r, oo, os_)
+        # camera-pose gradient (fused_rendervar(camera_grad=True)): (pose_only, shape of cam_rot, shape of cam_trans); the world means are kept
+        ctx.pose_req = None
+        if cam_rot is not None and (cam_rot.requires_grad or cam_trans.requires_grad):
+            ctx.pose_req = (not gaussians_grad, cam_rot.shape, cam_trans.shape)
+        ctx.save_for_backward(r, oo, os_, m if ctx.pose_req is not None else None)
         ctx.pose, ctx.iso, ctx.st = pose, iso, st
         # accumulate: the backward adds its four gradients to the leaves' .grad inside the kernel (and hands autograd nothing)
         ctx.leaves = (means3D, unnorm_rotations, logit_opacities, log_scales) if accumulate else None
@@ -188,45 +193,77 @@ class _FusedRendervars(torch.autograd.Function):
         import ctypes as C
         from . import _lib
         lib = _lib.get()
-        r, oo, os_ = ctx.saved_tensors
+        r, oo, os_, m = ctx.saved_tensors
         P, dev = int(r.shape[0]), r.device
         c = lambda t: None if t is None else t.contiguous().float()  # noqa: E731
         gm, gr, go, gs_ = c(gm), c(gr), c(go), c(gs_)
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
         st = _lib.stream_ptr(dev)
+        pose_req, tail = ctx.pose_req, (None, None, None)
+        if pose_req is not None:
+            d_pose = torch.empty(7, device=dev)
+            pscr = torch.empty(int(lib.gs_pose_grad_scratch_bytes(P)), dtype=torch.uint8, device=dev)
+            tail = (d_pose[:4].view(pose_req[1]), d_pose[4:].view(pose_req[2]), None)
+            if pose_req[0]:
+                # tracking: the pose gradient only (no parameter gradient is formed)
+                _lib.check(lib.gs_activate_backward_pose(P, ctx.iso, ctx.pose, p(m), p(r), None, None, p(gm), p(gr), None, None, None, None, None,
+                                                         None, 0, 1, p(d_pose), p(pscr), st))
+                return (None,) * 6 + tail
+
+        def launch(d, acc):
+            # the four parameter gradients (added to d when acc); with a differentiable camera the same launch also reduces the pose gradient
+            if pose_req is not None:
+                _lib.check(lib.gs_activate_backward_pose(P, ctx.iso, ctx.pose, p(m), p(r), p(oo), p(os_), p(gm), p(gr), p(go), p(gs_), p(d[0]), p(d[1]),
+                                                         p(d[2]), p(d[3]), 1 if acc else 0, 0, p(d_pose), p(pscr), st))
+            else:
+                fn = lib.gs_activate_backward_accumulate if acc else lib.gs_activate_backward
+                _lib.check(fn(P, ctx.iso, ctx.pose, p(r), p(oo), p(os_), p(gm), p(gr), p(go), p(gs_), p(d[0]), p(d[1]), p(d[2]), p(d[3]), st))
         leaves = ctx.leaves
         if leaves is not None and all(x.is_leaf and x.requires_grad for x in leaves):
             # a keyframe batch (parallel.sharded_keyframe_step): what autograd would do with the four results is `leaf.grad += result`,
             # 3 x 44 bytes per Gaussian and keyframe of extra passes -- the kernel adds in place instead
             have = [x.grad is not None and x.grad.is_contiguous() and x.grad.dtype == torch.float32 and x.grad.shape == x.shape for x in leaves]
             if all(have):
-                g = [x.grad for x in leaves]
-                _lib.check(lib.gs_activate_backward_accumulate(P, ctx.iso, ctx.pose, p(r), p(oo), p(os_), p(gm), p(gr), p(go), p(gs_),
-                                                               p(g[0]), p(g[1]), p(g[2]), p(g[3]), st))
-                return None, None, None, None, None, None
+                launch([x.grad for x in leaves], True)
+                return (None,) * 6 + tail
             if not any(x.grad is not None for x in leaves):
                 g = [torch.empty_like(x, memory_format=torch.contiguous_format) for x in leaves]
-                _lib.check(lib.gs_activate_backward(P, ctx.iso, ctx.pose, p(r), p(oo), p(os_), p(gm), p(gr), p(go), p(gs_),
-                                                    p(g[0]), p(g[1]), p(g[2]), p(g[3]), st))
+                launch(g, False)
                 for x, t in zip(leaves, g):
                     x.grad = t
-                return None, None, None, None, None, None
+                return (None,) * 6 + tail
         dm, dr = torch.empty(P, 3, device=dev), torch.empty(P, 4, device=dev)
         dl, ds = torch.empty(P, 1, device=dev), torch.empty(P, 1 if ctx.iso else 3, device=dev)
-        _lib.check(lib.gs_activate_backward(P, ctx.iso, ctx.pose, p(r), p(oo), p(os_), p(gm), p(gr), p(go), p(gs_), p(dm), p(dr),
-                                            p(dl), p(ds), st))
-        return dm, dr, dl, ds, None, None
+        launch((dm, dr, dl, ds), False)
+        return (dm, dr, dl, ds, None, None) + tail
 
 
-def fused_rendervar(params, time_idx, pose7=None, accumulate_grads=False):
+def fused_rendervar(params, time_idx, pose7=None, accumulate_grads=False, camera_grad=False, gaussians_grad=True):
     """rendervar dict of transform_to_frame(gaussians_grad=True, camera_grad=False) +
     transformed_params2rendervar, built by ONE HIP launch (and one more in the backward).  pose7 = host
-    (qw,qx,qy,qz,tx,ty,tz) of the frame's relative w2c; read from params['cam_*'] (one small D2H) if omitted."""
-    if pose7 is None:
+    (qw,qx,qy,qz,tx,ty,tz) of the frame's relative w2c; read from params['cam_*'] (one small D2H) if omitted.
+    camera_grad=True: transform_to_frame(camera_grad=True) -- the backward launch also reduces dL/d(pose) (gs_activate_backward_pose), and
+    autograd carries it through F.normalize into params['cam_unnorm_rots'] / params['cam_trans'].  gaussians_grad=False (tracking, with
+    camera_grad): the pose gradient only; no Gaussian tensor (colours included) receives a gradient."""
+    if not gaussians_grad and not camera_grad:
+        raise Exception("fused_rendervar: gaussians_grad=False is the pose-only backward: it needs camera_grad=True")
+    cam = None
+    if camera_grad:
+        cam = (F.normalize(params["cam_unnorm_rots"][..., time_idx]).reshape(4), params["cam_trans"][..., time_idx].reshape(3))
+        if pose7 is None:
+            pose7 = torch.cat([cam[0].detach(), cam[1].detach()]).cpu().tolist()
+    elif pose7 is None:
         q = F.normalize(params["cam_unnorm_rots"][..., time_idx].detach()).reshape(4)
         pose7 = torch.cat([q, params["cam_trans"][..., time_idx].detach().reshape(3)]).cpu().tolist()
-    m, r, o, s = _FusedRendervars.apply(params["means3D"], params["unnorm_rotations"], params["logit_opacities"],
-                                        params["log_scales"], pose7, accumulate_grads)
+    g = (lambda t: t) if gaussians_grad else (lambda t: t.detach())
+    if cam is None:
+        m, r, o, s = _FusedRendervars.apply(params["means3D"], params["unnorm_rotations"], params["logit_opacities"],
+                                            params["log_scales"], pose7, accumulate_grads)
+    else:
+        m, r, o, s = _FusedRendervars.apply(g(params["means3D"]), g(params["unnorm_rotations"]), g(params["logit_opacities"]),
+                                            g(params["log_scales"]), pose7, accumulate_grads and gaussians_grad, cam[0], cam[1], gaussians_grad)
+        return {"means3D": m, "colors_precomp": g(params["rgb_colors"]), "rotations": r, "opacities": o, "scales": s,
+                "means2D": torch.empty_like(params["means3D"], requires_grad=True)}
     # means2D only exists to receive the screen-space gradient: a fresh LEAF (autograd hands it the rasteriser's gradient
     # tensor as .grad without a copy; the reference's `zeros + 0` non-leaf costs an add and a retain_grad clone).  Its VALUES are
     # never read -- the rasteriser takes the tensor as a gradient carrier only -- so it is not filled either (one launch less)
@@ -348,7 +385,7 @@ def fused_mapping_loss(im, depth, depth_sq, gt_im, gt_depth, loss_weights):
 
 def get_loss(params, curr_data, variables, iter_time_idx, loss_weights, use_sil_for_loss=True, sil_thres=0.99,
              use_l1=True, ignore_outlier_depth_loss=False, do_ba=False, fused=False, fused_loss=False, fused_inputs=False,
-             pose7=None, accumulate_grads=False, fused_preprocess=False, fused_adam=None):
+             pose7=None, accumulate_grads=False, fused_preprocess=False, fused_adam=None, tracking=False, mapping=False):
     """Mapping loss: masked depth L1 + 0.8 L1 + 0.2 (1 - SSIM) on colour; updates
     variables['means2D'|'seen'|'max_2D_radius'].
     fused=False: the reference's two raster passes on the same geometry (RGB, then [z,1,z^2]).
@@ -365,24 +402,43 @@ def get_loss(params, curr_data, variables, iter_time_idx, loss_weights, use_sil_
                  rasteriser's per-Gaussian kernels take the PARAMETERS and do the frame transform + activations themselves, forward and
                  backward (rasterizer.render_rgbd_raw); with accumulate_grads the backward also adds into the parameters' .grad.
     fused_adam (with fused_preprocess; the GaussianAdam that owns the parameters): the backward kernel also applies this iteration's Adam
-                 step to the five per-Gaussian tensors in place (no gradient tensors; a following optimizer.step() skips them)."""
-    if fused_preprocess and fused and not do_ba:
-        if pose7 is None:
+                 step to the five per-Gaussian tensors in place (no gradient tensors; a following optimizer.step() skips them).
+    tracking (splatam.py:176-180,220-246): transform_to_frame(gaussians_grad=False, camera_grad=True) -- only params['cam_unnorm_rots'] /
+                 params['cam_trans'] receive a gradient -- and the tracking loss: SUMS of |depth error| and |colour error| over the valid-depth
+                 pixels, with use_sil_for_loss also over the rendered silhouette > sil_thres (the colour mask is that mask tiled to 3 channels;
+                 without use_sil_for_loss and ignore_outlier_depth_loss the colour sum runs over every pixel).  Always the torch loss (fused_loss
+                 does not apply).  On the fused paths (fused_preprocess / fused_inputs) the backward forms the pose gradient ONLY: the Gaussian
+                 tensors keep .grad = None (the reference hands the colours / opacities / scales gradients that its tracking optimiser, with their
+                 learning rates at 0, never uses).
+    do_ba (bundle adjustment, splatam.py:181-186): camera_grad=True next to the Gaussians' gradients.  `mapping` is accepted for the
+                 reference's signature: here do_ba selects bundle adjustment on its own, as it always has.  On the fused paths the pose
+                 gradient comes out of the same backward launch (rasterizer.render_rgbd_raw(camera=...), fused_rendervar(camera_grad=True)),
+                 the parameter gradients unchanged; with fused_adam the call keeps the unfused path (no pose-gradient form of that backward)."""
+    camera_grad = bool(tracking or do_ba)
+    cam_fusable = not camera_grad or fused_adam is None
+    if fused_preprocess and fused and cam_fusable:
+        cam = None
+        if camera_grad:
+            cam = (F.normalize(params["cam_unnorm_rots"][..., iter_time_idx]).reshape(4), params["cam_trans"][..., iter_time_idx].reshape(3))
+            if pose7 is None:
+                pose7 = torch.cat([cam[0].detach(), cam[1].detach()]).cpu().tolist()
+        elif pose7 is None:
             q = F.normalize(params["cam_unnorm_rots"][..., iter_time_idx].detach()).reshape(4)
             pose7 = torch.cat([q, params["cam_trans"][..., iter_time_idx].detach().reshape(3)]).cpu().tolist()
         m2d = torch.empty_like(params["means3D"], requires_grad=True)      # gradient carrier only (see fused_rendervar)
         # seen + the running max radius are written by the render's per-Gaussian kernel where the tensors allow it
         mx = variables["max_2D_radius"]
-        stats_in_render = fused_loss and use_l1 and not ignore_outlier_depth_loss and mx.dtype == torch.float32 and mx.is_contiguous() \
-            and mx.device == params["means3D"].device and mx.numel() == params["means3D"].shape[0]
+        stats_in_render = not tracking and fused_loss and use_l1 and not ignore_outlier_depth_loss and mx.dtype == torch.float32 \
+            and mx.is_contiguous() and mx.device == params["means3D"].device and mx.numel() == params["means3D"].shape[0]
         seen = torch.empty(mx.numel(), dtype=torch.bool, device=mx.device) if stats_in_render else None
         im, radius, depth, _sil, depth_sq = render_rgbd_raw(curr_data["cam"], params["means3D"], m2d, params["logit_opacities"],
                                                              params["log_scales"], params["unnorm_rotations"], pose7,
                                                              colors_precomp=None if "shs" in params else params["rgb_colors"],
                                                              shs=params.get("shs"), accumulate_grads=accumulate_grads, adam=fused_adam,
-                                                             visibility=(mx, seen) if stats_in_render else None)
+                                                             visibility=(mx, seen) if stats_in_render else None, camera=cam,
+                                                             gaussians_grad=not tracking)
         variables["means2D"] = m2d
-        if fused_loss and use_l1 and not ignore_outlier_depth_loss:
+        if fused_loss and use_l1 and not ignore_outlier_depth_loss and not tracking:
             loss, weighted = fused_mapping_loss(im, depth, depth_sq, curr_data["im"], curr_data["depth"], loss_weights)
             if stats_in_render:
                 variables["seen"] = seen
@@ -391,11 +447,11 @@ def get_loss(params, curr_data, variables, iter_time_idx, loss_weights, use_sil_
                 variables["seen"] = O.visibility_stats(radius, variables["max_2D_radius"])
             return loss, variables, weighted
         rendervar = None
-    elif fused_inputs and not do_ba:
+    elif fused_inputs and cam_fusable:
         tg = None
-        rendervar = fused_rendervar(params, iter_time_idx, pose7, accumulate_grads)
+        rendervar = fused_rendervar(params, iter_time_idx, pose7, accumulate_grads, camera_grad=camera_grad, gaussians_grad=not tracking)
     else:
-        tg = transform_to_frame(params, iter_time_idx, gaussians_grad=True, camera_grad=do_ba)
+        tg = transform_to_frame(params, iter_time_idx, gaussians_grad=not tracking, camera_grad=camera_grad)
         rendervar = transformed_params2rendervar(params, tg)
     if rendervar is not None:
         rendervar["means2D"].retain_grad()
@@ -405,15 +461,16 @@ def get_loss(params, curr_data, variables, iter_time_idx, loss_weights, use_sil_
         im, radius, depth, _sil, depth_sq = render_rgbd(curr_data["cam"], **rendervar)
     else:
         if tg is None:
-            tg = transform_to_frame(params, iter_time_idx, gaussians_grad=True, camera_grad=do_ba)
+            tg = transform_to_frame(params, iter_time_idx, gaussians_grad=not tracking, camera_grad=camera_grad)
         depth_sil_rendervar = transformed_params2depthplussilhouette(params, curr_data["w2c"], tg)
         im, radius, _, _ = Renderer(raster_settings=curr_data["cam"])(**rendervar)
         depth_sil, _, _, _ = Renderer(raster_settings=curr_data["cam"])(**depth_sil_rendervar)
         depth = depth_sil[0].unsqueeze(0)
+        _sil = depth_sil[1].unsqueeze(0)
         depth_sq = depth_sil[2].unsqueeze(0)
     if rendervar is not None:
         variables["means2D"] = rendervar["means2D"]      # densification reads the colour pass' gradient only
-    if fused_loss and use_l1 and not ignore_outlier_depth_loss:
+    if fused_loss and use_l1 and not ignore_outlier_depth_loss and not tracking:
         loss, weighted = fused_mapping_loss(im, depth, depth_sq, curr_data["im"], curr_data["depth"], loss_weights)
         from . import optim as O
         variables["seen"] = O.visibility_stats(radius, variables["max_2D_radius"])      # one launch: seen + max radius in place
@@ -423,11 +480,22 @@ def get_loss(params, curr_data, variables, iter_time_idx, loss_weights, use_sil_
     if ignore_outlier_depth_loss:
         err = (curr_data["depth"] - depth).abs() * mask
         mask = mask & (err < 10 * err.median())
-    mask = (mask & ~torch.isnan(depth) & ~torch.isnan(uncertainty)).detach()
+    mask = mask & ~torch.isnan(depth) & ~torch.isnan(uncertainty)
+    if tracking and use_sil_for_loss:
+        mask = mask & (_sil > sil_thres)                  # presence silhouette: pixels the map already explains
+    mask = mask.detach()
     losses = {}
     if use_l1:
-        losses["depth"] = (curr_data["depth"] - depth).abs()[mask].mean()
-    losses["im"] = 0.8 * l1_loss_v1(im, curr_data["im"]) + 0.2 * (1.0 - calc_ssim(im, curr_data["im"]))
+        if tracking:
+            losses["depth"] = (curr_data["depth"] - depth).abs()[mask].sum()
+        else:
+            losses["depth"] = (curr_data["depth"] - depth).abs()[mask].mean()
+    if tracking and (use_sil_for_loss or ignore_outlier_depth_loss):
+        losses["im"] = (curr_data["im"] - im).abs()[torch.tile(mask, (3, 1, 1))].sum()
+    elif tracking:
+        losses["im"] = (curr_data["im"] - im).abs().sum()
+    else:
+        losses["im"] = 0.8 * l1_loss_v1(im, curr_data["im"]) + 0.2 * (1.0 - calc_ssim(im, curr_data["im"]))
     weighted = {k: v * loss_weights[k] for k, v in losses.items()}
     loss = sum(weighted.values())
     seen = radius > 0

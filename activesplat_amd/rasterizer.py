@@ -150,9 +150,12 @@ class _RasterizeGaussians(torch.autograd.Function):
                  (= opacity) and depth^2 -- see render_rgbd()."""
 
     @staticmethod
-    def forward(ctx, means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, rs, fused=False, raw=None):
+    def forward(ctx, means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, rs, fused=False, raw=None,
+                cam_rot=None, cam_trans=None):
         """raw = (pose7, isotropic, accumulate): means3D / opacities / scales / rotations are the mapper's PARAMETERS (world-frame means, logit
-        opacities, log scales, unnormalised quaternions); frame transform + activations run inside the per-Gaussian kernels (render_rgbd_raw)."""
+        opacities, log scales, unnormalised quaternions); frame transform + activations run inside the per-Gaussian kernels (render_rgbd_raw).
+        cam_rot [4] / cam_trans [3] (raw only): device tensors whose VALUES are pose7; the backward returns dL/d of them (raw[5] False: of them
+        only -- the pose-only backward of tracking)."""
         lib = _lib.get()
         device = means3D.device
         leaves = (means3D, opacities, scales, rotations, colors_precomp)     # (raw + accumulate: the backward adds into these tensors' .grad)
@@ -177,7 +180,13 @@ class _RasterizeGaussians(torch.autograd.Function):
         radii = torch.empty(P, dtype=torch.int32, device=device)
         d_num = torch.empty(2, dtype=torch.int32, device=device)
         h_num = _host_counters(device, st_handle) if device.type == "cuda" else torch.zeros(2, dtype=torch.int32)
-        want_bwd = 1 if any(ctx.needs_input_grad[:8]) else 0
+        # camera-pose gradient (render_rgbd_raw(camera=...)): (pose_only, shape of cam_rot, shape of cam_trans)
+        pose_req = None
+        if raw is not None and cam_rot is not None and (cam_rot.requires_grad or cam_trans.requires_grad):
+            pose_req = (len(raw) > 5 and not raw[5], cam_rot.shape, cam_trans.shape)
+        ctx.pose_req = pose_req
+        ctx.cam_inputs = cam_rot is not None         # the backward then owes autograd two more entries (None when the camera is frozen)
+        want_bwd = 1 if any(ctx.needs_input_grad[:8]) or pose_req is not None else 0
         pose = None
         if raw is not None:
             pose = (C.c_float * 7)(*[float(v) for v in raw[0]])
@@ -196,7 +205,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         # the backward's gradient records: allocated now (when a backward can follow) so that the blend kernel of this
         # forward zero-fills them as a side job instead of a fill launch in front of the backward
         scratch = None
-        if any(ctx.needs_input_grad[:8]) and P > 0:
+        if want_bwd and P > 0:
             scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=device)
 
         def render(cap_d, cap_tile):
@@ -259,6 +268,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             # the optimiser step inside the backward kernel: it updates the caller's parameter tensors in place
             if raw[2]:
                 raise Exception("render_rgbd_raw: adam= and accumulate_grads= exclude each other")
+            if pose_req is not None:
+                raise Exception("render_rgbd_raw: adam= and a differentiable camera exclude each other (the library has no pose-gradient form of the "
+                                "backward with the optimiser step)")
             if not same or (shs is not None and shs is not shs_in):
                 raise Exception("render_rgbd_raw(adam=...): the parameters must be contiguous, 16-byte aligned fp32 tensors on the device (they are updated in place)")
             ctx.adam = (adam, leaves[:4] + (shs_in if shs_in is not None else leaves[4],))
@@ -278,6 +290,13 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_color, _gr=None, grad_depth=None, _go=None, _gq=None):
+        out = _RasterizeGaussians._backward(ctx, grad_color, grad_depth)
+        if getattr(ctx, "cam_inputs", False) and len(out) == 11:
+            out = out + (None, None)                     # camera tensors given but not differentiable (frozen pose)
+        return out
+
+    @staticmethod
+    def _backward(ctx, grad_color, grad_depth):
         lib = _lib.get()
         means3D, shs, colors, scales, rots, cov3Dp, radii, geom, point_list, image = ctx.saved_tensors
         has_sh, has_col, has_sc, has_rot, has_cov = ctx.has
@@ -326,6 +345,18 @@ class _RasterizeGaussians(torch.autograd.Function):
         d_sc = z(P, 3) if has_sc else None
         d_rot = z(P, 4) if has_rot else None
         d_cov = z(P, 6) if has_cov else None
+        pose_req = getattr(ctx, "pose_req", None)
+        if ctx.raw is not None and pose_req is not None and pose_req[0]:
+            # tracking: the pose gradient only -- no parameter gradient is formed (gs_render_backward_raw_pose, pose_only = 1)
+            pose, iso, _acc, logit = ctx.raw
+            d_pose = z(7)
+            pscr = torch.empty(int(lib.gs_pose_grad_scratch_bytes(P)), dtype=torch.uint8, device=device)
+            _lib.check(lib.gs_render_backward_raw_pose(
+                C.byref(cam), P, ctx.D, _ptr(means3D), _ptr(shs if has_sh else None), _ptr(colors if has_col else None), _ptr(logit),
+                _ptr(scales), _ptr(rots), pose, iso, 0, _ptr(radii), _ptr(geom), _ptr(point_list), _ptr(image), _ptr(grad_color),
+                _ptr(grad_depth), _ptr(d_m2d), None, None, None, None, None, None, _ptr(scratch), 1 if clean else 0, int(ctx.sh_jac), 1,
+                _ptr(d_pose), _ptr(pscr), _stream(device)))
+            return (None, d_m2d) + (None,) * 9 + (d_pose[:4].view(pose_req[1]), d_pose[4:].view(pose_req[2]))
         if ctx.raw is not None:
             pose, iso, accumulate, logit = ctx.raw
             d_sc = z(P, 1 if iso else 3)                  # (gradients w.r.t. the parameters: log scales are [P,1] for an isotropic map)
@@ -344,18 +375,26 @@ class _RasterizeGaussians(torch.autograd.Function):
                 d_m3d, d_op, d_sc, d_rot = into[0], into[1], into[2], into[3]
                 if has_col:
                     d_col = into[4]
-            _lib.check(lib.gs_render_backward_raw(
-                C.byref(cam), P, ctx.D, _ptr(means3D), _ptr(shs if has_sh else None), _ptr(colors if has_col else None), _ptr(logit),
-                _ptr(scales), _ptr(rots), pose, iso, acc, _ptr(radii), _ptr(geom), _ptr(point_list), _ptr(image), _ptr(grad_color),
-                _ptr(grad_depth), _ptr(d_m2d), _ptr(d_m3d), _ptr(d_op), _ptr(d_col), _ptr(d_shs), _ptr(d_sc), _ptr(d_rot),
-                _ptr(scratch), 1 if clean else 0, int(ctx.sh_jac), _stream(device)))
+            args = (C.byref(cam), P, ctx.D, _ptr(means3D), _ptr(shs if has_sh else None), _ptr(colors if has_col else None), _ptr(logit),
+                    _ptr(scales), _ptr(rots), pose, iso, acc, _ptr(radii), _ptr(geom), _ptr(point_list), _ptr(image), _ptr(grad_color),
+                    _ptr(grad_depth), _ptr(d_m2d), _ptr(d_m3d), _ptr(d_op), _ptr(d_col), _ptr(d_shs), _ptr(d_sc), _ptr(d_rot),
+                    _ptr(scratch), 1 if clean else 0, int(ctx.sh_jac))
+            tail = ()
+            if pose_req is not None:
+                # bundle adjustment: the same launch also reduces the camera-pose gradient (parameter gradients bit-identical to the plain call)
+                d_pose = z(7)
+                pscr = torch.empty(int(lib.gs_pose_grad_scratch_bytes(P)), dtype=torch.uint8, device=device)
+                _lib.check(lib.gs_render_backward_raw_pose(*args, 0, _ptr(d_pose), _ptr(pscr), _stream(device)))
+                tail = (d_pose[:4].view(pose_req[1]), d_pose[4:].view(pose_req[2]))
+            else:
+                _lib.check(lib.gs_render_backward_raw(*args, _stream(device)))
             if into is not None:
                 if not acc:
                     for x, t in zip(leaves, into):
                         if x is not None:
                             x.grad = t
-                return None, d_m2d, d_shs, None, None, None, None, None, None, None, None
-            return d_m3d, d_m2d, d_shs, d_col, d_op, d_sc, d_rot, None, None, None, None
+                return (None, d_m2d, d_shs, None, None, None, None, None, None, None, None) + tail
+            return (d_m3d, d_m2d, d_shs, d_col, d_op, d_sc, d_rot, None, None, None, None) + tail
         _lib.check(lib.gs_render_backward(
             C.byref(cam), P, ctx.D, _ptr(means3D), _ptr(shs if has_sh else None), _ptr(colors if has_col else None),
             _ptr(scales if has_sc else None), _ptr(rots if has_rot else None), _ptr(cov3Dp if has_cov else None),
@@ -449,7 +488,7 @@ def render_rgbd(raster_settings, means3D, means2D, opacities, shs=None, colors_p
 
 
 def render_rgbd_raw(raster_settings, means3D, means2D, logit_opacities, log_scales, unnorm_rotations, pose7, shs=None, colors_precomp=None,
-                    accumulate_grads=False, visibility=None, adam=None):
+                    accumulate_grads=False, visibility=None, adam=None, camera=None, gaussians_grad=True):
     """render_rgbd straight from the mapper's PARAMETERS: the frame transform + activations of transform_to_frame /
     transformed_params2rendervar (slam_helpers.py:252-304,124-139; `mapping.fused_rendervar` does them in two launches of their own) happen
     inside the per-Gaussian kernels of the rasteriser, forward and backward.  pose7 = host (qw,qx,qy,qz,tx,ty,tz) of the frame's relative
@@ -463,7 +502,15 @@ def render_rgbd_raw(raster_settings, means3D, means2D, logit_opacities, log_scal
     to parameters and moments IN PLACE (gs_render_backward_raw_adam; same arithmetic as optimizer.step(), bit for bit) and writes no
     gradient tensors -- the five tensors keep .grad = None, a following optimizer.step() skips them; means2D.grad is delivered as usual.
     Not for gradient accumulation over several keyframes, and not on iterations whose densify / prune event replaces the tensors between
-    backward and step (optim.densify_event)."""
+    backward and step (optim.densify_event).
+    camera = (cam_rot [4], cam_trans [3]) device tensors (tracking / bundle adjustment, transform_to_frame(camera_grad=True)): the pose of the
+    render -- cam_rot the NORMALISED camera quaternion (w,x,y,z), e.g. F.normalize(params['cam_unnorm_rots'][..., t]); torch differentiates that
+    normalisation -- and autograd returns dL/dcam_rot, dL/dcam_trans from the same backward launch (gs_render_backward_raw_pose; a deterministic
+    reduction, the parameter gradients bit-identical to the call without a camera).  dL/dcam_rot is the reference's: the rotation matrix
+    is taken as build_rotation(cam_rot) (which renormalises) and the Gaussians' rotations as quat_mult(cam_rot, .), so the gradient is right
+    for a unit-quaternion leaf passed as is as well as after F.normalize.  Camera tensors that do not require grad are a frozen pose (no pose
+    reduction runs).  pose7 = None reads the values from the two tensors (one small device-to-host copy).  gaussians_grad=False (tracking): the pose gradient only -- the backward forms no parameter gradient and the
+    Gaussian tensors (colours / SH rows included) receive none; means2D.grad and the visibility statistics are delivered as usual.  Not with adam=."""
     if (shs is None) == (colors_precomp is None):
         raise Exception("Please provide excatly one of either SHs or precomputed colors!")
     if shs is not None and int(shs.shape[1]) != 16:
@@ -475,8 +522,26 @@ def render_rgbd_raw(raster_settings, means3D, means2D, logit_opacities, log_scal
         if not (mx.dtype == torch.float32 and mx.is_contiguous() and mx.numel() == P and seen.dtype == torch.bool and seen.is_contiguous()
                 and seen.numel() == P and mx.device == means3D.device and seen.device == means3D.device):
             raise Exception("render_rgbd_raw: visibility = (float32 [P], bool [P]) contiguous tensors on the parameters' device")
+    if camera is None:
+        if not gaussians_grad:
+            raise Exception("render_rgbd_raw: gaussians_grad=False is the pose-only backward: it needs camera=(cam_rot, cam_trans)")
+        return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, None,
+                                         raster_settings, True, (pose7, iso, accumulate_grads, visibility, adam))
+    cam_rot, cam_trans = camera
+    if cam_rot.numel() != 4 or cam_trans.numel() != 3:
+        raise Exception("render_rgbd_raw: camera = (cam_rot with 4 values, cam_trans with 3)")
+    if adam is not None:
+        raise Exception("render_rgbd_raw: adam= and a differentiable camera exclude each other (the library has no pose-gradient form of the "
+                        "backward with the optimiser step)")
+    if pose7 is None:
+        pose7 = torch.cat([cam_rot.detach().reshape(4), cam_trans.detach().reshape(3)]).float().cpu().tolist()
+    if not gaussians_grad:
+        d = lambda t: None if t is None else t.detach()  # noqa: E731
+        means3D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations = (d(means3D), d(shs), d(colors_precomp), d(logit_opacities),
+                                                                                      d(log_scales), d(unnorm_rotations))
+        accumulate_grads = False
     return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, None,
-                                     raster_settings, True, (pose7, iso, accumulate_grads, visibility, adam))
+                                     raster_settings, True, (pose7, iso, accumulate_grads, visibility, None, gaussians_grad), cam_rot, cam_trans)
 
 
 class GaussianRasterizer(nn.Module):

@@ -181,7 +181,7 @@ const char* gs_version(void);
 /* Integer version of THIS binary interface: bumped whenever an entry point's argument list or a published record layout changes (e.g.
  * the seed argument of gs_densify_children, the 40-byte SH Jacobian record).  A host binding compares it with the GS_ABI_VERSION it was
  * written against before the first call, so that a stale prebuilt library fails at load time instead of misreading its arguments. */
-#define GS_ABI_VERSION 10
+#define GS_ABI_VERSION 11
 int32_t gs_abi_version(void);
 
 /* Optional per-stage timing (hipEvents recorded on the caller's stream around each stage's launches).
@@ -267,6 +267,25 @@ int gs_render_backward_raw(const GsCamera* cam, int32_t P, int64_t D, const floa
                            float* dL_dlogit_opacities, float* dL_dcolors_precomp, float* dL_dshs, float* dL_dlog_scales,
                            float* dL_dunnorm_rotations, void* scratch, int32_t scratch_zeroed, int32_t have_sh_jacobian, gs_stream_t stream);
 
+/* Camera-pose gradient (tracking / bundle adjustment: transform_to_frame(camera_grad=True), slam_helpers.py:252-304).  The same backward as
+ * gs_render_backward_raw, which also writes dL_dpose7[7] (DEVICE) = dL/d(qw,qx,qy,qz,tx,ty,tz) of the h_pose7 the call received: through the
+ * frame transform of every rendered Gaussian's mean and, for an anisotropic map, through q_cam (x) normalize(q) of its rotation.  The
+ * reduction is deterministic (per-workgroup rows in pose_scratch, gs_pose_grad_scratch_bytes(P) bytes, summed in a fixed order in fp64):
+ * two calls on the same inputs give the same bits, and the parameter gradients are bit-identical to gs_render_backward_raw's.
+ * The rotation part is the reference's (slam_helpers.py:252-304): the matrix as build_rotation(q) = R(q / |q|), the Gaussians' rotations as
+ * quat_mult(q, normalize(q_i)) -- the derivative of both as written, including build_rotation's normalisation.
+ * pose_only != 0 (tracking): no parameter gradient is formed -- the five dL_d* parameter outputs may be NULL and are not written,
+ * `accumulate` is ignored; dL_dmeans2D and the pose gradient are written as usual.  dL_dpose7 is always overwritten (never accumulated).
+ * There is no pose-gradient form of gs_render_backward_raw_adam. */
+uint64_t gs_pose_grad_scratch_bytes(int32_t P);
+int gs_render_backward_raw_pose(const GsCamera* cam, int32_t P, int64_t D, const float* means3D, const float* shs, const float* colors_precomp,
+                                const float* logit_opacities, const float* log_scales, const float* unnorm_rotations, const float* h_pose7,
+                                int32_t isotropic, int32_t accumulate, const int32_t* radii, const void* geom_state, const uint32_t* point_list,
+                                const void* image_state, const float* dL_dcolor, const float* dL_ddepth, float* dL_dmeans2D, float* dL_dmeans3D,
+                                float* dL_dlogit_opacities, float* dL_dcolors_precomp, float* dL_dshs, float* dL_dlog_scales,
+                                float* dL_dunnorm_rotations, void* scratch, int32_t scratch_zeroed, int32_t have_sh_jacobian, int32_t pose_only,
+                                float* dL_dpose7, void* pose_scratch, gs_stream_t stream);
+
 /* Fused dense Adam step over one flat parameter tensor with torch.optim.Adam semantics
  * (non-amsgrad, no weight decay): splatam.py:118-124 uses betas (0.9,0.999), eps 1e-15.
  * `step` is the 1-based step count of this tensor AFTER the increment.  Hyper-parameters are doubles (as the
@@ -345,6 +364,16 @@ int gs_activate_backward_accumulate(int32_t P, int32_t isotropic, const float* h
                                     const float* out_opacities, const float* out_scales, const float* g_means3D, const float* g_rotations,
                                     const float* g_opacities, const float* g_scales, float* d_means3D, float* d_unnorm_rotations,
                                     float* d_logit_opacities, float* d_log_scales, gs_stream_t stream);
+
+/* gs_activate_backward / _accumulate (accumulate != 0) with the camera-pose gradient: dL_dpose7[7] (DEVICE) as for gs_render_backward_raw_pose,
+ * from g_means3D / g_rotations and the world-frame means3D; pose_scratch = gs_pose_grad_scratch_bytes(P) bytes.  pose_only != 0: only the pose
+ * gradient (out_opacities, out_scales and the four d_* may be NULL).  A row whose g_means3D and g_rotations are all zero (a Gaussian the
+ * rasteriser did not render) adds nothing, whatever its parameters hold. */
+int gs_activate_backward_pose(int32_t P, int32_t isotropic, const float* h_pose7, const float* means3D, const float* unnorm_rotations,
+                              const float* out_opacities, const float* out_scales, const float* g_means3D, const float* g_rotations,
+                              const float* g_opacities, const float* g_scales, float* d_means3D, float* d_unnorm_rotations,
+                              float* d_logit_opacities, float* d_log_scales, int32_t accumulate, int32_t pose_only, float* dL_dpose7,
+                              void* pose_scratch, gs_stream_t stream);
 
 /* Fused mapping loss, forward AND backward (replaces src/mapper/splatam/splatam.py:213-249 + the SSIM of
  * utils/slam_external.py:54-97 and their autograd):
