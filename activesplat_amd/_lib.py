@@ -54,7 +54,7 @@ SORT_AUTO, SORT_TILE_LDS, SORT_RADIX = 0, 1, 2
 
 # every symbol include/gsplat_hip.h declares (tests check the library exports all of them)
 #: the GS_ABI_VERSION of include/gsplat_hip.h this binding was written against (checked when a library is bound)
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 SYMBOLS = ("gs_abi_version", "gs_geom_layout", "gs_image_layout", "gs_bin_layout", "gs_backward_scratch_bytes", "gs_last_error",
            "gs_version", "gs_set_sort_path", "gs_set_forward_segments", "gs_set_half_quadrants", "gs_set_backward_chain", "gs_set_backward_chain_tickets", "gs_set_backward_chain_polls", "gs_async_status_word", "gs_async_status_clear", "gs_recorded_cut", "gs_set_backward_segments", "gs_preprocess_forward", "gs_preprocess_forward_raw", "gs_render_forward", "gs_render_backward", "gs_render_backward_raw", "gs_render_backward_raw_adam", "gs_adam_step", "gs_adam_step_multi",
@@ -63,7 +63,9 @@ SYMBOLS = ("gs_abi_version", "gs_geom_layout", "gs_image_layout", "gs_bin_layout
            "gs_grow_scratch_bytes", "gs_grow_gaussians", "gs_keyframe_overlap", "gs_visibility_stats", "gs_accumulate_grad2d",
            "gs_gather_rows_zero_tail", "gs_densify_classify", "gs_densify_children", "gs_atlas_layout",
            "gs_pack_columns", "gs_adam_rows", "gs_unpack_columns", "gs_compact3_scratch_bytes", "gs_compact_index3",
-           "gs_pose_grad_scratch_bytes", "gs_render_backward_raw_pose", "gs_activate_backward_pose")
+           "gs_pose_grad_scratch_bytes", "gs_render_backward_raw_pose", "gs_activate_backward_pose",
+           "gs_tracking_loss_scratch_bytes", "gs_tracking_loss", "gs_preprocess_forward_raw_dev", "gs_render_backward_raw_pose_dev",
+           "gs_tracking_state_bytes", "gs_tracking_begin", "gs_tracking_step")
 
 
 def _bind(lib):
@@ -123,6 +125,25 @@ def _bind(lib):
     lib.gs_render_backward_raw_pose.argtypes = [C.POINTER(GsCamera), i32, i64] + [vp] * 6 + [vp, i32, i32] + [vp] * 4 + [vp] * 2 + [vp] * 7 + \
         [vp, i32, i32, i32, vp, vp, vp]
     lib.gs_render_backward_raw_pose.restype = C.c_int
+    # tracking: (cam, P, means3D, shs, colors, logit, log_scales, unnorm_rot, cam_unnorm_rots, cam_trans, num_frames, time_idx, isotropic,
+    #  max_2D_radius, seen, radii, geom, image, d_counts, h_counts, want_backward, stream)
+    lib.gs_preprocess_forward_raw_dev.argtypes = [C.POINTER(GsCamera), i32] + [vp] * 6 + [vp, vp, i64, i64, i32] + [vp] * 7 + [i32, vp]
+    lib.gs_preprocess_forward_raw_dev.restype = C.c_int
+    # (cam, P, D, means3D, shs, colors, logit, log_scales, unnorm_rot, cam_unnorm_rots, cam_trans, num_frames, time_idx, isotropic, radii, geom,
+    #  point_list, image, dL_dcolor, dL_ddepth, dL_dmeans2D, scratch, scratch_zeroed, have_sh_jacobian, dL_dpose7, pose_scratch, stream)
+    lib.gs_render_backward_raw_pose_dev.argtypes = [C.POINTER(GsCamera), i32, i64] + [vp] * 6 + [vp, vp, i64, i64, i32] + [vp] * 7 + \
+        [vp, i32, i32, vp, vp, vp]
+    lib.gs_render_backward_raw_pose_dev.restype = C.c_int
+    lib.gs_tracking_loss_scratch_bytes.argtypes = [i32, i32]
+    lib.gs_tracking_loss_scratch_bytes.restype = C.c_uint64
+    lib.gs_tracking_loss.argtypes = [i32, i32] + [vp] * 6 + [i32, f32, f32, f32] + [vp] * 4 + [vp]
+    lib.gs_tracking_loss.restype = C.c_int
+    lib.gs_tracking_state_bytes.argtypes = []
+    lib.gs_tracking_state_bytes.restype = C.c_uint64
+    lib.gs_tracking_begin.argtypes = [vp, vp, i64, i64, vp, vp]
+    lib.gs_tracking_begin.restype = C.c_int
+    lib.gs_tracking_step.argtypes = [i32, vp, i32, i32, vp, f32, f32, vp, vp, i64, i64, C.c_double, C.c_double, i32, vp, vp, vp]
+    lib.gs_tracking_step.restype = C.c_int
     lib.gs_pose_grad_scratch_bytes.argtypes = [i32]
     lib.gs_pose_grad_scratch_bytes.restype = C.c_uint64
     lib.gs_preprocess_forward_raw.restype = C.c_int

@@ -136,40 +136,94 @@ pose_reduce:
     if (POSE != 0) pose_grad_block_row(pacc, pose_rows + (size_t)blockIdx.x * kPoseAcc);
 }
 
-// Final pass of the camera-pose gradient: the per-workgroup rows summed in fp64 in a fixed order (thread t adds column t % 16 of rows
-// t / 16, t / 16 + 16, ...; then the 16 slices in order), dL/dR turned into dL/dq_cam through build_rotation's normalisation and quat_to_rot's
-// formula and added to the rotation term; out = dL/d(qw,qx,qy,qz,tx,ty,tz) of the pose7 the launch received.  One workgroup: the same numbers on every run.
+// Final pass of the camera-pose gradient (pose_grad_finish_block, gs_common.h): out = dL/d(qw,qx,qy,qz,tx,ty,tz) of the pose7 the launch received.
+// One workgroup: the same numbers on every run.
 __global__ __launch_bounds__(kBlock) void pose_grad_finish_kernel(int64_t nrows, Pose pose, const float* __restrict__ rows, float* __restrict__ out)
 {
-    constexpr int kSlices = kBlock / kPoseAcc;
-    __shared__ double s[kSlices][kPoseAcc];
-    const int c = threadIdx.x % kPoseAcc, sl = threadIdx.x / kPoseAcc;
-    double acc = 0.0;
-    for (int64_t r = sl; r < nrows; r += kSlices) acc += (double)rows[r * kPoseAcc + c];
-    s[sl][c] = acc;
+    pose_grad_finish_block(nrows, pose, rows, out);
+}
+
+// The same with the pose read from the device column (the device-pose backward, gs_render_backward_raw_pose_dev): dL/d of the normalised column.
+__global__ __launch_bounds__(kBlock) void pose_grad_finish_dev_kernel(int64_t nrows, const float* __restrict__ dev_q, int64_t stride,
+                                                                      const float* __restrict__ rows, float* __restrict__ out)
+{
+    Pose p;
+    float n;
+    normalize_pose_column(dev_q, stride, p.q, n);
+    pose_grad_finish_block(nrows, p, rows, out);
+}
+
+// ---- tracking (SplaTAM's per-frame pose optimisation, torch.optim.Adam on cam_unnorm_rots[..., t] / cam_trans[..., t]) ----
+// state (kTrackState floats, gs_tracking_state_bytes): [0,7) first moments, [7,14) second moments, [14] the smallest loss so far, [15,22) the
+// candidate pose (the column after the step of that iteration), [22,25) the last iteration's {loss, depth, im}, [25] steps skipped
+__global__ void tracking_begin_kernel(const float* __restrict__ rots_col, const float* __restrict__ trans_col, int64_t stride,
+                                      float* __restrict__ state)
+{
+    const int k = threadIdx.x;
+    if (k >= kTrackState) return;
+    float v = 0.f;
+    if (k == 14) v = 1e20f;                                        // SplaTAM's current_min_loss = float(1e20)
+    else if (k >= 15 && k < 19) v = rots_col[(k - 15) * stride];  // the candidate starts as the initial pose
+    else if (k >= 19 && k < 22) v = trans_col[(k - 19) * stride];
+    state[k] = v;
+}
+
+// One tracking iteration's tail, one workgroup, after the pose-only backward: (1) the loss rows reduced in fp64 in a fixed order, (2) the pose
+// rows reduced exactly as pose_grad_finish_kernel reduces them, at the normalised column, then taken through F.normalize's Jacobian at the
+// unnormalised column (dL/dcam_unnorm_rots[..., t] as autograd delivers it), (3) torch.optim.Adam's step on the 7 values in place (torch's fp32
+// operation order of the foreach path; skipped, with the candidate, while a chained backward in front has failed -- Cam::chain_fail), (4) the
+// best candidate: loss < min_loss (strict: the first minimum wins, a NaN never does) -> min_loss = loss, candidate = the column AFTER this step,
+// (5) the last losses and, if asked, a history row {loss, depth, im, 7 post-step values}.
+__global__ __launch_bounds__(kBlock) void tracking_step_kernel(int64_t pose_nrows, const float* __restrict__ pose_rows, int64_t loss_nrows,
+                                                               const float* __restrict__ loss_rows, float w_im, float w_depth,
+                                                               float* __restrict__ rots_col, float* __restrict__ trans_col, int64_t stride,
+                                                               TrackAdam c, float* __restrict__ state, float* __restrict__ history_row,
+                                                               const uint32_t* __restrict__ fail)
+{
+    float L[3];
+    tracking_loss_reduce(loss_nrows, loss_rows, w_im, w_depth, L);       // (all threads; thread 0 comes back with L)
     __syncthreads();
+    Pose pu;                                                             // the normalised column (the pose the rows were formed at)
+    float norm;
+    normalize_pose_column(rots_col, stride, pu.q, norm);
+    const float* u = pu.q;
+    float g[7];
+    pose_grad_finish_block(pose_nrows, pu, pose_rows, g);                 // (all threads; thread 0 comes back with g)
     if (threadIdx.x != 0) return;
-    double t[kPoseAcc];
-    for (int k = 0; k < kPoseAcc; k++) {
-        double v = 0.0;
-        for (int j = 0; j < kSlices; j++) v += s[j][k];
-        t[k] = v;
+    // F.normalize backward: x / max(|x|, eps) -> dL/dx = (g - u (u . g)) / |x|  (|x| below eps: the clamp passes g / eps)
+    const double n = norm, ug = (double)u[0] * g[0] + (double)u[1] * g[1] + (double)u[2] * g[2] + (double)u[3] * g[3];
+    float grad[7];
+    for (int k = 0; k < 4; k++) grad[k] = n >= 1e-12 ? (float)((g[k] - (double)u[k] * ug) / n) : (float)((double)g[k] / 1e-12);
+    for (int k = 4; k < 7; k++) grad[k] = g[k];
+    float p[7];
+    for (int k = 0; k < 4; k++) p[k] = rots_col[k * stride];
+    for (int k = 0; k < 3; k++) p[4 + k] = trans_col[k * stride];
+    const bool skip = chain_failed(fail);
+    if (!skip) {
+#pragma clang fp contract(off)
+        for (int k = 0; k < 7; k++) {
+            float m = state[k], v = state[7 + k];
+            m = m + c.one_m_b1 * (grad[k] - m);                          // exp_avg.lerp_(grad, 1 - beta1)
+            v = v * c.b2;                                                 // exp_avg_sq.mul_(beta2)
+            v = v + c.one_m_b2 * (grad[k] * grad[k]);                     //           .addcmul_(grad, grad, 1 - beta2)
+            const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;            // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
+            p[k] = p[k] + c.neg_step_size[k < 4 ? 0 : 1] * (m / denom);  // param.addcdiv_(exp_avg, denom, -lr / bias_correction1)
+            state[k] = m; state[7 + k] = v;
+        }
+        for (int k = 0; k < 4; k++) rots_col[k * stride] = p[k];
+        for (int k = 0; k < 3; k++) trans_col[k * stride] = p[4 + k];
+        if (L[0] < state[14]) {
+            state[14] = L[0];
+            for (int k = 0; k < 7; k++) state[15 + k] = p[k];
+        }
+    } else {
+        state[25] = state[25] + 1.f;
     }
-    const double* dR = t + 3;            // row-major dL/dR
-    // the reference builds the matrix as build_rotation(q) = R(q / |q|) (slam_external.py:25-42): dL/dR reaches q through quat_to_rot at the unit
-    // quaternion AND that normalisation -- (I - u u^T) / |q| -- so the result is the reference's dL/dq for any q the caller chains it into
-    // (a unit leaf passed as is included), not only after a further F.normalize.  (The rotation term is taken as quat_mult(q, .) takes it: as is.)
-    const double q0 = pose.q[0], q1 = pose.q[1], q2 = pose.q[2], q3 = pose.q[3];
-    const double nq = sqrt(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
-    const double r = q0 / nq, x = q1 / nq, y = q2 / nq, z = q3 / nq;
-    const double d0 = 2.0 * (-z * dR[1] + y * dR[2] + z * dR[3] - x * dR[5] - y * dR[6] + x * dR[7]);
-    const double d1 = 2.0 * (y * dR[1] + z * dR[2] + y * dR[3] - 2.0 * x * dR[4] - r * dR[5] + z * dR[6] + r * dR[7] - 2.0 * x * dR[8]);
-    const double d2 = 2.0 * (-2.0 * y * dR[0] + x * dR[1] + r * dR[2] + x * dR[3] + z * dR[5] - r * dR[6] + z * dR[7] - 2.0 * y * dR[8]);
-    const double d3 = 2.0 * (-2.0 * z * dR[0] - r * dR[1] + x * dR[2] + r * dR[3] - 2.0 * z * dR[4] + y * dR[5] + x * dR[6] + y * dR[7]);
-    const double dot = r * d0 + x * d1 + y * d2 + z * d3;
-    out[0] = (float)((d0 - r * dot) / nq + t[12]); out[1] = (float)((d1 - x * dot) / nq + t[13]);
-    out[2] = (float)((d2 - y * dot) / nq + t[14]); out[3] = (float)((d3 - z * dot) / nq + t[15]);
-    out[4] = (float)t[0]; out[5] = (float)t[1]; out[6] = (float)t[2];
+    state[22] = L[0]; state[23] = L[1]; state[24] = L[2];
+    if (history_row) {
+        for (int k = 0; k < 3; k++) history_row[k] = L[k];
+        for (int k = 0; k < 7; k++) history_row[3 + k] = p[k];
+    }
 }
 
 hipError_t launch_activate_forward(int P, int iso, const float* pose7, const float* means3D, const float* rots, const float* logit_op,
@@ -211,6 +265,27 @@ hipError_t launch_activate_backward_pose(int P, int iso, const float* pose7, con
     else if (nb > 0 && accumulate) GS_ABWD_POSE(true, 1);
     else if (nb > 0) GS_ABWD_POSE(false, 1);
 #undef GS_ABWD_POSE
+    return hipGetLastError();
+}
+
+hipError_t launch_pose_grad_finish_dev(int64_t nrows, const float* dev_q, int64_t stride, const float* pose_rows, float* dpose7, hipStream_t st)
+{
+    hipLaunchKernelGGL(pose_grad_finish_dev_kernel, dim3(1), dim3(kBlock), 0, st, nrows, dev_q, stride, pose_rows, dpose7);
+    return hipGetLastError();
+}
+
+hipError_t launch_tracking_begin(const float* rots_col, const float* trans_col, int64_t stride, float* state, hipStream_t st)
+{
+    hipLaunchKernelGGL(tracking_begin_kernel, dim3(1), dim3(kTrackState), 0, st, rots_col, trans_col, stride, state);
+    return hipGetLastError();
+}
+
+hipError_t launch_tracking_step(int64_t pose_nrows, const float* pose_rows, int64_t loss_nrows, const float* loss_rows, float w_im, float w_depth,
+                                float* rots_col, float* trans_col, int64_t stride, const TrackAdam& c, float* state, float* history_row,
+                                hipStream_t st)
+{
+    hipLaunchKernelGGL(tracking_step_kernel, dim3(1), dim3(kBlock), 0, st, pose_nrows, pose_rows, loss_nrows, loss_rows, w_im, w_depth,
+                       rots_col, trans_col, stride, c, state, history_row, (const uint32_t*)chain_fail_word());
     return hipGetLastError();
 }
 

@@ -331,11 +331,29 @@ static bool set_input_activation(gs::Cam& k, const float* h_pose7, int32_t isotr
     return k.V == 1;
 }
 
+// the device-resident pose of the tracking entry points (gs::CamDP)
+struct DevPose { const float* q; const float* t; int64_t stride; };
+
+static bool dev_pose(const float* cam_unnorm_rots, const float* cam_trans, int64_t num_frames, int64_t time_idx, DevPose& dp)
+{
+    if (!cam_unnorm_rots || !cam_trans || num_frames < 1 || time_idx < 0 || time_idx >= num_frames) return false;
+    dp.q = cam_unnorm_rots + time_idx; dp.t = cam_trans + time_idx; dp.stride = num_frames;
+    return true;
+}
+
+static gs::CamDP with_dev_pose(const gs::Cam& k, const DevPose& dp)
+{
+    gs::CamDP kd;
+    static_cast<gs::Cam&>(kd) = k;
+    kd.dev_q = dp.q; kd.dev_t = dp.t; kd.stride = dp.stride;
+    return kd;
+}
+
 static int preprocess_forward_impl(const GsCamera* cam, int32_t P, const float* means3D, const float* shs,
                                    const float* colors_precomp, const float* opacities, const float* scales,
                                    const float* rotations, const float* cov3D_precomp, int32_t* radii, void* geom_state,
                                    void* image_state, uint32_t* d_counts, uint32_t* h_counts, int32_t want_backward, gs_stream_t stream,
-                                   const float* h_pose7, int32_t isotropic, float* max_2D_radius, uint8_t* seen)
+                                   const float* h_pose7, int32_t isotropic, float* max_2D_radius, uint8_t* seen, const DevPose* dp = nullptr)
 {
     gs::Cam k;
     if (!make_cam(cam, k)) return fail(GS_EINVAL, "gs_preprocess_forward: invalid camera settings");
@@ -362,8 +380,11 @@ static int preprocess_forward_impl(const GsCamera* cam, int32_t P, const float* 
     hipError_t e;
     {
         ScopedStage ps(ST_PREPROCESS, st);
-        e = gs::launch_preprocess_forward(k, P, means3D, shs, colors_precomp, opacities, scales, rotations,
-                                          cov3D_precomp, radii, gp, d_counts, st);
+        if (dp)
+            e = gs::launch_preprocess_forward_dev(with_dev_pose(k, *dp), P, means3D, shs, colors_precomp, opacities, scales, rotations, radii, gp, st);
+        else
+            e = gs::launch_preprocess_forward(k, P, means3D, shs, colors_precomp, opacities, scales, rotations,
+                                              cov3D_precomp, radii, gp, d_counts, st);
     }
     if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_preprocess_forward: %s", hipGetErrorString(e));
     bool mirrored = false;
@@ -407,6 +428,20 @@ int gs_preprocess_forward_raw(const GsCamera* cam, int32_t P, const float* means
                                    geom_state, image_state, d_counts, h_counts, want_backward, stream, h_pose7, isotropic, max_2D_radius, seen);
 }
 
+int gs_preprocess_forward_raw_dev(const GsCamera* cam, int32_t P, const float* means3D, const float* shs, const float* colors_precomp,
+                                  const float* logit_opacities, const float* log_scales, const float* unnorm_rotations,
+                                  const float* cam_unnorm_rots, const float* cam_trans, int64_t num_frames, int64_t time_idx, int32_t isotropic,
+                                  float* max_2D_radius, uint8_t* seen, int32_t* radii, void* geom_state, void* image_state, uint32_t* d_counts,
+                                  uint32_t* h_counts, int32_t want_backward, gs_stream_t stream)
+{
+    DevPose dp;
+    if (!dev_pose(cam_unnorm_rots, cam_trans, num_frames, time_idx, dp))
+        return fail(GS_EINVAL, "gs_preprocess_forward_raw_dev: null pose columns or time index outside [0, num_frames)");
+    if (P > 0 && (!log_scales || !unnorm_rotations)) return fail(GS_EINVAL, "gs_preprocess_forward_raw_dev: null scale / rotation parameters");
+    const float ident[7] = {1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};          // (sets the raw-parameter mode; the kernels read the pose themselves)
+    return preprocess_forward_impl(cam, P, means3D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, nullptr, radii,
+                                   geom_state, image_state, d_counts, h_counts, want_backward, stream, ident, isotropic, max_2D_radius, seen, &dp);
+}
 
 int gs_render_forward(const GsCamera* cam, int32_t P, int64_t D, uint32_t max_tile_instances, void* geom_state,
                       void* bin_state, uint32_t* point_list, void* image_state, float* out_color, float* out_depth,
@@ -481,7 +516,7 @@ static int render_backward_impl(const GsCamera* cam, int32_t P, int64_t D, const
                                 float* dL_dshs, float* dL_dscales, float* dL_drotations, float* dL_dcov3D, void* scratch,
                                 int32_t scratch_zeroed, int32_t have_sh_jacobian, gs_stream_t stream, const float* logit,
                                 const float* h_pose7, int32_t isotropic, int32_t accumulate, const GsAdamTensor* adam5 = nullptr,
-                                int32_t pose_mode = 0, float* dL_dpose7 = nullptr, void* pose_scratch = nullptr)
+                                int32_t pose_mode = 0, float* dL_dpose7 = nullptr, void* pose_scratch = nullptr, const DevPose* dp = nullptr)
 {
     gs::Cam k;
     if (!make_cam(cam, k)) return fail(GS_EINVAL, "gs_render_backward: invalid camera settings");
@@ -491,10 +526,11 @@ static int render_backward_impl(const GsCamera* cam, int32_t P, int64_t D, const
     if (k.V > 1) return fail(GS_EINVAL, "gs_render_backward: multi-view atlas renders are forward-only");
     if (P < 0 || D < 0 || !geom_state || !image_state || !dL_dcolor || !scratch)
         return fail(GS_EINVAL, "gs_render_backward: null pointer");
-    if (pose_mode && (!k.act || adam5 || !dL_dpose7 || !pose_scratch))
+    if (pose_mode && (!k.act || adam5 || (!dL_dpose7 && !dp) || !pose_scratch))
         return fail(GS_EINVAL, "gs_render_backward_raw_pose: raw-parameter mode with a pose-gradient output and its scratch only");
+    if (dp && pose_mode != 2) return fail(GS_EINVAL, "gs_render_backward_raw_pose_dev: the pose-only backward only");
     if (P == 0) {
-        if (pose_mode) {
+        if (pose_mode && dL_dpose7) {
             const hipError_t e0 = hipMemsetAsync(dL_dpose7, 0, 7 * sizeof(float), (hipStream_t)stream);
             if (e0 != hipSuccess) return fail(GS_ELAUNCH, "gs_render_backward_raw_pose: memset %s", hipGetErrorString(e0));
         }
@@ -547,12 +583,22 @@ static int render_backward_impl(const GsCamera* cam, int32_t P, int64_t D, const
     }
     {
         ScopedStage ps(ST_PREPROCESS_BWD, st);
-        e = gs::launch_preprocess_backward(k, P, means3D, shs, scales, rotations, cov3D_precomp, radii, gp.clamped, (shs && have_sh_jacobian) ? gp.sh_jac : nullptr, grad2d,
-                                           dL_dmeans2D, dL_dmeans3D, dL_dopacities, dL_dcolors_precomp, dL_dshs, dL_dscales,
-                                           dL_drotations, dL_dcov3D, logit, adam5 ? &fa : nullptr, st, pose_mode, (float*)pose_scratch);
+        if (dp)
+            e = gs::launch_preprocess_backward_pose_dev(with_dev_pose(k, *dp), P, means3D, shs, scales, rotations, radii, gp.clamped,
+                                                        (shs && have_sh_jacobian) ? gp.sh_jac : nullptr, grad2d, dL_dmeans2D, logit,
+                                                        (float*)pose_scratch, st);
+        else
+            e = gs::launch_preprocess_backward(k, P, means3D, shs, scales, rotations, cov3D_precomp, radii, gp.clamped, (shs && have_sh_jacobian) ? gp.sh_jac : nullptr, grad2d,
+                                               dL_dmeans2D, dL_dmeans3D, dL_dopacities, dL_dcolors_precomp, dL_dshs, dL_dscales,
+                                               dL_drotations, dL_dcov3D, logit, adam5 ? &fa : nullptr, st, pose_mode, (float*)pose_scratch);
     }
     if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_backward: preprocess %s", hipGetErrorString(e));
-    if (pose_mode) {
+    if (dp) {
+        if (dL_dpose7) {
+            e = gs::launch_pose_grad_finish_dev(gs::pose_rows_count(P), dp->q, dp->stride, (const float*)pose_scratch, dL_dpose7, st);
+            if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_backward_raw_pose_dev: pose reduction %s", hipGetErrorString(e));
+        }
+    } else if (pose_mode) {
         e = gs::launch_pose_grad_finish(gs::pose_rows_count(P), h_pose7, (const float*)pose_scratch, dL_dpose7, st);
         if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_backward_raw_pose: pose reduction %s", hipGetErrorString(e));
     }
@@ -602,6 +648,78 @@ int gs_render_backward_raw_pose(const GsCamera* cam, int32_t P, int64_t D, const
                                 image_state, dL_dcolor, dL_ddepth, dL_dmeans2D, dL_dmeans3D, dL_dlogit_opacities, dL_dcolors_precomp, dL_dshs,
                                 dL_dlog_scales, dL_dunnorm_rotations, nullptr, scratch, scratch_zeroed, have_sh_jacobian, stream,
                                 logit_opacities, h_pose7, isotropic, pose_only ? 0 : accumulate, nullptr, pose_only ? 2 : 1, dL_dpose7, pose_scratch);
+}
+
+int gs_render_backward_raw_pose_dev(const GsCamera* cam, int32_t P, int64_t D, const float* means3D, const float* shs, const float* colors_precomp,
+                                    const float* logit_opacities, const float* log_scales, const float* unnorm_rotations,
+                                    const float* cam_unnorm_rots, const float* cam_trans, int64_t num_frames, int64_t time_idx, int32_t isotropic,
+                                    const int32_t* radii, const void* geom_state, const uint32_t* point_list, const void* image_state,
+                                    const float* dL_dcolor, const float* dL_ddepth, float* dL_dmeans2D, void* scratch, int32_t scratch_zeroed,
+                                    int32_t have_sh_jacobian, float* dL_dpose7, void* pose_scratch, gs_stream_t stream)
+{
+    DevPose dp;
+    if (!dev_pose(cam_unnorm_rots, cam_trans, num_frames, time_idx, dp))
+        return fail(GS_EINVAL, "gs_render_backward_raw_pose_dev: null pose columns or time index outside [0, num_frames)");
+    if (P > 0 && !logit_opacities) return fail(GS_EINVAL, "gs_render_backward_raw_pose_dev: null opacity parameters");
+    if (!pose_scratch) return fail(GS_EINVAL, "gs_render_backward_raw_pose_dev: null pose scratch");
+    const float ident[7] = {1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    return render_backward_impl(cam, P, D, means3D, shs, colors_precomp, log_scales, unnorm_rotations, nullptr, radii, geom_state, point_list,
+                                image_state, dL_dcolor, dL_ddepth, dL_dmeans2D, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                scratch, scratch_zeroed, have_sh_jacobian, stream, logit_opacities, ident, isotropic, 0, nullptr, 2, dL_dpose7,
+                                pose_scratch, &dp);
+}
+
+uint64_t gs_tracking_loss_scratch_bytes(int32_t width, int32_t height)
+{
+    const int64_t n = (int64_t)(width > 0 ? width : 1) * (height > 0 ? height : 1);
+    return align_up((uint64_t)gs::tracking_loss_rows(n) * gs::kTrackRow * 4);
+}
+
+int gs_tracking_loss(int32_t width, int32_t height, const float* im, const float* gt_im, const float* depth, const float* depth_sq,
+                     const float* gt_depth, const float* silhouette, int32_t use_sil_for_loss, float sil_thres, float w_im, float w_depth,
+                     float* dL_dim, float* dL_ddepth, void* loss_rows, float* losses, gs_stream_t stream)
+{
+    if (width <= 0 || height <= 0 || (int64_t)width * height >= ((int64_t)1 << 31)) return fail(GS_EINVAL, "gs_tracking_loss: bad image size");
+    if (!im || !gt_im || !depth || !depth_sq || !gt_depth || !dL_dim || !dL_ddepth || !loss_rows || (use_sil_for_loss && !silhouette))
+        return fail(GS_EINVAL, "gs_tracking_loss: null pointer");
+    const hipError_t e = gs::launch_tracking_loss(width, height, im, gt_im, depth, depth_sq, gt_depth, silhouette, use_sil_for_loss != 0, sil_thres,
+                                                  w_im, w_depth, dL_dim, dL_ddepth, (float*)loss_rows, losses, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_tracking_loss: %s", hipGetErrorString(e));
+    return GS_OK;
+}
+
+uint64_t gs_tracking_state_bytes(void) { return align_up((uint64_t)gs::kTrackState * 4); }
+
+int gs_tracking_begin(const float* cam_unnorm_rots, const float* cam_trans, int64_t num_frames, int64_t time_idx, void* state, gs_stream_t stream)
+{
+    DevPose dp;
+    if (!dev_pose(cam_unnorm_rots, cam_trans, num_frames, time_idx, dp) || !state)
+        return fail(GS_EINVAL, "gs_tracking_begin: null pointer or time index outside [0, num_frames)");
+    const hipError_t e = gs::launch_tracking_begin(dp.q, dp.t, dp.stride, (float*)state, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_tracking_begin: %s", hipGetErrorString(e));
+    return GS_OK;
+}
+
+int gs_tracking_step(int32_t P, const void* pose_scratch, int32_t width, int32_t height, const void* loss_rows, float w_im, float w_depth,
+                     float* cam_unnorm_rots, float* cam_trans, int64_t num_frames, int64_t time_idx, double lr_rot, double lr_trans, int32_t step,
+                     void* state, float* history_row, gs_stream_t stream)
+{
+    DevPose dp;
+    if (!dev_pose(cam_unnorm_rots, cam_trans, num_frames, time_idx, dp) || !state || !loss_rows || (P > 0 && !pose_scratch))
+        return fail(GS_EINVAL, "gs_tracking_step: null pointer or time index outside [0, num_frames)");
+    if (P < 0 || width <= 0 || height <= 0 || step < 1) return fail(GS_EINVAL, "gs_tracking_step: bad size or step (the first step is 1)");
+    // torch.optim.Adam (splatam.py:118-124, tracking=True): betas (0.9, 0.999), eps 1e-8; bias corrections of step `step` in double, as torch forms
+    // them for its python-number step counts, handed to the kernel as the fp32 scalars its foreach kernels take
+    const double b1 = 0.9, b2 = 0.999, bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
+    gs::TrackAdam c;
+    c.one_m_b1 = (float)(1.0 - b1); c.b2 = (float)b2; c.one_m_b2 = (float)(1.0 - b2); c.bc2_sqrt = (float)pow(bc2, 0.5); c.eps = (float)1e-8;
+    c.neg_step_size[0] = (float)(-(lr_rot / bc1)); c.neg_step_size[1] = (float)(-(lr_trans / bc1));
+    const int64_t npix = (int64_t)width * height;
+    const hipError_t e = gs::launch_tracking_step(gs::pose_rows_count(P), (const float*)pose_scratch, gs::tracking_loss_rows(npix), (const float*)loss_rows,
+                                                  w_im, w_depth, cam_unnorm_rots + time_idx, cam_trans + time_idx, num_frames, c, (float*)state,
+                                                  history_row, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_tracking_step: %s", hipGetErrorString(e));
+    return GS_OK;
 }
 
 int gs_render_backward_raw_adam(const GsCamera* cam, int32_t P, int64_t D, const float* means3D, const float* shs, const float* colors_precomp,

@@ -66,6 +66,35 @@ struct Cam {
     float act_q[4], act_t[3];
 };
 
+// Device-resident pose of the raw-parameter mode (tracking: gs_preprocess_forward_raw_dev / gs_render_backward_raw_pose_dev): the kernels
+// instantiated with this camera type read params['cam_unnorm_rots'][0, :, t] and params['cam_trans'][0, :, t] in place (column stride `stride`,
+// the frame count T) when they start, normalise the quaternion as F.normalize does, and overwrite act_q / act_t of their own copy of the camera
+// block.  The kernels of every other mode take Cam and do nothing of the sort (load_device_pose(Cam&) is empty).
+struct CamDP : Cam {
+    const float* dev_q;          // &cam_unnorm_rots[0, 0, t]
+    const float* dev_t;          // &cam_trans[0, 0, t]
+    int64_t stride;              // T
+};
+// F.normalize(x) = x / max(|x|, 1e-12) of one [4] column, the squares summed in index order; no FMA contraction, so that the forward, the
+// backward and the tracking step (translation units built with and without contraction) all see the same normalised quaternion
+__device__ __forceinline__ void normalize_pose_column(const float* x, int64_t stride, float (&u)[4], float& norm)
+{
+#pragma clang fp contract(off)
+    const float a = x[0], b = x[stride], c = x[2 * stride], d = x[3 * stride];
+    norm = sqrtf(((a * a + b * b) + c * c) + d * d);
+    const float n = fmaxf(norm, 1e-12f);
+    u[0] = a / n; u[1] = b / n; u[2] = c / n; u[3] = d / n;
+}
+// (the kernels take the camera as `typename CamArg<CamT>::type`: not deducible, so that a launch names the instantiation it means)
+template <class T> struct CamArg { typedef T type; };
+__device__ __forceinline__ void load_device_pose(Cam&) {}
+__device__ __forceinline__ void load_device_pose(CamDP& c)
+{
+    float n;
+    normalize_pose_column(c.dev_q, c.stride, c.act_q, n);
+    for (int k = 0; k < 3; k++) c.act_t[k] = c.dev_t[k * c.stride];
+}
+
 // frame transform + activation algebra shared by activate.hip and the raw-parameter mode of the per-Gaussian kernels
 __device__ __forceinline__ void quat_to_rot(const float* q, float (&R)[3][3])
 {
@@ -238,6 +267,68 @@ __device__ __forceinline__ void pose_grad_block_row(float (&acc)[kPoseAcc], floa
         float s = 0.f;
         for (int w = 0; w < kBlock / kWave; w++) s += s_red[w][threadIdx.x];
         row[threadIdx.x] = s;
+    }
+}
+// Final pass of the camera-pose gradient (pose_grad_finish_kernel and the tracking step, activate.hip): the per-workgroup rows summed in fp64 in
+// a fixed order (thread t adds column t % 16 of rows t / 16, t / 16 + 16, ...; then the 16 slices in order), dL/dR turned into dL/dq_cam through
+// build_rotation's normalisation and quat_to_rot's formula and added to the rotation term; thread 0 writes out[7] = dL/d(qw,qx,qy,qz,tx,ty,tz)
+// of the pose the rows were formed at (pose.q = its quaternion (w,x,y,z)).  Every thread of the workgroup must call it; only thread 0 comes back with `out` written.
+template <class PoseT>
+__device__ __forceinline__ void pose_grad_finish_block(int64_t nrows, const PoseT& pose, const float* __restrict__ rows, float* __restrict__ out)
+{
+    constexpr int kSlices = kBlock / kPoseAcc;
+    __shared__ double s[kSlices][kPoseAcc];
+    const int c = threadIdx.x % kPoseAcc, sl = threadIdx.x / kPoseAcc;
+    double acc = 0.0;
+    for (int64_t r = sl; r < nrows; r += kSlices) acc += (double)rows[r * kPoseAcc + c];
+    s[sl][c] = acc;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double t[kPoseAcc];
+    for (int k = 0; k < kPoseAcc; k++) {
+        double v = 0.0;
+        for (int j = 0; j < kSlices; j++) v += s[j][k];
+        t[k] = v;
+    }
+    const double* dR = t + 3;            // row-major dL/dR
+    // the reference builds the matrix as build_rotation(q) = R(q / |q|) (slam_external.py:25-42): dL/dR reaches q through quat_to_rot at the unit
+    // quaternion AND that normalisation -- (I - u u^T) / |q| -- so the result is the reference's dL/dq for any q the caller chains it into
+    // (a unit leaf passed as is included), not only after a further F.normalize.  (The rotation term is taken as quat_mult(q, .) takes it: as is.)
+    const double q0 = pose.q[0], q1 = pose.q[1], q2 = pose.q[2], q3 = pose.q[3];
+    const double nq = sqrt(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
+    const double r = q0 / nq, x = q1 / nq, y = q2 / nq, z = q3 / nq;
+    const double d0 = 2.0 * (-z * dR[1] + y * dR[2] + z * dR[3] - x * dR[5] - y * dR[6] + x * dR[7]);
+    const double d1 = 2.0 * (y * dR[1] + z * dR[2] + y * dR[3] - 2.0 * x * dR[4] - r * dR[5] + z * dR[6] + r * dR[7] - 2.0 * x * dR[8]);
+    const double d2 = 2.0 * (-2.0 * y * dR[0] + x * dR[1] + r * dR[2] + x * dR[3] + z * dR[5] - r * dR[6] + z * dR[7] - 2.0 * y * dR[8]);
+    const double d3 = 2.0 * (-2.0 * z * dR[0] - r * dR[1] + x * dR[2] + r * dR[3] - 2.0 * z * dR[4] + y * dR[5] + x * dR[6] + y * dR[7]);
+    const double dot = r * d0 + x * d1 + y * d2 + z * d3;
+    out[0] = (float)((d0 - r * dot) / nq + t[12]); out[1] = (float)((d1 - x * dot) / nq + t[13]);
+    out[2] = (float)((d2 - y * dot) / nq + t[14]); out[3] = (float)((d3 - z * dot) / nq + t[15]);
+    out[4] = (float)t[0]; out[5] = (float)t[1]; out[6] = (float)t[2];
+}
+
+// Tracking loss (loss.hip): one row of kTrackRow partial sums per workgroup -- {sum of masked |gt_depth - depth|, sum of |gt_im - im| over the
+// colour mask} -- reduced by tracking_loss_reduce in fp64, in a fixed order (thread t adds rows t, t + kBlock, ...; then a pairwise tree over the
+// kBlock partials in LDS), and weighted as the reference weights them in fp32: out = {w_depth d + w_im c, w_depth d, w_im c} (thread 0 only).
+// Every thread of the workgroup must call it.
+constexpr int kTrackRow = 2;
+__device__ __forceinline__ void tracking_loss_reduce(int64_t nrows, const float* __restrict__ rows, float w_im, float w_depth, float (&out)[3])
+{
+    __shared__ double s_l[kTrackRow][kBlock];
+    double a = 0.0, b = 0.0;
+    for (int64_t r = threadIdx.x; r < nrows; r += kBlock) { a += (double)rows[r * kTrackRow]; b += (double)rows[r * kTrackRow + 1]; }
+    s_l[0][threadIdx.x] = a; s_l[1][threadIdx.x] = b;
+    __syncthreads();
+    for (int h = kBlock / 2; h > 0; h >>= 1) {
+        if (threadIdx.x < h) { s_l[0][threadIdx.x] += s_l[0][threadIdx.x + h]; s_l[1][threadIdx.x] += s_l[1][threadIdx.x + h]; }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const double d = s_l[0][0], c = s_l[1][0];
+    {
+#pragma clang fp contract(off)
+        const float wd = (float)d * w_depth, wc = (float)c * w_im;
+        out[0] = wd + wc; out[1] = wd; out[2] = wc;
     }
 }
 
@@ -591,6 +682,12 @@ hipError_t launch_preprocess_forward(const Cam& cam, int P, const float* means3D
                                      const float* colors, const float* opac, const float* scales,
                                      const float* rots, const float* cov3Dp, int32_t* radii, GeomPtrs gp,
                                      uint32_t* d_num_rendered, hipStream_t st);
+// device-resident pose (CamDP): raw-parameter forward, and the pose-only raw-parameter backward (pose_rows as launch_preprocess_backward's)
+hipError_t launch_preprocess_forward_dev(const CamDP& cam, int P, const float* means3D, const float* shs, const float* colors,
+                                         const float* opac, const float* scales, const float* rots, int32_t* radii, GeomPtrs gp, hipStream_t st);
+hipError_t launch_preprocess_backward_pose_dev(const CamDP& cam, int P, const float* means3D, const float* shs, const float* scales,
+                                               const float* rots, const int32_t* radii, const uint32_t* clamped, const float2* sh_jac,
+                                               const float* grad2d, float* dmeans2D, const float* logit, float* pose_rows, hipStream_t st);
 hipError_t launch_scan_block_sums(int P, GeomPtrs gp, uint32_t* d_total, hipStream_t st);
 hipError_t launch_preprocess_backward(const Cam& cam, int P, const float* means3D, const float* shs,
                                       const float* scales, const float* rots, const float* cov3Dp,
@@ -698,6 +795,19 @@ hipError_t launch_activate_backward_pose(int P, int iso, const float* pose7, con
                                          int pose_mode, float* pose_rows, hipStream_t st);
 inline int64_t pose_rows_count(int64_t P) { return (P + kBlock - 1) / kBlock; }
 hipError_t launch_pose_grad_finish(int64_t nrows, const float* pose7, const float* pose_rows, float* dpose7, hipStream_t st);
+// the same with the pose read from the device column (CamDP's dev_q / stride)
+hipError_t launch_pose_grad_finish_dev(int64_t nrows, const float* dev_q, int64_t stride, const float* pose_rows, float* dpose7, hipStream_t st);
+// tracking (activate.hip): per-frame optimiser state, and the step of one iteration (see gs_tracking_step in include/gsplat_hip.h)
+constexpr int kTrackState = 32;             // floats: m[7] v[7] min_loss cand[7] last{loss, depth, im} skipped, padding
+struct TrackAdam { float one_m_b1, b2, one_m_b2, bc2_sqrt, eps, neg_step_size[2]; };
+hipError_t launch_tracking_begin(const float* rots_col, const float* trans_col, int64_t stride, float* state, hipStream_t st);
+hipError_t launch_tracking_step(int64_t pose_nrows, const float* pose_rows, int64_t loss_nrows, const float* loss_rows, float w_im, float w_depth,
+                                float* rots_col, float* trans_col, int64_t stride, const TrackAdam& c, float* state, float* history_row,
+                                hipStream_t st);
+inline int64_t tracking_loss_rows(int64_t npix) { return (npix + kBlock - 1) / kBlock; }
+hipError_t launch_tracking_loss(int W, int H, const float* im, const float* gt, const float* depth, const float* depth_sq, const float* gt_depth,
+                                const float* sil, int use_sil, float sil_thres, float w_im, float w_depth, float* dL_dim, float* dL_ddepth,
+                                float* rows, float* losses, hipStream_t st);
 constexpr int kLossAccSlots = 256;          // 64-byte accumulator lines at the head of the mapping loss' scratch (loss.hip)
 hipError_t launch_mapping_loss(int W, int H, const float* im, const float* gt, const float* depth, const float* depth_sq,
                                const float* gt_depth, float w_im, float w_depth, float* losses, float* dL_dim,

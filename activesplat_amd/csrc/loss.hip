@@ -253,4 +253,72 @@ hipError_t launch_mapping_loss(int W, int H, const float* im, const float* gt, c
     return hipGetLastError();
 }
 
+// ---- tracking loss (src/mapper/splatam/splatam.py:220-249 with tracking=True, use_l1=True): value AND gradient in one pass over the image ----
+//   mask   = (gt_depth > 0) & !isnan(depth) & !isnan(depth_sq - depth^2)  [& (silhouette > sil_thres) with use_sil_for_loss]
+//   depth  = sum_mask |gt_depth - depth|,   im = sum |gt_im - im| over the mask tiled to 3 channels (use_sil) or over every pixel
+//   dL/ddepth = -(w_depth [mask] * sgn(gt_depth - depth)),  dL/dim = -(w_im [colour mask] * sgn(gt_im - im))  -- autograd's own expression
+//   (abs' backward grad * sgn, then the subtraction's negation; sgn(0) = sgn(NaN) = 0), so the images are bit-identical to torch's.
+// Every workgroup writes one row of kTrackRow partial sums (no float atomics); tracking_loss_reduce (gs_common.h) sums the rows in a fixed order.
+// ignore_outlier_depth_loss needs the median of the depth error: that option stays on the torch loss (mapping.get_loss).
+__device__ __forceinline__ float sgnf(float x) { return (float)((0.f < x) - (x < 0.f)); }
+
+__global__ __launch_bounds__(kBlock) void tracking_loss_kernel(int npix, const float* __restrict__ im, const float* __restrict__ gt,
+                                                               const float* __restrict__ depth, const float* __restrict__ depth_sq,
+                                                               const float* __restrict__ gt_depth, const float* __restrict__ sil, int use_sil,
+                                                               float sil_thres, float w_im, float w_depth, float* __restrict__ dL_dim,
+                                                               float* __restrict__ dL_ddepth, float* __restrict__ rows)
+{
+#pragma clang fp contract(off)
+    __shared__ float s_red[kTrackRow][kBlock / kWave];
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    float dsum = 0.f, csum = 0.f;
+    if (i < npix) {
+        const float d = depth[i], gd = gt_depth[i];
+        const float unc = depth_sq[i] - d * d;
+        bool m = gd > 0.f && !__builtin_isnan(d) && !__builtin_isnan(unc);
+        if (use_sil) m = m && sil[i] > sil_thres;
+        const float ed = gd - d;
+        if (m) dsum = fabsf(ed);
+        dL_ddepth[i] = -((m ? w_depth : 0.f) * sgnf(ed));
+        const bool cm = !use_sil || m;
+        const float gc = cm ? w_im : 0.f;
+        for (int ch = 0; ch < 3; ch++) {
+            const size_t j = (size_t)ch * npix + i;
+            const float ec = gt[j] - im[j];
+            if (cm) csum += fabsf(ec);
+            dL_dim[j] = -(gc * sgnf(ec));
+        }
+    }
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    dsum = wave_sum(dsum); csum = wave_sum(csum);
+    if (lane == 0) { s_red[0][wave] = dsum; s_red[1][wave] = csum; }
+    __syncthreads();
+    if (threadIdx.x < kTrackRow) {
+        float v = 0.f;
+        for (int w = 0; w < kBlock / kWave; w++) v += s_red[threadIdx.x][w];
+        rows[(size_t)blockIdx.x * kTrackRow + threadIdx.x] = v;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void tracking_loss_finish_kernel(int64_t nrows, const float* __restrict__ rows, float w_im, float w_depth,
+                                                                      float* __restrict__ losses)
+{
+    float L[3];
+    tracking_loss_reduce(nrows, rows, w_im, w_depth, L);
+    if (threadIdx.x == 0) { losses[0] = L[0]; losses[1] = L[1]; losses[2] = L[2]; }
+}
+
+hipError_t launch_tracking_loss(int W, int H, const float* im, const float* gt, const float* depth, const float* depth_sq, const float* gt_depth,
+                                const float* sil, int use_sil, float sil_thres, float w_im, float w_depth, float* dL_dim, float* dL_ddepth,
+                                float* rows, float* losses, hipStream_t st)
+{
+    const int npix = W * H;
+    const int64_t nb = tracking_loss_rows(npix);
+    if (nb > 0)
+        hipLaunchKernelGGL(tracking_loss_kernel, dim3((unsigned)nb), dim3(kBlock), 0, st, npix, im, gt, depth, depth_sq, gt_depth, sil, use_sil,
+                           sil_thres, w_im, w_depth, dL_dim, dL_ddepth, rows);
+    if (losses) hipLaunchKernelGGL(tracking_loss_finish_kernel, dim3(1), dim3(kBlock), 0, st, nb, rows, w_im, w_depth, losses);
+    return hipGetLastError();
+}
+
 }  // namespace gs

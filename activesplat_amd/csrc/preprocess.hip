@@ -227,12 +227,14 @@ __device__ __forceinline__ float activate_staged_rows(const Cam& cam, int tid, b
 
 // SH: 0 = colours given, 1 = coefficient rows of any width through per-wave LDS slabs (16-coefficient rows, the layout every caller of
 // the reference uses, take preprocess_forward_sh48_kernel below)
-template <int SH, bool ACT = false>        // ACT: raw-parameter mode (colours given or 16-coefficient rows only)
+// CamT = CamDP (the raw-parameter mode only): the pose is read from device memory when the kernel starts (load_device_pose, gs_common.h)
+template <int SH, bool ACT = false, class CamT = Cam>        // ACT: raw-parameter mode (colours given or 16-coefficient rows only)
 __global__ __launch_bounds__(kBlock) void preprocess_forward_kernel(
-    Cam cam, int P, const float* __restrict__ means3D, const float* __restrict__ shs,
+    typename CamArg<CamT>::type cam, int P, const float* __restrict__ means3D, const float* __restrict__ shs,
     const float* __restrict__ colors, const float* __restrict__ opac, const float* __restrict__ scales,
     const float* __restrict__ rots, const float* __restrict__ cov3Dp, int32_t* __restrict__ radii, GeomPtrs gp)
 {
+    load_device_pose(cam);
     // LDS: means | one pool that holds, in turn, the per-wave SH slabs (HAS_SH, first phase) and the staged
     // scale+rotation (or covariance) rows and colours (second phase)
     constexpr bool HAS_SH = SH != 0;
@@ -334,11 +336,12 @@ __global__ __launch_bounds__(kBlock) void preprocess_forward_kernel(
 // four workgroups per CU instead of three); slabs with 16-byte aligned rows (gs_common.h: kShPad4), i.e. 128-bit LDS accesses.
 // Measured at 2 M Gaussians against the generic design with compile-time row width (three barriers, both halves' loads held in 48
 // registers: 167 VGPRs, three workgroups per CU, 49-float slab rows): 155 -> 131 us; same arithmetic, same results to the bit.
-template <bool ACT>
+template <bool ACT, class CamT = Cam>
 __global__ __launch_bounds__(kBlock, 4) void preprocess_forward_sh48_kernel(
-    Cam cam, int P, const float* __restrict__ means3D, const float* __restrict__ shs, const float* __restrict__ opac,
+    typename CamArg<CamT>::type cam, int P, const float* __restrict__ means3D, const float* __restrict__ shs, const float* __restrict__ opac,
     const float* __restrict__ scales, const float* __restrict__ rots, const float* __restrict__ cov3Dp, int32_t* __restrict__ radii, GeomPtrs gp)
 {
+    load_device_pose(cam);
     __shared__ __attribute__((aligned(16))) float s_mean[kBlock * 3];
     __shared__ __attribute__((aligned(16))) float s_geo[kBlock * 7];
     __shared__ __attribute__((aligned(16))) float s_sh[(kBlock / kWave) * kShHalf * kShPad4];
@@ -455,6 +458,25 @@ hipError_t launch_preprocess_forward(const Cam& cam, int P, const float* means3D
         hipLaunchKernelGGL(preprocess_forward_kernel<0>, dim3(nb), dim3(kBlock), 0, st, cam, P, means3D, shs, colors, opac,
                            scales, rots, cov3Dp, radii, gp);
     // tile_total must be zero even when the grid above does not cover every tile (tiny P, many tiles)
+    if ((size_t)nb * kBlock < (size_t)cam.gx * cam.gy) {
+        hipError_t e = hipMemsetAsync(gp.tile_total, 0, (size_t)cam.gx * cam.gy * 4, st);
+        if (e != hipSuccess) return e;
+    }
+    return hipGetLastError();
+}
+
+// raw-parameter mode with the pose in device memory (tracking): the two ACT kernels above, instantiated with CamDP
+hipError_t launch_preprocess_forward_dev(const CamDP& cam, int P, const float* means3D, const float* shs, const float* colors,
+                                         const float* opac, const float* scales, const float* rots, int32_t* radii, GeomPtrs gp, hipStream_t st)
+{
+    const int nb = (P + kBlock - 1) / kBlock;
+    if (!cam.act || cam.V != 1 || (shs && cam.sh_coeffs != 16)) return hipErrorInvalidValue;
+    if (nb > 0 && shs)
+        hipLaunchKernelGGL((preprocess_forward_sh48_kernel<true, CamDP>), dim3(nb), dim3(kBlock), 0, st, cam, P, means3D, shs, opac, scales, rots,
+                           nullptr, radii, gp);
+    else if (nb > 0)
+        hipLaunchKernelGGL((preprocess_forward_kernel<0, true, CamDP>), dim3(nb), dim3(kBlock), 0, st, cam, P, means3D, shs, colors, opac,
+                           scales, rots, nullptr, radii, gp);
     if ((size_t)nb * kBlock < (size_t)cam.gx * cam.gy) {
         hipError_t e = hipMemsetAsync(gp.tile_total, 0, (size_t)cam.gx * cam.gy * 4, st);
         if (e != hipSuccess) return e;

@@ -36,9 +36,10 @@ template <> struct ParamPtr<false> { typedef const float* type; };
 // early jumps to the reduction instead of returning -- writes one row of kPoseAcc partial sums to pose_rows (no float atomics; reduced in a fixed
 // order by pose_grad_finish_kernel, activate.hip); 2 = the pose share ONLY: no parameter gradient row is written and the parameter-side chain that
 // only feeds those rows is skipped (dmeans2D is written as always).  POSE = 0: the instantiations of every other mode, unchanged.
-template <int SH, bool ACT = false, bool ADAM = false, int POSE = 0>
+// CamT = CamDP (POSE = 2 only: the tracking backward): the pose is read from device memory when the kernel starts (load_device_pose, gs_common.h)
+template <int SH, bool ACT = false, bool ADAM = false, int POSE = 0, class CamT = Cam>
 __global__ __launch_bounds__(kBlock, (ACT && SH == 3) ? GS_PBWD_RAW_SH_WGS : 4) void preprocess_backward_kernel(
-    Cam cam, int P, typename ParamPtr<!ADAM>::type means3D, typename ParamPtr<!ADAM>::type shs,
+    typename CamArg<CamT>::type cam, int P, typename ParamPtr<!ADAM>::type means3D, typename ParamPtr<!ADAM>::type shs,
     typename ParamPtr<!ADAM>::type scales, typename ParamPtr<!ADAM>::type rots, const float* __restrict__ cov3Dp,
     const int32_t* __restrict__ radii, const uint32_t* __restrict__ clamped, const float2* __restrict__ sh_jac,
     const float* __restrict__ grad2d, float* __restrict__ dmeans2D, float* __restrict__ dmeans3D, float* __restrict__ dopac,
@@ -46,6 +47,7 @@ __global__ __launch_bounds__(kBlock, (ACT && SH == 3) ? GS_PBWD_RAW_SH_WGS : 4) 
     float* __restrict__ drots, float* __restrict__ dcov3D, typename ParamPtr<!ADAM>::type logit, FusedAdam ad, float* __restrict__ pose_rows)
 {
     static_assert(POSE == 0 || (ACT && !ADAM && SH != 1), "the pose gradient is a raw-parameter mode without the optimiser step");
+    load_device_pose(cam);
     float pacc[kPoseAcc];
     for (int k = 0; k < kPoseAcc; k++) pacc[k] = 0.f;
 #define GS_PBWD_LEAVE do { if (POSE != 0) goto pose_reduce; return; } while (0)
@@ -456,13 +458,29 @@ hipError_t launch_preprocess_backward(const Cam& cam, int P, const float* means3
                                         cov3Dp, radii, clamped, sh_jac, grad2d, dmeans2D, dmeans3D, dopac, dcolors, dshs, dscales, drots, dcov3D, logit, ad, \
                                         pose_rows)
     if (nb > 0 && pose_mode) {
-        if (shs) { if (pose_only) GS_PBWD(3, true, false, 2); else GS_PBWD(3, true, false, 1); }
-        else { if (pose_only) GS_PBWD(0, true, false, 2); else GS_PBWD(0, true, false, 1); }
+        if (shs) { if (pose_only) GS_PBWD(3, true, false, 2, Cam); else GS_PBWD(3, true, false, 1, Cam); }
+        else { if (pose_only) GS_PBWD(0, true, false, 2, Cam); else GS_PBWD(0, true, false, 1, Cam); }
     }
     else if (nb > 0 && shs && cam.sh_coeffs == 16) { if (adam) GS_PBWD(3, true, true); else if (cam.act) GS_PBWD(3, true); else GS_PBWD(3, false); }
     else if (nb > 0 && shs) GS_PBWD(1, false);
     else if (nb > 0) { if (adam) GS_PBWD(0, true, true); else if (cam.act) GS_PBWD(0, true); else GS_PBWD(0, false); }
 #undef GS_PBWD
+    return hipGetLastError();
+}
+
+hipError_t launch_preprocess_backward_pose_dev(const CamDP& cam, int P, const float* means3D, const float* shs, const float* scales,
+                                               const float* rots, const int32_t* radii, const uint32_t* clamped, const float2* sh_jac,
+                                               const float* grad2d, float* dmeans2D, const float* logit, float* pose_rows, hipStream_t st)
+{
+    const int nb = (P + kBlock - 1) / kBlock;
+    if (!cam.act || !logit || !scales || !rots || !pose_rows || (shs && cam.sh_coeffs != 16)) return hipErrorInvalidValue;
+    const FusedAdam ad{};
+#define GS_PBWD_DEV(SH_) hipLaunchKernelGGL((preprocess_backward_kernel<SH_, true, false, 2, CamDP>), dim3(nb), dim3(kBlock), 0, st, cam, P, means3D, \
+                                            shs, scales, rots, nullptr, radii, clamped, sh_jac, grad2d, dmeans2D, nullptr, nullptr, nullptr, \
+                                            nullptr, nullptr, nullptr, nullptr, logit, ad, pose_rows)
+    if (nb > 0 && shs) GS_PBWD_DEV(3);
+    else if (nb > 0) GS_PBWD_DEV(0);
+#undef GS_PBWD_DEV
     return hipGetLastError();
 }
 

@@ -5,7 +5,9 @@ habitat).  It reproduces the CALL PATTERN and SCHEDULE of the hot loop, nothing 
   frame 0                       : back-project the RGB-D frame -> initialize_params; scene_radius = max depth / 3
                                   (__init__.py:382-386, config/splatam/online_habitat_sim.py:6)
   every frame                   : write the ground-truth pose into params['cam_*'][..., id] (tracking is skipped,
-                                  __init__.py:400-405)
+                                  __init__.py:400-405) -- or, with tracking=dict(use_gt_poses=False), frame 0 takes its pose and
+                                  every later frame is TRACKED (mapping.initialize_camera_pose + mapping.track_frame, SplaTAM's
+                                  loop) before the high-loss render, growth and mapping, which all use the tracked pose
   frames with id == 0 or (id+1) % map_every == 0
                                 : add_new_gaussians (id > 0), keyframe_selection_overlap over keyframe_list[:-1]
                                   (window = mapping_window_size - 2, + last keyframe + current frame), FRESH Adam
@@ -53,6 +55,7 @@ DEFAULT_CONFIG = dict(
     fused_iteration=False,   # ... and the whole iteration (get_loss + backward + step + zero_grad) as four library calls without autograd
                              # (mapping.mapping_iteration; needs fused_render, fused_loss, fused_preprocess; event iterations take the usual path)
     fused_growth=False,      # add_new_gaussians: one forward + gs_grow_gaussians
+    fused_tracking=False,    # tracking (tracking.use_gt_poses=False): mapping.track_frame's HIP loop (tracking_iteration) instead of the reference pattern
     fused_keyframes=True,    # (accepted for older configs; no effect: the keyframe overlap scores always come from gs_keyframe_overlap, one launch)
     high_loss_samples=True,  # the per-frame no-grad render of get_high_loss_samples (__init__.py:184-258) before mapping a frame
     mapping=dict(
@@ -66,6 +69,9 @@ DEFAULT_CONFIG = dict(
         densify_dict=dict(start_after=500, remove_big_after=3000, stop_after=5000, densify_every=100, grad_thresh=0.0002,
                           num_to_split_into=2, removal_opacity_threshold=0.005, final_removal_opacity_threshold=0.005,
                           reset_opacities=False, reset_opacities_every=3000)),
+    # the reference's tracking section (config/splatam/online_habitat_sim.py:20-45, mapping.TRACKING_DEFAULTS) -- except use_gt_poses, True
+    # here: the reference mapper writes the simulator's poses whatever its config says (__init__.py:400-405), and so does this one by default
+    tracking=dict(M.TRACKING_DEFAULTS, use_gt_poses=True),
     viz=dict(viz_near=0.01, viz_far=100.0),
 )
 
@@ -85,7 +91,9 @@ class SplatMapper:
         self._k_host = np.asarray(intrinsics, dtype=np.float64)
         self._pose_host = {}               # frame id -> (quaternion, translation) as this mapper wrote them into the camera parameters (host tensors)
         lrs = self.cfg["mapping"]["lrs"]
-        self._poses_fixed = float(lrs.get("cam_unnorm_rots", 0.0)) == 0.0 and float(lrs.get("cam_trans", 0.0)) == 0.0
+        self.cfg["tracking"] = M.tracking_config(self.cfg["tracking"])
+        self._tracking = not self.cfg["tracking"]["use_gt_poses"]
+        self._poses_fixed = float(lrs.get("cam_unnorm_rots", 0.0)) == 0.0 and float(lrs.get("cam_trans", 0.0)) == 0.0 and not self._tracking
         self.first_frame_w2c = torch.eye(4, device=self.device)
         self.cam = setup_camera(self.W, self.H, np.asarray(intrinsics), np.eye(4), device=self.device)
         self.densify_cam, self.densify_intrinsics = self.cam, self.intrinsics      # replaced when frames carry a densify copy
@@ -94,7 +102,7 @@ class SplatMapper:
         self.params = self.variables = self.optimizer = None
         self.keyframe_list, self.selected_keyframes, self.gt_w2c_all_frames = [], [], []
         self.rng = np.random.RandomState(self.cfg["seed"])
-        self.stats = dict(iters=0, iter_time=0.0, frames=0, frame_time=0.0)
+        self.stats = dict(iters=0, iter_time=0.0, frames=0, frame_time=0.0, tracking_iters=0, tracking_time=0.0, tracked_frames=0)
         self._last_losses = None           # device scalars of the most recent iteration (read through `last_losses`)
         self.high_loss_mask = None          # bool [H,W] of the most recent frame (None before the first map exists)
 
@@ -141,8 +149,19 @@ class SplatMapper:
         pos_h = torch.as_tensor(np.asarray(frame["position"], dtype=np.float32)).reshape(3).clone()
         self._pose_host[fid] = (quat_h, pos_h)
         quat, pos = quat_h.to(self.device), pos_h.to(self.device)
+        tracked = self._tracking and fid > 0 and self.params is not None
+        if tracked:
+            # SplaTAM's tracking of this frame: constant-velocity start, then the tracking loop; the frame's own pose only goes to gt_w2c_all_frames
+            t_track = time.perf_counter()
+            M.initialize_camera_pose(self.params, fid, self.cfg["tracking"]["forward_prop"])
+            res = M.track_frame(self.params, self._data(color, depth, fid), self.variables, fid, self.cfg["tracking"],
+                                fused=cfg.get("fused_tracking", False))
+            self.stats["tracking_iters"] += res["iterations"]
+            self.stats["tracking_time"] += time.perf_counter() - t_track
+            self.stats["tracked_frames"] += 1
         if self.params is not None and cfg.get("high_loss_samples", True):
-            self.high_loss_mask = self.high_loss_samples_mask(self._w2c_host(quat_h, pos_h), depth)       # (host pose: the camera block is built on the host)
+            view = self._w2c(fid) if tracked else self._w2c_host(quat_h, pos_h)      # (host pose: the camera block is built on the host)
+            self.high_loss_mask = self.high_loss_samples_mask(view, depth)
         # densification-resolution copy of the frame (reference :362-376); defaults to the mapping resolution
         d_color = frame["densify_color"].to(self.device).float() if "densify_color" in frame else color
         d_depth = frame["densify_depth"].to(self.device).float() if "densify_depth" in frame else depth
@@ -164,18 +183,22 @@ class SplatMapper:
         iter_per_frame = int(cfg["mapping_iters"] // map_every)
         if iter_per_frame == 0 and fid % map_every == 0:
             iter_per_frame = cfg["mapping_iters"]
-        with torch.no_grad():                                    # tracking skip: ground-truth pose
-            self.params["cam_unnorm_rots"][..., fid] = quat
-            self.params["cam_trans"][..., fid] = pos
+        if not tracked:
+            with torch.no_grad():                                # tracking skip: ground-truth pose (and frame 0's pose when tracking)
+                self.params["cam_unnorm_rots"][..., fid] = quat
+                self.params["cam_trans"][..., fid] = pos
         if fid == 0 or (fid + 1) % map_every == 0:
             if mc["add_new_gaussians"] and fid > 0:
                 d_data = {"cam": self.densify_cam, "im": d_color, "depth": d_depth, "id": fid, "intrinsics": self.densify_intrinsics,
                           "w2c": self.first_frame_w2c}
+                pose7 = None
+                if cfg.get("fused_growth", False):
+                    q_g, t_g = (self.params["cam_unnorm_rots"][0, :, fid].detach().cpu(), self.params["cam_trans"][0, :, fid].detach().cpu()) \
+                        if tracked else (quat_h, pos_h)
+                    pose7 = [float(v) for v in F.normalize(q_g.view(1, 4)).view(4).tolist()] + [float(v) for v in t_g.tolist()]
                 self.params, self.variables = M.add_new_gaussians(self.params, self.variables, d_data,
                                                                   mc["sil_thres"], fid, cfg["gaussian_distribution"],
-                                                                  fused=cfg.get("fused_growth", False),
-                                                                  pose7=[float(v) for v in F.normalize(quat_h.view(1, 4)).view(4).tolist()]
-                                                                  + [float(v) for v in pos_h.tolist()] if cfg.get("fused_growth", False) else None)
+                                                                  fused=cfg.get("fused_growth", False), pose7=pose7)
             with torch.no_grad():
                 sel = keyframe_selection_overlap(depth, self._w2c(fid), self.intrinsics, self.keyframe_list[:-1],
                                                  cfg["mapping_window_size"] - 2)
@@ -238,8 +261,9 @@ class SplatMapper:
             self.stats["frame_time"] += time.perf_counter() - t_frame
         with torch.no_grad():
             # the simulator's pose when the caller hands one over (run_raw), the pose written into the camera parameters otherwise
+            # (tracking: the frame's own pose -- the parameters hold the estimate)
             gt_w2c = torch.as_tensor(np.asarray(frame["gt_w2c"]), dtype=torch.float32, device=self.device) if "gt_w2c" in frame \
-                else self._w2c(fid)
+                else (self._w2c_host(quat_h, pos_h).to(self.device) if self._tracking else self._w2c(fid))
             pose_ok = bool(torch.isfinite(gt_w2c).all())
             if (fid == 0 or (fid + 1) % cfg["keyframe_every"] == 0 or fid == cfg["step_num"] - 2) and pose_ok:
                 self.keyframe_list.append({"id": fid, "est_w2c": self._w2c(fid), "color": color, "depth": depth})

@@ -12,6 +12,7 @@ functions that produce every tensor handed to / consumed from the rasteriser:
   get_rendervars, render                  src/mapper/splatam/splatam.py:436-468,413-434
   calc_ssim                               slam_external.py:54-97
   get_loss (mapping branch)               splatam.py:172-301
+  initialize_camera_pose                  splatam.py:382-402
   get_pointcloud, initialize_params,
   initialize_new_params, add_new_gaussians splatam.py:25-115,304-379
 
@@ -564,6 +565,202 @@ def mapping_iteration(params, curr_data, variables, iter_time_idx, loss_weights,
 # ---------------------------------------------------------------------------------------------------
 # map initialisation / growth (splatam.py:25-115,304-379)
 # ---------------------------------------------------------------------------------------------------
+def initialize_camera_pose(params, curr_time_idx, forward_prop):
+    """The pose column of frame curr_time_idx before tracking (splatam.py:382-402): constant velocity from the two frames before it with
+    forward_prop (from the third frame on), else the previous frame's pose."""
+    with torch.no_grad():
+        rots, trans = params["cam_unnorm_rots"], params["cam_trans"]
+        if curr_time_idx > 1 and forward_prop:
+            prev_rot1 = F.normalize(rots[..., curr_time_idx - 1].detach())
+            prev_rot2 = F.normalize(rots[..., curr_time_idx - 2].detach())
+            rots[..., curr_time_idx] = F.normalize(prev_rot1 + (prev_rot1 - prev_rot2)).detach()
+            prev_tran1 = trans[..., curr_time_idx - 1].detach()
+            prev_tran2 = trans[..., curr_time_idx - 2].detach()
+            trans[..., curr_time_idx] = (prev_tran1 + (prev_tran1 - prev_tran2)).detach()
+        else:
+            rots[..., curr_time_idx] = rots[..., curr_time_idx - 1].detach()
+            trans[..., curr_time_idx] = trans[..., curr_time_idx - 1].detach()
+    return params
+
+
+#: the reference's tracking section (config/splatam/online_habitat_sim.py:20-45) plus tracking_iters (SplaTAM's 40 per frame)
+TRACKING_DEFAULTS = dict(use_gt_poses=False, forward_prop=True, use_sil_for_loss=True, sil_thres=0.99, use_l1=True, use_depth_loss_thres=True,
+                         depth_loss_thres=20000, ignore_outlier_depth_loss=False, loss_weights=dict(im=0.5, depth=1.0),
+                         lrs=dict(means3D=0.0, rgb_colors=0.0, unnorm_rotations=0.0, logit_opacities=0.0, log_scales=0.0, cam_unnorm_rots=0.001,
+                                  cam_trans=0.004), tracking_iters=40)
+
+
+def tracking_config(cfg=None):
+    out = dict(TRACKING_DEFAULTS, **(cfg or {}))
+    out["loss_weights"] = dict(TRACKING_DEFAULTS["loss_weights"], **(cfg or {}).get("loss_weights", {}))
+    out["lrs"] = dict(TRACKING_DEFAULTS["lrs"], **(cfg or {}).get("lrs", {}))
+    return out
+
+
+class TrackingState:
+    """Device buffers of one frame's fused tracking (include/gsplat_hip.h, gs_tracking_*): the optimiser state (moments, smallest loss, candidate
+    pose), the tracking loss' gradient images and rows, the pose rows of the backward.  begin() starts a frame as the reference builds a fresh
+    optimiser per frame; `step` counts the Adam steps of the frame."""
+
+    def __init__(self, params, W, H):
+        from . import _lib
+        lib = _lib.get()
+        dev = params["means3D"].device
+        P = int(params["means3D"].shape[0])
+        self.device, self.P, self.W, self.H = dev, P, W, H
+        self.state = torch.empty(int(lib.gs_tracking_state_bytes()) // 4, dtype=torch.float32, device=dev)
+        self.grads = torch.empty(4, H, W, dtype=torch.float32, device=dev)          # dL/dim [3,H,W], dL/ddepth [1,H,W]
+        self.loss_rows = torch.empty(int(lib.gs_tracking_loss_scratch_bytes(W, H)), dtype=torch.uint8, device=dev)
+        self.pose_rows = torch.empty(int(lib.gs_pose_grad_scratch_bytes(P)), dtype=torch.uint8, device=dev)
+        self.step = 0
+
+    def begin(self, params, time_idx):
+        import ctypes as C
+        from . import _lib
+        rots, trans = _pose_columns(params)
+        _lib.check(_lib.get().gs_tracking_begin(C.c_void_p(rots.data_ptr()), C.c_void_p(trans.data_ptr()), int(rots.shape[-1]), int(time_idx),
+                                                C.c_void_p(self.state.data_ptr()), _lib.stream_ptr(self.device)))
+        self.step = 0
+
+
+def _pose_columns(params):
+    rots, trans = params["cam_unnorm_rots"].data, params["cam_trans"].data
+    ok = all(x.dtype == torch.float32 and x.is_contiguous() and x.device == params["means3D"].device and x.dim() == 3 and x.shape[0] == 1
+             for x in (rots, trans))
+    if not ok or rots.shape[1] != 4 or trans.shape[1] != 3 or rots.shape[2] != trans.shape[2]:
+        raise RuntimeError("tracking: params['cam_unnorm_rots'] [1,4,T] and params['cam_trans'] [1,3,T] must be contiguous float32 tensors on the "
+                           "parameters' device (the kernels update column t in place)")
+    return rots, trans
+
+
+@torch.no_grad()
+def tracking_render(params, curr_data, variables, time_idx):
+    """The forward of one fused tracking iteration: the raw-parameter per-Gaussian kernels with the pose read from params['cam_unnorm_rots'] /
+    params['cam_trans'][..., time_idx] on the device (gs_preprocess_forward_raw_dev), then the render.  variables['max_2D_radius'] and ['seen']
+    are updated in the kernel, as get_loss(tracking=True) updates them.  -> (ctx for rasterizer.backward_pose_dev, (im, radius, depth,
+    silhouette, depth_sq))."""
+    from . import rasterizer as R
+    rots, trans = _pose_columns(params)
+    mx = variables["max_2D_radius"]
+    means = params["means3D"]
+    if not (mx.dtype == torch.float32 and mx.is_contiguous() and mx.device == means.device and mx.numel() == means.shape[0]):
+        raise RuntimeError("tracking: variables['max_2D_radius'] must be a contiguous float32 [N] tensor on the parameters' device")
+    shs = params.get("shs")
+    if shs is not None and int(shs.shape[1]) != 16:
+        raise Exception("tracking: SH rows of 16 coefficients only")
+    seen = torch.empty(mx.numel(), dtype=torch.bool, device=mx.device)
+    m2d = torch.empty_like(means)
+    iso = int(params["log_scales"].shape[1]) == 1
+    rctx = _DirectCtx()
+    out = R._RasterizeGaussians.forward(
+        rctx, means, m2d, shs, None if shs is not None else params["rgb_colors"], params["logit_opacities"], params["log_scales"],
+        params["unnorm_rotations"], None, curr_data["cam"], True, (None, iso, False, (mx, seen), None, False, (rots, trans, int(time_idx))))
+    variables["seen"] = seen
+    return rctx, out
+
+
+@torch.no_grad()
+def tracking_iteration(params, curr_data, variables, time_idx, tracking_cfg, state, history_row=None):
+    """One fused tracking iteration without autograd and without a host wait beyond the render's counters: device-pose forward + render,
+    gs_tracking_loss (value and gradient images), the pose-only backward (gs_render_backward_raw_pose_dev), gs_tracking_step (loss and pose
+    reductions, F.normalize's Jacobian, torch.optim.Adam on params['cam_*'][..., time_idx] in place, the best candidate).  `state`: a
+    TrackingState of this frame (begin() called); history_row: an optional [10] device row {loss, depth, im, the 7 post-step values}.
+    use_l1 with ignore_outlier_depth_loss=False only (the outlier rule needs a median: track_frame(fused=False))."""
+    import ctypes as C
+    from . import _lib
+    from . import rasterizer as R
+    cfg = tracking_cfg
+    if not cfg.get("use_l1", True) or cfg.get("ignore_outlier_depth_loss", False):
+        raise Exception("tracking_iteration: use_l1 without ignore_outlier_depth_loss only (the outlier rule's median stays on the torch loss: "
+                        "track_frame(fused=False))")
+    lib = _lib.get()
+    rctx, (im, _radius, depth, sil, depth_sq) = tracking_render(params, curr_data, variables, time_idx)
+    dev = state.device
+    st = _lib.stream_ptr(dev)
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    lw = cfg["loss_weights"]
+    use_sil = bool(cfg["use_sil_for_loss"])
+    gt_im, gt_d = R._f32(curr_data["im"], dev), R._f32(curr_data["depth"], dev)
+    g = state.grads
+    _lib.check(lib.gs_tracking_loss(state.W, state.H, p(im), p(gt_im), p(depth), p(depth_sq), p(gt_d), p(sil if use_sil else None), 1 if use_sil else 0,
+                                    float(cfg["sil_thres"]), float(lw["im"]), float(lw["depth"]), p(g[:3]), p(g[3:]), p(state.loss_rows), None, st))
+    R.backward_pose_dev(rctx, g[:3], g[3:], state.pose_rows)
+    rots, trans = _pose_columns(params)
+    state.step += 1
+    lrs = cfg["lrs"]
+    _lib.check(lib.gs_tracking_step(state.P, p(state.pose_rows), state.W, state.H, p(state.loss_rows), float(lw["im"]), float(lw["depth"]),
+                                    p(rots), p(trans), int(rots.shape[-1]), int(time_idx), float(lrs["cam_unnorm_rots"]), float(lrs["cam_trans"]),
+                                    state.step, p(state.state), p(history_row), st))
+
+
+def track_frame(params, curr_data, variables, time_idx, tracking_cfg=None, fused=True, history=False):
+    """SplaTAM's tracking of frame time_idx: tracking_iters iterations of the tracking loss on params['cam_unnorm_rots'] / params['cam_trans']
+    [..., time_idx] (Adam, lrs of the tracking config), then -- with use_depth_loss_thres, when the last iteration's depth loss is not below
+    depth_loss_thres -- as many again (no third round); the column ends as the best candidate: the pose after the step of the first iteration
+    with the smallest loss.  fused=True: tracking_iteration (HIP; one host read of the last depth loss per round).  fused=False: the reference
+    call pattern -- get_loss(tracking=True) on the unfused path, backward, optim.initialize_optimizer(tracking=True), the candidate and the
+    doubling rule in Python.  -> dict(iterations, final_loss, candidate_loss[, history [iterations, 10]: loss, depth, im, post-step pose])."""
+    cfg = tracking_config(tracking_cfg)
+    n = int(cfg["tracking_iters"])
+    if fused:
+        W, H = int(curr_data["cam"].image_width), int(curr_data["cam"].image_height)
+        state = TrackingState(params, W, H)
+        state.begin(params, time_idx)
+        hist = torch.empty(2 * n, 10, dtype=torch.float32, device=state.device) if history else None
+        total = n
+        k = 0
+        while True:
+            while k < total:
+                tracking_iteration(params, curr_data, variables, time_idx, cfg, state, None if hist is None else hist[k])
+                k += 1
+            if total == n and cfg["use_depth_loss_thres"] and not float(state.state[23]) < float(cfg["depth_loss_thres"]):
+                total = 2 * n
+                continue
+            break
+        with torch.no_grad():
+            params["cam_unnorm_rots"].data[0, :, time_idx] = state.state[15:19]
+            params["cam_trans"].data[0, :, time_idx] = state.state[19:22]
+        out = dict(iterations=k, final_loss=float(state.state[22]), candidate_loss=float(state.state[14]))
+        if hist is not None:
+            out["history"] = hist[:k].cpu()
+        return out
+    from . import optim as O
+    track = {k: params[k] for k in ("cam_unnorm_rots", "cam_trans")}
+    opt = O.initialize_optimizer(track, cfg["lrs"], tracking=True)
+    min_loss, cand = 1e20, None
+    cand = (params["cam_unnorm_rots"][..., time_idx].detach().clone(), params["cam_trans"][..., time_idx].detach().clone())
+    rows = []
+    total, k = n, 0
+    while True:
+        loss, variables, losses = get_loss(params, curr_data, variables, time_idx, cfg["loss_weights"], cfg["use_sil_for_loss"], cfg["sil_thres"],
+                                           cfg["use_l1"], cfg["ignore_outlier_depth_loss"], tracking=True)
+        loss.backward()
+        opt.step()
+        opt.zero_grad(set_to_none=True)
+        with torch.no_grad():
+            if loss < min_loss:
+                min_loss = loss
+                cand = (params["cam_unnorm_rots"][..., time_idx].detach().clone(), params["cam_trans"][..., time_idx].detach().clone())
+            if history:
+                rows.append(torch.cat([torch.stack([loss.detach(), losses["depth"].detach(), losses["im"].detach()]).float(),
+                                       params["cam_unnorm_rots"][0, :, time_idx].detach(), params["cam_trans"][0, :, time_idx].detach()]))
+        k += 1
+        if k == total:
+            if losses["depth"] < cfg["depth_loss_thres"] and cfg["use_depth_loss_thres"]:
+                break
+            elif cfg["use_depth_loss_thres"] and total == n:
+                total = 2 * n
+            else:
+                break
+    with torch.no_grad():
+        params["cam_unnorm_rots"][..., time_idx] = cand[0]
+        params["cam_trans"][..., time_idx] = cand[1]
+    out = dict(iterations=k, final_loss=float(loss.detach()), candidate_loss=float(min_loss.detach() if torch.is_tensor(min_loss) else min_loss))
+    if history:
+        out["history"] = torch.stack(rows).cpu()
+    return out
+
+
 def get_pointcloud(color, depth, intrinsics, w2c, transform_pts=True, mask=None, compute_mean_sq_dist=False):
     H, W = color.shape[1], color.shape[2]
     dev = color.device

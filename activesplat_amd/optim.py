@@ -191,7 +191,8 @@ def prune_event(iter, prune_dict) -> bool:
 
 def initialize_optimizer(params, lrs_dict, tracking=False):
     groups = [{"params": [v], "name": k, "lr": lrs_dict[k]} for k, v in params.items()]
-    return GaussianAdam(groups) if tracking else GaussianAdam(groups, lr=0.0, eps=1e-15)
+    # tracking: torch.optim.Adam(param_groups) -- eps 1e-8 (splatam.py:118-124); mapping: lr 0, eps 1e-15
+    return GaussianAdam(groups, eps=1e-8) if tracking else GaussianAdam(groups, lr=0.0, eps=1e-15)
 
 
 def inverse_sigmoid(x):

@@ -188,7 +188,17 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.cam_inputs = cam_rot is not None         # the backward then owes autograd two more entries (None when the camera is frozen)
         want_bwd = 1 if any(ctx.needs_input_grad[:8]) or pose_req is not None else 0
         pose = None
-        if raw is not None:
+        devpose = raw[6] if raw is not None and len(raw) > 6 else None
+        ctx.devpose = devpose
+        if devpose is not None:
+            # tracking (mapping.tracking_iteration): the pose is read by the kernels from cam_unnorm_rots[0, :, t] / cam_trans[0, :, t] in place
+            rots_p, trans_p, t_idx = devpose
+            vis_max, vis_seen = raw[3] if raw[3] is not None else (None, None)
+            _lib.check(lib.gs_preprocess_forward_raw_dev(C.byref(cam), P, _ptr(means3D), _ptr(shs), _ptr(colors_precomp), _ptr(opacities),
+                                                         _ptr(scales), _ptr(rotations), _ptr(rots_p), _ptr(trans_p), int(rots_p.shape[-1]),
+                                                         int(t_idx), 1 if raw[1] else 0, _ptr(vis_max), _ptr(vis_seen), _ptr(radii), _ptr(geom),
+                                                         _ptr(image), _ptr(d_num), _ptr(h_num), want_bwd, st))
+        elif raw is not None:
             pose = (C.c_float * 7)(*[float(v) for v in raw[0]])
             vis_max, vis_seen = raw[3] if len(raw) > 3 and raw[3] is not None else (None, None)
             _lib.check(lib.gs_preprocess_forward_raw(C.byref(cam), P, _ptr(means3D), _ptr(shs), _ptr(colors_precomp), _ptr(opacities),
@@ -402,6 +412,30 @@ class _RasterizeGaussians(torch.autograd.Function):
             _ptr(d_m2d), _ptr(d_m3d), _ptr(d_op), _ptr(d_col), _ptr(d_shs), _ptr(d_sc), _ptr(d_rot), _ptr(d_cov),
             _ptr(scratch), 1 if clean else 0, int(ctx.sh_jac), _stream(device)))
         return d_m3d, d_m2d, d_shs, d_col, d_op, d_sc, d_rot, d_cov, None, None, None
+
+
+def backward_pose_dev(ctx, grad_color, grad_depth, pose_scratch, d_pose=None):
+    """The pose-only backward of a render whose forward read the pose from the device (raw[6], mapping.tracking_iteration):
+    gs_render_backward_raw_pose_dev.  The per-workgroup pose rows go to pose_scratch (gs_pose_grad_scratch_bytes(P) bytes); d_pose [7] (optional)
+    receives dL/d(qw,qx,qy,qz,tx,ty,tz) of the normalised column.  -> dL/dmeans2D [P,3]."""
+    lib = _lib.get()
+    means3D, shs, colors, scales, rots, _cov, radii, geom, point_list, image = ctx.saved_tensors
+    has_sh, has_col = ctx.has[0], ctx.has[1]
+    device = means3D.device
+    P = int(means3D.shape[0])
+    _pose, iso, _acc, logit = ctx.raw
+    rots_p, trans_p, t_idx = ctx.devpose
+    scratch, clean = ctx.scratch, ctx.scratch_clean
+    if scratch is None:
+        scratch, clean = torch.empty(int(lib.gs_backward_scratch_bytes(P)), dtype=torch.uint8, device=device), False
+    ctx.scratch, ctx.scratch_clean = None, False
+    d_m2d = torch.empty(P, 3, dtype=torch.float32, device=device)
+    _lib.check(lib.gs_render_backward_raw_pose_dev(
+        C.byref(ctx.cam), P, ctx.D, _ptr(means3D), _ptr(shs if has_sh else None), _ptr(colors if has_col else None), _ptr(logit), _ptr(scales),
+        _ptr(rots), _ptr(rots_p), _ptr(trans_p), int(rots_p.shape[-1]), int(t_idx), iso, _ptr(radii), _ptr(geom), _ptr(point_list), _ptr(image),
+        _ptr(_f32(grad_color, device)), _ptr(None if grad_depth is None else _f32(grad_depth, device)), _ptr(d_m2d), _ptr(scratch),
+        1 if clean else 0, int(ctx.sh_jac), _ptr(d_pose), _ptr(pose_scratch), _stream(device)))
+    return d_m2d
 
 
 #: the drop-in call goes through the C++ autograd front-end (csrc/torch_frontend.cpp: the same library calls in the same order as

@@ -181,7 +181,7 @@ const char* gs_version(void);
 /* Integer version of THIS binary interface: bumped whenever an entry point's argument list or a published record layout changes (e.g.
  * the seed argument of gs_densify_children, the 40-byte SH Jacobian record).  A host binding compares it with the GS_ABI_VERSION it was
  * written against before the first call, so that a stale prebuilt library fails at load time instead of misreading its arguments. */
-#define GS_ABI_VERSION 11
+#define GS_ABI_VERSION 12
 int32_t gs_abi_version(void);
 
 /* Optional per-stage timing (hipEvents recorded on the caller's stream around each stage's launches).
@@ -388,6 +388,62 @@ uint64_t gs_mapping_loss_scratch_bytes(int32_t width, int32_t height);
 int gs_mapping_loss(int32_t width, int32_t height, const float* im, const float* gt_im, const float* depth,
                     const float* depth_sq, const float* gt_depth, float w_im, float w_depth, float* losses,
                     float* dL_dim, float* dL_ddepth, void* scratch, int64_t persistent_call, gs_stream_t stream);
+
+/* ---- Camera tracking on the device (SplaTAM's per-frame pose optimisation; tracking loss src/mapper/splatam/splatam.py:220-249) ----
+ * One iteration, no host round trip beyond the render's counters:
+ *   gs_preprocess_forward_raw_dev -> gs_render_forward -> gs_tracking_loss -> gs_render_backward_raw_pose_dev -> gs_tracking_step
+ * The pose lives in the caller's parameter tensors cam_unnorm_rots [1,4,T] and cam_trans [1,3,T] (contiguous fp32, DEVICE): column time_idx
+ * (stride num_frames = T) is read in place by the kernels, the quaternion normalised as F.normalize does (x / max(|x|, 1e-12)), and the step
+ * updates that column in place.  What stays on torch: ignore_outlier_depth_loss (a median), and tracking on the activation path. */
+
+/* Tracking loss, value and gradient in one pass (tracking=True, use_l1=True):
+ *   mask  = (gt_depth > 0) & !isnan(depth) & !isnan(depth_sq - depth^2), & (silhouette > sil_thres) when use_sil_for_loss
+ *   depth = sum_mask |gt_depth - depth| ;  im = sum |gt_im - im| over the mask tiled to 3 channels (use_sil_for_loss) or over every pixel
+ *   dL_ddepth [1,H,W] = w_depth sign(depth - gt_depth) [mask], dL_dim [3,H,W] = w_im sign(im - gt_im) [colour mask]  (sign(0) = 0; the
+ *   values, signed zeros included, are autograd's for loss = w_depth depth + w_im im).  silhouette [1,H,W] may be NULL without use_sil_for_loss.
+ * loss_rows: gs_tracking_loss_scratch_bytes(width, height) bytes, one row of partial sums per workgroup (no atomics).  losses (DEVICE, may be
+ * NULL) = {w_depth depth + w_im im, w_depth depth, w_im im}, the rows reduced in fp64 in a fixed order: bit-identical from call to call.
+ * gs_tracking_step reduces the same rows itself. */
+uint64_t gs_tracking_loss_scratch_bytes(int32_t width, int32_t height);
+int gs_tracking_loss(int32_t width, int32_t height, const float* im, const float* gt_im, const float* depth, const float* depth_sq,
+                     const float* gt_depth, const float* silhouette, int32_t use_sil_for_loss, float sil_thres, float w_im, float w_depth,
+                     float* dL_dim, float* dL_ddepth, void* loss_rows, float* losses, gs_stream_t stream);
+
+/* gs_preprocess_forward_raw with the pose read from device memory: cam_unnorm_rots[0, :, time_idx], cam_trans[0, :, time_idx] in place of
+ * h_pose7 (everything else, the visibility statistics included, as gs_preprocess_forward_raw). */
+int gs_preprocess_forward_raw_dev(const GsCamera* cam, int32_t P, const float* means3D, const float* shs, const float* colors_precomp,
+                                  const float* logit_opacities, const float* log_scales, const float* unnorm_rotations,
+                                  const float* cam_unnorm_rots, const float* cam_trans, int64_t num_frames, int64_t time_idx, int32_t isotropic,
+                                  float* max_2D_radius, uint8_t* seen, int32_t* radii, void* geom_state, void* image_state, uint32_t* d_counts,
+                                  uint32_t* h_counts, int32_t want_backward, gs_stream_t stream);
+
+/* gs_render_backward_raw_pose with pose_only = 1 and the pose read from device memory (as gs_preprocess_forward_raw_dev).  The per-workgroup
+ * pose rows go to pose_scratch (gs_pose_grad_scratch_bytes(P)); dL_dpose7 (DEVICE, may be NULL: gs_tracking_step reduces the rows itself) =
+ * dL/d(qw,qx,qy,qz,tx,ty,tz) of the NORMALISED column, as gs_render_backward_raw_pose's of the h_pose7 it receives.  dL_dmeans2D is written. */
+int gs_render_backward_raw_pose_dev(const GsCamera* cam, int32_t P, int64_t D, const float* means3D, const float* shs, const float* colors_precomp,
+                                    const float* logit_opacities, const float* log_scales, const float* unnorm_rotations,
+                                    const float* cam_unnorm_rots, const float* cam_trans, int64_t num_frames, int64_t time_idx, int32_t isotropic,
+                                    const int32_t* radii, const void* geom_state, const uint32_t* point_list, const void* image_state,
+                                    const float* dL_dcolor, const float* dL_ddepth, float* dL_dmeans2D, void* scratch, int32_t scratch_zeroed,
+                                    int32_t have_sh_jacobian, float* dL_dpose7, void* pose_scratch, gs_stream_t stream);
+
+/* Per-frame tracking state (gs_tracking_state_bytes() bytes, DEVICE; 32 floats): [0,7) Adam first moments, [7,14) second moments, [14] the
+ * smallest loss so far, [15,22) the candidate pose (qw..qz unnormalised, tx..tz), [22,25) the last step's {loss, depth, im} (weighted), [25] the
+ * number of steps skipped.  gs_tracking_begin starts a frame: moments 0, smallest loss 1e20, candidate = the column as it is (a fresh
+ * torch.optim.Adam per frame, as the reference builds one). */
+uint64_t gs_tracking_state_bytes(void);
+int gs_tracking_begin(const float* cam_unnorm_rots, const float* cam_trans, int64_t num_frames, int64_t time_idx, void* state, gs_stream_t stream);
+
+/* The tail of tracking iteration `step` (1-based), one workgroup: (1) the loss rows of gs_tracking_loss (same width, height, weights) reduced as
+ * that call reduces them; (2) the pose rows of gs_render_backward_raw_pose_dev (same P) reduced as gs_render_backward_raw_pose reduces them, then
+ * taken through F.normalize's Jacobian at the unnormalised column: dL/dcam_unnorm_rots[..., t] and dL/dcam_trans[..., t]; (3) torch.optim.Adam's
+ * update of those 7 values in place (betas 0.9 / 0.999, eps 1e-8, lr_rot for the quaternion and lr_trans for the translation, the bias
+ * corrections of `step`, torch's fp32 operation order); skipped while a chained backward in front has failed (gs_async_status_word);
+ * (4) the best candidate: loss < the smallest loss so far (strict) -> that loss and the column AFTER this update become the candidate;
+ * (5) history_row (DEVICE, may be NULL) = {loss, depth, im, the 7 values after the update}. */
+int gs_tracking_step(int32_t P, const void* pose_scratch, int32_t width, int32_t height, const void* loss_rows, float w_im, float w_depth,
+                     float* cam_unnorm_rots, float* cam_trans, int64_t num_frames, int64_t time_idx, double lr_rot, double lr_trans, int32_t step,
+                     void* state, float* history_row, gs_stream_t stream);
 
 
 /* Stream compaction for prune / densify surgery (replaces the boolean-mask gathers of
