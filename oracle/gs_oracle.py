@@ -83,16 +83,19 @@ class Oracle:
         return c
 
     # -- forward --------------------------------------------------------------------------
-    def forward(self, cam: dict, means3D, opacities, colors=None, shs=None, scales=None, rotations=None,
-                cov3D_precomp=None) -> dict:
+    def preprocess(self, cam: dict, means3D, opacities, colors=None, shs=None, scales=None, rotations=None,
+                   cov3D_precomp=None) -> dict:
+        """The per-Gaussian stage alone (gso_preprocess): radii, xy, depth, cov2d, conic_opacity, rgb, clamped, rect, tiles_touched,
+        offsets, cov3d and D -- no binning, no blending."""
+        return self._preprocess(cam, means3D, opacities, colors, shs, scales, rotations, cov3D_precomp)[0]
+
+    def _preprocess(self, cam, means3D, opacities, colors, shs, scales, rotations, cov3D_precomp):
         r = self._r
         means3D = r(means3D); P = means3D.shape[0]
         opac = r(opacities).reshape(-1)
         colors, shs, scales, rots, cov3 = r(colors), r(shs), r(scales), r(rotations), r(cov3D_precomp)
         M = 0 if shs is None else shs.shape[1]
         c = self._cam(cam, P, M)
-        W, H = c.W, c.H
-        gx, gy = (W + 15) // 16, (H + 15) // 16
         o = dict(radii=np.zeros(P, np.int32), xy=np.zeros((P, 2), self.real), depth=np.zeros(P, self.real),
                  cov2d=np.zeros((P, 3), self.real), conic_opacity=np.zeros((P, 4), self.real),
                  rgb=np.zeros((P, 3), self.real), clamped=np.zeros((P, 3), np.uint8),
@@ -103,6 +106,14 @@ class Oracle:
                                     _ptr(o["cov2d"]), _ptr(o["conic_opacity"]), _ptr(o["rgb"]), _ptr(o["clamped"]),
                                     _ptr(o["rect"]), _ptr(o["tiles_touched"]), _ptr(o["offsets"]), _ptr(o["cov3d"]))
         o["D"] = int(D)
+        return o, c, dict(means3D=means3D, shs=shs, scales=scales, rots=rots, colors=colors)
+
+    def forward(self, cam: dict, means3D, opacities, colors=None, shs=None, scales=None, rotations=None,
+                cov3D_precomp=None) -> dict:
+        r = self._r
+        o, c, inp = self._preprocess(cam, means3D, opacities, colors, shs, scales, rotations, cov3D_precomp)
+        W, H, D = c.W, c.H, o["D"]
+        gx, gy = (W + 15) // 16, (H + 15) // 16
         n = max(int(D), 1)
         o.update(keys_unsorted=np.zeros(n, np.uint64), ids_unsorted=np.zeros(n, np.uint32),
                  keys_sorted=np.zeros(n, np.uint64), ids_sorted=np.zeros(n, np.uint32),
@@ -120,7 +131,7 @@ class Oracle:
                                    _ptr(o["depth"]), _ptr(o["conic_opacity"]), _ptr(o["rgb"]), _ptr(o["color"]),
                                    _ptr(o["out_depth"]), _ptr(o["opacity"]), _ptr(o["final_T"]), _ptr(o["n_contrib"]),
                                    _ptr(o["depth_sq"]))
-        o["_ctx"] = dict(c=c, means3D=means3D, shs=shs, scales=scales, rots=rots, bg=bg, colors=colors)
+        o["_ctx"] = dict(c=c, bg=bg, **inp)
         return o
 
     # -- backward -------------------------------------------------------------------------
