@@ -353,7 +353,8 @@ static int preprocess_forward_impl(const GsCamera* cam, int32_t P, const float* 
                                    const float* colors_precomp, const float* opacities, const float* scales,
                                    const float* rotations, const float* cov3D_precomp, int32_t* radii, void* geom_state,
                                    void* image_state, uint32_t* d_counts, uint32_t* h_counts, int32_t want_backward, gs_stream_t stream,
-                                   const float* h_pose7, int32_t isotropic, float* max_2D_radius, uint8_t* seen, const DevPose* dp = nullptr)
+                                   const float* h_pose7, int32_t isotropic, float* max_2D_radius, uint8_t* seen, const DevPose* dp = nullptr,
+                                   const float* band = nullptr)
 {
     gs::Cam k;
     if (!make_cam(cam, k)) return fail(GS_EINVAL, "gs_preprocess_forward: invalid camera settings");
@@ -380,7 +381,12 @@ static int preprocess_forward_impl(const GsCamera* cam, int32_t P, const float* 
     hipError_t e;
     {
         ScopedStage ps(ST_PREPROCESS, st);
-        if (dp)
+        if (band) {                             // the planner's top-down maps: raw parameters + height band {upper, lower}
+            gs::CamBand kb;
+            static_cast<gs::Cam&>(kb) = k;
+            kb.band_upper = band[0]; kb.band_lower = band[1];
+            e = gs::launch_preprocess_forward_band(kb, P, means3D, colors_precomp, opacities, scales, rotations, radii, gp, st);
+        } else if (dp)
             e = gs::launch_preprocess_forward_dev(with_dev_pose(k, *dp), P, means3D, shs, colors_precomp, opacities, scales, rotations, radii, gp, st);
         else
             e = gs::launch_preprocess_forward(k, P, means3D, shs, colors_precomp, opacities, scales, rotations,
@@ -443,6 +449,53 @@ int gs_preprocess_forward_raw_dev(const GsCamera* cam, int32_t P, const float* m
                                    geom_state, image_state, d_counts, h_counts, want_backward, stream, ident, isotropic, max_2D_radius, seen, &dp);
 }
 
+static int fail_at(const char* who, const char* what, hipError_t e)
+{
+    char buf[160];
+    snprintf(buf, sizeof buf, "%s: %s %s", who, what, hipGetErrorString(e));
+    return fail(GS_ELAUNCH, "%s", buf);
+}
+
+// binning + depth sort of one forward (the tile lists behind `ranges` / point_list): shared by gs_render_forward and gs_render_forward_topdown
+static int bin_tile_lists(const char* who, const gs::Cam& k, int32_t P, int64_t D, uint32_t max_tile_instances, gs::GeomPtrs gp, uint2* ranges,
+                          const GsBinLayout& BL, char* bb, uint32_t* point_list, hipStream_t st)
+{
+    hipError_t e;
+    if (BL.path == GS_SORT_TILE_LDS) {
+        if (D > 0) {          // ranges were written by gs_preprocess_forward
+            ScopedStage ps(ST_TILE_SCATTER_SORT, st);
+            e = gs::launch_tile_scatter_sort(k, P, gp, gp.tile_base, ranges, max_tile_instances,
+                                             (unsigned long long*)(bb + BL.pairs), (unsigned long long*)(bb + BL.pairs_alt), point_list, (uint32_t)D, st);
+            if (e != hipSuccess) return fail_at(who, "tile scatter/sort", e);
+        }
+    } else {
+        e = hipMemsetAsync(ranges, 0, (size_t)k.gx * k.gy * 8, st);
+        if (e != hipSuccess) return fail_at(who, "memset", e);
+        if (k.gx * k.gy <= gs::kMaxLdsTiles) {   // per-Gaussian offsets were not needed before the sync: scan them now
+            e = gs::launch_scan_block_sums(P, gp, gp.block_sums + (P + gs::kBlock - 1) / gs::kBlock, st);
+            if (e != hipSuccess) return fail_at(who, "scan", e);
+        }
+        if (D == 0) {   // nothing visible: the emitter still writes the (all-zero) scan offsets
+            e = gs::launch_emit(k, P, gp, nullptr, nullptr, st);
+            if (e != hipSuccess) return fail_at(who, "emit", e);
+        } else {
+            uint64_t* ku = (uint64_t*)(bb + BL.keys_unsorted); uint32_t* vu = (uint32_t*)(bb + BL.vals_unsorted);
+            uint64_t* ks = (uint64_t*)(bb + BL.keys_sorted);
+            { ScopedStage ps(ST_EMIT, st); e = gs::launch_emit(k, P, gp, ku, vu, st); }
+            if (e != hipSuccess) return fail_at(who, "emit", e);
+            const int end_bit = 32 + tile_bits(k.gx * k.gy);
+            {
+                ScopedStage ps(ST_SORT, st);
+                e = gs::sort_pairs(bb + BL.sort_temp, (size_t)(BL.total_bytes - BL.sort_temp), ku, ks, vu, point_list, D, end_bit, st);
+            }
+            if (e != hipSuccess) return fail_at(who, "sort", e);
+            { ScopedStage ps(ST_RANGES, st); e = gs::launch_ranges(D, ks, ranges, st); }
+            if (e != hipSuccess) return fail_at(who, "ranges", e);
+        }
+    }
+    return GS_OK;
+}
+
 int gs_render_forward(const GsCamera* cam, int32_t P, int64_t D, uint32_t max_tile_instances, void* geom_state,
                       void* bin_state, uint32_t* point_list, void* image_state, float* out_color, float* out_depth,
                       float* out_opacity, float* out_depth_sq, void* backward_scratch, gs_stream_t stream)
@@ -462,39 +515,8 @@ int gs_render_forward(const GsCamera* cam, int32_t P, int64_t D, uint32_t max_ti
     uint2* ranges = (uint2*)(ib + IL.ranges);
     GsBinLayout BL; gs_bin_layout(D, max_tile_instances, k.W, k.H, &BL);
     char* bb = (char*)bin_state;
+    if (int rc = bin_tile_lists("gs_render_forward", k, P, D, max_tile_instances, gp, ranges, BL, bb, point_list, st)) return rc;
     hipError_t e;
-    if (BL.path == GS_SORT_TILE_LDS) {
-        if (D > 0) {          // ranges were written by gs_preprocess_forward
-            ScopedStage ps(ST_TILE_SCATTER_SORT, st);
-            e = gs::launch_tile_scatter_sort(k, P, gp, gp.tile_base, ranges, max_tile_instances,
-                                             (unsigned long long*)(bb + BL.pairs), (unsigned long long*)(bb + BL.pairs_alt), point_list, (uint32_t)D, st);
-            if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_forward: tile scatter/sort %s", hipGetErrorString(e));
-        }
-    } else {
-        e = hipMemsetAsync(ranges, 0, (size_t)k.gx * k.gy * 8, st);
-        if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_forward: memset %s", hipGetErrorString(e));
-        if (k.gx * k.gy <= gs::kMaxLdsTiles) {   // per-Gaussian offsets were not needed before the sync: scan them now
-            e = gs::launch_scan_block_sums(P, gp, gp.block_sums + (P + gs::kBlock - 1) / gs::kBlock, st);
-            if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_forward: scan %s", hipGetErrorString(e));
-        }
-        if (D == 0) {   // nothing visible: the emitter still writes the (all-zero) scan offsets
-            e = gs::launch_emit(k, P, gp, nullptr, nullptr, st);
-            if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_forward: emit %s", hipGetErrorString(e));
-        } else {
-            uint64_t* ku = (uint64_t*)(bb + BL.keys_unsorted); uint32_t* vu = (uint32_t*)(bb + BL.vals_unsorted);
-            uint64_t* ks = (uint64_t*)(bb + BL.keys_sorted);
-            { ScopedStage ps(ST_EMIT, st); e = gs::launch_emit(k, P, gp, ku, vu, st); }
-            if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_forward: emit %s", hipGetErrorString(e));
-            const int end_bit = 32 + tile_bits(k.gx * k.gy);
-            {
-                ScopedStage ps(ST_SORT, st);
-                e = gs::sort_pairs(bb + BL.sort_temp, (size_t)(BL.total_bytes - BL.sort_temp), ku, ks, vu, point_list, D, end_bit, st);
-            }
-            if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_forward: sort %s", hipGetErrorString(e));
-            { ScopedStage ps(ST_RANGES, st); e = gs::launch_ranges(D, ks, ranges, st); }
-            if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_forward: ranges %s", hipGetErrorString(e));
-        }
-    }
     {
         ScopedStage ps(ST_BLEND_FWD, st);
         e = gs::launch_blend_forward(k, ranges, point_list, gp.geom, out_color, out_depth, out_opacity,
@@ -505,6 +527,50 @@ int gs_render_forward(const GsCamera* cam, int32_t P, int64_t D, uint32_t max_ti
                                      (float*)backward_scratch, st);
     }
     if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_forward: blend %s", hipGetErrorString(e));
+    return GS_OK;
+}
+
+int gs_preprocess_forward_topdown(const GsCamera* cam, int32_t P, const float* means3D, const float* colors_precomp, const float* logit_opacities,
+                                  const float* log_scales, const float* unnorm_rotations, int32_t isotropic, float band_upper, float band_lower,
+                                  int32_t* radii, void* geom_state, void* image_state, uint32_t* d_counts, uint32_t* h_counts, gs_stream_t stream)
+{
+    if (cam && cam->num_views > 1) return fail(GS_EINVAL, "gs_preprocess_forward_topdown: one view only");
+    if (P > 0 && (!colors_precomp || !log_scales || !unnorm_rotations))
+        return fail(GS_EINVAL, "gs_preprocess_forward_topdown: null colour / scale / rotation parameters");
+    if (band_upper != band_upper || band_lower != band_lower) return fail(GS_EINVAL, "gs_preprocess_forward_topdown: NaN height band");
+    const float ident[7] = {1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};          // the parameters are rendered in the world frame: the view matrix is the camera
+    const float band[2] = {band_upper, band_lower};
+    return preprocess_forward_impl(cam, P, means3D, nullptr, colors_precomp, logit_opacities, log_scales, unnorm_rotations, nullptr, radii,
+                                   geom_state, image_state, d_counts, h_counts, 0, stream, ident, isotropic, nullptr, nullptr, nullptr, band);
+}
+
+int gs_render_forward_topdown(const GsCamera* cam, int32_t P, int64_t D, uint32_t max_tile_instances, void* geom_state, void* bin_state,
+                              uint32_t* point_list, void* image_state, float* free_opacity, uint8_t* free_map_binary, uint8_t* visible_rgb,
+                              uint8_t* visible_map_binary, gs_stream_t stream)
+{
+    gs::Cam k;
+    if (!make_cam(cam, k)) return fail(GS_EINVAL, "gs_render_forward_topdown: invalid camera settings");
+    if (k.V != 1) return fail(GS_EINVAL, "gs_render_forward_topdown: one view only");
+    if (P < 0 || D < 0 || !geom_state || !image_state || !free_opacity || !free_map_binary || !visible_rgb || !visible_map_binary)
+        return fail(GS_EINVAL, "gs_render_forward_topdown: null pointer");
+    if (((uintptr_t)free_map_binary | (uintptr_t)visible_rgb | (uintptr_t)visible_map_binary | (uintptr_t)free_opacity) & 3)
+        return fail(GS_EINVAL, "gs_render_forward_topdown: output maps must be 4-byte aligned");
+    if (D > 0 && (!bin_state || !point_list)) return fail(GS_EINVAL, "gs_render_forward_topdown: null binning workspace");
+    if (D >= (int64_t)1 << 32) return fail(GS_ECAPACITY, "gs_render_forward_topdown: more than 2^32 tile instances");
+    hipStream_t st = (hipStream_t)stream;
+    virtual_count(k, P);
+    gs::GeomPtrs gp = carve_geom(geom_state, P, k);
+    GsImageLayout IL; gs_image_layout(k.W, k.H, &IL);
+    uint2* ranges = (uint2*)((char*)image_state + IL.ranges);
+    GsBinLayout BL; gs_bin_layout(D, max_tile_instances, k.W, k.H, &BL);
+    if (int rc = bin_tile_lists("gs_render_forward_topdown", k, P, D, max_tile_instances, gp, ranges, BL, (char*)bin_state, point_list, st)) return rc;
+    hipError_t e;
+    {
+        ScopedStage ps(ST_BLEND_FWD, st);
+        e = gs::launch_blend_topdown(k, ranges, point_list, gp.geom, free_opacity, free_map_binary, visible_rgb, visible_map_binary,
+                                     BL.path == GS_SORT_TILE_LDS ? (uint32_t)D : 0xffffffffu, (uint32_t)P, st);
+    }
+    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_forward_topdown: blend %s", hipGetErrorString(e));
     return GS_OK;
 }
 

@@ -361,6 +361,163 @@ __global__ __launch_bounds__(NW * kWave) void blend_forward_streams_kernel(
 #undef GS_FILL_REST
 
 // ---------------------------------------------------------------------------------------------------
+// The planner's top-down maps (gs_render_forward_topdown; visualizer.py:923-965 renders them as two raster passes over one camera): the plain
+// streams forward above (SEG = 0, NW = 4: same gather, scan, per-stream lists and pipelining) with TWO running states per pixel --
+//   all  : (C, T) over every list entry            -> visible_rgb = bytes of C + T bg, visible_binary = grey(bytes) == 255
+//   band : T_band over the entries whose record carries the height-band bit (the sign of its opacity, preprocess.hip: CamBand)
+//                                                  -> free_opacity = 1 - T_band, free_binary = free_opacity <= 0.4
+// A tile's in-band list is a subsequence of its full list in the same order, so every entry is tested once (power, alpha >= 1/255) and
+// applied to `all`, and to `band` iff flagged; each state has its own stop (T (1 - alpha) < 1e-4) and per state the fp32 operations are the
+// ones of the forward above, in its order.  A stream's walk ends when its pixels have stopped in BOTH states.
+// No depth sums, contributor index, final_T or gradient-record side job (this path has no backward): the epilogue converts and thresholds
+// in registers and stores the four maps directly; where the image width is a multiple of 4 the four pixels of a block row go out as one
+// dword per byte map and three for the interleaved RGB bytes.  Used for every tile count: top-down grids are at most 360 pixels on the long
+// side (<= 529 tiles), so the few-tile pipeline and the segmented compositing above have no variant of this.
+// ---------------------------------------------------------------------------------------------------
+// OpenCV's 8-bit COLOR_RGB2GRAY in its published fixed-point form (14 fractional bits, coefficients 0.299 / 0.587 / 0.114, rounded)
+__host__ __device__ __forceinline__ uint32_t rgb_to_grey_u8(uint32_t r, uint32_t g, uint32_t b)
+{
+    return (4899u * r + 9617u * g + 1868u * b + 8192u) >> 14;
+}
+// (clamp(c, 0, 1) * 255) truncated: torch's / numpy's float -> uint8 conversion of the reference's image path
+__device__ __forceinline__ uint32_t unit_to_u8(float c)
+{
+    return (uint32_t)(fminf(fmaxf(c, 0.0f), 1.0f) * 255.0f);
+}
+
+__global__ __launch_bounds__(kBlock) void blend_topdown_kernel(
+    Cam cam, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, const float4* __restrict__ geom,
+    float* __restrict__ free_opacity, uint8_t* __restrict__ free_binary, uint8_t* __restrict__ visible_rgb, uint8_t* __restrict__ visible_binary,
+    uint32_t cap, uint32_t P)
+{
+    constexpr int NW = 4, NS = kFwdStreams, LS = kWave / NS;
+    __shared__ float4 s_rec[NW][3][kWave + 1];           // + the sentinel slot
+    __shared__ __attribute__((aligned(16))) uint8_t s_list[NW][NS * kWave + 16];
+    static_assert(NS == 4 && kWave / NS == 16, "the scan tests the four 4x4 blocks of a quadrant");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    TileCtx c;
+    if (!tile_ctx_nw<NW>(cam, wave, lane, c)) return;
+    const int sid = lane / LS, l = lane % LS;
+    const int px = (int)c.qx0 + (sid & 1) * 4 + (l & 3), py = (int)c.qy0 + (sid >> 1) * 4 + (l >> 2);
+    const bool inside = px < cam.W && py < cam.H;
+    const float pxf = (float)px, pyf = (float)py;
+    float4* s0 = s_rec[wave][0]; float4* s1 = s_rec[wave][1]; float4* s2 = s_rec[wave][2];
+    write_sentinel(s0, s1, s2, lane);
+    uint8_t* my_list = s_list[wave] + sid * kWave;
+    uint2 range = ranges[c.tile];
+    range.x = min(range.x, cap); range.y = min(range.y, cap);
+    const uint32_t n = range.y - range.x;
+    const uint32_t* list = point_list + range.x;
+    float T = 1.0f, Tb = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f;
+    bool done = !inside, done_b = !inside;
+
+    if (!__all(done)) {
+        // (ids that are not Gaussian indices -- the unwritten tail of an undersized list -- are "no record", as in the forward above)
+        uint32_t id_next = (uint32_t)lane < n ? list[lane] : kNoId;
+        uint32_t id_next2 = (uint32_t)lane + 64u < n ? list[lane + 64] : kNoId;
+        if (id_next >= P) id_next = kNoId;
+        if (id_next2 >= P) id_next2 = kNoId;
+        float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = make_float4(0.f, 0.f, -1.f, -1.f);
+        if (0u < n) {
+            const float4* gr = geom + (size_t)(id_next != kNoId ? id_next : 0u) * 3;
+            r0 = gr[0]; r1 = gr[1]; r2 = gr[2];
+        }
+        for (uint32_t base = 0; base < n; base += kWave) {
+            const float4 q0 = r0, q1 = r1, q2 = r2;
+            const uint32_t id_cur = id_next;
+            id_next = id_next2;
+            id_next2 = base + 128u + (uint32_t)lane < n ? list[base + 128u + lane] : kNoId;
+            if (id_next2 >= P) id_next2 = kNoId;
+            {
+                const float4* gr = geom + (size_t)(id_next != kNoId ? id_next : 0u) * 3;
+                r0 = gr[0]; r1 = gr[1]; r2 = gr[2];
+            }
+            // a stream is switched off when all its pixels have stopped in both states
+            const unsigned long long going = ~__ballot(done && done_b);
+            unsigned long long m_any, mb[4];
+            scan_blocks(q0, q2, id_cur != kNoId, c.qx0, c.qy0, (going & 0xffffull) != 0ull, (going & 0xffff0000ull) != 0ull,
+                        (going & 0xffff00000000ull) != 0ull, (going >> 48) != 0ull, m_any, mb);
+            if (m_any == 0ull) continue;
+            // staging form of the forward above; the opacity without its sign, the band bit and the blue channel in the third plane's first half
+            s0[lane] = make_float4(q0.x, q0.y, -0.5f * kLog2e * q0.z, -kLog2e * q0.w);
+            s1[lane] = make_float4(-0.5f * kLog2e * q1.x, fabsf(q1.y), q1.z, q1.w);
+            s2[lane] = make_float4(q2.x, __uint_as_float(__float_as_uint(q1.y) >> 31), 0.0f, 0.0f);
+            {
+                uint32_t* fill = reinterpret_cast<uint32_t*>(s_list[wave]);
+                constexpr int kWords = NS * kWave / 4;
+                for (int w = lane; w < kWords; w += kWave) fill[w] = 0x40404040u;
+            }
+            __builtin_amdgcn_wave_barrier();
+            int ntrips = 0;
+#pragma unroll
+            for (int s = 0; s < NS; s++) {
+                const unsigned long long m = mb[s];
+                const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                if (__builtin_amdgcn_inverse_ballot_w64(m)) s_list[wave][s * kWave + rank] = (uint8_t)lane;
+                ntrips = max(ntrips, (int)__popcll(m));
+            }
+            __builtin_amdgcn_wave_barrier();
+            uint32_t jj2_next = *reinterpret_cast<const uint16_t*>(my_list);
+            for (int t = 0; t < ntrips; t += 2) {
+                const uint32_t jj2 = jj2_next;
+                jj2_next = *reinterpret_cast<const uint16_t*>(my_list + t + 2);
+                const int jj[2] = {(int)(jj2 & 0xffu), (int)(jj2 >> 8)};
+                float4 a0[2], a1[2];
+                float2 a2[2];
+#pragma unroll
+                for (int u = 0; u < 2; u++) { a0[u] = s0[jj[u]]; a1[u] = s1[jj[u]]; a2[u] = *reinterpret_cast<const float2*>(&s2[jj[u]]); }
+#pragma unroll
+                for (int u = 0; u < 2; u++) {
+                    const float dx = a0[u].x - pxf, dy = a0[u].y - pyf;
+                    const float p = (a0[u].z * dx + a0[u].w * dy) * dx + (a1[u].x * dy) * dy;
+                    const float alpha = fminf(0.99f, a1[u].y * __builtin_amdgcn_exp2f(p));
+                    const bool hit = p <= 0.0f && alpha >= kAlphaMin;                // sentinel: alpha = 0
+                    // state `all`
+                    const float test_T = T * (1.0f - alpha);
+                    const bool vis = !done && hit;
+                    const bool ok = vis && test_T >= kTmin;
+                    done = done || (vis != ok);
+                    const float w = ok ? alpha * T : 0.0f;
+                    C0 += a1[u].z * w; C1 += a1[u].w * w; C2 += a2[u].x * w;
+                    T = ok ? test_T : T;
+                    // state `band`
+                    const float test_b = Tb * (1.0f - alpha);
+                    const bool vis_b = !done_b && hit && __float_as_uint(a2[u].y) != 0u;
+                    const bool ok_b = vis_b && test_b >= kTmin;
+                    done_b = done_b || (vis_b != ok_b);
+                    Tb = ok_b ? test_b : Tb;
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            if (__all(done && done_b)) break;
+        }
+    }
+    // epilogue: every lane takes part in the exchanges; lanes outside the image hold zeros and store nothing
+    const float fo = 1.0f - Tb;
+    const uint32_t r = unit_to_u8(C0 + T * cam.bg[0]), g = unit_to_u8(C1 + T * cam.bg[1]), b = unit_to_u8(C2 + T * cam.bg[2]);
+    const uint32_t fbit = fo <= 0.4f ? 1u : 0u, vbit = rgb_to_grey_u8(r, g, b) == 255u ? 1u : 0u;
+    const size_t pix = (size_t)py * cam.W + px;
+    if (inside) free_opacity[pix] = fo;
+    if ((cam.W & 3) == 0) {
+        // W % 4 == 0: the block row's four pixels (lanes l .. l + 3, px % 4 == 0) are all inside or all outside, and their bytes are dword-aligned
+        const uint32_t pk = r | (g << 8) | (b << 16) | (fbit << 24) | (vbit << 25);
+        const uint32_t p1 = __shfl_down(pk, 1), p2 = __shfl_down(pk, 2), p3 = __shfl_down(pk, 3);
+        if (inside && (l & 3) == 0) {
+            *reinterpret_cast<uint32_t*>(free_binary + pix) = ((pk >> 24) & 1u) | (((p1 >> 24) & 1u) << 8) | (((p2 >> 24) & 1u) << 16) | (((p3 >> 24) & 1u) << 24);
+            *reinterpret_cast<uint32_t*>(visible_binary + pix) = ((pk >> 25) & 1u) | (((p1 >> 25) & 1u) << 8) | (((p2 >> 25) & 1u) << 16) | (((p3 >> 25) & 1u) << 24);
+            uint32_t* rgb = reinterpret_cast<uint32_t*>(visible_rgb + pix * 3);
+            rgb[0] = (pk & 0xffffffu) | (p1 << 24);
+            rgb[1] = ((p1 >> 8) & 0xffffu) | (p2 << 16);
+            rgb[2] = ((p2 >> 16) & 0xffu) | (p3 << 8);
+        }
+    } else if (inside) {
+        free_binary[pix] = (uint8_t)fbit;
+        visible_binary[pix] = (uint8_t)vbit;
+        visible_rgb[pix * 3] = (uint8_t)r; visible_rgb[pix * 3 + 1] = (uint8_t)g; visible_rgb[pix * 3 + 2] = (uint8_t)b;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Forward for images of FEW tiles (at most 256: the reference's 256 x 256 frames, the planner's views): a three-stage pipeline per quadrant.
 // 256 tiles x 4 quadrants are one walker per SIMD of this chip, and a walker's trip through a 64-record chunk is one serial chain --
 // gather + stage + lists, then alpha (12 VALU + exp) and the compositing step (T, stop test, four sums: 12 more) for every list entry.
@@ -1129,6 +1286,18 @@ hipError_t launch_blend_forward(const Cam& cam_in, const uint2* ranges, const ui
         if (out_depth_sq) GS_FWD(true, 0, dim3(nb)); else GS_FWD(false, 0, dim3(nb));
     }
 #undef GS_FWD
+    return hipGetLastError();
+}
+
+hipError_t launch_blend_topdown(const Cam& cam_in, const uint2* ranges, const uint32_t* point_list, const float4* geom, float* free_opacity,
+                                uint8_t* free_binary, uint8_t* visible_rgb, uint8_t* visible_binary, uint32_t cap, uint32_t P, hipStream_t st)
+{
+    Cam cam = cam_in;
+    cam.half = 0; cam.split = 0; cam.chain = 0;
+    if (cam.V != 1) return hipErrorInvalidValue;
+    const int nb = ((cam.gx * cam.gy + 7) >> 3) << 3;
+    hipLaunchKernelGGL(blend_topdown_kernel, dim3(nb), dim3(kBlock), 0, st, cam, ranges, point_list, geom, free_opacity, free_binary, visible_rgb,
+                       visible_binary, cap, P);
     return hipGetLastError();
 }
 

@@ -75,6 +75,13 @@ struct CamDP : Cam {
     const float* dev_t;          // &cam_trans[0, 0, t]
     int64_t stride;              // T
 };
+// Height band of the planner's top-down maps (gs_preprocess_forward_topdown): the raw-parameter colour kernel instantiated with this camera type
+// also tests every Gaussian's WORLD-frame height -- in band iff !(-y < band_upper || -y > band_lower), y = means3D[i][1] as it is stored, fp32
+// (the complement of the reference's __cut_gaussian_by_height, visualizer.py: a NaN y is in band and is then culled like any non-finite input) --
+// and hands the bit to blend_topdown_kernel as the SIGN of the record's opacity (a sigmoid: never negative).  No other kernel reads such records.
+struct CamBand : Cam {
+    float band_upper, band_lower;
+};
 // F.normalize(x) = x / max(|x|, 1e-12) of one [4] column, the squares summed in index order; no FMA contraction, so that the forward, the
 // backward and the tracking step (translation units built with and without contraction) all see the same normalised quaternion
 __device__ __forceinline__ void normalize_pose_column(const float* x, int64_t stride, float (&u)[4], float& norm)
@@ -688,6 +695,8 @@ hipError_t launch_preprocess_forward_dev(const CamDP& cam, int P, const float* m
 hipError_t launch_preprocess_backward_pose_dev(const CamDP& cam, int P, const float* means3D, const float* shs, const float* scales,
                                                const float* rots, const int32_t* radii, const uint32_t* clamped, const float2* sh_jac,
                                                const float* grad2d, float* dmeans2D, const float* logit, float* pose_rows, hipStream_t st);
+hipError_t launch_preprocess_forward_band(const CamBand& cam, int P, const float* means3D, const float* colors, const float* opac, const float* scales,
+                                          const float* rots, int32_t* radii, GeomPtrs gp, hipStream_t st);
 hipError_t launch_scan_block_sums(int P, GeomPtrs gp, uint32_t* d_total, hipStream_t st);
 hipError_t launch_preprocess_backward(const Cam& cam, int P, const float* means3D, const float* shs,
                                       const float* scales, const float* rots, const float* cov3Dp,
@@ -773,6 +782,9 @@ hipError_t launch_blend_forward(const Cam& cam, const uint2* ranges, const uint3
                                 float* out_color, float* out_depth, float* out_opacity, float* final_T,
                                 uint32_t* n_contrib, float* out_depth_sq, uint32_t cap, int segments, float* seg_T, float* split_state, uint32_t P, float* zero_fill,
                                 hipStream_t st);
+// the planner's top-down maps (blend_topdown_kernel, blend.hip): geom = records of launch_preprocess_forward_band
+hipError_t launch_blend_topdown(const Cam& cam, const uint2* ranges, const uint32_t* point_list, const float4* geom, float* free_opacity,
+                                uint8_t* free_binary, uint8_t* visible_rgb, uint8_t* visible_binary, uint32_t cap, uint32_t P, hipStream_t st);
 hipError_t launch_blend_backward(const Cam& cam, const uint2* ranges, const uint32_t* point_list, const float4* geom, const float* split_state,
                                  const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor,
                                  const float* dL_ddepth, float* grad2d, hipStream_t st);

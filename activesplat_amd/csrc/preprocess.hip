@@ -9,6 +9,7 @@
 // parenthesised exactly as DESIGN.md section 3 states, so radii, tile rects, tile counts and depth-key bits
 // are reproducible to the bit by the CPU oracle.
 #include "gs_common.h"
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -54,7 +55,7 @@ template <bool HAS_SH>
 __device__ __forceinline__ uint32_t project_gaussian(const Cam& cam, int P, int view, int i, int io, int tid, const float* s_mean,
                                                      const float* s_scale, const float* s_rot, const float* s_cov, const float* s_col,
                                                      bool has_cov, float o, const float (&sh_rgb)[3], uint32_t sh_clamp,
-                                                     int32_t* __restrict__ radii, const GeomPtrs& gp, int* radius_out = nullptr)
+                                                     int32_t* __restrict__ radii, const GeomPtrs& gp, int* radius_out = nullptr, bool band = false)
 {
     uint32_t ntiles = 0;
     if (radius_out) *radius_out = 0;
@@ -168,7 +169,7 @@ __device__ __forceinline__ uint32_t project_gaussian(const Cam& cam, int P, int 
                         ey = sqrtf(tau2 * k11) + 0.01f;
                     }
                     g0 = make_float4(pxx, pyy, con_a, con_b);
-                    g1 = make_float4(con_c, o, cr, cg);
+                    g1 = make_float4(con_c, band ? -o : o, cr, cg);      // (band: CamBand kernels only -- the height-band bit as the opacity's sign)
                     g2 = make_float4(cb, tz, ex, ey);
                 }
             }
@@ -228,6 +229,8 @@ __device__ __forceinline__ float activate_staged_rows(const Cam& cam, int tid, b
 // SH: 0 = colours given, 1 = coefficient rows of any width through per-wave LDS slabs (16-coefficient rows, the layout every caller of
 // the reference uses, take preprocess_forward_sh48_kernel below)
 // CamT = CamDP (the raw-parameter mode only): the pose is read from device memory when the kernel starts (load_device_pose, gs_common.h)
+// CamT = CamBand (raw parameters with colours only): the height-band test of the planner's top-down maps on the world-frame y as it is staged,
+// BEFORE the frame transform overwrites it; the bit leaves as the sign of the record's opacity (gs_common.h)
 template <int SH, bool ACT = false, class CamT = Cam>        // ACT: raw-parameter mode (colours given or 16-coefficient rows only)
 __global__ __launch_bounds__(kBlock) void preprocess_forward_kernel(
     typename CamArg<CamT>::type cam, int P, const float* __restrict__ means3D, const float* __restrict__ shs,
@@ -270,6 +273,12 @@ __global__ __launch_bounds__(kBlock) void preprocess_forward_kernel(
         if (SH == 0) stage_rows<3>(s_col, colors, base, nrows, tid);
     }
     __syncthreads();
+    constexpr bool BAND = std::is_same<CamT, CamBand>::value;
+    bool in_band = false;
+    if constexpr (BAND) {
+        const float up = -s_mean[tid * 3 + 1];           // (rows behind P hold stale LDS: their lanes write nothing)
+        in_band = !(up < cam.band_upper || up > cam.band_lower);
+    }
     if (ACT) o_in = activate_staged_rows(cam, tid, tid < nrows, s_mean, s_scale, s_rot, o_in);
 
     // SH -> RGB for every Gaussian: each wavefront streams its own 64 coefficient rows through a private padded LDS slab,
@@ -318,7 +327,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_forward_kernel(
     }
     int radius = 0;
     const uint32_t ntiles = project_gaussian<HAS_SH>(cam, P, view, i, io, tid, s_mean, s_scale, s_rot, s_cov, s_col, cov3Dp != nullptr, o_in,
-                                                     sh_rgb, sh_clamp, radii, gp, ACT ? &radius : nullptr);
+                                                     sh_rgb, sh_clamp, radii, gp, ACT ? &radius : nullptr, in_band);
     if (ACT && i < P) {                                   // the mapper's visibility statistics of this render (raw-parameter mode)
         if (gp.vis_max) gp.vis_max[i] = fmaxf(gp.vis_max[i], (float)radius);
         if (gp.vis_seen) gp.vis_seen[i] = radius > 0 ? 1 : 0;
@@ -476,6 +485,22 @@ hipError_t launch_preprocess_forward_dev(const CamDP& cam, int P, const float* m
                            nullptr, radii, gp);
     else if (nb > 0)
         hipLaunchKernelGGL((preprocess_forward_kernel<0, true, CamDP>), dim3(nb), dim3(kBlock), 0, st, cam, P, means3D, shs, colors, opac,
+                           scales, rots, nullptr, radii, gp);
+    if ((size_t)nb * kBlock < (size_t)cam.gx * cam.gy) {
+        hipError_t e = hipMemsetAsync(gp.tile_total, 0, (size_t)cam.gx * cam.gy * 4, st);
+        if (e != hipSuccess) return e;
+    }
+    return hipGetLastError();
+}
+
+// raw parameters + height band (the planner's top-down maps): preprocess_forward_kernel<0, true> instantiated with CamBand
+hipError_t launch_preprocess_forward_band(const CamBand& cam, int P, const float* means3D, const float* colors, const float* opac, const float* scales,
+                                          const float* rots, int32_t* radii, GeomPtrs gp, hipStream_t st)
+{
+    const int nb = (P + kBlock - 1) / kBlock;
+    if (!cam.act || cam.V != 1) return hipErrorInvalidValue;
+    if (nb > 0)
+        hipLaunchKernelGGL((preprocess_forward_kernel<0, true, CamBand>), dim3(nb), dim3(kBlock), 0, st, cam, P, means3D, nullptr, colors, opac,
                            scales, rots, nullptr, radii, gp);
     if ((size_t)nb * kBlock < (size_t)cam.gx * cam.gy) {
         hipError_t e = hipMemsetAsync(gp.tile_total, 0, (size_t)cam.gx * cam.gy * 4, st);

@@ -335,6 +335,15 @@ class SplatMapper:
         return im, depth, opacity
 
     @torch.no_grad()
+    def topdown_maps(self, world_center, world_shape, grid_shape, upper, lower, height=1000.0, scale_modifier=0.01):
+        """The planner's free map and visible map (visualizer.py:923-965) of the current map in one fused raster pass: world_center = (x, z),
+        world_shape = (metres along x, metres along z), grid_shape = (W, H) as `get_topdown_cam` takes them from `topdown_info`; the height
+        band as the visualiser cuts it (upper = agent_head, lower = agent_foot - agent_foot_adjust).  -> topdown.TopdownMaps (device tensors)."""
+        from . import topdown as TD
+        cam = TD.topdown_camera(world_center, world_shape, grid_shape, height=height, scale_modifier=scale_modifier, device=self.device)
+        return TD.topdown_maps(self.params, cam, upper, lower, scale_modifier=scale_modifier)
+
+    @torch.no_grad()
     def invisibility(self, w2c, width=120, height=150, intrinsics=None):
         """1 - opacity, the quantity the planner scores view points with (__init__.py:739,795)."""
         _, _, opacity = self.render_rgbd(w2c, width=width, height=height, intrinsics=intrinsics)

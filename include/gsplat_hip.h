@@ -181,7 +181,7 @@ const char* gs_version(void);
 /* Integer version of THIS binary interface: bumped whenever an entry point's argument list or a published record layout changes (e.g.
  * the seed argument of gs_densify_children, the 40-byte SH Jacobian record).  A host binding compares it with the GS_ABI_VERSION it was
  * written against before the first call, so that a stale prebuilt library fails at load time instead of misreading its arguments. */
-#define GS_ABI_VERSION 12
+#define GS_ABI_VERSION 13
 int32_t gs_abi_version(void);
 
 /* Optional per-stage timing (hipEvents recorded on the caller's stream around each stage's launches).
@@ -416,6 +416,35 @@ int gs_preprocess_forward_raw_dev(const GsCamera* cam, int32_t P, const float* m
                                   const float* cam_unnorm_rots, const float* cam_trans, int64_t num_frames, int64_t time_idx, int32_t isotropic,
                                   float* max_2D_radius, uint8_t* seen, int32_t* radii, void* geom_state, void* image_state, uint32_t* d_counts,
                                   uint32_t* h_counts, int32_t want_backward, gs_stream_t stream);
+
+/* The planner's top-down maps (src/visualizer/visualizer.py:923-965: the free map and the visible map the Voronoi planner thresholds) from the
+ * map's PARAMETERS in ONE raster pass.  The reference renders them as two passes through one camera (1000 m above the scene, scale_modifier
+ * 0.01): the Gaussians between the agent's head and foot (__cut_gaussian_by_height) for the accumulated opacity, every Gaussian on a white
+ * background for the image.  Both share camera, projection, tile rectangles and depth order, and a tile's in-band list is a subsequence of its
+ * full list, so here every pixel carries two running states through one walk.
+ *   gs_preprocess_forward_topdown : gs_preprocess_forward_raw (colours given, identity pose: cam->viewmatrix is the world-to-camera matrix)
+ *       that also tests every Gaussian's height -- IN BAND iff !(-y < band_upper || -y > band_lower), y = means3D[i][1] as stored, fp32: the
+ *       complement of the reference's cut, both ends inclusive; a NaN y is in band and is then culled like any non-finite input.  The
+ *       visualiser passes band_upper = agent_head, band_lower = agent_foot - agent_foot_adjust.  The bit travels as the SIGN of the opacity
+ *       in the 48-byte record: geom_state of this call is for gs_render_forward_topdown only.  Everything else -- radii, rects, counts,
+ *       d_counts / h_counts, the caller's synchronisation -- as gs_preprocess_forward_raw.  image_state: only its tile ranges are used
+ *       (GsImageLayout.ranges, the first region: a buffer of GsImageLayout.final_T bytes is enough).  A NaN band is refused (GS_EINVAL).
+ *   gs_render_forward_topdown : binning and depth sort as gs_render_forward (same capacities, also capacity-safe and idempotent), then one
+ *       blend launch that writes, all DEVICE, 4-byte aligned:
+ *         free_opacity       float32 [H*W]   : 1 - T composited over the in-band Gaussians only
+ *         free_map_binary    uint8   [H*W]   : free_opacity <= 0.4f
+ *         visible_rgb        uint8   [H*W*3] : (clamp(colour, 0, 1) * 255) truncated, interleaved RGB; colour = all Gaussians over cam->bg
+ *                                              (the reference: white)
+ *         visible_map_binary uint8   [H*W]   : grey(visible_rgb) == 255, grey = (4899 R + 9617 G + 1868 B + 8192) >> 14 (OpenCV's 8-bit
+ *                                              COLOR_RGB2GRAY in its published fixed-point form)
+ *       Per state the fp32 operations per list entry are gs_render_forward's, in its order (stop rule T (1 - alpha) < 1e-4 per state).
+ *       No depth, final_T, contributor index or backward state is written: there is no backward of this path.  One view only. */
+int gs_preprocess_forward_topdown(const GsCamera* cam, int32_t P, const float* means3D, const float* colors_precomp, const float* logit_opacities,
+                                  const float* log_scales, const float* unnorm_rotations, int32_t isotropic, float band_upper, float band_lower,
+                                  int32_t* radii, void* geom_state, void* image_state, uint32_t* d_counts, uint32_t* h_counts, gs_stream_t stream);
+int gs_render_forward_topdown(const GsCamera* cam, int32_t P, int64_t D, uint32_t max_tile_instances, void* geom_state, void* bin_state,
+                              uint32_t* point_list, void* image_state, float* free_opacity, uint8_t* free_map_binary, uint8_t* visible_rgb,
+                              uint8_t* visible_map_binary, gs_stream_t stream);
 
 /* gs_render_backward_raw_pose with pose_only = 1 and the pose read from device memory (as gs_preprocess_forward_raw_dev).  The per-workgroup
  * pose rows go to pose_scratch (gs_pose_grad_scratch_bytes(P)); dL_dpose7 (DEVICE, may be NULL: gs_tracking_step reduces the rows itself) =

@@ -1,6 +1,9 @@
 """The planner's top-down map camera on the HIP path (GPU box): src/visualizer/visualizer.py:923-937 renders the map TWICE per GUI tick through a
 camera 1000 m up (:1577-1601) with scale_modifier 0.01 -- the height-cut "free map" with opacity colours and the visible map -- both
-forward-only.  Prints JSON: per-render and per-tick milliseconds, per-stage hipEvent averages, and the blend forward with the few-tile
+forward-only.  Second part ("one_tick_from_parameters"): one tick = both boolean maps from the map's PARAMETERS, (a) the composition a port of
+visualizer.py:923-965 makes on this library -- clone, cut_gaussian_by_height, torch activations, two renders, byte / grey / threshold in torch
+on the device -- against (b) topdown.topdown_maps, one fused pass: five alternating repeats of 60 ticks between device events each, medians
+and spread, and the raster stages of both.  (Every kernel (a) launches is instruction-for-instruction the parent commit's.)  Prints JSON: per-render and per-tick milliseconds, per-stage hipEvent averages, and the blend forward with the few-tile
 (producer / consumer) kernel forced on for this 437 / 529-tile view against the plain streams kernel (which the 257..768-tile band uses)."""
 import json
 import os
@@ -69,4 +72,69 @@ for W, H in ((360, 300), (368, 368)):
         finally:
             _lib.check(lib.gs_set_half_quadrants(256))
     out[f"{W}x{H}"] = res
+
+
+def one_tick_from_parameters(W, H, reps=5, ticks=60):
+    import statistics
+    import torch.nn.functional as F
+    from activesplat_amd import io as IO, topdown as TD
+    from tests import topdown_cases as tc
+    params = tc.scene_params(N, W, H, dev)
+    upper, lower = tc.BAND
+    cam = TD.topdown_camera(tc.CENTRE, tc.EXTENT, (W, H), device=dev)
+    black = cam._replace(bg=torch.zeros(3, device=dev))
+    m2d = torch.zeros(N, 3, device=dev)
+
+    def activate(p):
+        ls = p["log_scales"]
+        return dict(means3D=p["means3D"], colors_precomp=p["rgb_colors"], rotations=F.normalize(p["unnorm_rotations"]),
+                    opacities=torch.sigmoid(p["logit_opacities"]), scales=torch.exp(torch.tile(ls, (1, 3)) if ls.shape[1] == 1 else ls))
+
+    def tick_a():
+        with torch.no_grad():
+            p = IO.cut_gaussian_by_height({k: v.clone() for k, v in params.items()}, upper, lower)
+            free = activate(p)
+            opacity = GaussianRasterizer(raster_settings=black)(means2D=torch.zeros_like(free["means3D"]), **free)[3]
+            color = GaussianRasterizer(raster_settings=cam)(means2D=m2d, **activate(params))[0]
+            free_bin = (opacity[0] <= 0.4).to(torch.uint8)
+            rgb = (color.clamp(0.0, 1.0) * 255.0).to(torch.uint8).permute(1, 2, 0).contiguous()
+            return opacity[0], free_bin, rgb, (TD.rgb_to_grey_u8(rgb) == 255).to(torch.uint8)
+
+    def tick_b():
+        return TD.topdown_maps(params, cam, upper, lower)
+
+    def window(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(ticks):
+            fn()
+        e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / ticks
+
+    for fn in (tick_a, tick_b):
+        for _ in range(10):
+            fn()
+    torch.cuda.synchronize()
+    ta, tb = [], []
+    for _ in range(reps):                                  # alternating: both see the same neighbours on a shared host
+        ta.append(window(tick_a)); tb.append(window(tick_b))
+    res = {"composition_ms": [round(t, 4) for t in ta], "fused_ms": [round(t, 4) for t in tb],
+           "composition_median_ms": round(statistics.median(ta), 4), "composition_spread_ms": round(max(ta) - min(ta), 4),
+           "fused_median_ms": round(statistics.median(tb), 4), "fused_spread_ms": round(max(tb) - min(tb), 4)}
+    res["fused_wins_by_more_than_the_spread"] = bool(statistics.median(ta) - statistics.median(tb) > max(ta) - min(ta))
+    for name, fn in (("composition", tick_a), ("fused", tick_b)):
+        lib.gs_profile_enable(1)
+        for _ in range(20):
+            fn()
+        torch.cuda.synchronize()
+        st = {k: (ms, c) for k, (ms, c) in _lib.profile_collect().items() if c}
+        lib.gs_profile_enable(0)
+        res["stages_us_per_tick_" + name] = {k: round(ms / 20 * 1e3, 1) for k, (ms, c) in st.items()}
+        res["raster_us_per_tick_" + name] = round(sum(ms for ms, _ in st.values()) / 20 * 1e3, 1)
+    a, b = tick_a(), tick_b()
+    res["differing_pixels_composition_vs_fused"] = [int((x != y).reshape(H * W, -1).any(1).sum()) for x, y in zip(a, b)]
+    return res
+
+
+out["one_tick_from_parameters"] = {f"{W}x{H}": one_tick_from_parameters(W, H) for W, H in ((360, 300), (368, 368))}
 print(json.dumps(out))
