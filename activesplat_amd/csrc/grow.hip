@@ -28,14 +28,18 @@ __device__ __forceinline__ float depth_error(const float* __restrict__ gt, const
 
 // torch.median of a flat tensor = the LOWER median, element (n-1)/2 of the sorted values.  err >= 0, so the order of the
 // floats is the order of their bit patterns: three histogram passes (11 + 11 + 10 bits) pin the value exactly.
+// NaN rule: torch.median propagates NaN -- if ANY error is NaN (a NaN in either depth image, or inf * 0 where gt <= 0) the median is NaN,
+// `err > 2 median` is false everywhere and only the silhouette candidates remain.  The first pass raises a flag for it (a NaN's bit pattern
+// would otherwise be counted as the largest value and a finite median come out).
 __global__ __launch_bounds__(kSelectThreads) void grow_median_kernel(int64_t n, const float* __restrict__ gt,
                                                                       const float* __restrict__ rd, float* __restrict__ d_median)
 {
     __shared__ uint32_t s_hist[kSelectBins];
     __shared__ uint32_t s_prefix, s_mask;
     __shared__ uint64_t s_k;
+    __shared__ uint32_t s_nan;
     const int tid = threadIdx.x;
-    if (tid == 0) { s_prefix = 0u; s_mask = 0u; s_k = (uint64_t)((n - 1) / 2); }
+    if (tid == 0) { s_prefix = 0u; s_mask = 0u; s_k = (uint64_t)((n - 1) / 2); s_nan = 0u; }
     const int shifts[3] = {21, 10, 0};
     const int widths[3] = {11, 11, 10};
     for (int pass = 0; pass < 3; ++pass) {
@@ -45,7 +49,9 @@ __global__ __launch_bounds__(kSelectThreads) void grow_median_kernel(int64_t n, 
         const int sh = shifts[pass];
         const uint32_t bm = (1u << widths[pass]) - 1u;
         for (int64_t i = tid; i < n; i += kSelectThreads) {
-            const uint32_t bits = __float_as_uint(depth_error(gt, rd, i));
+            const float err = depth_error(gt, rd, i);
+            if (pass == 0 && err != err) s_nan = 1u;           // (every writer stores the same value)
+            const uint32_t bits = __float_as_uint(err);
             if ((bits & mask) == prefix) atomicAdd(&s_hist[(bits >> sh) & bm], 1u);
         }
         __syncthreads();
@@ -63,7 +69,7 @@ __global__ __launch_bounds__(kSelectThreads) void grow_median_kernel(int64_t n, 
         }
         __syncthreads();
     }
-    if (tid == 0) *d_median = __uint_as_float(s_prefix);
+    if (tid == 0) *d_median = s_nan ? __uint_as_float(0x7fc00000u) : __uint_as_float(s_prefix);
 }
 
 __global__ __launch_bounds__(kBlock) void grow_mask_kernel(int64_t n, const float* __restrict__ gt, const float* __restrict__ rd,

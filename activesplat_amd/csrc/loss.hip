@@ -9,9 +9,17 @@
 // convolutions alone cost ~1.7 ms per iteration through MIOpen; here every 16x16 pixel tile stages the rendered
 // and target tiles (+5 px halo) in LDS and runs the separable window there.
 //
-//   loss_stats_kernel : per tile and channel, mu1, mu2, E[x^2], E[y^2], E[xy] by separable 11-tap passes in LDS ->
-//                       SSIM value and its partials w.r.t. (mu1, E[x^2], E[xy]) per pixel; block-reduced sums of
-//                       SSIM, |x-y|, masked |depth error| and the mask count go to 4 device accumulators.
+//   loss_stats_kernel : per tile and channel, the window moments by separable 11-tap passes in LDS -> SSIM value and its
+//                       partials w.r.t. (mu1, E[x^2], E[xy]) per pixel; block-reduced sums of 1 - SSIM, |x-y|, masked
+//                       |depth error| and the mask count go to 4 device accumulators.
+//                       Arithmetic: the moments are CENTRED -- both tiles are staged minus one pivot c (the target's value at
+//                       the tile's first pixel; the zero padding becomes -c), and the five moments are those of x' = x - c,
+//                       y' = y - c and (x' - y')^2.  Variances do not move with c, mu = mu' + c.  On a smooth render close to a
+//                       smooth target E[x^2] - mu^2 of the raw values cancels seven digits against C2 = 9e-4 (a relative
+//                       error of 1e-4 per pixel in SSIM, and the loss' image term off by 1e-4 .. 7e-3 relative); centred, the
+//                       moments are small.  sigma_12 comes from var(x - y) = s1 + s2 - 2 s12, and what is summed is
+//                       1 - SSIM = (B1 var(x - y) + A2 (mu1 - mu2)^2) / (B1 B2), a sum of non-negative terms (exactly 0 for
+//                       im == gt), not 1 - (a sum of values near 1).
 //   loss_grad_kernel  : convolves the three partial maps with the (symmetric) window, combines them into dL/dim,
 //                       adds the L1 terms, writes dL/ddepth (needs the mask count of pass 1 -- read from device
 //                       memory, no host sync) and the three loss scalars.
@@ -36,7 +44,7 @@ __device__ __forceinline__ float block_sum(float v, float* s_red, int tid)
     return s_red[0] + s_red[1] + s_red[2] + s_red[3];
 }
 
-// Accumulators: kAccSlots copies of {sum SSIM, sum |im - gt|, sum masked |gt_depth - depth|, mask count}, one 64-byte line
+// Accumulators: kAccSlots copies of {sum (1 - SSIM), sum |im - gt|, sum masked |gt_depth - depth|, mask count}, one 64-byte line
 // each; a block adds to slot (block index mod kAccSlots).  With a single copy the 4 x 1200 same-line device atomics of a
 // 640x480 frame serialise at the memory side and cost ~70 us -- more than all the arithmetic of the loss.
 // (round 3: 256 copies, and a block's four sums leave as ONE request -- four lanes of one atomic instruction on one line -- instead of four:
@@ -65,20 +73,21 @@ __global__ __launch_bounds__(kBlock) void loss_stats_kernel(int W, int H, const 
 {
     __shared__ float s_x[kLP][kLP + 1];
     __shared__ float s_y[kLP][kLP + 1];
-    __shared__ float s_h[5][kLP][kLT + 1];          // horizontal-pass results of x, y, xx, yy, xy
+    __shared__ float s_h[5][kLP][kLT + 1];          // horizontal-pass results of x', y', x'x', y'y', (x' - y')^2
     __shared__ float s_red[16];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int x0 = blockIdx.x * kLT, y0 = blockIdx.y * kLT;
     const int px = x0 + tx, py = y0 + ty;
     const bool inside = px < W && py < H;
     const size_t HW = (size_t)W * H;
-    float sum_ssim = 0.f, sum_l1 = 0.f;
+    float sum_ssim = 0.f, sum_l1 = 0.f;         // (sum_ssim: of 1 - SSIM)
     const int ch = blockIdx.z;                  // one colour channel per workgroup: 3x the workgroups, a third of the serial chain
     {
         // the tile + halo: 676 values of each image, three per thread.  ALL loads are issued before the first LDS store: as a loop with a store
         // behind each load the staging was three dependent memory round trips -- 5 of a wavefront's 6.8 us (round 6, rocprofv3 SQ_WAVE_CYCLES)
         constexpr int kStage = (kLP * kLP + kBlock - 1) / kBlock;
         float vx[kStage], vy[kStage];
+        const float pivot = gt[ch * HW + (size_t)y0 * W + x0];          // (x0 < W and y0 < H for every workgroup of the grid)
 #pragma unroll
         for (int it = 0; it < kStage; it++) {
             const int e = tid + it * kBlock;
@@ -92,34 +101,36 @@ __global__ __launch_bounds__(kBlock) void loss_stats_kernel(int W, int H, const 
 #pragma unroll
         for (int it = 0; it < kStage; it++) {
             const int e = tid + it * kBlock;
-            if (e < kLP * kLP) { const int r = e / kLP, c = e - r * kLP; s_x[r][c] = vx[it]; s_y[r][c] = vy[it]; }
+            if (e < kLP * kLP) { const int r = e / kLP, c = e - r * kLP; s_x[r][c] = vx[it] - pivot; s_y[r][c] = vy[it] - pivot; }
         }
         __syncthreads();
         for (int e = tid; e < kLP * kLT; e += kBlock) {       // horizontal pass: 26 rows x 16 columns
             const int r = e / kLT, c = e - r * kLT;
-            float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, ab = 0.f;
+            float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, dd = 0.f;
 #pragma unroll
             for (int k = 0; k < 11; k++) {
-                const float w = kWin[k], xv = s_x[r][c + k], yv = s_y[r][c + k];
-                a += w * xv; b += w * yv; aa += w * xv * xv; bb += w * yv * yv; ab += w * xv * yv;
+                const float w = kWin[k], xv = s_x[r][c + k], yv = s_y[r][c + k], dv = xv - yv;
+                a += w * xv; b += w * yv; aa += w * xv * xv; bb += w * yv * yv; dd += w * dv * dv;
             }
-            s_h[0][r][c] = a; s_h[1][r][c] = b; s_h[2][r][c] = aa; s_h[3][r][c] = bb; s_h[4][r][c] = ab;
+            s_h[0][r][c] = a; s_h[1][r][c] = b; s_h[2][r][c] = aa; s_h[3][r][c] = bb; s_h[4][r][c] = dd;
         }
         __syncthreads();
-        float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
+        float n1 = 0.f, n2 = 0.f, e11 = 0.f, e22 = 0.f, edd = 0.f;           // centred: n = mu - pivot
 #pragma unroll
         for (int k = 0; k < 11; k++) {                         // vertical pass
             const float w = kWin[k];
-            m1 += w * s_h[0][ty + k][tx]; m2 += w * s_h[1][ty + k][tx]; e11 += w * s_h[2][ty + k][tx];
-            e22 += w * s_h[3][ty + k][tx]; e12 += w * s_h[4][ty + k][tx];
+            n1 += w * s_h[0][ty + k][tx]; n2 += w * s_h[1][ty + k][tx]; e11 += w * s_h[2][ty + k][tx];
+            e22 += w * s_h[3][ty + k][tx]; edd += w * s_h[4][ty + k][tx];
         }
         if (inside) {
             const float c1 = 0.0001f, c2 = 0.0009f;
-            const float A1 = 2.f * m1 * m2 + c1, A2 = 2.f * (e12 - m1 * m2) + c2;
-            const float B1 = m1 * m1 + m2 * m2 + c1, B2 = (e11 - m1 * m1) + (e22 - m2 * m2) + c2;
+            const float dm = n1 - n2, vd = edd - dm * dm;                    // mu1 - mu2, var(x - y)
+            const float m1 = n1 + pivot, m2 = n2 + pivot;
+            const float B2 = (e11 - n1 * n1) + (e22 - n2 * n2) + c2, A2 = B2 - vd;   // A2 = 2 sigma_12 + C2
+            const float A1 = 2.f * m1 * m2 + c1, B1 = m1 * m1 + m2 * m2 + c1;
             const float inv = 1.0f / (B1 * B2);
             const float S = A1 * A2 * inv;
-            sum_ssim += S;
+            sum_ssim += (B1 * vd + A2 * (dm * dm)) * inv;                     // 1 - S
             const size_t o = ch * HW + (size_t)py * W + px;
             partials[o] = 2.f * m2 * (A2 - A1) * inv - 2.f * m1 * S * (1.0f / B1 - 1.0f / B2);   // dS/dmu1
             partials[3 * HW + o] = -S / B2;                                                      // dS/dE[x^2]
@@ -224,7 +235,7 @@ __global__ __launch_bounds__(kBlock) void loss_grad_kernel(int W, int H, const f
         dL_ddepth[o] = m ? w_depth * sgn / cnt : 0.f;
     }
     if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && tid == 0) {
-        const float l_im = w_im * (0.8f * s_tot[1] / n3 + 0.2f * (1.0f - s_tot[0] / n3));
+        const float l_im = w_im * (0.8f * s_tot[1] / n3 + 0.2f * (s_tot[0] / n3));                  // s_tot[0] = sum of 1 - SSIM
         const float l_depth = w_depth * s_tot[2] / cnt;
         losses[0] = l_im + l_depth; losses[1] = l_im; losses[2] = l_depth;
         losses[3] = l_im + l_depth;      // second copy: the host side hands out [0..2] as the report and [3] as the loss value

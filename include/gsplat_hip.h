@@ -531,7 +531,10 @@ int gs_accumulate_grad2d(int32_t P, const float* means2D_grad, const uint8_t* se
  * h_intrinsics4 = HOST {fx,fy,cx,cy}; h_c2w12 = HOST row-major 3x4 camera-to-world of the frame.  Outputs must hold H*W
  * rows (the worst case); d_counts[0] = pixels flagged non-present BEFORE the valid-depth mask (the reference enters its
  * append branch, which also resets the densification statistics, iff this is > 0), d_counts[1] = rows written, in
- * row-major pixel order.  log_scales is [rows,1] when isotropic != 0, else [rows,3]. */
+ * row-major pixel order.  log_scales is [rows,1] when isotropic != 0, else [rows,3].
+ * NaN rule: the median of the depth error is torch.median's -- the lower median, and NaN as soon as ONE error is NaN (a NaN pixel in
+ * render_depth or gt_depth, or an infinite render_depth where gt_depth <= 0).  `error > 2 median` is then false for every pixel and only
+ * the silhouette test (silhouette < sil_thres) flags pixels. */
 uint64_t gs_grow_scratch_bytes(int32_t width, int32_t height);
 int gs_grow_gaussians(int32_t width, int32_t height, const float* render_depth, const float* silhouette,
                       const float* gt_depth, const float* color, const float* h_intrinsics4, const float* h_c2w12,
