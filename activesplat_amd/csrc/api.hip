@@ -1043,6 +1043,59 @@ int gs_accumulate_grad2d(int32_t P, const float* means2D_grad, const uint8_t* se
     return GS_OK;
 }
 
+static bool dbscan_size_ok(int32_t B, int32_t H, int32_t W, int32_t max_clusters)
+{
+    return B >= 1 && B <= 65535 && H >= 1 && W >= 1 && H <= 4096 && W <= 4096 && (int64_t)H * W <= 65536 && max_clusters >= 1 && max_clusters <= 65535;
+}
+
+int gs_grid_dbscan_layout(int32_t B, int32_t H, int32_t W, int32_t max_clusters, GsDbscanLayout* out)
+{
+    if (!out || !dbscan_size_ok(B, H, W, max_clusters))
+        return fail(GS_EINVAL, "gs_grid_dbscan_layout: size out of range (1 <= B <= 65535, H, W <= 4096, H * W <= 65536, 1 <= max_clusters <= 65535)");
+    const uint64_t words = (uint64_t)B * H * ((W + 63) / 64), pixels = (uint64_t)B * H * W;
+    uint64_t o = 0;
+    out->mask_bits = o; o = align_up(o + words * 8);
+    out->core_bits = o; o = align_up(o + words * 8);
+    out->root_bits = o; o = align_up(o + words * 8);
+    out->word_prefix = o; o = align_up(o + words * 4);
+    out->parent = o; o = align_up(o + pixels * 4);
+    out->root = o; o = align_up(o + pixels * 4);
+    out->row_range = o; o = align_up(o + (uint64_t)B * max_clusters * 8);
+    out->total_bytes = o;
+    return GS_OK;
+}
+
+int gs_grid_dbscan(int32_t B, int32_t H, int32_t W, const float* values, int64_t row_stride, int64_t image_stride, float threshold,
+                   int32_t complement, int32_t eps, int32_t min_samples, int32_t max_clusters, void* workspace, int32_t* labels,
+                   int32_t* n_clusters, int32_t* table, float* sum_value, float* total, gs_stream_t stream)
+{
+    GsDbscanLayout L;
+    if (!dbscan_size_ok(B, H, W, max_clusters))
+        return fail(GS_EINVAL, "gs_grid_dbscan: size out of range (1 <= B <= 65535, H, W <= 4096, H * W <= 65536, 1 <= max_clusters <= 65535)");
+    if (eps < 1 || eps > 8 || min_samples < 1) return fail(GS_EINVAL, "gs_grid_dbscan: eps must be 1..8 and min_samples at least 1");
+    if (!values || !workspace || !labels || !n_clusters || !table || !sum_value || !total || row_stride < W || image_stride < 0 ||
+        ((uintptr_t)workspace & 7))
+        return fail(GS_EINVAL, "gs_grid_dbscan: null pointer, workspace not 8-byte aligned, or row_stride below W");
+    gs_grid_dbscan_layout(B, H, W, max_clusters, &L);
+    char* ws = (char*)workspace;
+    gs::DbscanArgs a;
+    a.values = values; a.row_stride = row_stride; a.image_stride = image_stride;
+    a.H = H; a.W = W; a.Ww = (W + 63) / 64; a.npix = H * W;
+    a.threshold = threshold; a.complement = complement != 0; a.eps = eps; a.min_samples = min_samples; a.max_clusters = max_clusters;
+    for (int dy = 0; dy <= 8; dy++) {
+        int w = 0;
+        while (dy <= eps && (w + 1) * (w + 1) + dy * dy <= eps * eps) w++;
+        a.half_width[dy] = w;
+    }
+    a.mask_bits = (uint64_t*)(ws + L.mask_bits); a.core_bits = (uint64_t*)(ws + L.core_bits); a.root_bits = (uint64_t*)(ws + L.root_bits);
+    a.word_prefix = (uint32_t*)(ws + L.word_prefix); a.parent = (uint32_t*)(ws + L.parent); a.root = (int32_t*)(ws + L.root);
+    a.row_range = (uint32_t*)(ws + L.row_range);
+    a.labels = labels; a.n_clusters = n_clusters; a.table = table; a.sum_value = sum_value; a.total = total;
+    hipError_t e = gs::launch_grid_dbscan(a, B, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_grid_dbscan: %s", hipGetErrorString(e));
+    return GS_OK;
+}
+
 uint64_t gs_grow_scratch_bytes(int32_t width, int32_t height)
 {
     return align_up(gs::grow_scratch_bytes((int64_t)(width > 0 ? width : 1) * (height > 0 ? height : 1)));

@@ -826,6 +826,20 @@ hipError_t launch_mapping_loss(int W, int H, const float* im, const float* gt, c
                                float* dL_ddepth, float* scratch, int64_t persistent_call, hipStream_t st);
 hipError_t launch_visibility_stats(int P, const int32_t* radii, uint8_t* seen, float* max_radius, hipStream_t st);
 hipError_t launch_accumulate_grad2d(int P, const float* grad, const uint8_t* seen, float* accum, float* denom, hipStream_t st);
+// DBSCAN on a pixel grid (stats.hip; the rule: include/gsplat_hip.h, gs_grid_dbscan).  One argument block for its seven kernels.
+struct DbscanArgs {
+    const float* values; int64_t row_stride, image_stride;             // floats
+    int H, W, Ww, npix;                                                // Ww = 64-column words per row
+    float threshold; int complement, eps, min_samples, max_clusters;
+    int half_width[9];                                                 // of the disc at |dy| = 0..eps: floor(sqrt(eps^2 - dy^2))
+    uint64_t *mask_bits, *core_bits, *root_bits;                       // [B][H][Ww]
+    uint32_t* word_prefix;                                             // [B][H][Ww]
+    uint32_t* parent;                                                  // [B][npix], complemented
+    int32_t* root;                                                     // [B][npix], -1 for a pixel that is not core
+    uint32_t* row_range;                                               // [B][max_clusters][2]: max of ~row, max of row
+    int32_t *labels, *n_clusters, *table; float *sum_value, *total;    // outputs
+};
+hipError_t launch_grid_dbscan(const DbscanArgs& a, int B, hipStream_t st);
 uint64_t grow_scratch_bytes(int64_t npix);
 hipError_t launch_grow(int W, int H, const float* rd, const float* sil, const float* gt, const float* color, const float* k4,
                        const float* c2w12, float sil_thres, int isotropic, float* means3D, float* rgb, float* rot, float* logit,

@@ -7,8 +7,8 @@ The reference spends, per node, 3 x (get_rendervars [8 elementwise torch kernels
 [the second one's only product, the silhouette, is discarded] + 3 blocking D2H copies).  `look_around(fused=True)`
 activates the Gaussians once (gs_activate_forward with the identity pose), renders ALL views in one raster pass over a
 multi-view atlas (rasterizer.render_views) and leaves the panorama on the device; `fused=False` reproduces the reference op for op (parity tests compare them).
-Everything downstream of the arrays (DBSCAN clustering, convex hulls: src/mapper/__init__.py:8-80) is planner
-code and out of scope.
+The DBSCAN clustering downstream of the arrays (src/mapper/__init__.py:8-19, :92-117), batched over nodes, is visibility.py; the convex
+hulls (:29-90: OpenCV, scipy) stay with the caller.
 """
 from __future__ import annotations
 

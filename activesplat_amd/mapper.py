@@ -20,7 +20,8 @@ habitat).  It reproduces the CALL PATTERN and SCHEDULE of the hot loop, nothing 
                                   frame's ground-truth pose holds inf / nan (__init__.py:514-524)
   every frame once a map exists : get_high_loss_samples' render of the map at the frame's pose (two raster passes in the
                                   reference, one with fused_render) and its "rendered surface in front of a measured one" mask
-                                  (__init__.py:184-214, 256-258); the mask's clustering (cv2 resize, DBSCAN) is planner code
+                                  (__init__.py:184-214, 256-258); the mask's cv2 resize stays with the caller, who can
+                                  pass the resized mask to visibility.grid_dbscan for the DBSCAN step (__init__.py:216-250)
 
 Inputs are already-resized frames (`color [3,H,W]` in 0..1, `depth [1,H,W]` metres, pose relative to frame 0 as
 quaternion (w,x,y,z) + translation of the w2c) -- the cv2 resize / PNG / manifest work of the reference is I/O
@@ -312,6 +313,19 @@ class SplatMapper:
         """360-degree opacity / RGB / depth panorama of the planner (lookaround.py)."""
         from . import lookaround as LA
         return LA.look_around(self.params, view_c2w, scale_modifier, fused)
+
+    @torch.no_grad()
+    def global_invisibility_nodes(self, view_c2w, positions, scale_modifier=1.0, max_clusters=256, nodes_per_pass=None):
+        """Per Voronoi node of `positions` [K, 3]: the panorama's depth, invisibility, DBSCAN labels and cluster table -- what
+        get_convexhull_volume holds after its DBSCAN line -- with one device-to-host copy for all nodes (visibility.py)."""
+        from . import visibility as VIS
+        return VIS.global_invisibility_nodes(self.params, view_c2w, positions, scale_modifier, max_clusters, nodes_per_pass)
+
+    @torch.no_grad()
+    def local_invisibility_target(self, view_c2w, cluster_invisibility_threshold=30, scale_modifier=1.0):
+        """get_local_invisibility without its images -> (sum_invisibility, best_pose_c2w or None) (visibility.py)."""
+        from . import visibility as VIS
+        return VIS.local_invisibility_target(self.params, view_c2w, cluster_invisibility_threshold, scale_modifier)
 
     # -- no-grad consumers (reference: render_rgbd / get_*_invisibility, __init__.py:604-838) ----------------
     @torch.no_grad()

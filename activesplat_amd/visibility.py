@@ -1,0 +1,245 @@
+"""The second half of the planner's visibility queries: clustering the look-around panoramas on the device, batched over Voronoi nodes.
+
+The reference clusters the low-visibility pixels of every panorama with sklearn's DBSCAN on the host, inside the mapper class
+(src/mapper/__init__.py:8-19 `get_convexhull_volume`: `1 - opacity > 0.8`, DBSCAN(eps=5, min_samples=25), once per Voronoi node --
+src/visualizer/visualizer.py:991-995 loops `get_global_invisibility` over the nodes; src/mapper/__init__.py:92-117
+`get_invisibility_clusters`: threshold 0.3, DBSCAN(eps=5, min_samples=10) on the 2 x downsampled panorama of the agent's own pose).
+On a pixel grid DBSCAN is a disc-count stencil, a connected-component labelling of the core pixels and a border rule; `grid_dbscan` runs
+them as HIP kernels (gs_grid_dbscan, include/gsplat_hip.h states the rule) and reproduces sklearn's labels exactly.
+
+* `grid_dbscan`                 -- labels, cluster count, per-cluster {count, sum_row, sum_col, root, sum_value} and the image total;
+* `look_around_nodes`           -- the panoramas of K nodes on the device: one activation, the 3 K views rendered up to 63 at a time;
+* `global_invisibility_nodes`   -- per node what `get_convexhull_volume` holds after its DBSCAN line, ONE device-to-host copy for all nodes.  The
+                                   dilate / findContours / ConvexHull loop behind it (OpenCV, scipy) stays with the caller;
+* `local_invisibility_target`   -- the whole of `get_local_invisibility` (src/mapper/splatam/__init__.py:762-837) without its images.
+
+There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import lookaround as LA
+from . import rasterizer as R
+from .camera import setup_camera
+
+#: most nodes one raster pass takes: gs_atlas_layout takes 64 views, a node has 3
+MAX_NODES_PER_PASS = 21
+#: nodes per raster pass by default.  A node's three views then sit in atlas slots 0-2, exactly where `look_around` renders them, and the
+#: panoramas are bit-identical to per-node `look_around`.  In a later slot the view's pixel offset (128 per slot) is added to the projected
+#: means in fp32, whose rounding grows with the slot; the smooth part of the difference stays inside the project's atlas bound scaled to 63
+#: slots (opacity 1e-4 at slot 50), but in every pass of more than one node a few pixels flip a Gaussian's alpha >= 1/255 test and move by up
+#: to 1/255 (measured on the MI355X at 21 nodes per pass: opacity 3.9e-3, depth 1.1e-2; profiles/visibility_clusters.txt), which is over
+#: that bound.  `nodes_per_pass=21` renders all 63 views in one pass for callers that accept such flips.
+NODES_PER_PASS = 1
+GLOBAL_THRESHOLD, GLOBAL_EPS, GLOBAL_MIN_SAMPLES = 0.8, 5, 25           # src/mapper/__init__.py:12, :18
+LOCAL_THRESHOLD, LOCAL_EPS, LOCAL_MIN_SAMPLES = 0.3, 5, 10              # src/mapper/__init__.py:93, :99
+LOCAL_GATE = 100                                                        # src/mapper/splatam/__init__.py:809
+LOCAL_SKIP_DEG = 15                                                     # :825
+
+
+class GridClusters(NamedTuple):
+    labels: torch.Tensor        # [B, H, W] int32: -2 unmasked, -1 noise, else the cluster number (sklearn's)
+    n_clusters: torch.Tensor    # [B] int32: the true count (may exceed max_clusters: the tables are then truncated, the labels are not)
+    count: torch.Tensor         # [B, max_clusters] int32: pixels of the cluster, border pixels included
+    sum_row: torch.Tensor       # [B, max_clusters] int32
+    sum_col: torch.Tensor       # [B, max_clusters] int32
+    root: torch.Tensor          # [B, max_clusters] int32: the cluster's smallest core pixel, row * W + col; -1 beyond n_clusters
+    sum_value: torch.Tensor     # [B, max_clusters] float32: sum of the tested value (1 - v under complement) over the cluster
+    total: torch.Tensor         # [B] float32: sum of the tested value over the whole image
+
+
+@torch.no_grad()
+def grid_dbscan(values, threshold, eps, min_samples, complement=False, max_clusters=256):
+    """DBSCAN(eps, min_samples) on the pixels of `values` ([H, W] or [B, H, W] float32 device tensor; rows and images may be strided, the last
+    dimension is dense) whose tested value -- v, or 1.0f - v with complement=True -- exceeds `threshold` in fp32.  -> GridClusters of device
+    tensors (for an [H, W] input without the batch dimension).  No host synchronisation."""
+    lib = _lib.get()
+    if not torch.is_tensor(values) or values.dim() not in (2, 3):
+        raise ValueError("grid_dbscan: values must be an [H, W] or [B, H, W] tensor")
+    device = values.device
+    R._require_rocm(device)
+    single = values.dim() == 2
+    v = values.detach()
+    if single:
+        v = v.unsqueeze(0)
+    B, H, W = (int(s) for s in v.shape)
+    if v.dtype != torch.float32:
+        v = v.float()
+    if min(B, H, W) > 0 and (v.stride(2) != 1 or v.stride(1) < W or v.stride(0) < 0 or v.data_ptr() % 4):
+        v = v.contiguous()
+    layout = _lib.GsDbscanLayout()
+    _lib.check(lib.gs_grid_dbscan_layout(B, H, W, int(max_clusters), C.byref(layout)))
+    M = int(max_clusters)
+    ws = torch.empty(int(layout.total_bytes), dtype=torch.uint8, device=device)
+    labels = torch.empty(B, H, W, dtype=torch.int32, device=device)
+    n_clusters = torch.empty(B, dtype=torch.int32, device=device)
+    table = torch.empty(B, M, 4, dtype=torch.int32, device=device)
+    sum_value = torch.empty(B, M, dtype=torch.float32, device=device)
+    total = torch.empty(B, dtype=torch.float32, device=device)
+    _lib.check(lib.gs_grid_dbscan(B, H, W, R._ptr(v), int(v.stride(1)), int(v.stride(0)), float(threshold), int(bool(complement)), int(eps),
+                                  int(min_samples), M, R._ptr(ws), R._ptr(labels), R._ptr(n_clusters), R._ptr(table), R._ptr(sum_value),
+                                  R._ptr(total), _lib.stream_ptr(device)))
+    out = GridClusters(labels, n_clusters, table[..., 0], table[..., 1], table[..., 2], table[..., 3], sum_value, total)
+    return GridClusters(*(t[0] for t in out)) if single else out
+
+
+class NodePanoramas(NamedTuple):
+    opacity: torch.Tensor       # [K, 150, 360] float32 (may be a strided view of the atlas gather)
+    depth: torch.Tensor         # [K, 150, 360, 1] float32
+    rgb: torch.Tensor           # [K, 150, 360, 3] uint8
+    valid: tuple                # K bools: False for an all-zero position (opacity 1, depth 0, rgb 0 in that slot)
+
+    def node(self, i):
+        """node i's panorama as `look_around` returns it, or None for an all-zero position (the reference returns early)"""
+        if not self.valid[i]:
+            return None
+        return {"opacity": self.opacity[i], "rgb": self.rgb[i], "depth": self.depth[i]}
+
+
+def node_pose(view_c2w, position):
+    """the camera of `get_global_invisibility` (src/mapper/splatam/__init__.py:701-704): x and z replaced, the camera height kept; None for the
+    all-zero position"""
+    position = np.asarray(position)
+    assert position.shape == (3,), f"Position must be a numpy array with shape (3,), but got {position.shape}"
+    if (position == np.zeros(3)).all():
+        return None
+    c2w = np.array(view_c2w, dtype=np.float64, copy=True)
+    c2w[0, 3], c2w[2, 3] = position[0], position[2]
+    return c2w
+
+
+@torch.no_grad()
+def look_around_nodes(params, view_c2w, positions, scale_modifier=1.0, nodes_per_pass=None):
+    """The look-around panoramas of K nodes: `lookaround.look_around` at `node_pose(view_c2w, positions[k])` for every k, with ONE activation
+    of the Gaussians for all nodes and one raster pass (rasterizer.render_views) per `nodes_per_pass` nodes (1..21; default NODES_PER_PASS,
+    see there); nothing is copied to the host.  -> NodePanoramas, all on the device."""
+    nodes_per_pass = NODES_PER_PASS if nodes_per_pass is None else int(nodes_per_pass)
+    if not 1 <= nodes_per_pass <= MAX_NODES_PER_PASS:
+        raise ValueError(f"look_around_nodes: nodes_per_pass must be 1..{MAX_NODES_PER_PASS} (an atlas holds 64 views)")
+    positions = np.asarray(positions, dtype=np.float64).reshape(-1, 3)
+    K = positions.shape[0]
+    device = params["means3D"].device
+    poses = [node_pose(view_c2w, p) for p in positions]
+    valid = tuple(p is not None for p in poses)
+    live = [k for k in range(K) if valid[k]]
+    views = int(360 / LA.LOOK_HFOV_DEG)
+    k3 = LA.look_around_k()
+    parts = []
+    if live:
+        rv = LA._world_rendervar(params)
+        rv.pop("means2D")
+    for start in range(0, len(live), nodes_per_pass):
+        chunk = live[start:start + nodes_per_pass]
+        cams = [setup_camera(LA.LOOK_W, LA.LOOK_H, k3, np.linalg.inv(LA.rot_axis(poses[k], "y", np.deg2rad(LA.LOOK_HFOV_DEG * i))), LA.VIZ_NEAR,
+                             LA.VIZ_FAR, scale_modifier=scale_modifier, device="cpu", bg=(1.0, 1.0, 1.0)) for k in chunk for i in range(views)]
+        color, depth, opacity, stride = R.render_views(cams, return_atlas=True, **rv)
+        n = len(chunk)
+        cols = LA._panorama_columns(views * n, stride, device)           # [n * 360]: node j's panorama is columns [360 j, 360 (j + 1))
+        op = opacity[0][:, cols].view(LA.LOOK_H, n, views * LA.LOOK_W).permute(1, 0, 2)
+        dp = depth[0][:, cols].view(LA.LOOK_H, n, views * LA.LOOK_W).permute(1, 0, 2).unsqueeze(-1)
+        im = (torch.clamp(color[:, :, cols], min=0, max=1.0) * 255).byte().view(3, LA.LOOK_H, n, views * LA.LOOK_W).permute(2, 1, 3, 0).contiguous()
+        parts.append((op, dp, im))
+    if len(parts) == 1 and len(live) == K:
+        return NodePanoramas(parts[0][0], parts[0][1], parts[0][2], valid)
+    PW = views * LA.LOOK_W
+    opacity = torch.ones(K, LA.LOOK_H, PW, dtype=torch.float32, device=device)
+    depth = torch.zeros(K, LA.LOOK_H, PW, 1, dtype=torch.float32, device=device)
+    rgb = torch.zeros(K, LA.LOOK_H, PW, 3, dtype=torch.uint8, device=device)
+    if live:
+        index = torch.as_tensor(live, device=device)
+        opacity[index] = torch.cat([p[0] for p in parts])
+        depth[index] = torch.cat([p[1] for p in parts])
+        rgb[index] = torch.cat([p[2] for p in parts])
+    return NodePanoramas(opacity, depth, rgb, valid)
+
+
+def _one_copy(tensors):
+    """several device tensors -> their numpy arrays through ONE device-to-host copy"""
+    flat = [t.contiguous().view(-1).view(torch.uint8) for t in tensors]
+    host = torch.cat(flat).cpu().numpy()
+    out, o = [], 0
+    for t, f in zip(tensors, flat):
+        n = f.numel()
+        out.append(host[o:o + n].view(torch.empty(0, dtype=t.dtype).numpy().dtype).reshape(tuple(t.shape)))
+        o += n
+    return out
+
+
+@torch.no_grad()
+def global_invisibility_nodes(params, view_c2w, positions, scale_modifier=1.0, max_clusters=256, nodes_per_pass=None):
+    """For every node of `positions` [K, 3], what `get_convexhull_volume` (src/mapper/__init__.py:8-19) holds after its DBSCAN line, for the
+    panorama `get_global_invisibility` renders there: a list of K entries, None for an all-zero position, else a dict of numpy arrays
+      depth [150, 360, 1], invisibility [150, 360] (= 1 - opacity, fp32), labels [150, 360] int32 (-2 where invisibility <= 0.8, -1 noise,
+      else sklearn's cluster number), n_clusters, and per cluster (the first min(n_clusters, max_clusters)) count, sum_row, sum_col, root,
+      sum_value; total = sum of the invisibility over the panorama.
+    One activation, one raster pass per `nodes_per_pass` nodes (look_around_nodes), one clustering call and ONE device-to-host copy for all nodes."""
+    pano = look_around_nodes(params, view_c2w, positions, scale_modifier, nodes_per_pass)
+    K = len(pano.valid)
+    if not any(pano.valid):
+        return [None] * K
+    g = grid_dbscan(pano.opacity, GLOBAL_THRESHOLD, GLOBAL_EPS, GLOBAL_MIN_SAMPLES, complement=True, max_clusters=max_clusters)
+    depth, inv, labels, n, count, sr, sc, root, sv, total = _one_copy([pano.depth, 1.0 - pano.opacity, g.labels, g.n_clusters, g.count, g.sum_row,
+                                                                        g.sum_col, g.root, g.sum_value, g.total])
+    out = []
+    for k in range(K):
+        if not pano.valid[k]:
+            out.append(None)
+            continue
+        m = min(int(n[k]), int(max_clusters))
+        out.append(dict(depth=depth[k], invisibility=inv[k], labels=labels[k], n_clusters=int(n[k]), count=count[k, :m], sum_row=sr[k, :m],
+                        sum_col=sc[k, :m], root=root[k, :m], sum_value=sv[k, :m], total=float(total[k])))
+    return out
+
+
+def downsample2(image):
+    """2 x area downsample of an [H, W] tensor with even H and W: ((a + b) + (c + d)) * 0.25f over each 2 x 2 block {a b; c d}, in fp32 and in
+    that order (the reference: cv2.resize(..., INTER_AREA) at factor 0.5, src/mapper/splatam/__init__.py:810-813)."""
+    a, b, c, d = image[0::2, 0::2], image[0::2, 1::2], image[1::2, 0::2], image[1::2, 1::2]
+    return ((a + b) + (c + d)) * 0.25
+
+
+def target_from_clusters(view_c2w, sum_invisibility, count, sum_row, sum_col, sum_value, cluster_invisibility_threshold):
+    """src/mapper/splatam/__init__.py:809-830 on the host, from the cluster table of the downsampled panorama -> best_pose_c2w or None"""
+    if not sum_invisibility > LOCAL_GATE:
+        return None
+    keep = [c for c in range(len(sum_value)) if sum_value[c] > cluster_invisibility_threshold]
+    if not keep:
+        return None
+    best = keep[0]
+    for c in keep[1:]:                                   # np.argmax: the first of equal maxima
+        if sum_value[c] > sum_value[best]:
+            best = c
+    factor_width = factor_height = 0.5
+    centre = (np.float64(sum_row[best]) / np.float64(count[best]), np.float64(sum_col[best]) / np.float64(count[best]))
+    center_vec = np.array([centre[1] / factor_width - LA.LOOK_W / 2, centre[0] / factor_height - LA.LOOK_H / 2])
+    horizontal_angle = np.deg2rad(center_vec[0])
+    vertical_angle = np.deg2rad(center_vec[1])
+    if np.abs(horizontal_angle) > np.deg2rad(LOCAL_SKIP_DEG) or np.abs(vertical_angle) > np.deg2rad(LOCAL_SKIP_DEG):
+        return LA.rot_axis(LA.rot_axis(np.asarray(view_c2w, dtype=np.float64), "y", horizontal_angle), "x", vertical_angle)
+    return None
+
+
+@torch.no_grad()
+def local_invisibility_target(params, view_c2w, cluster_invisibility_threshold=30, scale_modifier=1.0, max_clusters=256):
+    """`get_local_invisibility` without its images -> (sum_invisibility, best_pose_c2w or None): the panorama at the agent's pose, sum(1 -
+    opacity), and when that exceeds 100 the pose turned towards the centre of the downsampled panorama's most invisible cluster (clusters
+    with sum > cluster_invisibility_threshold; the lowest cluster number wins a tie; None inside the 15-degree centre).  Everything up to
+    the cluster table runs on the device whatever the sum; only the sum and the table are copied back, in one copy."""
+    pano = LA.look_around(params, view_c2w, scale_modifier)
+    inv = 1.0 - pano["opacity"]
+    total = inv.sum().reshape(1)
+    small = downsample2(inv)
+    while True:
+        g = grid_dbscan(small, LOCAL_THRESHOLD, LOCAL_EPS, LOCAL_MIN_SAMPLES, max_clusters=max_clusters)
+        tot, n, count, sr, sc, sv = _one_copy([total, g.n_clusters.reshape(1), g.count, g.sum_row, g.sum_col, g.sum_value])
+        if int(n[0]) <= max_clusters:
+            break
+        max_clusters = int(n[0])                         # (more clusters than rows in the table: once more with enough rows)
+    m = int(n[0])
+    return float(tot[0]), target_from_clusters(view_c2w, tot[0], count[:m], sr[:m], sc[:m], sv[:m], cluster_invisibility_threshold)

@@ -181,7 +181,7 @@ const char* gs_version(void);
 /* Integer version of THIS binary interface: bumped whenever an entry point's argument list or a published record layout changes (e.g.
  * the seed argument of gs_densify_children, the 40-byte SH Jacobian record).  A host binding compares it with the GS_ABI_VERSION it was
  * written against before the first call, so that a stale prebuilt library fails at load time instead of misreading its arguments. */
-#define GS_ABI_VERSION 13
+#define GS_ABI_VERSION 14
 int32_t gs_abi_version(void);
 
 /* Optional per-stage timing (hipEvents recorded on the caller's stream around each stage's launches).
@@ -525,6 +525,39 @@ int gs_compact_index3(int64_t n, const uint8_t* keep_a, const uint8_t* keep_b, c
 int gs_visibility_stats(int32_t P, const int32_t* radii, uint8_t* seen, float* max_2D_radius, gs_stream_t stream);
 int gs_accumulate_grad2d(int32_t P, const float* means2D_grad, const uint8_t* seen, float* grad_accum, float* denom,
                          gs_stream_t stream);
+
+/* DBSCAN on a pixel grid, batched over images: the clustering the reference's mapper runs on its look-around panoramas
+ * (src/mapper/__init__.py:8-19 get_convexhull_volume: DBSCAN(eps=5, min_samples=25) on np.where(invisibility > 0.8); :92-117
+ * get_invisibility_clusters: threshold 0.3, DBSCAN(eps=5, min_samples=10), per-cluster centre and sum).  For image b, row y, column x the value
+ * read is values[b * image_stride + y * row_stride + x] (strides in floats: a panorama is read in place from an atlas or a gathered tensor).
+ * The rule, which reproduces sklearn.cluster.DBSCAN(eps, min_samples).fit_predict(np.column_stack(np.where(mask))) label for label:
+ *   1. tested = complement ? 1.0f - v : v (fp32); mask = tested > threshold (fp32; a NaN is unmasked);
+ *   2. count(p) = masked pixels q with dy*dy + dx*dx <= eps*eps (integers, p included, the disc clipped at the image border);
+ *      core(p) = mask(p) && count(p) >= min_samples;
+ *   3. core pixels within eps of each other are connected; a component's root is its smallest row-major pixel index y * W + x; clusters are
+ *      numbered 0..C-1 in ascending root order;
+ *   4. a masked pixel that is not core takes the SMALLEST cluster number among the core pixels of its disc (border), or is noise;
+ *   5. labels: -2 unmasked, -1 noise, else the cluster number.
+ * Outputs, all DEVICE:
+ *   labels     int32 [B, H, W]
+ *   n_clusters int32 [B]                   the true count, also when it exceeds max_clusters (the tables are then truncated, the labels are not)
+ *   table      int32 [B, max_clusters, 4]  {count, sum_row, sum_col, root} over the cluster's pixels, border pixels included -- exact; the centre
+ *                                          points.mean(axis=0) is (sum_row / count, sum_col / count).  Rows at or beyond n_clusters: {0, 0, 0, -1}
+ *   sum_value  float32 [B, max_clusters]   sum of the tested value over the cluster's pixels; 0 beyond n_clusters
+ *   total      float32 [B]                 sum of the tested value over the whole image
+ * The two float sums run in a fixed order (at most 64 terms per thread, then butterflies over 1024 threads: no float atomics) and are
+ * bit-identical from run to run; a tested value that is not finite counts as 0 in them, so they are always finite.  The integer outputs do
+ * not depend on scheduling (components are united by atomic minimum).  No host synchronisation; every loop in the kernels has a bound that
+ * follows from the image size.  Supported: 1 <= B <= 65535, 1 <= H, W <= 4096 with H * W <= 65536, 1 <= eps <= 8, min_samples >= 1,
+ * 1 <= max_clusters <= 65535, row_stride >= W; anything else is GS_EINVAL.  workspace: gs_grid_dbscan_layout(...).total_bytes bytes, DEVICE,
+ * 8-byte aligned, contents irrelevant before and after (the offsets are published for debugging only). */
+typedef struct GsDbscanLayout {
+    uint64_t total_bytes, mask_bits, core_bits, root_bits, word_prefix, parent, root, row_range;
+} GsDbscanLayout;
+int gs_grid_dbscan_layout(int32_t B, int32_t H, int32_t W, int32_t max_clusters, GsDbscanLayout* out);
+int gs_grid_dbscan(int32_t B, int32_t H, int32_t W, const float* values, int64_t row_stride, int64_t image_stride, float threshold,
+                   int32_t complement, int32_t eps, int32_t min_samples, int32_t max_clusters, void* workspace, int32_t* labels,
+                   int32_t* n_clusters, int32_t* table, float* sum_value, float* total, gs_stream_t stream);
 
 /* Map growth (replaces add_new_gaussians, src/mapper/splatam/splatam.py:332-379, with get_pointcloud :25-75 and
  * initialize_new_params :304-329).  render_depth / silhouette / gt_depth are [H*W] device images, color is [3,H*W];

@@ -1,0 +1,559 @@
+"""Shared checks of the on-device grid DBSCAN and the node look-arounds (activesplat_amd/visibility.py, gs_grid_dbscan): run on the
+host-emulated kernels by tests/test_cluster.py and on the MI355X by tests/test_gpu_cluster.py.
+
+References
+* `restate` below: the labelling rule of include/gsplat_hip.h (gs_grid_dbscan) in numpy.  tests/golden/make_cluster_golden.py ran it against
+  sklearn.cluster.DBSCAN(...).fit_predict(np.column_stack(np.where(mask))) on every case of this file and stored sklearn's labels in
+  tests/golden/cluster.npz; tests/test_cluster.py compares the two again from the fixture, so the restatement is pinned to sklearn without sklearn
+  on the machine that runs the tests.
+* the fixture also holds what the reference's own `get_invisibility_clusters` (src/mapper/__init__.py:92-117) returned for the 75 x 180 cases.
+* The fixture keeps the bit-packed masks and sklearn's labels (int16) of every case; the fp32 values are kept for the sizes up to 33 x 70
+  only (a 150 x 360 fp32 image does not compress) -- the larger images are rebuilt by `smooth_field` from their seed and the rebuilt mask
+  is compared with the stored one before anything else, so a numpy whose generator drew other numbers fails loudly instead of testing another
+  case.
+
+Tolerances (none of them comes from the code under test)
+* labels, n_clusters, count, sum_row, sum_col, root: exact.
+* sum_value, total against the fp64 sum of the same fp32 values: relative 1e-5 (the issue's figure).  The kernel's order: per thread a serial
+  run of at most 64 terms (1024 threads, at most 65 536 pixels), a butterfly over the 64 lanes (6 levels), a butterfly over the 16 wavefront
+  sums (4 levels): for terms of one sign the relative error is at most (63 + 6 + 4) * 2^-24 = 4.4e-6, inside the issue's (64 + 16) * 2^-24 =
+  4.8e-6 < 1e-5.  The tested values of every case here are positive.
+* look_around_nodes against per-node look_around: tests/test_lookaround.py:51-56 (opacity atol 1e-5, depth atol 2e-5 / rtol 1e-5, set for 3
+  atlas slots, the difference being fp32 rounding of the slot offset) scaled by 63 / 3 for the 63 slots of a full pass: opacity atol 2.1e-4,
+  depth atol 4.2e-4 / rtol 2.1e-4.
+* the pose of local_invisibility_target: 1e-12 against the op-for-op restatement of src/mapper/splatam/__init__.py:795-830.
+"""
+import os
+
+import numpy as np
+import torch
+
+from activesplat_amd import lookaround as LA
+from activesplat_amd import synthetic as syn
+from activesplat_amd import visibility as VIS
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cluster.npz")
+SUM_RTOL = 1e-5
+ATLAS_SCALE = 63 / 3
+OPACITY_ATOL, DEPTH_ATOL, DEPTH_RTOL = 1e-5 * ATLAS_SCALE, 2e-5 * ATLAS_SCALE, 1e-5 * ATLAS_SCALE
+
+#: (name, H, W, threshold, eps, min_samples, complement); every random case at SEEDS
+RANDOM_CASES = (("ragged", 33, 70, 0.8, 5, 25, False), ("local", 75, 180, 0.3, 5, 10, False), ("global", 150, 360, 0.8, 5, 25, True),
+                ("eps1", 24, 40, 0.5, 1, 1, False), ("eps8", 24, 40, 0.5, 8, 80, False))
+SEEDS = (0, 1, 2)
+#: eps8: 80 of the disc's 197 pixels and blobs of sigma 3 -- at min_samples 25 a 24 x 40 image at radius 8 is one cluster for every seed tried, so
+#: there would be no border pixel between two clusters; chosen on the restatement (assert_case_set_is_hard), not on the device
+SIGMA = {"eps8": 3.0}
+VALUES_STORED_UP_TO = 33 * 70
+
+
+# ---- the rule, restated -----------------------------------------------------------------------------------------------------------------
+
+def disc(eps):
+    return [(dy, dx) for dy in range(-eps, eps + 1) for dx in range(-eps, eps + 1) if dy * dy + dx * dx <= eps * eps]
+
+
+def _shift(a, dy, dx, fill):
+    """b[y, x] = a[y + dy, x + dx], `fill` outside"""
+    H, W = a.shape
+    b = np.full_like(a, fill)
+    if abs(dy) >= H or abs(dx) >= W:
+        return b
+    ys, yd = slice(max(dy, 0), H + min(dy, 0)), slice(max(-dy, 0), H + min(-dy, 0))
+    xs, xd = slice(max(dx, 0), W + min(dx, 0)), slice(max(-dx, 0), W + min(-dx, 0))
+    b[yd, xd] = a[ys, xs]
+    return b
+
+
+def tested_values(values, complement):
+    v = np.asarray(values, np.float32)
+    with np.errstate(invalid="ignore"):
+        return (np.float32(1.0) - v) if complement else v
+
+
+def restate(values, threshold, eps, min_samples, complement=False):
+    """The labelling rule for one [H, W] image -> dict(labels int32 [H, W], n_clusters, count, sum_row, sum_col, root (int64 each),
+    sum_value, total (fp64 sums of the fp32 tested values, non-finite values counted as 0), mask, core, contested (border pixels with core
+    pixels of two clusters in their disc))."""
+    t = tested_values(values, complement)
+    H, W = t.shape
+    with np.errstate(invalid="ignore"):
+        mask = t > np.float32(threshold)
+    offs = disc(eps)
+    count = sum(_shift(mask.astype(np.int64), dy, dx, 0) for dy, dx in offs)
+    core = mask & (count >= min_samples)
+    BIG = H * W
+    idx = np.arange(H * W, dtype=np.int64).reshape(H, W)
+    lab = np.where(core, idx, BIG)
+    while True:                                          # smallest index over the disc, then pointer jumping (lab[p] is a core pixel of p's
+        new = lab.copy()                                 # component): ends when a sweep changes nothing
+        for dy, dx in offs:
+            new = np.minimum(new, _shift(lab, dy, dx, BIG))
+        new = np.where(core, new, BIG)
+        flat, c = new.ravel(), core.ravel()
+        while True:
+            jumped = flat[flat[c]]
+            if np.array_equal(jumped, flat[c]):
+                break
+            flat[c] = jumped
+        if np.array_equal(new, lab):
+            break
+        lab = new
+    roots = np.unique(lab[core])
+    number = np.full(H * W + 1, -1, np.int64)
+    number[roots] = np.arange(len(roots))
+    lo = np.full((H, W), BIG, np.int64)
+    hi = np.full((H, W), -1, np.int64)
+    for dy, dx in offs:
+        s = _shift(lab, dy, dx, BIG)
+        lo = np.minimum(lo, s)
+        hi = np.maximum(hi, np.where(s == BIG, -1, s))
+    border = mask & ~core & (lo < BIG)
+    labels = np.full((H, W), -2, np.int32)
+    labels[mask] = -1
+    labels[core] = number[lab[core]]
+    labels[border] = number[lo[border]]                  # cluster numbers ascend with the roots: the smallest root is the smallest number
+    finite = np.where(np.isfinite(t), t, np.float32(0)).astype(np.float64)
+    n = len(roots)
+    rows, cols = np.indices((H, W))
+    sel = labels >= 0
+    out = dict(labels=labels, n_clusters=n, root=roots, mask=mask, core=core, contested=border & (hi != lo),
+               count=np.bincount(labels[sel], minlength=n), sum_row=np.bincount(labels[sel], rows[sel], minlength=n).astype(np.int64),
+               sum_col=np.bincount(labels[sel], cols[sel], minlength=n).astype(np.int64),
+               sum_value=np.bincount(labels[sel], finite[sel], minlength=n), total=float(finite.sum()))
+    return out
+
+
+# ---- input builders ---------------------------------------------------------------------------------------------------------------------
+
+def contested_mask(col):
+    """24 x 40: solid 7 x 7 blocks at rows 4-10, columns 4-10 and 18-24, one extra pixel at (7, col)"""
+    m = np.zeros((24, 40), bool)
+    m[4:11, 4:11] = True
+    m[4:11, 18:25] = True
+    m[7, col] = True
+    return m
+
+
+def serpentine_mask():
+    """150 x 360: bands 6 pixels high over columns 2-357, one every 12 rows, joined alternately at the right and the left end by 6 x 6 blocks:
+    one cluster of 28 200 pixels that a min-label sweep needs 913 rounds for"""
+    m = np.zeros((150, 360), bool)
+    tops = list(range(0, 150 - 5, 12))
+    for i, y in enumerate(tops):
+        m[y:y + 6, 2:358] = True
+        if i + 1 < len(tops):
+            x = 352 if i % 2 == 0 else 2
+            m[y + 6:y + 12, x:x + 6] = True
+    return m
+
+
+def mask_values(mask, threshold=0.8, complement=False):
+    """fp32 values whose tested value is 0.95 inside the mask and 0.05 outside (threshold between)"""
+    t = np.where(mask, np.float32(0.95), np.float32(0.05)).astype(np.float32)
+    assert 0.05 < threshold < 0.95
+    return (np.float32(1.0) - t) if complement else t
+
+
+def _blur(a, sigma):
+    r = int(3 * sigma)
+    k = np.exp(-0.5 * (np.arange(-r, r + 1) / sigma) ** 2)
+    k /= k.sum()
+    a = np.apply_along_axis(lambda v: np.convolve(np.pad(v, r, mode="reflect"), k, mode="valid"), 0, a)
+    return np.apply_along_axis(lambda v: np.convolve(np.pad(v, r, mode="reflect"), k, mode="valid"), 1, a)
+
+
+def smooth_field(H, W, threshold, seed, complement=False, sigma=4.0, spread=0.25, jitter=0.05):
+    """A Gaussian-filtered noise field scaled around the threshold plus per-pixel jitter -> fp32 [H, W] whose TESTED value is the field (under
+    `complement` the image is 1 - field): blobs (clusters), ragged rims (border pixels) and speckle (noise)."""
+    g = np.random.default_rng(1000 * H + 10 * W + seed)
+    f = _blur(g.standard_normal((H + 8, W + 8)), sigma)[4:-4, 4:-4]
+    f = f / f.std()
+    field = (threshold + spread * f + jitter * g.standard_normal((H, W))).astype(np.float32)
+    return (np.float32(1.0) - field).astype(np.float32) if complement else field
+
+
+def random_case(name, seed):
+    _, H, W, thr, eps, ms, comp = next(c for c in RANDOM_CASES if c[0] == name)
+    return smooth_field(H, W, thr, seed, comp, sigma=SIGMA.get(name, 4.0)), thr, eps, ms, comp
+
+
+def assert_case_set_is_hard(name, refs):
+    """the issue's condition on every set of random cases, asserted on the restatement: a border pixel between two clusters, noise, and masked
+    pixels in the first and last row and column"""
+    if name != "eps1":                                   # (min_samples = 1: every masked pixel is core -- there is no border and no noise to ask for)
+        assert any(r["contested"].any() for r in refs), name
+        assert any((r["labels"] == -1).any() for r in refs), name
+    assert any(r["mask"][0].any() and r["mask"][-1].any() and r["mask"][:, 0].any() and r["mask"][:, -1].any() for r in refs), name
+
+
+_GOLDEN = None
+
+
+def golden():
+    global _GOLDEN
+    if _GOLDEN is None:
+        with np.load(GOLDEN) as z:
+            _GOLDEN = {k: z[k] for k in z.files}
+    return _GOLDEN
+
+
+def golden_mask(key, H, W):
+    return np.unpackbits(golden()[key + "_mask"])[:H * W].reshape(H, W).astype(bool)
+
+
+def golden_labels(key, H, W):
+    """sklearn's labels in this file's convention: -2 unmasked, -1 noise, else the cluster number"""
+    m = golden_mask(key, H, W)
+    out = np.full((H, W), -2, np.int32)
+    out[m] = golden()[key + "_sklearn"].astype(np.int32)                # (np.where order: row-major)
+    return out
+
+
+_REF = {}
+
+
+def reference(name, seed):
+    """(values, restatement) of one random case: computed once per process, shared by every test, and checked against the fixture's mask"""
+    key = f"{name}_{seed}"
+    if key not in _REF:
+        values, thr, eps, ms, comp = random_case(name, seed)
+        r = restate(values, thr, eps, ms, comp)
+        assert np.array_equal(r["mask"], golden_mask(key, *values.shape)), f"{key}: the rebuilt image is not the fixture's"
+        if values.size <= VALUES_STORED_UP_TO:
+            assert np.array_equal(values, golden()[key + "_values"]), key
+        values.setflags(write=False)
+        _REF[key] = (values, r)
+    return _REF[key]
+
+
+# ---- running the device and comparing ---------------------------------------------------------------------------------------------------------
+
+def run(device, values, thr, eps, ms, comp=False, max_clusters=256):
+    v = values if torch.is_tensor(values) else torch.from_numpy(np.array(values, np.float32)).to(device)
+    g = VIS.grid_dbscan(v, thr, eps, ms, complement=comp, max_clusters=max_clusters)
+    return {k: getattr(g, k).cpu().numpy() for k in g._fields}
+
+
+def compare(got, ref, b=None, max_clusters=256, what=""):
+    """one image of a device result against its restatement: integers exact, the two sums to SUM_RTOL; figures printed before the assertions"""
+    g = {k: (v[b] if b is not None else v) for k, v in got.items()}
+    n = ref["n_clusters"]
+    m = min(n, max_clusters)
+    assert np.array_equal(g["labels"], ref["labels"]), f"{what}: {int((g['labels'] != ref['labels']).sum())} labels differ"
+    assert int(g["n_clusters"]) == n, what
+    for k in ("count", "sum_row", "sum_col", "root"):
+        assert np.array_equal(g[k][:m].astype(np.int64), np.asarray(ref[k][:m], np.int64)), (what, k)
+    assert (g["count"][m:] == 0).all() and (g["root"][m:] == -1).all() and (g["sum_value"][m:] == 0).all(), what
+    assert np.isfinite(g["sum_value"]).all() and np.isfinite(g["total"]), what
+    rel = np.abs(g["sum_value"][:m].astype(np.float64) - ref["sum_value"][:m]) / np.maximum(np.abs(ref["sum_value"][:m]), 1e-30) if m else np.zeros(1)
+    rel_total = abs(float(g["total"]) - ref["total"]) / max(abs(ref["total"]), 1e-30)
+    print(f"{what}: clusters {n}, border {int(((ref['labels'] >= 0) & ~ref['core']).sum())}, noise {int((ref['labels'] == -1).sum())}, "
+          f"sum_value rel {rel.max():.2e}, total rel {rel_total:.2e}")
+    assert rel.max() <= SUM_RTOL and rel_total <= SUM_RTOL, (what, rel.max(), rel_total)
+
+
+def check_contested(device):
+    for col, want in ((15, 0), (16, 1), (13, 0)):
+        v = mask_values(contested_mask(col))
+        ref = restate(v, 0.8, 5, 25)
+        # (7, 16) is 6 columns from the first block: only the second reaches it; at columns 13 and 15 both do
+        assert ref["n_clusters"] == 2 and ref["labels"][7, col] == want and bool(ref["contested"][7, col]) == (col != 16)
+        got = run(device, v, 0.8, 5, 25)
+        compare(got, ref, what=f"contested border, column {col}")
+        assert got["labels"][7, col] == want and np.array_equal(golden_labels(f"contested_{col}", 24, 40), got["labels"])
+
+
+def check_serpentine(device):
+    m = serpentine_mask()
+    assert int(m.sum()) == 28200
+    v = mask_values(m, complement=True)
+    got = run(device, v, 0.8, 5, 25, comp=True)
+    assert int(got["n_clusters"]) == 1 and (got["labels"][m] == 0).all() and (got["labels"][~m] == -2).all()
+    assert int(got["count"][0]) == 28200 and int(got["root"][0]) == 2
+    compare(got, restate(v, 0.8, 5, 25, True), what="serpentine")
+
+
+def check_random(device, name):
+    """the three seeds of one random case; `global` runs them as the issue's batch of three with an all-below and an all-above image"""
+    _, H, W, thr, eps, ms, comp = next(c for c in RANDOM_CASES if c[0] == name)
+    refs = [reference(name, s) for s in SEEDS]
+    assert_case_set_is_hard(name, [r for _, r in refs])
+    if name == "global":
+        below, above = mask_values(np.zeros((H, W), bool), thr, comp), mask_values(np.ones((H, W), bool), thr, comp)
+        r_below, r_above = restate(below, thr, eps, ms, comp), restate(above, thr, eps, ms, comp)
+        assert r_below["n_clusters"] == 0 and (r_below["labels"] == -2).all() and r_above["n_clusters"] == 1 and (r_above["labels"] == 0).all()
+        for s, (values, ref) in zip(SEEDS, refs):
+            batch = np.stack([below, above, values])
+            # guard words around the batch: a write outside the images' own outputs would have to land in tensors the call allocates, so what
+            # can be checked from here is that the INPUT and its neighbours are untouched
+            padded = torch.full((5, H, W), 7.0)
+            padded[1:4] = torch.from_numpy(batch)
+            padded = padded.to(device)
+            got = run(device, padded[1:4], thr, eps, ms, comp)
+            assert torch.equal(padded[0].cpu(), torch.full((H, W), 7.0)) and torch.equal(padded[4].cpu(), torch.full((H, W), 7.0))
+            assert torch.equal(padded[1:4].cpu(), torch.from_numpy(batch))
+            compare(got, r_below, 0, what=f"{name} seed {s}: all below")
+            compare(got, r_above, 1, what=f"{name} seed {s}: all above")
+            compare(got, ref, 2, what=f"{name} seed {s}")
+    else:
+        batch = np.stack([v for v, _ in refs])
+        got = run(device, batch, thr, eps, ms, comp)
+        for i, (s, (_, ref)) in enumerate(zip(SEEDS, refs)):
+            compare(got, ref, i, what=f"{name} seed {s}")
+            one = run(device, refs[i][0], thr, eps, ms, comp)            # the [H, W] form of the call
+            assert all(np.array_equal(one[k], got[k][i]) for k in one), name
+
+
+def check_small_sizes(device):
+    """images smaller than the disc, a single pixel, a single row, a single column, a row of exactly 64 and of 65 columns (the word boundary)"""
+    for i, (H, W, eps, ms) in enumerate(((1, 1, 5, 1), (1, 1, 5, 2), (1, 70, 5, 3), (70, 1, 8, 3), (3, 5, 5, 4), (7, 64, 2, 3), (7, 65, 2, 3), (9, 129, 8, 30))):
+        v = smooth_field(H, W, 0.5, i, sigma=1.5, jitter=0.2) if H * W > 1 else np.full((1, 1), 0.9, np.float32)
+        compare(run(device, v, 0.5, eps, ms), restate(v, 0.5, eps, ms), what=f"{H} x {W}, eps {eps}, min_samples {ms}")
+
+
+def check_nonfinite(device):
+    values, _ = reference("ragged", 0)
+    for comp in (False, True):
+        v = (np.float32(1.0) - values if comp else values).copy()
+        v[3:9, 5:20] = np.nan
+        v[12:20, 30:45] = -np.inf if comp else np.inf                   # tested value +inf: masked, a solid block
+        v[22:30, 50:60] = np.inf if comp else -np.inf                   # tested value -inf: unmasked
+        v[0, 0], v[-1, -1] = np.nan, (-np.inf if comp else np.inf)
+        ref = restate(v, 0.8, 5, 25, comp)
+        assert not ref["mask"][3:9, 5:20].any() and ref["mask"][12:20, 30:45].all() and not ref["mask"][22:30, 50:60].any()
+        got = run(device, v, 0.8, 5, 25, comp)
+        compare(got, ref, what=f"non-finite values, complement {comp}")
+
+
+def check_truncated(device):
+    values, ref = reference("eps1", 0)
+    n = ref["n_clusters"]
+    assert n > 8
+    got = run(device, values, 0.5, 1, 1, max_clusters=5)
+    assert got["count"].shape == (5,)
+    compare(got, ref, max_clusters=5, what=f"max_clusters 5 of {n}")
+
+
+def check_refusals(device, batch64=True):
+    from activesplat_amd import _lib
+    lib = _lib.get()
+    ok = torch.zeros(2, 24, 40, device=device)
+    for kw, text in ((dict(values=torch.zeros(0, 24, 40, device=device)), "size out of range"), (dict(values=torch.zeros(1, 0, 40, device=device)), "size out of range"),
+                     (dict(values=torch.zeros(1, 40, 0, device=device)), "size out of range"), (dict(values=torch.zeros(1, 257, 256, device=device)), "H * W <= 65536"),
+                     (dict(values=torch.zeros(1, 1, 4097, device=device)), "W <= 4096"), (dict(eps=0), "eps must be 1..8"), (dict(eps=9), "eps must be 1..8"),
+                     (dict(min_samples=0), "min_samples at least 1"), (dict(max_clusters=0), "max_clusters"), (dict(max_clusters=65536), "max_clusters")):
+        args = dict(values=ok, threshold=0.5, eps=5, min_samples=10, max_clusters=16)
+        args.update(kw)
+        try:
+            VIS.grid_dbscan(**args)
+        except Exception as e:
+            assert text in str(e) and "gs_grid_dbscan" in str(e), (kw, str(e))
+            assert text.encode() in lib.gs_last_error()
+        else:
+            raise AssertionError(f"grid_dbscan accepted {list(kw)}")
+    assert lib.gs_grid_dbscan(1, 24, 40, None, 40, 960, 0.5, 0, 5, 10, 16, None, None, None, None, None, None, None) == 1       # GS_EINVAL
+    assert b"gs_grid_dbscan" in lib.gs_last_error()
+    B = 64 if batch64 else 2                             # the size the issue requires: 150 x 360, B = 64 (on the emulated kernels: 2 images)
+    big = VIS.grid_dbscan(torch.zeros(B, 150, 360, device=device), 0.8, 5, 25, complement=True)
+    assert big.labels.shape == (B, 150, 360) and bool((big.n_clusters == 1).all()) and bool((big.count[:, 0] == 54000).all())
+    assert bool((big.labels == 0).all()) and bool((big.total == 54000).all())
+
+
+def check_repeatable(device):
+    values, _ = reference("global", 0)
+    v = torch.from_numpy(np.stack([values, values[::-1].copy()])).to(device)
+    a = VIS.grid_dbscan(v, 0.8, 5, 25, complement=True)
+    b = VIS.grid_dbscan(v, 0.8, 5, 25, complement=True)
+    for k in a._fields:
+        assert torch.equal(getattr(a, k), getattr(b, k)), k              # (bit-identical: integer tensors and the two float sums)
+
+
+# ---- the queries ----------------------------------------------------------------------------------------------------------------------------
+
+def shell_params(device, n=1500, seed=2):
+    p = syn.shell_scene(n, seed=seed, W=LA.LOOK_W, H=LA.LOOK_H)
+    return {k: v.to(device) for k, v in p.items()}
+
+
+def base_pose():
+    c2w = np.eye(4)
+    c2w[:3, 3] = [0.1, 0.0, -0.2]
+    return c2w
+
+
+def node_positions(K, zero_at=None):
+    g = np.random.default_rng(K)
+    p = np.stack([0.4 * g.uniform(-1, 1, K), g.uniform(1, 9, K), 0.4 * g.uniform(-1, 1, K)], 1)
+    if zero_at is not None:
+        p[zero_at] = 0.0
+    return p
+
+
+def check_look_around_nodes(device, K, params=None, nodes_per_pass=None):
+    """look_around_nodes against per-node look_around (parent-commit code), one position all zero.
+    nodes_per_pass=None, the default of the call: the issue's cap, the atlas bound of tests/test_lookaround.py scaled by 63 / 3, for EVERY value.
+      Measured on the MI355X with all 63 slots in one pass (K = 21): max |opacity difference| 3.9e-3 (cap 2.1e-4), max |depth difference| 1.1e-2
+      (cap 4.2e-4 + 2.1e-4 |depth|): single pixels where a Gaussian's alpha >= 1/255 test flips; the smooth part (fp32 rounding of the slot offset)
+      is 2e-5 per node, 1e-4 at node 17, inside the cap.  On the emulated kernels a pass of only TWO nodes already has such a pixel (2.3e-3), so
+      the call renders ONE node per pass by default, as the issue prescribes for a measured maximum over the cap: a node's views then sit in
+      slots 0-2, where look_around renders them, and the measured maximum is 0 (every figure printed below).
+    nodes_per_pass=21 (the option that renders 63 views in one pass): the same cap under the project's rule for alpha = 1/255 decision flips
+      (tests/parity_cases.py: at least 99.9 % of the values inside the tolerance, none further out than 0.02)."""
+    params = shell_params(device) if params is None else params
+    c2w = base_pose()
+    pos = node_positions(K, zero_at=K // 2 if K > 1 else None)
+    pano = VIS.look_around_nodes(params, c2w, pos, nodes_per_pass=nodes_per_pass)
+    assert pano.opacity.shape == (K, 150, 360) and pano.depth.shape == (K, 150, 360, 1) and pano.rgb.shape == (K, 150, 360, 3)
+    assert pano.rgb.dtype == torch.uint8
+    worst = [0.0, 0.0]
+    for k in range(K):
+        pose = VIS.node_pose(c2w, pos[k])
+        if K > 1 and k == K // 2:
+            assert pose is None and pano.node(k) is None and not pano.valid[k]
+            continue
+        one = LA.look_around(params, pose)
+        got = pano.node(k)
+        worst[0] = max(worst[0], float((got["opacity"] - one["opacity"]).abs().max()))
+        worst[1] = max(worst[1], float((got["depth"] - one["depth"]).abs().max()))
+        if nodes_per_pass is None:
+            assert torch.allclose(got["opacity"], one["opacity"], atol=OPACITY_ATOL, rtol=0), (K, k, worst)
+            assert torch.allclose(got["depth"], one["depth"], atol=DEPTH_ATOL, rtol=DEPTH_RTOL), (K, k, worst)
+        else:
+            d_op, d_dp = (got["opacity"] - one["opacity"]).abs(), (got["depth"] - one["depth"]).abs()
+            assert float((d_op > OPACITY_ATOL).float().mean()) <= 1e-3 and float(d_op.max()) <= 0.02, (K, k, worst)
+            assert float((d_dp > DEPTH_ATOL + DEPTH_RTOL * one["depth"].abs()).float().mean()) <= 1e-3, (K, k, worst)
+            assert float(d_dp.max()) <= 0.02 * max(1.0, float(one["depth"].abs().max())), (K, k, worst)
+        assert int((got["rgb"].int() - one["rgb"].int()).abs().max()) <= 1
+        assert float(one["opacity"].max()) > 0.5
+    print(f"look_around_nodes K={K}, nodes per pass {nodes_per_pass or VIS.NODES_PER_PASS}: max |opacity difference| {worst[0]:.3e} (cap {OPACITY_ATOL:.1e}), max |depth difference| {worst[1]:.3e} "
+          f"(cap {DEPTH_ATOL:.1e} + {DEPTH_RTOL:.1e} |depth|)")
+    return pano
+
+
+def check_global_nodes(device, K, nodes_per_pass=None):
+    """global_invisibility_nodes = look_around_nodes + grid_dbscan(complement) on the same tensors, exactly.  With all K nodes valid and in one
+    pass the panoramas are a strided view of the atlas gather (rows K * 360 floats apart): the strided read of gs_grid_dbscan."""
+    params = shell_params(device, n=400)                 # a sparse shell: holes of low opacity, so the panoramas have clusters
+    c2w = base_pose()
+    pos = node_positions(K, zero_at=1 if K > 2 else None)
+    nodes = VIS.global_invisibility_nodes(params, c2w, pos, nodes_per_pass=nodes_per_pass)
+    pano = VIS.look_around_nodes(params, c2w, pos, nodes_per_pass=nodes_per_pass)
+    if nodes_per_pass is not None and nodes_per_pass >= K > 1 and all(pano.valid):
+        assert pano.opacity.stride() == (360, K * 360, 1) and not pano.opacity.is_contiguous()
+    g = VIS.grid_dbscan(pano.opacity, 0.8, 5, 25, complement=True)
+    assert len(nodes) == K
+    seen = 0
+    for k in range(K):
+        if not pano.valid[k]:
+            assert nodes[k] is None
+            continue
+        d = nodes[k]
+        m = min(int(g.n_clusters[k]), 256)
+        seen += m
+        assert np.array_equal(d["labels"], g.labels[k].cpu().numpy()) and d["n_clusters"] == int(g.n_clusters[k])
+        for f in ("count", "sum_row", "sum_col", "root", "sum_value"):
+            assert np.array_equal(d[f], getattr(g, f)[k, :m].cpu().numpy()), f
+        assert d["total"] == float(g.total[k])
+        assert np.array_equal(d["depth"], pano.depth[k].cpu().numpy()) and d["depth"].shape == (150, 360, 1)
+        assert np.array_equal(d["invisibility"], (1.0 - pano.opacity[k]).cpu().numpy())
+        # and the labels are the rule's, on the invisibility the caller receives
+        ref = restate(pano.opacity[k].cpu().numpy(), 0.8, 5, 25, True)
+        assert np.array_equal(d["labels"], ref["labels"]) and np.array_equal((d["invisibility"] > np.float32(0.8)), ref["mask"])
+    assert seen > 0, "no clusters in any panorama: the scene does not exercise the query"
+    return nodes
+
+
+def restate_local(opacity, view_c2w, threshold=30):
+    """src/mapper/splatam/__init__.py:795-830 op for op on the panorama's opacity (numpy fp32 [150, 360]); cv2.resize(INTER_AREA) at 0.5 as
+    ((a + b) + (c + d)) * 0.25f; get_invisibility_clusters with the restated labels and fp64 sums -> (sum, pose or None, cluster sums)"""
+    invisibility_np = np.float32(1) - opacity
+    sum_invisibility = float(invisibility_np.astype(np.float64).sum())
+    a, b, c, d = invisibility_np[0::2, 0::2], invisibility_np[0::2, 1::2], invisibility_np[1::2, 0::2], invisibility_np[1::2, 1::2]
+    small = ((a + b) + (c + d)) * np.float32(0.25)
+    r = restate(small, 0.3, 5, 10)
+    best_pose_c2w = None
+    sums = r["sum_value"]
+    if sum_invisibility > 100:
+        cluster_centers = [np.array([r["sum_row"][c] / r["count"][c], r["sum_col"][c] / r["count"][c]]) for c in range(r["n_clusters"]) if sums[c] > threshold]
+        cluster_invisibilities = [sums[c] for c in range(r["n_clusters"]) if sums[c] > threshold]
+        if len(cluster_invisibilities) > 0:
+            max_area_center = cluster_centers[int(np.argmax(cluster_invisibilities))]
+            factor_width = factor_height = 0.5
+            width, height = 120, 150
+            center_vec = np.array([max_area_center[1] / factor_width - width / 2, max_area_center[0] / factor_height - height / 2])
+            horizontal_angle = np.deg2rad(center_vec[0])
+            vertical_angle = np.deg2rad(center_vec[1])
+            if np.abs(horizontal_angle) > np.deg2rad(15) or np.abs(vertical_angle) > np.deg2rad(15):
+                best_pose_c2w = LA.rot_axis(view_c2w, "y", horizontal_angle)
+                best_pose_c2w = LA.rot_axis(best_pose_c2w, "x", vertical_angle)
+    return sum_invisibility, best_pose_c2w, sums
+
+
+def cap_params(device, yaw_deg, pitch_deg, half_angle_deg, n=12000, seed=3, radius=3.0, scale=0.12, logit=6.0, more_holes=()):
+    """A dense opaque sphere of Gaussians around the origin with a circular hole of `half_angle_deg` around the direction (yaw, pitch) of the
+    camera frame x right, y down, z forward: the panorama is opaque except for one blob of invisibility there."""
+    g = torch.Generator().manual_seed(seed)
+    d = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=1)
+    yaw, pitch = np.deg2rad(yaw_deg), np.deg2rad(pitch_deg)
+    axis = torch.tensor([np.sin(yaw) * np.cos(pitch), np.sin(pitch), np.cos(yaw) * np.cos(pitch)], dtype=torch.float32)
+    keep = (d @ axis) < np.cos(np.deg2rad(half_angle_deg))
+    for yaw2, pitch2, half2 in more_holes:
+        y2, p2 = np.deg2rad(yaw2), np.deg2rad(pitch2)
+        keep &= (d @ torch.tensor([np.sin(y2) * np.cos(p2), np.sin(p2), np.cos(y2) * np.cos(p2)], dtype=torch.float32)) < np.cos(np.deg2rad(half2))
+    d = d[keep]
+    m = d.shape[0]
+    p = dict(means3D=(radius * d).contiguous(), rgb_colors=torch.rand(m, 3, generator=g), unnorm_rotations=torch.randn(m, 4, generator=g),
+             logit_opacities=torch.full((m, 1), logit), log_scales=torch.log(torch.full((m, 1), scale)))
+    return {k: v.to(device) for k, v in p.items()}
+
+
+#: (name, hole yaw, pitch, half angle, cluster threshold, what the reference returns)
+LOCAL_SCENES = (("turn", 100.0, 10.0, 25.0, 30, "pose"), ("turn to the larger of two", -120.0, -20.0, 17.0, 30, "pose"), ("below the gate", 100.0, 10.0, 3.0, 30, "gate"),
+                ("clusters under the threshold", 100.0, 10.0, 25.0, 10 ** 6, "threshold"), ("inside the centre", 2.0, 1.0, 20.0, 30, "centre"))
+
+
+def check_local_target(device, name):
+    _, yaw, pitch, half, thr, kind = next(s for s in LOCAL_SCENES if s[0] == name)
+    params = cap_params(device, yaw, pitch, half, more_holes=((100.0, 10.0, 25.0),) if name == "turn to the larger of two" else ())
+    c2w = base_pose()
+    c2w[:3, 3] = [0.05, 0.0, -0.05]
+    c2w = LA.rot_axis(c2w, "y", 0.3)
+    opacity = LA.look_around(params, c2w)["opacity"].cpu().numpy()
+    want_sum, want_pose, sums = restate_local(opacity, c2w, thr)
+    # the input condition, on the restatement alone: no cluster sum within 1e-3 (relative) of the threshold, the best two 1e-3 apart, and the
+    # gate not within 1e-3 of the sum
+    assert abs(want_sum - 100) > 1e-3 * 100
+    assert all(abs(s - thr) > 1e-3 * thr for s in sums), sums
+    top = np.sort(sums)[::-1]
+    assert len(top) < 2 or top[0] - top[1] > 1e-3 * top[0], top
+    over = [s for s in sums if s > thr]
+    assert {"pose": want_pose is not None, "gate": want_sum <= 100 and want_pose is None, "threshold": want_sum > 100 and not over and len(sums) > 0,
+            "centre": want_sum > 100 and len(over) > 0 and want_pose is None}[kind], (name, want_sum, sums)
+    got_sum, got_pose = VIS.local_invisibility_target(params, c2w, cluster_invisibility_threshold=thr)
+    print(f"local target '{name}': sum {got_sum:.3f} (restated {want_sum:.3f}), cluster sums {np.round(sums, 2)}")
+    assert abs(got_sum - want_sum) <= SUM_RTOL * want_sum
+    assert (got_pose is None) == (want_pose is None)
+    if want_pose is not None:
+        assert np.abs(got_pose - want_pose).max() <= 1e-12
+
+
+def check_mapper(device, frames=2, W=64, H=48):
+    """SplatMapper.global_invisibility_nodes / local_invisibility_target after a few mapped frames: the module's functions on the mapper's parameters"""
+    from activesplat_amd.mapper import SplatMapper
+    gt = syn.shell_scene(3000, seed=2, W=W, H=H)
+    gt["logit_opacities"] = gt["logit_opacities"] + 3.0
+    mp = SplatMapper(syn.intrinsics(W, H), W, H, config=dict(step_num=frames), device=device)
+    for fr in syn.orbit_sequence(gt, frames, W, H, device):
+        mp.run(fr)
+    c2w = base_pose()
+    pos = node_positions(3, zero_at=0)
+    got, want = mp.global_invisibility_nodes(c2w, pos), VIS.global_invisibility_nodes(mp.params, c2w, pos)
+    assert got[0] is None and want[0] is None
+    for a, b in zip(got[1:], want[1:]):
+        assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)
+    s_got, p_got = mp.local_invisibility_target(c2w)
+    s_want, p_want = VIS.local_invisibility_target(mp.params, c2w)
+    assert s_got == s_want and (p_got is None) == (p_want is None) and (p_got is None or np.array_equal(p_got, p_want))
+    print(f"[visibility mapper] {mp.params['means3D'].shape[0]} Gaussians: local sum {s_got:.1f}, pose {'yes' if p_got is not None else 'none'}, "
+          f"clusters per node {[d['n_clusters'] for d in got[1:]]}")
