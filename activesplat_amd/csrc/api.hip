@@ -17,6 +17,18 @@ int fail(int code, const char* fmt, const char* a = "")
     return code;
 }
 
+// adam.hip and the Adam inside the per-Gaussian backward reinterpret these pointers as float4*
+bool adam_aligned16(const void* p, const void* g, const void* m, const void* v)
+{
+    return (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15u) == 0;
+}
+
+int fail_adam_alignment(const char* who, int tensor)
+{
+    snprintf(g_err, sizeof(g_err), "%s: tensor %d: param / grad / exp_avg / exp_avg_sq must be 16-byte aligned (the kernel makes 128-bit accesses)", who, tensor);
+    return GS_EINVAL;
+}
+
 uint64_t align_up(uint64_t v, uint64_t a = 256) { return (v + a - 1) / a * a; }
 
 // ---- optional per-stage timing with HIP events on the caller's stream (bench.py roofline leg) ----
@@ -617,6 +629,9 @@ static int render_backward_impl(const GsCamera* cam, int32_t P, int64_t D, const
             if (a.param != par[t] || !a.exp_avg || !a.exp_avg_sq || a.step < 1 || a.n != width[t] * (int64_t)P)
                 return fail(GS_EINVAL, "gs_render_backward_raw_adam: descriptor of %s does not describe the input tensor (param / moments / n / step)",
                             t == 0 ? "means3D" : t == 1 ? "logit_opacities" : t == 2 ? "log_scales" : t == 3 ? "unnorm_rotations" : "the colours");
+            // the kernel reads and writes the rotation rows, and the SH rows, of parameter and moments as float4
+            if (P > 0 && (t == 3 || (t == 4 && shs)) && !adam_aligned16(a.param, a.param, a.exp_avg, a.exp_avg_sq))
+                return fail_adam_alignment("gs_render_backward_raw_adam", t);
             fa.p[t] = a.param; fa.m[t] = a.exp_avg; fa.v[t] = a.exp_avg_sq;
             fa.c[t] = gs::adam_coef(a.lr, a.beta1, a.beta2, a.eps, a.step);
         }
@@ -805,6 +820,8 @@ int gs_adam_step(int64_t n, float* param, const float* grad, float* exp_avg, flo
 {
     if (n < 0 || step < 1) return fail(GS_EINVAL, "gs_adam_step: bad n/step");
     if (n > 0 && (!param || !grad || !exp_avg || !exp_avg_sq)) return fail(GS_EINVAL, "gs_adam_step: null pointer");
+    if (n > 0 && !adam_aligned16(param, grad, exp_avg, exp_avg_sq))
+        return fail_adam_alignment("gs_adam_step", 0);
     hipError_t e;
     {
         ScopedStage ps(ST_ADAM, (hipStream_t)stream);
@@ -821,6 +838,9 @@ int gs_adam_step_multi(int32_t count, const GsAdamTensor* tensors, gs_stream_t s
         const GsAdamTensor& t = tensors[i];
         if (t.n < 0 || t.step < 1) return fail(GS_EINVAL, "gs_adam_step_multi: a tensor has bad n/step");
         if (t.n > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq)) return fail(GS_EINVAL, "gs_adam_step_multi: a tensor has a null pointer");
+        // checked for the whole array before the first launch: a refusal leaves every tensor of the call untouched
+        if (t.n > 0 && !adam_aligned16(t.param, t.grad, t.exp_avg, t.exp_avg_sq))
+            return fail_adam_alignment("gs_adam_step_multi", i);
     }
     hipError_t e;
     {

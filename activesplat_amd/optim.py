@@ -71,7 +71,7 @@ class GaussianAdam:
     def step(self):
         """All parameter tensors that hold a gradient advance in ONE kernel launch (gs_adam_step_multi)."""
         lib = _lib.get()
-        live, keep, stream = [], [], None
+        live, keep, fresh = [], [], []
         for g in self.param_groups:
             for p in g["params"]:
                 if p.grad is None:
@@ -81,6 +81,7 @@ class GaussianAdam:
                 st = self.state.get(p)
                 if st is None or len(st) == 0:
                     st = self.state[p] = {"step": 0, "exp_avg": torch.zeros_like(p), "exp_avg_sq": torch.zeros_like(p)}
+                    fresh.append(p)
                 # the step counter is a host NUMBER (torch.optim.Adam keeps a host tensor; every use here and in the reference --
                 # float(), +, comparison -- works on both, and a 0-dim tensor increment costs 3.6 us per parameter per step)
                 st["step"] = int(st["step"]) + 1
@@ -111,8 +112,17 @@ class GaussianAdam:
             b1, b2 = g["betas"]
             t.n = p.numel(); t.grad = grad.data_ptr(); t.step = st["step"]; t.lr = float(g["lr"])
             t.beta1 = float(b1); t.beta2 = float(b2); t.eps = float(g["eps"])
-        _lib.check(lib.gs_adam_step_multi(len(live), arr, _stream(live[0][1])))
-
+        try:
+            _lib.check(lib.gs_adam_step_multi(len(live), arr, _stream(live[0][1])))
+        except Exception:
+            # the library refuses the whole call before its first launch (a parameter, gradient or moment that is not 16-byte aligned: a
+            # contiguous view at an odd element offset): no tensor was stepped, so no counter may stay advanced (rollback_backward_step's rule)
+            for _, p, st, _ in live:
+                st["step"] = int(st["step"]) - 1
+            for p in fresh:
+                del self.state[p]
+            self._launch_cache = None
+            raise
 
     @torch.no_grad()
     def backward_step_descriptors(self, tensors):

@@ -290,7 +290,11 @@ int gs_render_backward_raw_pose(const GsCamera* cam, int32_t P, int64_t D, const
  * (non-amsgrad, no weight decay): splatam.py:118-124 uses betas (0.9,0.999), eps 1e-15.
  * `step` is the 1-based step count of this tensor AFTER the increment.  Hyper-parameters are doubles (as the
  * Python floats torch receives): 1-beta, the bias corrections and lr/(1-beta1^t) are formed in double and
- * rounded to fp32 once, exactly like torch's scalar handling. */
+ * rounded to fp32 once, exactly like torch's scalar handling.
+ * param, grad, exp_avg and exp_avg_sq of a tensor with n > 0 must be 16-byte aligned (the kernels make 128-bit accesses): anything else --
+ * a contiguous view at an odd element offset -- is GS_EINVAL, with the index of the tensor in the message, before anything is launched
+ * (gs_adam_step_multi: before the first launch of the batch, so no tensor of a refused call is stepped).  gs_render_backward_raw_adam
+ * asks the same of param / exp_avg / exp_avg_sq of unnorm_rotations and of the SH rows.  gs_adam_rows takes any 4-byte-aligned pointer. */
 int gs_adam_step(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                  double lr, double beta1, double beta2, double eps, int32_t step, gs_stream_t stream);
 
