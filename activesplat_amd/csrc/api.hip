@@ -1116,6 +1116,28 @@ int gs_grid_dbscan(int32_t B, int32_t H, int32_t W, const float* values, int64_t
     return GS_OK;
 }
 
+int gs_high_loss_grid(int32_t width, int32_t height, const float* render_depth, const float* opacity, const float* gt_depth,
+                      float depth_err_thres, float opacity_thres, int32_t grid_width, int32_t grid_height, uint8_t* mask_full, float* grid,
+                      gs_stream_t stream)
+{
+    if (width < 1 || height < 1 || width > 16384 || height > 16384)
+        return fail(GS_EINVAL, "gs_high_loss_grid: image size out of range (1 <= width, height <= 16384)");
+    if (grid_width < 1 || grid_height < 1 || grid_width > 4096 || grid_height > 4096 || (int64_t)grid_width * grid_height > 65536)
+        return fail(GS_EINVAL, "gs_high_loss_grid: grid size out of range (1 <= grid_width, grid_height <= 4096, grid_width * grid_height <= 65536)");
+    // (written so that a NaN fails them: finite and not negative)
+    if (!(depth_err_thres >= 0.0f && depth_err_thres <= 3.402823466e38f) || !(opacity_thres >= 0.0f && opacity_thres <= 3.402823466e38f))
+        return fail(GS_EINVAL, "gs_high_loss_grid: thresholds must be finite and not negative");
+    if (!render_depth || !opacity || !gt_depth || !grid) return fail(GS_EINVAL, "gs_high_loss_grid: null pointer (only mask_full may be null)");
+    gs::HighLossArgs a;
+    a.depth = render_depth; a.opacity = opacity; a.gt = gt_depth;
+    a.W = width; a.H = height; a.gw = grid_width; a.gh = grid_height;
+    a.depth_thres = depth_err_thres; a.opacity_thres = opacity_thres;
+    a.mask_full = mask_full; a.grid = grid;
+    hipError_t e = gs::launch_high_loss_grid(a, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_high_loss_grid: %s", hipGetErrorString(e));
+    return GS_OK;
+}
+
 uint64_t gs_grow_scratch_bytes(int32_t width, int32_t height)
 {
     return align_up(gs::grow_scratch_bytes((int64_t)(width > 0 ? width : 1) * (height > 0 ? height : 1)));

@@ -840,6 +840,15 @@ struct DbscanArgs {
     int32_t *labels, *n_clusters, *table; float *sum_value, *total;    // outputs
 };
 hipError_t launch_grid_dbscan(const DbscanArgs& a, int B, hipStream_t st);
+// the per-frame high-loss mask and its one-pixel-per-degree grid (stats.hip; both rules: include/gsplat_hip.h, gs_high_loss_grid)
+struct HighLossArgs {
+    const float *depth, *opacity, *gt;                                 // [H * W] each
+    int W, H, gw, gh;                                                  // image and grid sizes
+    float depth_thres, opacity_thres;
+    uint8_t* mask_full;                                                // [H * W], nullable
+    float* grid;                                                       // [gh * gw]
+};
+hipError_t launch_high_loss_grid(const HighLossArgs& a, hipStream_t st);
 uint64_t grow_scratch_bytes(int64_t npix);
 hipError_t launch_grow(int W, int H, const float* rd, const float* sil, const float* gt, const float* color, const float* k4,
                        const float* c2w12, float sil_thres, int isotropic, float* means3D, float* rgb, float* rot, float* logit,

@@ -15,6 +15,9 @@
 //                       flatten + root bits -> per-image scan of the root bits (cluster number = rank of the root) -> labels (a border pixel
 //                       takes the smallest root in its disc) and each cluster's row range -> per-cluster sums in a fixed order.
 //                     Parents and roots are int32 arrays in global memory (216 KiB per 150 x 360 image: L2 resident); see DESIGN.md.
+//
+//  high_loss_grid   : the mask of get_high_loss_samples (src/mapper/splatam/__init__.py:212-215) and its cv2.resize to one pixel per degree
+//                     (:218) in integers, one launch; the grid is what grid_dbscan reads next.  Rules: include/gsplat_hip.h.
 #include "gs_common.h"
 
 namespace gs {
@@ -328,6 +331,52 @@ hipError_t launch_grid_dbscan(const DbscanArgs& a, int B, hipStream_t st)
     hipLaunchKernelGGL(dbscan_scan_kernel, dim3(B), dim3(kBlock), 0, st, a);
     hipLaunchKernelGGL(dbscan_label_kernel, waves, dim3(kBlock), 0, st, a);
     hipLaunchKernelGGL(dbscan_sums_kernel, dim3(1 + a.max_clusters, B), dim3(kDbscanSumBlock), 0, st, a);
+    return hipGetLastError();
+}
+
+// ---- the per-frame high-loss mask and its grid ------------------------------------------------------------------------------------------------
+// (src/mapper/splatam/__init__.py:212-218; both rules are stated in include/gsplat_hip.h, gs_high_loss_grid)
+
+// the pixel rule, fp32, operation for operation the reference's; every comparison with a NaN is false
+__device__ __forceinline__ int high_loss_pixel(const HighLossArgs& a, int i)
+{
+    const float d = a.depth[i], g = a.gt[i];
+    const float err = fabsf(d - g) * (g > 0.0f ? 1.0f : 0.0f);
+    return (d > g && err > a.depth_thres && a.opacity[i] > a.opacity_thres) ? 1 : 0;
+}
+
+// one axis of the resize in integers: the two taps (clamped into the source) and the weight of the second, out of den = 2 n_dst
+__device__ __forceinline__ void high_loss_taps(int d, int n_src, int n_dst, int& t0, int& t1, int& w1)
+{
+    const int den = 2 * n_dst, num = (2 * d + 1) * n_src - n_dst;      // |num| < 2^28 for the sizes the call admits
+    int i0 = num / den;
+    if (num - i0 * den < 0) i0 -= 1;                                   // floor towards -inf: num is negative at the first samples when upsampling
+    w1 = num - i0 * den;
+    t0 = i0 < 0 ? 0 : (i0 > n_src - 1 ? n_src - 1 : i0);
+    t1 = i0 + 1 < 0 ? 0 : (i0 + 1 > n_src - 1 ? n_src - 1 : i0 + 1);
+}
+
+// thread i: pixel i of the full-resolution mask (when asked for) and pixel i of the grid.  The grid evaluates the pixel rule at its four taps
+// itself, so it does not wait for (or depend on) the mask.
+__global__ __launch_bounds__(kBlock) void high_loss_grid_kernel(HighLossArgs a)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (a.mask_full && i < a.W * a.H) a.mask_full[i] = (uint8_t)high_loss_pixel(a, i);
+    if (i >= a.gw * a.gh) return;
+    const int gy = i / a.gw, gx = i - gy * a.gw;
+    int x0, x1, wx1, y0, y1, wy1;
+    high_loss_taps(gx, a.W, a.gw, x0, x1, wx1);
+    high_loss_taps(gy, a.H, a.gh, y0, y1, wy1);
+    const int den_x = 2 * a.gw, den_y = 2 * a.gh, wx0 = den_x - wx1, wy0 = den_y - wy1;
+    const int S = high_loss_pixel(a, y0 * a.W + x0) * wy0 * wx0 + high_loss_pixel(a, y0 * a.W + x1) * wy0 * wx1 +
+                  high_loss_pixel(a, y1 * a.W + x0) * wy1 * wx0 + high_loss_pixel(a, y1 * a.W + x1) * wy1 * wx1;
+    a.grid[i] = 2 * S >= den_x * den_y ? 1.0f : 0.0f;                  // S <= den_x * den_y <= 2^26: the bilinear value rounded half up
+}
+
+hipError_t launch_high_loss_grid(const HighLossArgs& a, hipStream_t st)
+{
+    const int npix = a.mask_full ? a.W * a.H : 0, ngrid = a.gw * a.gh, n = npix > ngrid ? npix : ngrid;
+    hipLaunchKernelGGL(high_loss_grid_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
     return hipGetLastError();
 }
 

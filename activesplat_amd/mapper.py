@@ -20,8 +20,10 @@ habitat).  It reproduces the CALL PATTERN and SCHEDULE of the hot loop, nothing 
                                   frame's ground-truth pose holds inf / nan (__init__.py:514-524)
   every frame once a map exists : get_high_loss_samples' render of the map at the frame's pose (two raster passes in the
                                   reference, one with fused_render) and its "rendered surface in front of a measured one" mask
-                                  (__init__.py:184-214, 256-258); the mask's cv2 resize stays with the caller, who can
-                                  pass the resized mask to visibility.grid_dbscan for the DBSCAN step (__init__.py:216-250)
+                                  (__init__.py:184-214, 256-258).  With high_loss_target=True the rest of that method runs on the
+                                  device too (visibility.high_loss_grid: the mask and its resize to one pixel per degree in one
+                                  launch; visibility.grid_dbscan), and `high_loss_samples_pose_c2w` resolves the look target
+                                  (__init__.py:216-250) from one small copy when it is first read
 
 Inputs are already-resized frames (`color [3,H,W]` in 0..1, `depth [1,H,W]` metres, pose relative to frame 0 as
 quaternion (w,x,y,z) + translation of the w2c) -- the cv2 resize / PNG / manifest work of the reference is I/O
@@ -59,6 +61,10 @@ DEFAULT_CONFIG = dict(
     fused_tracking=False,    # tracking (tracking.use_gt_poses=False): mapping.track_frame's HIP loop (tracking_iteration) instead of the reference pattern
     fused_keyframes=True,    # (accepted for older configs; no effect: the keyframe overlap scores always come from gs_keyframe_overlap, one launch)
     high_loss_samples=True,  # the per-frame no-grad render of get_high_loss_samples (__init__.py:184-258) before mapping a frame
+    high_loss_target=False,  # ... and the rest of get_high_loss_samples on the device (gs_high_loss_grid + gs_grid_dbscan): the look target of the
+                             # frame is then `SplatMapper.high_loss_samples_pose_c2w`, resolved from one small copy when it is read
+    cluster_invisibility_threshold=25,   # config/datasets/gibson.json:60
+    high_loss_fov=(90, 90),  # (hfov, vfov) of get_high_loss_samples: the grid has one pixel per degree
     mapping=dict(
         loss_weights=dict(im=0.5, depth=1.0), sil_thres=0.98, use_sil_for_loss=False, use_l1=True,
         ignore_outlier_depth_loss=False, add_new_gaussians=True, prune_gaussians=False,
@@ -106,6 +112,9 @@ class SplatMapper:
         self.stats = dict(iters=0, iter_time=0.0, frames=0, frame_time=0.0, tracking_iters=0, tracking_time=0.0, tracked_frames=0)
         self._last_losses = None           # device scalars of the most recent iteration (read through `last_losses`)
         self.high_loss_mask = None          # bool [H,W] of the most recent frame (None before the first map exists)
+        self.high_loss_grid = None          # float32 [vfov, hfov] of 0 / 1 (high_loss_target=True): the reference's non_presence_depth_mask_cv2 / 255
+        self._high_loss_pending = None      # (host w2c or None, device w2c or None, GridClusters) of the most recent frame, until the pose is read
+        self._high_loss_pose = None
 
     @property
     def last_losses(self):
@@ -113,6 +122,27 @@ class SplatMapper:
         if self._last_losses is None:
             return None
         return {k: float(v.detach()) for k, v in self._last_losses.items()}
+
+    @property
+    def high_loss_samples_pose_c2w(self):
+        """The look target of the most recent frame (get_high_loss_samples' return value; needs high_loss_target=True): the frame's camera turned
+        towards the centre of the largest high-loss cluster, or None -- also before the first map exists.  run() only enqueues the kernels; the first
+        read makes ONE small device-to-host copy (the grid's sum, the cluster table and, for a tracked frame, the pose matrix), which synchronises
+        with the device, and the result is kept for that frame."""
+        if self._high_loss_pending is not None:
+            from . import visibility as VIS
+            w2c_host, w2c_dev, g = self._high_loss_pending
+            hfov, vfov = (int(v) for v in self.cfg["high_loss_fov"])
+            tensors = [g.total.reshape(1), g.n_clusters.reshape(1), g.count, g.sum_row, g.sum_col] + ([w2c_dev] if w2c_dev is not None else [])
+            tot, n, count, sr, sc, *pose = VIS._one_copy(tensors)
+            total, m = float(tot[0]), int(n[0])
+            if m > count.shape[0]:                       # (more clusters than rows in the table: once more with enough rows)
+                total, count, sr, sc, _ = VIS.high_loss_clusters(self.high_loss_grid, m)
+            w2c = pose[0] if pose else w2c_host.numpy()
+            self._high_loss_pose = VIS.target_from_high_loss_clusters(np.linalg.inv(w2c.astype(np.float64)), total, count[:m], sr[:m], sc[:m],
+                                                                      self.cfg["cluster_invisibility_threshold"], hfov, vfov)
+            self._high_loss_pending = None
+        return self._high_loss_pose
 
     # -- helpers ---------------------------------------------------------------------------------
     @staticmethod
@@ -160,9 +190,10 @@ class SplatMapper:
             self.stats["tracking_iters"] += res["iterations"]
             self.stats["tracking_time"] += time.perf_counter() - t_track
             self.stats["tracked_frames"] += 1
-        if self.params is not None and cfg.get("high_loss_samples", True):
+        self._high_loss_pending = self._high_loss_pose = None
+        if self.params is not None and (cfg.get("high_loss_samples", True) or cfg.get("high_loss_target", False)):
             view = self._w2c(fid) if tracked else self._w2c_host(quat_h, pos_h)      # (host pose: the camera block is built on the host)
-            self.high_loss_mask = self.high_loss_samples_mask(view, depth)
+            self.high_loss_step(view, depth, tracked)
         # densification-resolution copy of the frame (reference :362-376); defaults to the mapping resolution
         d_color = frame["densify_color"].to(self.device).float() if "densify_color" in frame else color
         d_depth = frame["densify_depth"].to(self.device).float() if "densify_depth" in frame else depth
@@ -270,6 +301,22 @@ class SplatMapper:
                 self.keyframe_list.append({"id": fid, "est_w2c": self._w2c(fid), "color": color, "depth": depth})
             self.gt_w2c_all_frames.append(gt_w2c)
         return self.params
+
+    @torch.no_grad()
+    def high_loss_step(self, view_w2c, gt_depth, tracked=False):
+        """The per-frame step of run(): `high_loss_mask` of the frame and, with high_loss_target=True, `high_loss_grid` and the clustering that
+        `high_loss_samples_pose_c2w` resolves when it is read (tracked: view_w2c is the tracker's pose, a device tensor that travels in that copy).  Only
+        enqueues work: the render, then -- for the target -- two library calls in place of the mask's torch expression."""
+        self._high_loss_pending = self._high_loss_pose = None
+        if not self.cfg.get("high_loss_target", False):
+            self.high_loss_mask = self.high_loss_samples_mask(view_w2c, gt_depth)
+            return
+        from . import visibility as VIS
+        _, depth, opacity = self.render_rgbd(view_w2c)
+        hfov, vfov = (int(v) for v in self.cfg["high_loss_fov"])
+        self.high_loss_mask, self.high_loss_grid = VIS.high_loss_grid(depth, opacity, gt_depth, hfov, vfov)
+        g = VIS.grid_dbscan(self.high_loss_grid, 0.0, VIS.HIGH_LOSS_EPS, VIS.HIGH_LOSS_MIN_SAMPLES)
+        self._high_loss_pending = (None, view_w2c, g) if tracked else (view_w2c, None, g)
 
     @torch.no_grad()
     def high_loss_samples_mask(self, view_w2c, gt_depth):

@@ -12,6 +12,10 @@ them as HIP kernels (gs_grid_dbscan, include/gsplat_hip.h states the rule) and r
 * `global_invisibility_nodes`   -- per node what `get_convexhull_volume` holds after its DBSCAN line, ONE device-to-host copy for all nodes.  The
                                    dilate / findContours / ConvexHull loop behind it (OpenCV, scipy) stays with the caller;
 * `local_invisibility_target`   -- the whole of `get_local_invisibility` (src/mapper/splatam/__init__.py:762-837) without its images.
+* `high_loss_grid`              -- the mask of `get_high_loss_samples` (src/mapper/splatam/__init__.py:212-215) and its cv2.resize to one pixel per
+                                   degree (:218), one launch (gs_high_loss_grid; the header states the pixel rule and the integer resize rule);
+* `high_loss_target`            -- the whole of `get_high_loss_samples` behind its render: that grid, `grid_dbscan`, ONE small device-to-host copy
+                                   and `target_from_high_loss_clusters` (:219-250 from the cluster table) -> the pose turned to the largest cluster.
 
 There is no CPU fallback.
 """
@@ -41,6 +45,10 @@ GLOBAL_THRESHOLD, GLOBAL_EPS, GLOBAL_MIN_SAMPLES = 0.8, 5, 25           # src/ma
 LOCAL_THRESHOLD, LOCAL_EPS, LOCAL_MIN_SAMPLES = 0.3, 5, 10              # src/mapper/__init__.py:93, :99
 LOCAL_GATE = 100                                                        # src/mapper/splatam/__init__.py:809
 LOCAL_SKIP_DEG = 15                                                     # :825
+HIGH_LOSS_DEPTH_ERR, HIGH_LOSS_OPACITY = 0.3, 0.8                       # src/mapper/splatam/__init__.py:215
+HIGH_LOSS_EPS, HIGH_LOSS_MIN_SAMPLES = 5, 10                            # :228
+HIGH_LOSS_GATE = 20                                                     # :223
+HIGH_LOSS_SKIP_DEG = 5                                                  # :248
 
 
 class GridClusters(NamedTuple):
@@ -161,7 +169,9 @@ def look_around_nodes(params, view_c2w, positions, scale_modifier=1.0, nodes_per
 
 def _one_copy(tensors):
     """several device tensors -> their numpy arrays through ONE device-to-host copy"""
-    flat = [t.contiguous().view(-1).view(torch.uint8) for t in tensors]
+    flat = [t.contiguous().view(-1) for t in tensors]
+    # (a one-element slice of a table counts as contiguous with its element stride still that of the table: restated with stride 1 for the byte view)
+    flat = [(f.as_strided((f.numel(),), (1,)) if f.numel() == 1 else f).view(torch.uint8) for f in flat]
     host = torch.cat(flat).cpu().numpy()
     out, o = [], 0
     for t, f in zip(tensors, flat):
@@ -243,3 +253,78 @@ def local_invisibility_target(params, view_c2w, cluster_invisibility_threshold=3
         max_clusters = int(n[0])                         # (more clusters than rows in the table: once more with enough rows)
     m = int(n[0])
     return float(tot[0]), target_from_clusters(view_c2w, tot[0], count[:m], sr[:m], sc[:m], sv[:m], cluster_invisibility_threshold)
+
+
+def _image(t, name):
+    if not torch.is_tensor(t) or not (t.dim() == 2 or (t.dim() == 3 and t.shape[0] == 1)):
+        raise ValueError(f"high_loss_grid: {name} must be an [H, W] or [1, H, W] tensor")
+    t = t.detach()
+    t = t[0] if t.dim() == 3 else t
+    return (t if t.dtype == torch.float32 else t.float()).contiguous()
+
+
+@torch.no_grad()
+def high_loss_grid(render_depth, opacity, gt_depth, hfov=90, vfov=90):
+    """The image half of `get_high_loss_samples` (src/mapper/splatam/__init__.py:212-218) in one launch: the mask `rendered depth > measured
+    depth  and  |error| > 0.3 m (measured pixels only)  and  opacity > 0.8` and its cv2.resize(INTER_LINEAR) to hfov x vfov pixels in exact
+    integers (gs_high_loss_grid, include/gsplat_hip.h states both rules).  The three images are [H, W] or [1, H, W] device tensors (strided ones
+    are made contiguous).  -> (mask_full bool [H, W], grid float32 [vfov, hfov] of 0.0 / 1.0), on the device.  No host synchronisation."""
+    lib = _lib.get()
+    d, o, g = _image(render_depth, "render_depth"), _image(opacity, "opacity"), _image(gt_depth, "gt_depth")
+    device = d.device
+    R._require_rocm(device)
+    if o.device != device or g.device != device or o.shape != d.shape or g.shape != d.shape:
+        raise ValueError("high_loss_grid: render_depth, opacity and gt_depth must have one shape and one device")
+    H, W = (int(n) for n in d.shape)
+    gw, gh = int(hfov), int(vfov)
+    mask = torch.empty(max(H, 0), max(W, 0), dtype=torch.uint8, device=device)
+    grid = torch.empty(max(gh, 0), max(gw, 0), dtype=torch.float32, device=device)
+    _lib.check(lib.gs_high_loss_grid(W, H, R._ptr(d), R._ptr(o), R._ptr(g), HIGH_LOSS_DEPTH_ERR, HIGH_LOSS_OPACITY, gw, gh, R._ptr(mask), R._ptr(grid),
+                                     _lib.stream_ptr(device)))
+    return mask.view(torch.bool), grid
+
+
+def target_from_high_loss_clusters(view_c2w, total, count, sum_row, sum_col, cluster_invisibility_threshold, hfov=90, vfov=90):
+    """src/mapper/splatam/__init__.py:219-250 on the host, from the cluster table of the grid -> high_loss_samples_pose_c2w or None.  `total` is
+    the number of ones in the grid (np.sum of the resized mask: the "no points" return and the > 20 gate); a cluster's `invisibility_sum` is
+    the sum of a 0 / 1 mask over its pixels, its count."""
+    if not total > HIGH_LOSS_GATE:
+        return None
+    keep = [c for c in range(len(count)) if count[c] > cluster_invisibility_threshold]
+    if not keep:
+        return None
+    best = keep[0]
+    for c in keep[1:]:                                   # np.argmax: the first of equal maxima
+        if count[c] > count[best]:
+            best = c
+    centre = (np.float64(sum_row[best]) / np.float64(count[best]), np.float64(sum_col[best]) / np.float64(count[best]))
+    center_vec = np.array([centre[1] / hfov * hfov - hfov / 2, centre[0] / vfov * vfov - vfov / 2])
+    horizontal_angle = np.deg2rad(center_vec[0])
+    vertical_angle = np.deg2rad(center_vec[1])
+    if np.abs(horizontal_angle) > np.deg2rad(HIGH_LOSS_SKIP_DEG) or np.abs(vertical_angle) > np.deg2rad(HIGH_LOSS_SKIP_DEG):
+        return LA.rot_axis(LA.rot_axis(np.asarray(view_c2w, dtype=np.float64), "y", horizontal_angle), "x", vertical_angle)
+    return None
+
+
+def high_loss_clusters(grid, max_clusters=256, extra=()):
+    """`grid_dbscan(grid, 0.0, 5, 10)` and ONE device-to-host copy of {total, n_clusters, table} (and of the device tensors of `extra`, which
+    travel in the same copy) -> (total, count, sum_row, sum_col, the arrays of extra).  More clusters than table rows: once more with enough rows."""
+    while True:
+        g = grid_dbscan(grid, 0.0, HIGH_LOSS_EPS, HIGH_LOSS_MIN_SAMPLES, max_clusters=max_clusters)
+        tot, n, count, sr, sc, *rest = _one_copy([g.total.reshape(1), g.n_clusters.reshape(1), g.count, g.sum_row, g.sum_col, *extra])
+        if int(n[0]) <= max_clusters:
+            break
+        max_clusters = int(n[0])
+    m = int(n[0])
+    return float(tot[0]), count[:m], sr[:m], sc[:m], rest
+
+
+@torch.no_grad()
+def high_loss_target(view_c2w, render_depth, opacity, gt_depth, cluster_invisibility_threshold=25, hfov=90, vfov=90, max_clusters=256):
+    """`get_high_loss_samples` behind its render -> (high_loss_samples_pose_c2w or None, mask_full, grid): `high_loss_grid`, DBSCAN(eps=5,
+    min_samples=10) on the grid's ones, one device-to-host copy of the grid's sum and the cluster table, and the pose turned towards the centre
+    of the largest cluster over `cluster_invisibility_threshold` pixels (the lowest cluster number wins a tie; None inside the 5-degree centre,
+    for at most 20 ones, and without such a cluster)."""
+    mask_full, grid = high_loss_grid(render_depth, opacity, gt_depth, hfov, vfov)
+    total, count, sr, sc, _ = high_loss_clusters(grid, max_clusters)
+    return target_from_high_loss_clusters(view_c2w, total, count, sr, sc, cluster_invisibility_threshold, hfov, vfov), mask_full, grid

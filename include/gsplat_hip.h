@@ -181,7 +181,7 @@ const char* gs_version(void);
 /* Integer version of THIS binary interface: bumped whenever an entry point's argument list or a published record layout changes (e.g.
  * the seed argument of gs_densify_children, the 40-byte SH Jacobian record).  A host binding compares it with the GS_ABI_VERSION it was
  * written against before the first call, so that a stale prebuilt library fails at load time instead of misreading its arguments. */
-#define GS_ABI_VERSION 14
+#define GS_ABI_VERSION 15
 int32_t gs_abi_version(void);
 
 /* Optional per-stage timing (hipEvents recorded on the caller's stream around each stage's launches).
@@ -562,6 +562,29 @@ int gs_grid_dbscan_layout(int32_t B, int32_t H, int32_t W, int32_t max_clusters,
 int gs_grid_dbscan(int32_t B, int32_t H, int32_t W, const float* values, int64_t row_stride, int64_t image_stride, float threshold,
                    int32_t complement, int32_t eps, int32_t min_samples, int32_t max_clusters, void* workspace, int32_t* labels,
                    int32_t* n_clusters, int32_t* table, float* sum_value, float* total, gs_stream_t stream);
+
+/* The per-frame look target's image half (get_high_loss_samples, src/mapper/splatam/__init__.py:212-218): the mask of the pixels where the
+ * map's render lies behind the measured depth, and that mask shrunk to a grid_height x grid_width grid (90 x 90: one pixel per degree), which
+ * gs_grid_dbscan(grid, threshold 0, eps 5, min_samples 10) clusters next.  render_depth, opacity, gt_depth: [height * width] fp32, DEVICE.
+ * Pixel rule (fp32, operation for operation :212-215):
+ *   err = fabsf(depth - gt) * (gt > 0 ? 1.0f : 0.0f);   m = depth > gt && err > depth_err_thres && opacity > opacity_thres
+ *   -- a NaN in any of the three makes the pixel 0, and so does an infinite depth over gt <= 0 (inf * 0 is NaN).
+ * Resize rule: cv2.resize(mask_u8, (grid_width, grid_height), INTER_LINEAR) on the 0 / 1 image, in integers.  Per axis with n_src source and
+ * n_dst destination samples, for destination sample d:
+ *   den = 2 n_dst;  num = (2 d + 1) n_src - n_dst   (the pixel-centre coordinate (d + 0.5) n_src / n_dst - 0.5, times den);
+ *   i0 = floor(num / den) (towards -inf);  w1 = num - i0 den;  w0 = den - w1;  taps clamp(i0), clamp(i0 + 1) into [0, n_src - 1];
+ *   S = sum over the four taps of m[tap_y][tap_x] * wy * wx;   grid = 1.0f iff 2 S >= den_x * den_y (the bilinear value rounded half up), else 0.0f.
+ * The rule is exact on every machine and equals float64 bilinear sampling of that convention pixel for pixel, exact ties included.  NOT pinned:
+ * for uint8 input cv2 quantises the two weights of an axis to 11 bits, so a grid pixel whose exact value lies within about 2^-11 of one half
+ * may come out differently in cv2 (exact ties are about 0.6 % of the grid pixels at 256 x 256 -> 90 x 90 on random masks); nobody has run cv2
+ * against this rule.
+ * Outputs, DEVICE: mask_full uint8 [height * width] (0 / 1; nullable -- the grid is the same with and without it), grid fp32 [grid_height *
+ * grid_width].  One launch, integer arithmetic behind the pixel rule, no atomics, no host synchronisation: nothing depends on scheduling.
+ * Supported: 1 <= width, height <= 16384; 1 <= grid_width, grid_height <= 4096 with grid_width * grid_height <= 65536 (what gs_grid_dbscan
+ * takes); finite thresholds >= 0; anything else, or a null pointer other than mask_full, is GS_EINVAL before any launch. */
+int gs_high_loss_grid(int32_t width, int32_t height, const float* render_depth, const float* opacity, const float* gt_depth,
+                      float depth_err_thres, float opacity_thres, int32_t grid_width, int32_t grid_height, uint8_t* mask_full, float* grid,
+                      gs_stream_t stream);
 
 /* Map growth (replaces add_new_gaussians, src/mapper/splatam/splatam.py:332-379, with get_pointcloud :25-75 and
  * initialize_new_params :304-329).  render_depth / silhouette / gt_depth are [H*W] device images, color is [3,H*W];
