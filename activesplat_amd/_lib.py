@@ -53,12 +53,16 @@ class GsDbscanLayout(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("total_bytes", "mask_bits", "core_bits", "root_bits", "word_prefix", "parent", "root", "row_range")]
 
 
+class GsHullLayout(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("total_bytes", "cluster_status")]
+
+
 SORT_AUTO, SORT_TILE_LDS, SORT_RADIX = 0, 1, 2
 
 
 # every symbol include/gsplat_hip.h declares (tests check the library exports all of them)
 #: the GS_ABI_VERSION of include/gsplat_hip.h this binding was written against (checked when a library is bound)
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 SYMBOLS = ("gs_abi_version", "gs_geom_layout", "gs_image_layout", "gs_bin_layout", "gs_backward_scratch_bytes", "gs_last_error",
            "gs_version", "gs_set_sort_path", "gs_set_forward_segments", "gs_set_half_quadrants", "gs_set_backward_chain", "gs_set_backward_chain_tickets", "gs_set_backward_chain_polls", "gs_async_status_word", "gs_async_status_clear", "gs_recorded_cut", "gs_set_backward_segments", "gs_preprocess_forward", "gs_preprocess_forward_raw", "gs_render_forward", "gs_render_backward", "gs_render_backward_raw", "gs_render_backward_raw_adam", "gs_adam_step", "gs_adam_step_multi",
@@ -70,7 +74,8 @@ SYMBOLS = ("gs_abi_version", "gs_geom_layout", "gs_image_layout", "gs_bin_layout
            "gs_pose_grad_scratch_bytes", "gs_render_backward_raw_pose", "gs_activate_backward_pose",
            "gs_tracking_loss_scratch_bytes", "gs_tracking_loss", "gs_preprocess_forward_raw_dev", "gs_render_backward_raw_pose_dev",
            "gs_tracking_state_bytes", "gs_tracking_begin", "gs_tracking_step",
-           "gs_preprocess_forward_topdown", "gs_render_forward_topdown", "gs_grid_dbscan_layout", "gs_grid_dbscan", "gs_high_loss_grid")
+           "gs_preprocess_forward_topdown", "gs_render_forward_topdown", "gs_grid_dbscan_layout", "gs_grid_dbscan", "gs_high_loss_grid",
+           "gs_cluster_hulls_layout", "gs_cluster_hulls")
 
 
 def _bind(lib):
@@ -144,6 +149,13 @@ def _bind(lib):
     #  sum_value, total, stream)
     lib.gs_grid_dbscan.argtypes = [i32, i32, i32, vp, i64, i64, f32, i32, i32, i32, i32] + [vp] * 6 + [vp]
     lib.gs_grid_dbscan.restype = C.c_int
+    # (B, H, W, max_clusters, max_points, layout)
+    lib.gs_cluster_hulls_layout.argtypes = [i32, i32, i32, i32, i32, C.POINTER(GsHullLayout)]
+    lib.gs_cluster_hulls_layout.restype = C.c_int
+    # (B, H, W, labels, depth, row_stride, image_stride, n_clusters, sum_value, max_clusters, footprint_rows (host uint32[kh]), kh, kw, skip_depth,
+    #  x_scale, y_scale, max_points, workspace, volume, n_points, contour_xy, sum_volume, sum_invisibility, status, stream)
+    lib.gs_cluster_hulls.argtypes = [i32, i32, i32, vp, vp, i64, i64, vp, vp, i32, C.POINTER(C.c_uint32), i32, i32, f32, C.c_double, C.c_double, i32] + [vp] * 7 + [vp]
+    lib.gs_cluster_hulls.restype = C.c_int
     # (width, height, render_depth, opacity, gt_depth, depth_err_thres, opacity_thres, grid_width, grid_height, mask_full, grid, stream)
     lib.gs_high_loss_grid.argtypes = [i32, i32, vp, vp, vp, f32, f32, i32, i32, vp, vp, vp]
     lib.gs_high_loss_grid.restype = C.c_int

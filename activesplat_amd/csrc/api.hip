@@ -1116,6 +1116,51 @@ int gs_grid_dbscan(int32_t B, int32_t H, int32_t W, const float* values, int64_t
     return GS_OK;
 }
 
+int gs_cluster_hulls_layout(int32_t B, int32_t H, int32_t W, int32_t max_clusters, int32_t max_points, GsHullLayout* out)
+{
+    if (!out || !dbscan_size_ok(B, H, W, max_clusters) || max_points < 4 || max_points > 4096)
+        return fail(GS_EINVAL, "gs_cluster_hulls_layout: size out of range (1 <= B <= 65535, H, W <= 4096, H * W <= 65536, 1 <= max_clusters <= 65535, "
+                               "4 <= max_points <= 4096)");
+    out->cluster_status = 0;
+    out->total_bytes = align_up((uint64_t)B * max_clusters * 4);
+    return GS_OK;
+}
+
+int gs_cluster_hulls(int32_t B, int32_t H, int32_t W, const int32_t* labels, const float* depth, int64_t row_stride, int64_t image_stride,
+                     const int32_t* n_clusters, const float* sum_value, int32_t max_clusters, const uint32_t* footprint_rows, int32_t kh,
+                     int32_t kw, float skip_depth, double x_scale, double y_scale, int32_t max_points, void* workspace, double* volume,
+                     int32_t* n_points, int32_t* contour_xy, double* sum_volume, double* sum_invisibility, int32_t* status, gs_stream_t stream)
+{
+    GsHullLayout L;
+    if (!dbscan_size_ok(B, H, W, max_clusters) || max_points < 4 || max_points > 4096)
+        return fail(GS_EINVAL, "gs_cluster_hulls: size out of range (1 <= B <= 65535, H, W <= 4096, H * W <= 65536, 1 <= max_clusters <= 65535, "
+                               "4 <= max_points <= 4096)");
+    if (kh < 1 || kh > 15 || kw < 1 || kw > 15 || !(kh & 1) || !(kw & 1) || !footprint_rows)
+        return fail(GS_EINVAL, "gs_cluster_hulls: the footprint must have odd kh and kw in 1..15");
+    for (int i = 0; i < kh; i++)
+        if (footprint_rows[i] >> kw) return fail(GS_EINVAL, "gs_cluster_hulls: a footprint row has a cell at or beyond kw");
+    if (!labels || !depth || !n_clusters || !sum_value || !workspace || !volume || !n_points || !sum_volume || !sum_invisibility || !status ||
+        row_stride < W || image_stride < 0 || ((uintptr_t)workspace & 7))
+        return fail(GS_EINVAL, "gs_cluster_hulls: null pointer (only contour_xy may be null), workspace not 8-byte aligned, or row_stride below W");
+    // (written so that a NaN fails it)
+    if (!(fabs(x_scale) <= 1.7976931348623157e308) || !(fabs(y_scale) <= 1.7976931348623157e308))
+        return fail(GS_EINVAL, "gs_cluster_hulls: x_scale and y_scale must be finite");
+    gs_cluster_hulls_layout(B, H, W, max_clusters, max_points, &L);
+    gs::HullArgs a;
+    a.labels = labels; a.depth = depth; a.row_stride = row_stride; a.image_stride = image_stride;
+    a.n_clusters = n_clusters; a.sum_value = sum_value;
+    a.H = H; a.W = W; a.Ww = (W + 63) / 64; a.max_clusters = max_clusters; a.max_points = max_points;
+    a.kh = kh; a.kw = kw;
+    for (int i = 0; i < 15; i++) a.footprint[i] = i < kh ? footprint_rows[i] : 0u;
+    a.skip_depth = skip_depth; a.scale = x_scale * y_scale;
+    a.cluster_status = (int32_t*)((char*)workspace + L.cluster_status);
+    a.volume = volume; a.n_points = n_points; a.contour_xy = contour_xy;
+    a.sum_volume = sum_volume; a.sum_invisibility = sum_invisibility; a.status = status;
+    hipError_t e = gs::launch_cluster_hulls(a, B, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_cluster_hulls: %s", hipGetErrorString(e));
+    return GS_OK;
+}
+
 int gs_high_loss_grid(int32_t width, int32_t height, const float* render_depth, const float* opacity, const float* gt_depth,
                       float depth_err_thres, float opacity_thres, int32_t grid_width, int32_t grid_height, uint8_t* mask_full, float* grid,
                       gs_stream_t stream)

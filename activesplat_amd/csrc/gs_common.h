@@ -840,6 +840,19 @@ struct DbscanArgs {
     int32_t *labels, *n_clusters, *table; float *sum_value, *total;    // outputs
 };
 hipError_t launch_grid_dbscan(const DbscanArgs& a, int B, hipStream_t st);
+// per-cluster hull volumes behind the DBSCAN labels (stats.hip; the rule: include/gsplat_hip.h, gs_cluster_hulls).  One argument block for its two kernels.
+struct HullArgs {
+    const int32_t* labels;                                             // [B][H][W]
+    const float* depth; int64_t row_stride, image_stride;              // floats
+    const int32_t* n_clusters; const float* sum_value;                 // gs_grid_dbscan's outputs
+    int H, W, Ww, max_clusters, max_points;
+    int kh, kw; uint32_t footprint[15];                                // row i of the footprint: bit j = cell (i, j)
+    float skip_depth; double scale;                                    // x_scale * y_scale
+    int32_t* cluster_status;                                           // [B][max_clusters] (workspace)
+    double* volume; int32_t* n_points; int32_t* contour_xy;            // outputs; contour_xy nullable
+    double *sum_volume, *sum_invisibility; int32_t* status;            // [B] each
+};
+hipError_t launch_cluster_hulls(const HullArgs& a, int B, hipStream_t st);
 // the per-frame high-loss mask and its one-pixel-per-degree grid (stats.hip; both rules: include/gsplat_hip.h, gs_high_loss_grid)
 struct HighLossArgs {
     const float *depth, *opacity, *gt;                                 // [H * W] each

@@ -334,6 +334,328 @@ hipError_t launch_grid_dbscan(const DbscanArgs& a, int B, hipStream_t st)
     return hipGetLastError();
 }
 
+// ---- hull volumes of the clusters ----------------------------------------------------------------------------------------------------------------
+// (src/mapper/__init__.py:29-90; the rule a-f is stated in include/gsplat_hip.h, gs_cluster_hulls)
+// Workgroups of ONE wavefront, one per CU (kHullGroups), each walking the (image, cluster slot) pairs in cluster-major order with a stride of
+// the grid: the cluster counts stay on the device, a slot at or beyond n_clusters[b] costs one compare, and the LDS below is claimed once per
+// CU, not once per slot (a grid of max_clusters x B workgroups queues 5376 of them behind it: measured 1.86 ms against 0.56 ms
+// for 21 panoramas of three clusters, profiles/hull_volumes.txt).  Everything between
+// the labels and the volume stays in LDS: the cluster's bitmask as 64-bit row words, its dilation by word shifts, the border following by
+// lane 0 over the dilated words, then -- in the same LDS, the bitmasks being dead by then -- the contour points and the faces of an
+// incremental hull whose face tests, horizon search and face replacement are spread over the 64 lanes.  Nothing depends on scheduling: there
+// is no atomic, the faces are kept in an order that follows from the points alone, and the volume is summed per lane and by a butterfly.
+// LDS: 40 + 48 + 32 + 16 KiB = 136 KiB of the CU's 160, so one workgroup per CU -- a query has about as many live clusters as the chip has CUs,
+// and a workgroup's time is expected to go to the ~1000 dependent steps of the trace and the point-by-point hull, not to occupancy (the split
+// between the phases has not been measured; profiles/hull_volumes.txt has the kernel's time as a whole).
+// Cost of the hull per inserted point that sees V faces: the nf face tests over 64 lanes, then the horizon search, which tests each of the 3 V
+// edges against all V visible faces, 3 V^2 / 64 per lane.  V is a handful for a contour in general position but can reach all 2 n - 4 faces
+// (a point far outside a nearly flat cluster); with n at its limit of 4096 that is ~3e6 steps for one point, the worst case of this kernel.
+// Contours of the shipped query have a few hundred points (profiles/hull_volumes.txt).
+
+constexpr int kHullWords = 65536 / 64 + 4096;            // H * ceil(W / 64) for H * W <= 65536, H <= 4096
+constexpr int kHullMaxPoints = 4096;
+constexpr int kHullMaxFaces = 2 * kHullMaxPoints - 4;    // a triangulated sphere on n vertices has 2 n - 4 faces
+constexpr int kHullGroups = 256;                         // the workgroups of the grid: one per CU of the MI355X.  Any count gives the same results
+                                                         // (a workgroup takes every kHullGroups-th slot); on a part with fewer CUs the rest wait their turn
+constexpr int kHullOverflow = 1, kHullNonFinite = 2, kHullTruncated = 4, kHullFaces = 8;       // status bits
+
+struct HullPoint { int16_t x, y; float z; };
+
+// direction codes 0..7 of the border following: (dx, dy) = (1,0),(1,-1),(0,-1),(-1,-1),(-1,0),(-1,1),(0,1),(1,1), two bits each of dx + 1 / dy + 1
+__device__ __forceinline__ int hull_dx(int s) { return ((0x901A >> (2 * s)) & 3) - 1; }
+__device__ __forceinline__ int hull_dy(int s) { return ((0xA901 >> (2 * s)) & 3) - 1; }
+
+__device__ __forceinline__ bool hull_bit(const uint64_t* __restrict__ bits, int H, int W, int Ww, int x, int y)
+{
+    if (x < 0 || y < 0 || x >= W || y >= H) return false;
+    return (bits[y * Ww + (x >> 6)] >> (x & 63)) & 1ull;
+}
+
+// det [b - a; c - a; d - a] in pixel units, fp64, no contraction (the emulated build and the device then take the same decisions): > 0 iff d
+// sees the face (a, b, c) from outside.  Integer x and y differences are exact, so four points that share a column, a row or a depth give
+// exactly 0.
+__device__ __forceinline__ double hull_orient(const HullPoint& a, const HullPoint& b, const HullPoint& c, const HullPoint& d)
+{
+#pragma clang fp contract(off)
+    const double bx = (double)(b.x - a.x), by = (double)(b.y - a.y), bz = (double)b.z - (double)a.z;
+    const double cx = (double)(c.x - a.x), cy = (double)(c.y - a.y), cz = (double)c.z - (double)a.z;
+    const double dx = (double)(d.x - a.x), dy = (double)(d.y - a.y), dz = (double)d.z - (double)a.z;
+    const double m0 = cy * dz - cz * dy, m1 = cx * dz - cz * dx, m2 = cx * dy - cy * dx;
+    return (bx * m0 - by * m1) + bz * m2;
+}
+
+// true iff a, b, c are not on one line (a component of (b - a) x (c - a) is not 0)
+__device__ __forceinline__ bool hull_spans(const HullPoint& a, const HullPoint& b, const HullPoint& c)
+{
+#pragma clang fp contract(off)
+    const double bx = (double)(b.x - a.x), by = (double)(b.y - a.y), bz = (double)b.z - (double)a.z;
+    const double cx = (double)(c.x - a.x), cy = (double)(c.y - a.y), cz = (double)c.z - (double)a.z;
+    return by * cz - bz * cy != 0.0 || bz * cx - bx * cz != 0.0 || bx * cy - by * cx != 0.0;
+}
+
+// one live cluster c of image b, by the whole wavefront; the LDS arrays are the kernel's
+__device__ __forceinline__ void cluster_hull_slot(const HullArgs& a, int b, int c, uint64_t* s_mask, uint64_t* s_dil, uint32_t* s_horizon,
+                                                  uint16_t* s_vlist, int& s_emitted)
+{
+    const int lane = threadIdx.x, H = a.H, W = a.W, Ww = a.Ww, nwords = H * Ww;
+    const size_t slot = (size_t)b * a.max_clusters + c;
+    const uint64_t below = (1ull << lane) - 1ull;
+    int status = 0;
+    double volume = 0.0;
+    int n_emitted = 0;
+    HullPoint* pts = reinterpret_cast<HullPoint*>(s_mask);
+    uint16_t* faces = reinterpret_cast<uint16_t*>(s_dil);
+
+    // a. the mask: one ballot per 64 columns of a row
+    {
+        const int32_t* lab = a.labels + (size_t)b * H * W;
+        for (int idx0 = 0; idx0 < nwords; idx0 += 4) {                // four words per step: their loads are in flight together
+            bool m[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int idx = idx0 + k, y = idx / Ww, x = (idx - y * Ww) * kWave + lane;
+                m[k] = idx < nwords && x < W && lab[y * W + x] == c;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uint64_t bits = __ballot(m[k]);
+                if (lane == 0 && idx0 + k < nwords) s_mask[idx0 + k] = bits;
+            }
+        }
+    }
+    __syncthreads();
+    // b. the dilation: per output word and footprint row the three source words once, then one shift per set cell
+    {
+        const int ay = a.kh / 2, ax = a.kw / 2;
+        for (int idx = lane; idx < nwords; idx += kWave) {
+            const int y = idx / Ww, w = idx - y * Ww;
+            uint64_t out = 0;
+            for (int i = 0; i < a.kh; i++) {
+                const int yy = y + i - ay;
+                const uint32_t fr = a.footprint[i];
+                if (yy < 0 || yy >= H || !fr) continue;
+                const uint64_t* row = s_mask + yy * Ww;
+                const uint64_t cur = row[w], prev = w > 0 ? row[w - 1] : 0ull, next = w + 1 < Ww ? row[w + 1] : 0ull;
+                for (int j = 0; j < a.kw; j++) {
+                    if (!((fr >> j) & 1u)) continue;
+                    const int d = j - ax;                              // dil(x) |= mask(x + d), |d| <= 7
+                    out |= d == 0 ? cur : (d > 0 ? (cur >> d) | (next << (64 - d)) : (cur << -d) | (prev >> (64 + d)));
+                }
+            }
+            if (w == Ww - 1 && (W & 63)) out &= (1ull << (W & 63)) - 1ull;
+            s_dil[idx] = out;
+        }
+    }
+    __syncthreads();
+    // c. the start: the first set pixel in row-major order
+    int first = -1;
+    for (int base = 0; base < nwords; base += kWave) {
+        const uint64_t bal = __ballot(base + lane < nwords && s_dil[base + lane] != 0ull);
+        if (bal) { first = base + __ffsll((unsigned long long)bal) - 1; break; }
+    }
+    if (first >= 0) {
+        if (lane == 0) {
+            const int y0 = first / Ww, x0 = (first - y0 * Ww) * 64 + __ffsll((unsigned long long)s_dil[first]) - 1;
+            int n = 0, s = 4;
+            bool single = true;
+            do {
+                s = (s - 1) & 7;
+                if (hull_bit(s_dil, H, W, Ww, x0 + hull_dx(s), y0 + hull_dy(s))) { single = false; break; }
+            } while (s != 4);
+            if (single) {
+                pts[0].x = (int16_t)x0; pts[0].y = (int16_t)y0;
+                n = 1;
+            } else {
+                const int x1 = x0 + hull_dx(s), y1 = y0 + hull_dy(s), max_steps = 4 * H * W + 8;
+                int px = x0, py = y0, prev = s ^ 4;
+                for (int step = 0; step < max_steps; step++) {
+                    int sp = s, qx = 0, qy = 0;
+                    bool found = false;
+                    for (int k = 0; k < 8 && !found; k++) {
+                        sp = (sp + 1) & 7;
+                        qx = px + hull_dx(sp); qy = py + hull_dy(sp);
+                        found = hull_bit(s_dil, H, W, Ww, qx, qy);
+                    }
+                    if (!found) break;                                 // (p has a set neighbour: it was reached from one)
+                    if (sp != prev) {
+                        if (n < a.max_points) { pts[n].x = (int16_t)px; pts[n].y = (int16_t)py; }
+                        n++;
+                        prev = sp;
+                    }
+                    if (qx == x0 && qy == y0 && px == x1 && py == y1) break;
+                    px = qx; py = qy; s = (sp + 4) & 7;
+                }
+            }
+            s_emitted = n;
+        }
+        __syncthreads();
+        n_emitted = s_emitted;
+    }
+    if (n_emitted > a.max_points) status |= kHullOverflow;
+    // d. the depths of the emitted points; the points that stay are packed to the front in their order
+    const int n_stored = n_emitted < a.max_points ? n_emitted : a.max_points;
+    int n = 0, bad = 0;
+    for (int base = 0; base < n_stored; base += kWave) {
+        const int i = base + lane;
+        HullPoint p = {0, 0, 0.f};
+        bool keep = false;
+        if (i < n_stored) {
+            p = pts[i];
+            p.z = a.depth[(size_t)b * a.image_stride + (size_t)p.y * a.row_stride + p.x];
+            if (a.contour_xy) {
+                int32_t* xy = a.contour_xy + (slot * a.max_points + i) * 2;
+                xy[0] = p.x; xy[1] = p.y;
+            }
+            const bool finite = fabsf(p.z) <= 3.402823466e38f;
+            bad |= finite ? 0 : 1;
+            keep = finite && p.z != a.skip_depth;
+        }
+        const uint64_t bal = __ballot(keep);
+        __syncthreads();
+        if (keep) pts[n + __popcll(bal & below)] = p;
+        n += __popcll(bal);
+        __syncthreads();
+    }
+    if (__ballot(bad) != 0ull) status |= kHullNonFinite;
+    // e. the hull of the n points
+    if (!(status & kHullOverflow) && n >= 4) {
+        auto first_point = [&](auto pred) -> int {
+            for (int base = 0; base < n; base += kWave) {
+                const uint64_t bal = __ballot(base + lane < n && pred(pts[base + lane]));
+                if (bal) return base + __ffsll((unsigned long long)bal) - 1;
+            }
+            return -1;
+        };
+        const HullPoint P0 = pts[0];
+        int i1 = first_point([&](const HullPoint& p) { return p.x != P0.x || p.y != P0.y || p.z != P0.z; }), i2 = -1, i3 = -1;
+        HullPoint P1 = P0, P2 = P0;
+        if (i1 >= 0) { P1 = pts[i1]; i2 = first_point([&](const HullPoint& p) { return hull_spans(P0, P1, p); }); }
+        if (i2 >= 0) { P2 = pts[i2]; i3 = first_point([&](const HullPoint& p) { return hull_orient(P0, P1, P2, p) != 0.0; }); }
+        if (i3 >= 0) {
+            if (hull_orient(P0, P1, P2, pts[i3]) > 0.0) { const int t = i1; i1 = i2; i2 = t; }
+            if (lane == 0) {                                           // (a, b, c), (b, a, d), (c, b, d), (a, c, d): d = i3 behind every face
+                const uint16_t f0[12] = {0, (uint16_t)i1, (uint16_t)i2, (uint16_t)i1, 0, (uint16_t)i3, (uint16_t)i2, (uint16_t)i1, (uint16_t)i3, 0, (uint16_t)i2, (uint16_t)i3};
+                for (int k = 0; k < 12; k++) faces[k] = f0[k];
+            }
+            __syncthreads();
+            int nf = 4;
+            const int cap = 2 * n - 4;
+            bool failed = false;
+            for (int ip = 1; ip < n && !failed; ip++) {
+                if (ip == i1 || ip == i2 || ip == i3) continue;
+                const HullPoint P = pts[ip];
+                int V = 0;                                             // the faces P sees, in ascending order
+                for (int base = 0; base < nf; base += kWave) {
+                    const int f = base + lane;
+                    const bool vis = f < nf && hull_orient(pts[faces[3 * f]], pts[faces[3 * f + 1]], pts[faces[3 * f + 2]], P) > 0.0;
+                    const uint64_t bal = __ballot(vis);
+                    if (vis) s_vlist[V + __popcll(bal & below)] = (uint16_t)f;
+                    V += __popcll(bal);
+                }
+                if (V == 0) continue;                                  // inside or on the hull
+                __syncthreads();
+                int Hn = 0;                                            // horizon: the edges of visible faces whose reverse no visible face has
+                for (int base = 0; base < 3 * V; base += kWave) {
+                    const int t = base + lane;
+                    bool hz = false;
+                    uint32_t u = 0, v = 0;
+                    if (t < 3 * V) {
+                        const int f = s_vlist[t / 3], e = t % 3;
+                        u = faces[3 * f + e]; v = faces[3 * f + (e == 2 ? 0 : e + 1)];
+                        hz = true;
+                        for (int g = 0; g < V && hz; g++) {
+                            const uint16_t* fg = faces + 3 * s_vlist[g];
+                            hz = !((fg[0] == v && fg[1] == u) || (fg[1] == v && fg[2] == u) || (fg[2] == v && fg[0] == u));
+                        }
+                    }
+                    const uint64_t bal = __ballot(hz);
+                    const int at = Hn + __popcll(bal & below);
+                    if (hz && at < kHullMaxFaces) s_horizon[at] = u | (v << 16);
+                    Hn += __popcll(bal);
+                }
+                if (nf - V + Hn > cap) { failed = true; break; }      // (not a sphere any more: rounding made the visible set ragged)
+                __syncthreads();
+                for (int k = lane; k < Hn; k += kWave) {               // the fan over the horizon: into the holes first, then behind the last face
+                    const int at = k < V ? s_vlist[k] : nf + (k - V);
+                    const uint32_t e = s_horizon[k];
+                    faces[3 * at] = (uint16_t)(e & 0xffffu); faces[3 * at + 1] = (uint16_t)(e >> 16); faces[3 * at + 2] = (uint16_t)ip;
+                }
+                __syncthreads();
+                if (Hn < V) {                                          // holes left: filled from the tail, the highest hole first
+                    if (lane == 0) {
+                        int last = nf - 1;
+                        for (int k = V - 1; k >= Hn; k--, last--) {
+                            const int h = s_vlist[k];
+                            if (h != last) { faces[3 * h] = faces[3 * last]; faces[3 * h + 1] = faces[3 * last + 1]; faces[3 * h + 2] = faces[3 * last + 2]; }
+                        }
+                    }
+                    __syncthreads();
+                }
+                nf = nf - V + Hn;
+            }
+            if (failed) status |= kHullFaces;
+            else {
+                double acc = 0.0;                                      // six times the volume: the cones from point 0 over the faces
+                for (int f = lane; f < nf; f += kWave) acc += hull_orient(P0, pts[faces[3 * f]], pts[faces[3 * f + 1]], pts[faces[3 * f + 2]]);
+                for (int m = 1; m < kWave; m <<= 1) acc += __shfl_xor(acc, m);
+                volume = acc / 6.0 * a.scale;
+            }
+        }
+    }
+    if (lane == 0) { a.volume[slot] = volume; a.n_points[slot] = n_emitted; a.cluster_status[slot] = status; }
+}
+
+__global__ __launch_bounds__(kWave) void cluster_hull_kernel(HullArgs a, int B)
+{
+    __shared__ uint64_t s_mask[kHullWords];                            // the cluster's bitmask; from the trace on: the points
+    __shared__ uint64_t s_dil[kHullWords + 1024];                      // its dilation; from the hull on: the faces, three uint16 each
+    __shared__ uint32_t s_horizon[kHullMaxFaces + 4];                  // horizon edges u | v << 16
+    __shared__ uint16_t s_vlist[kHullMaxFaces + 4];                    // the visible faces, ascending
+    __shared__ int s_emitted;
+    static_assert(sizeof(HullPoint) == 8 && kHullMaxPoints * sizeof(HullPoint) <= sizeof(uint64_t) * kHullWords, "points alias the mask words");
+    static_assert(kHullMaxFaces * 6 <= (kHullWords + 1024) * 8, "faces alias the dilated words");
+    const int64_t total = (int64_t)B * a.max_clusters;
+    // the slots at or beyond n_clusters[b]: their zeros, one slot per lane
+    for (int64_t i = (int64_t)blockIdx.x * kWave + threadIdx.x; i < total; i += (int64_t)gridDim.x * kWave) {
+        const int b = (int)(i / a.max_clusters), c = (int)(i - (int64_t)b * a.max_clusters);
+        if (c >= a.n_clusters[b]) { a.volume[i] = 0.0; a.n_points[i] = 0; a.cluster_status[i] = 0; }
+    }
+    // the live ones, cluster-major: cluster c of every image before cluster c + 1 of any, so that they spread over the workgroups
+    for (int64_t i = blockIdx.x; i < total; i += gridDim.x) {
+        const int c = (int)(i / B), b = (int)(i - (int64_t)c * B);
+        if (c >= a.n_clusters[b]) continue;
+        cluster_hull_slot(a, b, c, s_mask, s_dil, s_horizon, s_vlist, s_emitted);
+        __syncthreads();                                               // (the next cluster overwrites the LDS)
+    }
+}
+
+// f. per image, thread b: the two sums over the clusters in ascending number, fp64
+__global__ __launch_bounds__(kWave) void cluster_hull_sums_kernel(HullArgs a, int B)
+{
+#pragma clang fp contract(off)
+    const int b = blockIdx.x * kWave + threadIdx.x;
+    if (b >= B) return;
+    const int n = a.n_clusters[b], m = n < a.max_clusters ? n : a.max_clusters;
+    double sv = 0.0, si = 0.0;
+    int st = n > a.max_clusters ? kHullTruncated : 0;
+    for (int c = 0; c < m; c++) {
+        const size_t slot = (size_t)b * a.max_clusters + c;
+        const double v = a.volume[slot];
+        sv += v;
+        si += (double)a.sum_value[slot] * v;
+        st |= a.cluster_status[slot];
+    }
+    a.sum_volume[b] = sv; a.sum_invisibility[b] = si; a.status[b] = st;
+}
+
+hipError_t launch_cluster_hulls(const HullArgs& a, int B, hipStream_t st)
+{
+    const int64_t total = (int64_t)B * a.max_clusters;
+    hipLaunchKernelGGL(cluster_hull_kernel, dim3((unsigned)(total < kHullGroups ? total : kHullGroups)), dim3(kWave), 0, st, a, B);
+    hipLaunchKernelGGL(cluster_hull_sums_kernel, dim3((B + kWave - 1) / kWave), dim3(kWave), 0, st, a, B);
+    return hipGetLastError();
+}
+
 // ---- the per-frame high-loss mask and its grid ------------------------------------------------------------------------------------------------
 // (src/mapper/splatam/__init__.py:212-218; both rules are stated in include/gsplat_hip.h, gs_high_loss_grid)
 

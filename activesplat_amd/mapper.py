@@ -369,6 +369,13 @@ class SplatMapper:
         return VIS.global_invisibility_nodes(self.params, view_c2w, positions, scale_modifier, max_clusters, nodes_per_pass)
 
     @torch.no_grad()
+    def global_invisibility_scores(self, view_c2w, positions, scale_modifier=1.0, max_clusters=256, nodes_per_pass=None):
+        """Per Voronoi node of `positions` [K, 3] the two floats of get_global_invisibility, (invisibility [K], volume [K]) float64 -- renders,
+        DBSCAN, contours and hull volumes on the device, one small copy (visibility.py)."""
+        from . import visibility as VIS
+        return VIS.global_invisibility_scores(self.params, view_c2w, positions, scale_modifier, max_clusters, nodes_per_pass)
+
+    @torch.no_grad()
     def local_invisibility_target(self, view_c2w, cluster_invisibility_threshold=30, scale_modifier=1.0):
         """get_local_invisibility without its images -> (sum_invisibility, best_pose_c2w or None) (visibility.py)."""
         from . import visibility as VIS

@@ -11,6 +11,9 @@ them as HIP kernels (gs_grid_dbscan, include/gsplat_hip.h states the rule) and r
 * `look_around_nodes`           -- the panoramas of K nodes on the device: one activation, the 3 K views rendered up to 63 at a time;
 * `global_invisibility_nodes`   -- per node what `get_convexhull_volume` holds after its DBSCAN line, ONE device-to-host copy for all nodes.  The
                                    dilate / findContours / ConvexHull loop behind it (OpenCV, scipy) stays with the caller;
+* `cluster_hulls`               -- that loop on the device (gs_cluster_hulls): per cluster the dilated mask's outer border, its depths and the
+                                   volume of their convex hull; per image the two sums `get_convexhull_volume` returns;
+* `global_invisibility_scores`  -- the planner's whole global query: per node the two floats of `get_global_invisibility`, ONE small copy;
 * `local_invisibility_target`   -- the whole of `get_local_invisibility` (src/mapper/splatam/__init__.py:762-837) without its images.
 * `high_loss_grid`              -- the mask of `get_high_loss_samples` (src/mapper/splatam/__init__.py:212-215) and its cv2.resize to one pixel per
                                    degree (:218), one launch (gs_high_loss_grid; the header states the pixel rule and the integer resize rule);
@@ -42,6 +45,11 @@ MAX_NODES_PER_PASS = 21
 #: that bound.  `nodes_per_pass=21` renders all 63 views in one pass for callers that accept such flips.
 NODES_PER_PASS = 1
 GLOBAL_THRESHOLD, GLOBAL_EPS, GLOBAL_MIN_SAMPLES = 0.8, 5, 25           # src/mapper/__init__.py:12, :18
+GLOBAL_FOOTPRINT = (15, 15)                                             # src/mapper/__init__.py:38
+GLOBAL_SKIP_DEPTH = 15.0                                                # :54
+GLOBAL_VFOV_DEG = 150                                                   # :8 (the call site passes the intrinsics as `hfov`, which is unused: :64-65)
+HULL_MAX_POINTS = 4096                                                  # contour points per cluster: the most gs_cluster_hulls takes (a 150 x 360 blob emits a few hundred)
+HULL_OVERFLOW, HULL_NONFINITE, HULL_TRUNCATED, HULL_FACES = 1, 2, 4, 8  # status bits of gs_cluster_hulls
 LOCAL_THRESHOLD, LOCAL_EPS, LOCAL_MIN_SAMPLES = 0.3, 5, 10              # src/mapper/__init__.py:93, :99
 LOCAL_GATE = 100                                                        # src/mapper/splatam/__init__.py:809
 LOCAL_SKIP_DEG = 15                                                     # :825
@@ -205,6 +213,116 @@ def global_invisibility_nodes(params, view_c2w, positions, scale_modifier=1.0, m
         out.append(dict(depth=depth[k], invisibility=inv[k], labels=labels[k], n_clusters=int(n[k]), count=count[k, :m], sum_row=sr[k, :m],
                         sum_col=sc[k, :m], root=root[k, :m], sum_value=sv[k, :m], total=float(total[k])))
     return out
+
+
+def ellipse_footprint(kh=15, kw=15):
+    """OpenCV's getStructuringElement(MORPH_ELLIPSE, (kw, kh)) restated -> uint32 [kh], bit j of word i = cell (i, j): with r = kh // 2 and
+    c = kw // 2, row i is the run of half-width round_half_even(c * sqrt((r * r - dy * dy) / (r * r))) around column c, dy = i - r (r = 0: the
+    centre cell alone, as OpenCV computes it).  Not run against cv2 (include/gsplat_hip.h, gs_cluster_hulls)."""
+    kh, kw = int(kh), int(kw)
+    if not (1 <= kh <= 15 and 1 <= kw <= 15 and kh % 2 == 1 and kw % 2 == 1):
+        raise ValueError("ellipse_footprint: kh and kw must be odd and in 1..15")
+    r, c = kh // 2, kw // 2
+    inv_r2 = 1.0 / (r * r) if r else 0.0
+    rows = np.zeros(kh, np.uint32)
+    for i in range(kh):
+        dy = i - r
+        dx = int(round(c * np.sqrt((r * r - dy * dy) * inv_r2)))         # (Python's round: half to even, as cvRound)
+        for j in range(max(c - dx, 0), min(c + dx + 1, kw)):
+            rows[i] |= np.uint32(1 << j)
+    return rows
+
+
+class ClusterHulls(NamedTuple):
+    volume: torch.Tensor            # [B, max_clusters] float64: the cluster's hull volume in the reference's units; 0 beyond n_clusters
+    n_points: torch.Tensor          # [B, max_clusters] int32: emitted contour points (before the depth skips)
+    sum_volume: torch.Tensor        # [B] float64: get_convexhull_volume's last_volume
+    sum_invisibility: torch.Tensor  # [B] float64: its last_invisibility
+    status: torch.Tensor            # [B] int32: HULL_* bits
+    contour_xy: object              # [B, max_clusters, max_points, 2] int32 (x, y), zero behind a cluster's points; None unless asked for
+
+
+@torch.no_grad()
+def cluster_hulls(labels, depth, clusters, footprint=None, kw=None, skip_depth=GLOBAL_SKIP_DEPTH, x_scale=None, y_scale=None, max_points=HULL_MAX_POINTS,
+                  contours=False):
+    """The loop of `get_convexhull_volume` behind its DBSCAN line (src/mapper/__init__.py:29-90) for every cluster of every image, on the device
+    (gs_cluster_hulls; include/gsplat_hip.h states the rule).  `labels` [B, H, W] (or [H, W]) and `clusters` are `grid_dbscan`'s result; `depth`
+    is [B, H, W] or [B, H, W, 1] float32 on the same device (rows and images may be strided).  `footprint`: uint32 row bitmasks as
+    `ellipse_footprint` returns them, `kw` columns wide (default: as wide as high; without a footprint the 15 x 15 ellipse); x_scale and
+    y_scale default to the reference's deg2rad(360 / W) and deg2rad(150 / H).  `contours=True` also returns the contour points (for tests
+    and debugging).  -> ClusterHulls of device tensors (without the batch dimension for [H, W] labels).  No host synchronisation."""
+    lib = _lib.get()
+    if not torch.is_tensor(labels) or labels.dim() not in (2, 3) or not torch.is_tensor(depth):
+        raise ValueError("cluster_hulls: labels must be an [H, W] or [B, H, W] tensor and depth a tensor")
+    device = labels.device
+    R._require_rocm(device)
+    single = labels.dim() == 2
+    lab = labels.detach().unsqueeze(0) if single else labels.detach()
+    B, H, W = (int(s) for s in lab.shape)
+    d = depth.detach()
+    if d.dim() == labels.dim() + 1 and d.shape[-1] == 1:
+        d = d.squeeze(-1)
+    if single and d.dim() == 2:
+        d = d.unsqueeze(0)
+    if tuple(d.shape) != (B, H, W) or d.device != device:
+        raise ValueError(f"cluster_hulls: depth must be {B} x {H} x {W} (x 1) on the labels' device, got {tuple(depth.shape)}")
+    if d.dtype != torch.float32:
+        d = d.float()
+    if min(B, H, W) > 0 and (d.stride(2) != 1 or d.stride(1) < W or d.stride(0) < 0 or d.data_ptr() % 4):
+        d = d.contiguous()
+    if lab.dtype != torch.int32 or not lab.is_contiguous():
+        lab = lab.int().contiguous()
+    n_clusters = clusters.n_clusters.reshape(-1).contiguous()
+    sum_value = clusters.sum_value.reshape(B, -1).contiguous() if B > 0 else clusters.sum_value
+    M = int(sum_value.shape[-1])
+    if n_clusters.numel() != B or n_clusters.dtype != torch.int32 or sum_value.dtype != torch.float32:
+        raise ValueError("cluster_hulls: clusters is not grid_dbscan's result for these labels")
+    if footprint is None:
+        footprint, kw = ellipse_footprint(*GLOBAL_FOOTPRINT), GLOBAL_FOOTPRINT[1]
+    fp = np.ascontiguousarray(footprint, dtype=np.uint32).reshape(-1)
+    kh = int(fp.shape[0])
+    kw = kh if kw is None else int(kw)
+    xs = np.deg2rad(360 / W) if x_scale is None else float(x_scale)
+    ys = np.deg2rad(GLOBAL_VFOV_DEG / H) if y_scale is None else float(y_scale)
+    P = int(max_points)
+    layout = _lib.GsHullLayout()
+    _lib.check(lib.gs_cluster_hulls_layout(B, H, W, M, P, C.byref(layout)))
+    ws = torch.empty(int(layout.total_bytes), dtype=torch.uint8, device=device)
+    volume = torch.empty(B, M, dtype=torch.float64, device=device)
+    n_points = torch.empty(B, M, dtype=torch.int32, device=device)
+    xy = torch.zeros(B, M, P, 2, dtype=torch.int32, device=device) if contours else None
+    sum_volume = torch.empty(B, dtype=torch.float64, device=device)
+    sum_invisibility = torch.empty(B, dtype=torch.float64, device=device)
+    status = torch.empty(B, dtype=torch.int32, device=device)
+    _lib.check(lib.gs_cluster_hulls(B, H, W, R._ptr(lab), R._ptr(d), int(d.stride(1)), int(d.stride(0)), R._ptr(n_clusters), R._ptr(sum_value), M,
+                                    fp.ctypes.data_as(C.POINTER(C.c_uint32)), kh, kw, float(skip_depth), xs, ys, P, R._ptr(ws), R._ptr(volume),
+                                    R._ptr(n_points), R._ptr(xy) if contours else None, R._ptr(sum_volume), R._ptr(sum_invisibility), R._ptr(status),
+                                    _lib.stream_ptr(device)))
+    out = ClusterHulls(volume, n_points, sum_volume, sum_invisibility, status, xy)
+    return ClusterHulls(*(t[0] if t is not None else None for t in out)) if single else out
+
+
+@torch.no_grad()
+def global_invisibility_scores(params, view_c2w, positions, scale_modifier=1.0, max_clusters=256, nodes_per_pass=None):
+    """The planner's global query, finished on the device: for every node of `positions` [K, 3] the two floats `get_global_invisibility`
+    (src/mapper/splatam/__init__.py:698-759) returns -- `get_convexhull_volume`'s (last_invisibility, last_volume) of the panorama rendered
+    there -- as two float64 numpy arrays [K]; (0, 0) for an all-zero position, as the reference returns.  `look_around_nodes`, `grid_dbscan`,
+    `cluster_hulls` and ONE device-to-host copy of [K] invisibility, [K] volume and [K] status.  Raises when a score would be silently
+    truncated: a contour of more than HULL_MAX_POINTS points, more than `max_clusters` clusters in a panorama, or a hull that left its face
+    bound (gs_cluster_hulls' status bits 0, 2, 3)."""
+    pano = look_around_nodes(params, view_c2w, positions, scale_modifier, nodes_per_pass)
+    K = len(pano.valid)
+    if not any(pano.valid):
+        return np.zeros(K), np.zeros(K)
+    g = grid_dbscan(pano.opacity, GLOBAL_THRESHOLD, GLOBAL_EPS, GLOBAL_MIN_SAMPLES, complement=True, max_clusters=max_clusters)
+    h = cluster_hulls(g.labels, pano.depth, g)
+    inv, vol, status = _one_copy([h.sum_invisibility, h.sum_volume, h.status])
+    valid = np.asarray(pano.valid)
+    bad = valid & ((status & (HULL_OVERFLOW | HULL_TRUNCATED | HULL_FACES)) != 0)
+    if bad.any():
+        raise RuntimeError(f"global_invisibility_scores: nodes {np.nonzero(bad)[0].tolist()} have status {status[bad].tolist()} (1: a contour of more "
+                           f"than {HULL_MAX_POINTS} points, 4: more than max_clusters={max_clusters} clusters, 8: hull face bound) -- the score would be truncated")
+    return np.where(valid, inv, 0.0), np.where(valid, vol, 0.0)
 
 
 def downsample2(image):

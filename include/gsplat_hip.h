@@ -181,7 +181,7 @@ const char* gs_version(void);
 /* Integer version of THIS binary interface: bumped whenever an entry point's argument list or a published record layout changes (e.g.
  * the seed argument of gs_densify_children, the 40-byte SH Jacobian record).  A host binding compares it with the GS_ABI_VERSION it was
  * written against before the first call, so that a stale prebuilt library fails at load time instead of misreading its arguments. */
-#define GS_ABI_VERSION 15
+#define GS_ABI_VERSION 16
 int32_t gs_abi_version(void);
 
 /* Optional per-stage timing (hipEvents recorded on the caller's stream around each stage's launches).
@@ -562,6 +562,55 @@ int gs_grid_dbscan_layout(int32_t B, int32_t H, int32_t W, int32_t max_clusters,
 int gs_grid_dbscan(int32_t B, int32_t H, int32_t W, const float* values, int64_t row_stride, int64_t image_stride, float threshold,
                    int32_t complement, int32_t eps, int32_t min_samples, int32_t max_clusters, void* workspace, int32_t* labels,
                    int32_t* n_clusters, int32_t* table, float* sum_value, float* total, gs_stream_t stream);
+
+/* Hull volumes of the clusters gs_grid_dbscan found: the loop of get_convexhull_volume behind its DBSCAN line (src/mapper/__init__.py:29-90:
+ * cv2.dilate, cv2.findContours, the contour's depth lookup, scipy.spatial.ConvexHull, the two sums), batched over images and clusters, so that
+ * a Voronoi node's score is two doubles.  labels [B, H, W] int32, n_clusters [B] and sum_value [B, max_clusters] are gs_grid_dbscan's outputs
+ * at the same max_clusters; depth is read as depth[b * image_stride + y * row_stride + x] (strides in floats).
+ * The rule, for image b and cluster c with 0 <= c < min(n_clusters[b], max_clusters):
+ *   a. mask(y, x) = labels[b, y, x] == c.
+ *   b. dil(y, x) = OR of mask(y + i - ay, x + j - ax) over the set cells (i, j) of the footprint, ay = kh / 2, ax = kw / 2; pixels outside the
+ *      image count as 0 (cv2.dilate with its default anchor and border).  The footprint is DATA: footprint_rows is a HOST array of kh words,
+ *      bit j of word i = cell (i, j); kh and kw odd, 1..15.  OpenCV's getStructuringElement(MORPH_ELLIPSE, (15, 15)) restated: row i is the run
+ *      of half-width round_half_even(7 * sqrt((49 - (i - 7)^2) / 49)) around column 7 -- 7,7,7,6,6,5,4,0 for |i - 7| = 0..7.
+ *   c. the outer border, OpenCV's border following with CHAIN_APPROX_SIMPLE.  Direction codes 0..7 are (dx, dy) = (1,0),(1,-1),(0,-1),(-1,-1),
+ *      (-1,0),(-1,1),(0,1),(1,1).  p0 = the first set pixel of dil in row-major order.  s = 4; repeat s = (s - 1) & 7 until the neighbour of p0
+ *      in direction s is set (call it p1) or s is 4 again (the contour is then the single point p0).  p = p0, prev = s ^ 4; loop: search
+ *      s + 1, s + 2, ... (mod 8, at most 8 candidates) for the first set neighbour q of p, in direction s'; if s' != prev emit p and set
+ *      prev = s'; if q == p0 and p == p1 stop; else p = q, s = (s' + 4) & 7.  At most 4 H W + 8 steps.
+ *      ONLY the 8-connected component of dil that contains p0 is traced.  The reference takes max(contours, key=contourArea); the two agree
+ *      when dil is one component, which holds for the shipped parameters (two pixels within eps = 5 of each other lie inside each other's
+ *      15 x 15 ellipse, so a DBSCAN cluster dilates to one component).  With a footprint smaller than the clustering radius a cluster can
+ *      dilate to several components, and this call then scores the one that holds the first pixel.
+ *   d. for every emitted (x, y): z = depth[b, y, x] (fp32); the point is skipped when z == skip_depth (the reference: 15.0f) and when z is not
+ *      finite (status bit 1).  Points may repeat (a thin shape is walked along both sides).
+ *   e. volume[b, c] = x_scale * y_scale * the volume of the convex hull of the points in PIXEL coordinates (x, y integers, z widened to fp64);
+ *      the reference scales x by deg2rad(360 / W) and y by deg2rad(150 / H) first, which multiplies the volume by their product.  In pixel
+ *      units four points that share a column, a row or a depth have an orientation determinant of exactly 0, which keeps the plateaus of a
+ *      depth image from deciding faces by rounding.  An incremental hull in fp64: a first simplex, a face is visible iff det > 0 strictly, the
+ *      visible faces are replaced by the fan over their horizon; the determinant is evaluated without FMA contraction.  Fewer than 4 points,
+ *      or no four points off one plane: volume 0 (the reference gives 0 or, through its 1e-10 jitter, something of that order).
+ *      More than max_points emitted points: status bit 0, volume 0.  More than 2 n - 4 faces (the visible set of a point was not a disc:
+ *      rounding on nearly coplanar points): status bit 3, volume 0.  That branch is DEFENSIVE: it keeps the face table in bounds, no input
+ *      is known that takes it (exact zeros in pixel units are what keeps the visible set a disc), and no test reaches it.
+ *   f. sum_volume[b] = sum over c of volume[b, c]; sum_invisibility[b] = sum over c of (double) sum_value[b, c] * volume[b, c]; ascending c,
+ *      fp64, one thread.  Status bit 2: n_clusters[b] > max_clusters (the sums then cover the first max_clusters clusters only).
+ * Outputs, all DEVICE: volume fp64 [B, max_clusters] (0 beyond n_clusters); n_points int32 [B, max_clusters], the number of EMITTED points
+ * (before the skips of d, and the true number when it exceeds max_points); contour_xy int32 [B, max_clusters, max_points, 2] (nullable; the
+ * first min(n_points, max_points) emitted points of a cluster, the rest is not written); sum_volume, sum_invisibility fp64 [B]; status int32
+ * [B], the OR over the image's clusters.  No atomics: two calls give the same bits.  Every loop is bounded by the image size, max_points or the
+ * face bound; the bound that matters is the horizon search of e, 3 V^2 edge-against-face tests for a point that sees V <= 2 n - 4 faces, shared
+ * by 64 lanes: a handful for a contour in general position, ~3e6 steps per lane for one point at V ~ 2 max_points = 8192.  The dilation and border rules restate OpenCV's documented behaviour; they were NOT run against cv2.
+ * Supported: the sizes of gs_grid_dbscan and 4 <= max_points <= 4096; anything else is GS_EINVAL.  workspace: gs_cluster_hulls_layout(...)
+ * .total_bytes bytes, DEVICE, 8-byte aligned. */
+typedef struct GsHullLayout {
+    uint64_t total_bytes, cluster_status;
+} GsHullLayout;
+int gs_cluster_hulls_layout(int32_t B, int32_t H, int32_t W, int32_t max_clusters, int32_t max_points, GsHullLayout* out);
+int gs_cluster_hulls(int32_t B, int32_t H, int32_t W, const int32_t* labels, const float* depth, int64_t row_stride, int64_t image_stride,
+                     const int32_t* n_clusters, const float* sum_value, int32_t max_clusters, const uint32_t* footprint_rows, int32_t kh,
+                     int32_t kw, float skip_depth, double x_scale, double y_scale, int32_t max_points, void* workspace, double* volume,
+                     int32_t* n_points, int32_t* contour_xy, double* sum_volume, double* sum_invisibility, int32_t* status, gs_stream_t stream);
 
 /* The per-frame look target's image half (get_high_loss_samples, src/mapper/splatam/__init__.py:212-218): the mask of the pixels where the
  * map's render lies behind the measured depth, and that mask shrunk to a grid_height x grid_width grid (90 x 90: one pixel per degree), which
