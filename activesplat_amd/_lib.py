@@ -62,7 +62,7 @@ SORT_AUTO, SORT_TILE_LDS, SORT_RADIX = 0, 1, 2
 
 # every symbol include/gsplat_hip.h declares (tests check the library exports all of them)
 #: the GS_ABI_VERSION of include/gsplat_hip.h this binding was written against (checked when a library is bound)
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 SYMBOLS = ("gs_abi_version", "gs_geom_layout", "gs_image_layout", "gs_bin_layout", "gs_backward_scratch_bytes", "gs_last_error",
            "gs_version", "gs_set_sort_path", "gs_set_forward_segments", "gs_set_half_quadrants", "gs_set_backward_chain", "gs_set_backward_chain_tickets", "gs_set_backward_chain_polls", "gs_async_status_word", "gs_async_status_clear", "gs_recorded_cut", "gs_set_backward_segments", "gs_preprocess_forward", "gs_preprocess_forward_raw", "gs_render_forward", "gs_render_backward", "gs_render_backward_raw", "gs_render_backward_raw_adam", "gs_adam_step", "gs_adam_step_multi",
@@ -75,7 +75,9 @@ SYMBOLS = ("gs_abi_version", "gs_geom_layout", "gs_image_layout", "gs_bin_layout
            "gs_tracking_loss_scratch_bytes", "gs_tracking_loss", "gs_preprocess_forward_raw_dev", "gs_render_backward_raw_pose_dev",
            "gs_tracking_state_bytes", "gs_tracking_begin", "gs_tracking_step",
            "gs_preprocess_forward_topdown", "gs_render_forward_topdown", "gs_grid_dbscan_layout", "gs_grid_dbscan", "gs_high_loss_grid",
-           "gs_cluster_hulls_layout", "gs_cluster_hulls")
+           "gs_cluster_hulls_layout", "gs_cluster_hulls",
+           "gs_depth_error_median_scratch_bytes", "gs_depth_error_median", "gs_depth_error_median_grid", "gs_depth_error_median_workgroups",
+           "gs_mapping_loss_outlier", "gs_tracking_loss_outlier")
 
 
 def _bind(lib):
@@ -172,6 +174,8 @@ def _bind(lib):
     lib.gs_tracking_loss_scratch_bytes.restype = C.c_uint64
     lib.gs_tracking_loss.argtypes = [i32, i32] + [vp] * 6 + [i32, f32, f32, f32] + [vp] * 4 + [vp]
     lib.gs_tracking_loss.restype = C.c_int
+    lib.gs_tracking_loss_outlier.argtypes = [i32, i32] + [vp] * 6 + [i32, f32, f32, f32] + [vp] * 4 + [vp, vp]       # (..., d_median, stream)
+    lib.gs_tracking_loss_outlier.restype = C.c_int
     lib.gs_tracking_state_bytes.argtypes = []
     lib.gs_tracking_state_bytes.restype = C.c_uint64
     lib.gs_tracking_begin.argtypes = [vp, vp, i64, i64, vp, vp]
@@ -203,6 +207,16 @@ def _bind(lib):
     lib.gs_mapping_loss_scratch_bytes.restype = C.c_uint64
     lib.gs_mapping_loss.argtypes = [i32, i32, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, i64, vp]
     lib.gs_mapping_loss.restype = C.c_int
+    lib.gs_mapping_loss_outlier.argtypes = [i32, i32, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, i64, vp, vp]    # (..., d_median, stream)
+    lib.gs_mapping_loss_outlier.restype = C.c_int
+    lib.gs_depth_error_median_scratch_bytes.argtypes = [i32, i32]
+    lib.gs_depth_error_median_scratch_bytes.restype = C.c_uint64
+    lib.gs_depth_error_median.argtypes = [i32, i32, vp, vp, vp, vp, vp]
+    lib.gs_depth_error_median.restype = C.c_int
+    lib.gs_depth_error_median_grid.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp]      # (..., workgroups, stream)
+    lib.gs_depth_error_median_grid.restype = C.c_int
+    lib.gs_depth_error_median_workgroups.argtypes = [i32, i32]
+    lib.gs_depth_error_median_workgroups.restype = i32
     lib.gs_compact_scratch_bytes.argtypes = [i64]
     lib.gs_compact_scratch_bytes.restype = C.c_uint64
     lib.gs_compact_index.argtypes = [i64, vp, vp, vp, vp, vp]

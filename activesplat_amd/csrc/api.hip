@@ -769,6 +769,19 @@ int gs_tracking_loss(int32_t width, int32_t height, const float* im, const float
     return GS_OK;
 }
 
+int gs_tracking_loss_outlier(int32_t width, int32_t height, const float* im, const float* gt_im, const float* depth, const float* depth_sq,
+                             const float* gt_depth, const float* silhouette, int32_t use_sil_for_loss, float sil_thres, float w_im, float w_depth,
+                             float* dL_dim, float* dL_ddepth, void* loss_rows, float* losses, const float* d_median, gs_stream_t stream)
+{
+    if (width <= 0 || height <= 0 || (int64_t)width * height >= ((int64_t)1 << 31)) return fail(GS_EINVAL, "gs_tracking_loss_outlier: bad image size");
+    if (!im || !gt_im || !depth || !depth_sq || !gt_depth || !dL_dim || !dL_ddepth || !loss_rows || !d_median || (use_sil_for_loss && !silhouette))
+        return fail(GS_EINVAL, "gs_tracking_loss_outlier: null pointer");
+    const hipError_t e = gs::launch_tracking_loss(width, height, im, gt_im, depth, depth_sq, gt_depth, silhouette, use_sil_for_loss != 0, sil_thres,
+                                                  w_im, w_depth, dL_dim, dL_ddepth, (float*)loss_rows, losses, (hipStream_t)stream, d_median);
+    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_tracking_loss_outlier: %s", hipGetErrorString(e));
+    return GS_OK;
+}
+
 uint64_t gs_tracking_state_bytes(void) { return align_up((uint64_t)gs::kTrackState * 4); }
 
 int gs_tracking_begin(const float* cam_unnorm_rots, const float* cam_trans, int64_t num_frames, int64_t time_idx, void* state, gs_stream_t stream)
@@ -976,6 +989,48 @@ int gs_mapping_loss(int32_t width, int32_t height, const float* im, const float*
                                            dL_ddepth, (float*)scratch, persistent_call, (hipStream_t)stream);
     if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_mapping_loss: %s", hipGetErrorString(e));
     return GS_OK;
+}
+
+int gs_mapping_loss_outlier(int32_t width, int32_t height, const float* im, const float* gt_im, const float* depth,
+                            const float* depth_sq, const float* gt_depth, float w_im, float w_depth, float* losses, float* dL_dim,
+                            float* dL_ddepth, void* scratch, int64_t persistent_call, const float* d_median, gs_stream_t stream)
+{
+    if (width <= 0 || height <= 0 || !im || !gt_im || !depth || !gt_depth || !losses || !dL_dim || !dL_ddepth || !scratch || persistent_call < 0 ||
+        !d_median)
+        return fail(GS_EINVAL, "gs_mapping_loss_outlier: bad argument");
+    hipError_t e = gs::launch_mapping_loss(width, height, im, gt_im, depth, depth_sq, gt_depth, w_im, w_depth, losses, dL_dim,
+                                           dL_ddepth, (float*)scratch, persistent_call, (hipStream_t)stream, d_median);
+    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_mapping_loss_outlier: %s", hipGetErrorString(e));
+    return GS_OK;
+}
+
+int32_t gs_depth_error_median_workgroups(int32_t width, int32_t height)
+{
+    return gs::depth_median_grid((int64_t)(width > 0 ? width : 1) * (height > 0 ? height : 1));
+}
+
+uint64_t gs_depth_error_median_scratch_bytes(int32_t width, int32_t height)
+{
+    (void)width; (void)height;          // three histograms and a flag, whatever the frame
+    return align_up((uint64_t)gs::kMedianScratchWords * 4);
+}
+
+int gs_depth_error_median_grid(int32_t width, int32_t height, const float* depth, const float* gt_depth, void* scratch, float* d_median,
+                               int32_t workgroups, gs_stream_t stream)
+{
+    if (width <= 0 || height <= 0 || (int64_t)width * height >= ((int64_t)1 << 31)) return fail(GS_EINVAL, "gs_depth_error_median: bad image size");
+    if (!depth || !gt_depth || !scratch || !d_median) return fail(GS_EINVAL, "gs_depth_error_median: null pointer");
+    if (workgroups < 0 || workgroups > gs::kMedianMaxGrid) return fail(GS_EINVAL, "gs_depth_error_median_grid: 0 (automatic) .. 1024 workgroups");
+    const hipError_t e = gs::launch_depth_error_median((int64_t)width * height, depth, gt_depth, (uint32_t*)scratch, d_median, workgroups,
+                                                       (hipStream_t)stream);
+    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_depth_error_median: %s", hipGetErrorString(e));
+    return GS_OK;
+}
+
+int gs_depth_error_median(int32_t width, int32_t height, const float* depth, const float* gt_depth, void* scratch, float* d_median,
+                          gs_stream_t stream)
+{
+    return gs_depth_error_median_grid(width, height, depth, gt_depth, scratch, d_median, 0, stream);
 }
 
 uint64_t gs_compact_scratch_bytes(int64_t n) { return align_up(gs::compact_scratch_bytes(n > 0 ? n : 1)); }

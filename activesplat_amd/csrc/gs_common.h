@@ -819,11 +819,21 @@ hipError_t launch_tracking_step(int64_t pose_nrows, const float* pose_rows, int6
 inline int64_t tracking_loss_rows(int64_t npix) { return (npix + kBlock - 1) / kBlock; }
 hipError_t launch_tracking_loss(int W, int H, const float* im, const float* gt, const float* depth, const float* depth_sq, const float* gt_depth,
                                 const float* sil, int use_sil, float sil_thres, float w_im, float w_depth, float* dL_dim, float* dL_ddepth,
-                                float* rows, float* losses, hipStream_t st);
+                                float* rows, float* losses, hipStream_t st, const float* d_median = nullptr);
 constexpr int kLossAccSlots = 256;          // 64-byte accumulator lines at the head of the mapping loss' scratch (loss.hip)
 hipError_t launch_mapping_loss(int W, int H, const float* im, const float* gt, const float* depth, const float* depth_sq,
                                const float* gt_depth, float w_im, float w_depth, float* losses, float* dL_dim,
-                               float* dL_ddepth, float* scratch, int64_t persistent_call, hipStream_t st);
+                               float* dL_ddepth, float* scratch, int64_t persistent_call, hipStream_t st, const float* d_median = nullptr);
+// (d_median != nullptr in the two launches above: the ignore_outlier_depth_loss instantiations, fed by the select below)
+// exact lower median of |gt_depth - depth| * (gt_depth > 0) over a grid of workgroups (loss.hip): three histograms of kMedianBins counts + the NaN flag
+constexpr int kMedianBins = 2048;
+constexpr int kMedianScratchWords = 3 * kMedianBins + 16;
+constexpr int kMedianChunk = 2048;          // the automatic grid: one workgroup per kMedianChunk pixels, at most kMedianAutoGrid of them
+constexpr int kMedianAutoGrid = 64;         // (G = 32 at 256 x 256, 64 at 640 x 480: the fastest rows of profiles/outlier_loss.txt)
+constexpr int kMedianMaxGrid = 1024;        // bound of a forced grid
+int depth_median_grid(int64_t n);
+hipError_t launch_depth_error_median(int64_t n, const float* depth, const float* gt_depth, uint32_t* scratch, float* d_median, int grid,
+                                     hipStream_t st);
 hipError_t launch_visibility_stats(int P, const int32_t* radii, uint8_t* seen, float* max_radius, hipStream_t st);
 hipError_t launch_accumulate_grad2d(int P, const float* grad, const uint8_t* seen, float* accum, float* denom, hipStream_t st);
 // DBSCAN on a pixel grid (stats.hip; the rule: include/gsplat_hip.h, gs_grid_dbscan).  One argument block for its seven kernels.

@@ -23,6 +23,9 @@
 //   loss_grad_kernel  : convolves the three partial maps with the (symmetric) window, combines them into dL/dim,
 //                       adds the L1 terms, writes dL/ddepth (needs the mask count of pass 1 -- read from device
 //                       memory, no host sync) and the three loss scalars.
+//   depth_median_kernel<0..3> + the kOutlier instantiations of the two kernels above and of tracking_loss_kernel: ignore_outlier_depth_loss
+//                       (splatam.py:220-228) -- torch.median of the depth error as an exact select over a grid of workgroups, and the depth
+//                       mask ANDed with err < 10 median.  The plain instantiations are what they were.
 #include "gs_common.h"
 
 namespace gs {
@@ -65,11 +68,140 @@ __device__ __forceinline__ void acc_totals(const float* __restrict__ acc, float*
     }
     __syncthreads();
 }
+// ---- ignore_outlier_depth_loss (src/mapper/splatam/splatam.py:220-228) ----
+//   err = |gt_depth - depth| * (gt_depth > 0),  keep = err < 10 * median(err)   (strict; torch.median over ALL pixels: the lower median, NaN as
+//   soon as one err is NaN).  The median is a DEVICE scalar of gs_depth_error_median; the kOutlier instantiations of the three loss kernels AND
+//   `keep` into their depth mask.  A median of 0 or NaN keeps nothing.  fp32 without contraction: the decision is torch's, bit for bit.
+__device__ __forceinline__ float outlier_depth_error(float g, float d)
+{
+#pragma clang fp contract(off)
+    return fabsf(g - d) * (g > 0.0f ? 1.0f : 0.0f);        // (the product: NaN * 0 and inf * 0 are NaN, as in torch)
+}
+__device__ __forceinline__ bool outlier_keep(float g, float d, float median)
+{
+#pragma clang fp contract(off)
+    return outlier_depth_error(g, d) < 10.0f * median;
+}
+
+// Exact select of the depth error's lower median over a GRID of workgroups.  err >= +0, so the floats order as their bit patterns do: three
+// passes over 11 + 11 + 10 bits pin the value (grow.hip's rule).  One launch per pass: a workgroup histograms its pixels in LDS and adds its
+// non-zero bins to the pass' global histogram with integer atomics (order-independent: the same bits on every run).  The workgroups of pass p + 1
+// each re-derive the prefix of pass p from that FINISHED histogram -- nothing is handed from workgroup to workgroup inside a launch, the
+// kernel boundary is the only synchronisation -- and a one-workgroup launch resolves the third pass.  A grid of 1 is the same code.
+constexpr int kMedThreads = 1024;
+constexpr int kMedBins = kMedianBins;                  // 2048
+constexpr int kMedPer = kMedBins / kMedThreads;        // bins per thread in the scan
+constexpr int kMedGroup = 32;                          // threads per second-level group of the scan (32 x 32 = 1024)
+
+struct MedianPick { uint32_t prefix, mask, k; };
+
+// the bin of `hist` (2048 counts, finished by an earlier launch) that holds the element of rank k, and the rank inside it.  All threads call;
+// all return the same pick.  Thread t owns bins [kMedPer t, kMedPer t + kMedPer): two-level sums in LDS give its exclusive prefix.
+__device__ __forceinline__ void median_pick(const uint32_t* __restrict__ hist, int shift, uint32_t bin_mask, MedianPick& p, uint32_t* s_part,
+                                            uint32_t* s_group, uint32_t* s_sel, int tid)
+{
+    uint32_t c[kMedPer], own = 0u;
+#pragma unroll
+    for (int j = 0; j < kMedPer; j++) { c[j] = hist[tid * kMedPer + j]; own += c[j]; }
+    __syncthreads();                                   // (s_part / s_group / s_sel of the previous pick are read no more)
+    s_part[tid] = own;
+    if (tid == 0) { s_sel[0] = 0u; s_sel[1] = 0u; }
+    __syncthreads();
+    if (tid < kMedThreads / kMedGroup) {
+        uint32_t g = 0u;
+        for (int j = 0; j < kMedGroup; j++) g += s_part[tid * kMedGroup + j];
+        s_group[tid] = g;
+    }
+    __syncthreads();
+    uint32_t excl = 0u;
+    const int grp = tid / kMedGroup;
+    for (int j = 0; j < grp; j++) excl += s_group[j];
+    for (int j = grp * kMedGroup; j < tid; j++) excl += s_part[j];
+    if (p.k >= excl && p.k - excl < own) {             // exactly one thread: the counts of the histogram sum to more than k
+        uint32_t k = p.k - excl;
+        int j = 0;
+        for (; j < kMedPer - 1; j++) {
+            if (k < c[j]) break;
+            k -= c[j];
+        }
+        s_sel[0] = (uint32_t)(tid * kMedPer + j); s_sel[1] = k;
+    }
+    __syncthreads();
+    p.prefix |= (s_sel[0] & bin_mask) << shift;
+    p.mask |= bin_mask << shift;
+    p.k = s_sel[1];
+}
+
+__device__ __forceinline__ int median_shift(int pass) { return pass == 0 ? 21 : (pass == 1 ? 10 : 0); }
+__device__ __forceinline__ uint32_t median_bin_mask(int pass) { return pass == 2 ? 0x3ffu : 0x7ffu; }
+
+// hists: three histograms of kMedBins counts, then the NaN flag.  kPass = 0..2: histogram pass; kPass = 3: the pick of the value.
+template <int kPass>
+__global__ __launch_bounds__(kMedThreads) void depth_median_kernel(int64_t n, const float* __restrict__ depth, const float* __restrict__ gt_depth,
+                                                                   uint32_t* __restrict__ hists, float* __restrict__ d_median)
+{
+    __shared__ uint32_t s_hist[kMedBins];
+    __shared__ uint32_t s_part[kMedThreads];
+    __shared__ uint32_t s_group[kMedThreads / kMedGroup];
+    __shared__ uint32_t s_sel[2];
+    const int tid = threadIdx.x;
+    MedianPick p;
+    p.prefix = 0u; p.mask = 0u; p.k = (uint32_t)((n - 1) / 2);
+    for (int q = 0; q < (kPass < 3 ? kPass : 3); q++)
+        median_pick(hists + q * kMedBins, median_shift(q), median_bin_mask(q), p, s_part, s_group, s_sel, tid);
+    if (kPass == 3) {
+        if (tid == 0) *d_median = hists[3 * kMedBins] ? __uint_as_float(0x7fc00000u) : __uint_as_float(p.prefix);
+        return;
+    }
+    for (int b = tid; b < kMedBins; b += kMedThreads) s_hist[b] = 0u;
+    __syncthreads();
+    const int sh = median_shift(kPass);
+    const uint32_t bm = median_bin_mask(kPass);
+    bool saw_nan = false;
+    const int64_t stride = (int64_t)gridDim.x * kMedThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kMedThreads + tid; i < n; i += stride) {
+        const float err = outlier_depth_error(gt_depth[i], depth[i]);
+        if (kPass == 0 && err != err) saw_nan = true;
+        const uint32_t bits = __float_as_uint(err);
+        if ((bits & p.mask) == p.prefix) atomicAdd(&s_hist[(bits >> sh) & bm], 1u);
+    }
+    if (kPass == 0 && saw_nan) hists[3 * kMedBins] = 1u;   // (every writer stores the same value)
+    __syncthreads();
+    uint32_t* out = hists + kPass * kMedBins;
+    for (int b = tid; b < kMedBins; b += kMedThreads) {
+        const uint32_t c = s_hist[b];
+        if (c) atomicAdd(out + b, c);
+    }
+}
+
+// grid of the three histogram passes: a function of n only.  A call is five short launches (memset, three passes, the pick).  Measured
+// (profiles/outlier_loss.txt): 20.6 us at 256 x 256 for every G from 32 to 256, 23.2 us at 640 x 480 with the minimum at G = 64; one workgroup
+// takes 58.6 / 206 us.  2048 pixels per workgroup up to 64 workgroups gives G = 32 and 64 there
+int depth_median_grid(int64_t n)
+{
+    const int64_t g = (n + kMedianChunk - 1) / kMedianChunk;
+    return (int)(g < 1 ? 1 : (g > kMedianAutoGrid ? kMedianAutoGrid : g));
+}
+
+hipError_t launch_depth_error_median(int64_t n, const float* depth, const float* gt_depth, uint32_t* scratch, float* d_median, int grid,
+                                     hipStream_t st)
+{
+    const int G = grid > 0 ? (grid > kMedianMaxGrid ? kMedianMaxGrid : grid) : depth_median_grid(n);
+    hipError_t e = hipMemsetAsync(scratch, 0, kMedianScratchWords * sizeof(uint32_t), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((depth_median_kernel<0>), dim3(G), dim3(kMedThreads), 0, st, n, depth, gt_depth, scratch, d_median);
+    hipLaunchKernelGGL((depth_median_kernel<1>), dim3(G), dim3(kMedThreads), 0, st, n, depth, gt_depth, scratch, d_median);
+    hipLaunchKernelGGL((depth_median_kernel<2>), dim3(G), dim3(kMedThreads), 0, st, n, depth, gt_depth, scratch, d_median);
+    hipLaunchKernelGGL((depth_median_kernel<3>), dim3(1), dim3(kMedThreads), 0, st, n, depth, gt_depth, scratch, d_median);
+    return hipGetLastError();
+}
+
+template <bool kOutlier>
 __global__ __launch_bounds__(kBlock) void loss_stats_kernel(int W, int H, const float* __restrict__ im,
                                                             const float* __restrict__ gt, const float* __restrict__ depth,
                                                             const float* __restrict__ depth_sq,
                                                             const float* __restrict__ gt_depth, float* __restrict__ partials,
-                                                            float* __restrict__ acc)
+                                                            float* __restrict__ acc, const float* __restrict__ d_median)
 {
     __shared__ float s_x[kLP][kLP + 1];
     __shared__ float s_y[kLP][kLP + 1];
@@ -143,7 +275,9 @@ __global__ __launch_bounds__(kBlock) void loss_stats_kernel(int W, int H, const 
         const size_t o = (size_t)py * W + px;
         const float d = depth[o], g = gt_depth[o];
         const float unc = depth_sq ? depth_sq[o] - d * d : 0.f;
-        if (g > 0.f && d == d && unc == unc) { sum_d = fabsf(g - d); cnt = 1.f; }
+        bool m = g > 0.f && d == d && unc == unc;
+        if (kOutlier) m = m && outlier_keep(g, d, d_median[0]);
+        if (m) { sum_d = fabsf(g - d); cnt = 1.f; }
     }
     // the four sums of the workgroup in ONE reduction (two barriers instead of eight): wave sums -> LDS -> four lanes add the four waves' values
     sum_ssim = wave_sum(sum_ssim); sum_l1 = wave_sum(sum_l1); sum_d = wave_sum(sum_d); cnt = wave_sum(cnt);
@@ -156,13 +290,15 @@ __global__ __launch_bounds__(kBlock) void loss_stats_kernel(int W, int H, const 
     }
 }
 
+template <bool kOutlier>
 __global__ __launch_bounds__(kBlock) void loss_grad_kernel(int W, int H, const float* __restrict__ im,
                                                            const float* __restrict__ gt, const float* __restrict__ depth,
                                                            const float* __restrict__ depth_sq,
                                                            const float* __restrict__ gt_depth, const float* __restrict__ partials,
                                                            const float* __restrict__ acc, float w_im, float w_depth,
                                                            float* __restrict__ dL_dim, float* __restrict__ dL_ddepth,
-                                                           float* __restrict__ losses, float* __restrict__ acc_other)
+                                                           float* __restrict__ losses, float* __restrict__ acc_other,
+                                                           const float* __restrict__ d_median)
 {
     __shared__ float s_p[3][kLP][kLP + 1];
     __shared__ float s_h[3][kLP][kLT + 1];
@@ -229,7 +365,8 @@ __global__ __launch_bounds__(kBlock) void loss_grad_kernel(int W, int H, const f
         const size_t o = (size_t)py * W + px;
         const float d = depth[o], g = gt_depth[o];
         const float unc = depth_sq ? depth_sq[o] - d * d : 0.f;
-        const bool m = g > 0.f && d == d && unc == unc;
+        bool m = g > 0.f && d == d && unc == unc;
+        if (kOutlier) m = m && outlier_keep(g, d, d_median[0]);
         const float diff = d - g;
         const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
         dL_ddepth[o] = m ? w_depth * sgn / cnt : 0.f;
@@ -244,7 +381,7 @@ __global__ __launch_bounds__(kBlock) void loss_grad_kernel(int W, int H, const f
 
 hipError_t launch_mapping_loss(int W, int H, const float* im, const float* gt, const float* depth, const float* depth_sq,
                                const float* gt_depth, float w_im, float w_depth, float* losses, float* dL_dim,
-                               float* dL_ddepth, float* scratch, int64_t persistent_call, hipStream_t st)
+                               float* dL_ddepth, float* scratch, int64_t persistent_call, hipStream_t st, const float* d_median)
 {
     // two sets of kAccSlots x 4 accumulators (one 64-byte line each), then 9 partial maps.  persistent_call = 0: any scratch, set 0 is
     // memset here.  persistent_call = k >= 1: the k-th call on a scratch its owner zeroed ONCE and keeps for this stream -- the call uses
@@ -258,9 +395,15 @@ hipError_t launch_mapping_loss(int W, int H, const float* im, const float* gt, c
         if (e != hipSuccess) return e;
     }
     const dim3 grid((W + kLT - 1) / kLT, (H + kLT - 1) / kLT, 3);
-    hipLaunchKernelGGL(loss_stats_kernel, grid, dim3(kBlock), 0, st, W, H, im, gt, depth, depth_sq, gt_depth, partials, acc);
-    hipLaunchKernelGGL(loss_grad_kernel, grid, dim3(kBlock), 0, st, W, H, im, gt, depth, depth_sq, gt_depth, partials, acc, w_im,
-                       w_depth, dL_dim, dL_ddepth, losses, acc_other);
+    if (d_median) {      // ignore_outlier_depth_loss: the same two launches, the depth mask ANDed with err < 10 median
+        hipLaunchKernelGGL((loss_stats_kernel<true>), grid, dim3(kBlock), 0, st, W, H, im, gt, depth, depth_sq, gt_depth, partials, acc, d_median);
+        hipLaunchKernelGGL((loss_grad_kernel<true>), grid, dim3(kBlock), 0, st, W, H, im, gt, depth, depth_sq, gt_depth, partials, acc, w_im,
+                           w_depth, dL_dim, dL_ddepth, losses, acc_other, d_median);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL((loss_stats_kernel<false>), grid, dim3(kBlock), 0, st, W, H, im, gt, depth, depth_sq, gt_depth, partials, acc, d_median);
+    hipLaunchKernelGGL((loss_grad_kernel<false>), grid, dim3(kBlock), 0, st, W, H, im, gt, depth, depth_sq, gt_depth, partials, acc, w_im,
+                       w_depth, dL_dim, dL_ddepth, losses, acc_other, d_median);
     return hipGetLastError();
 }
 
@@ -270,14 +413,17 @@ hipError_t launch_mapping_loss(int W, int H, const float* im, const float* gt, c
 //   dL/ddepth = -(w_depth [mask] * sgn(gt_depth - depth)),  dL/dim = -(w_im [colour mask] * sgn(gt_im - im))  -- autograd's own expression
 //   (abs' backward grad * sgn, then the subtraction's negation; sgn(0) = sgn(NaN) = 0), so the images are bit-identical to torch's.
 // Every workgroup writes one row of kTrackRow partial sums (no float atomics); tracking_loss_reduce (gs_common.h) sums the rows in a fixed order.
-// ignore_outlier_depth_loss needs the median of the depth error: that option stays on the torch loss (mapping.get_loss).
+// kOutlier (ignore_outlier_depth_loss): the mask is ANDed with err < 10 median (d_median: gs_depth_error_median's device scalar) and the colour
+// mask is ALWAYS the mask tiled to 3 channels (splatam.py:242), with or without use_sil_for_loss.  Same rows, same finish and step kernels.
 __device__ __forceinline__ float sgnf(float x) { return (float)((0.f < x) - (x < 0.f)); }
 
+template <bool kOutlier>
 __global__ __launch_bounds__(kBlock) void tracking_loss_kernel(int npix, const float* __restrict__ im, const float* __restrict__ gt,
                                                                const float* __restrict__ depth, const float* __restrict__ depth_sq,
                                                                const float* __restrict__ gt_depth, const float* __restrict__ sil, int use_sil,
                                                                float sil_thres, float w_im, float w_depth, float* __restrict__ dL_dim,
-                                                               float* __restrict__ dL_ddepth, float* __restrict__ rows)
+                                                               float* __restrict__ dL_ddepth, float* __restrict__ rows,
+                                                               const float* __restrict__ d_median)
 {
 #pragma clang fp contract(off)
     __shared__ float s_red[kTrackRow][kBlock / kWave];
@@ -287,11 +433,12 @@ __global__ __launch_bounds__(kBlock) void tracking_loss_kernel(int npix, const f
         const float d = depth[i], gd = gt_depth[i];
         const float unc = depth_sq[i] - d * d;
         bool m = gd > 0.f && !__builtin_isnan(d) && !__builtin_isnan(unc);
+        if (kOutlier) m = m && outlier_keep(gd, d, d_median[0]);
         if (use_sil) m = m && sil[i] > sil_thres;
         const float ed = gd - d;
         if (m) dsum = fabsf(ed);
         dL_ddepth[i] = -((m ? w_depth : 0.f) * sgnf(ed));
-        const bool cm = !use_sil || m;
+        const bool cm = kOutlier ? m : (!use_sil || m);
         const float gc = cm ? w_im : 0.f;
         for (int ch = 0; ch < 3; ch++) {
             const size_t j = (size_t)ch * npix + i;
@@ -321,13 +468,16 @@ __global__ __launch_bounds__(kBlock) void tracking_loss_finish_kernel(int64_t nr
 
 hipError_t launch_tracking_loss(int W, int H, const float* im, const float* gt, const float* depth, const float* depth_sq, const float* gt_depth,
                                 const float* sil, int use_sil, float sil_thres, float w_im, float w_depth, float* dL_dim, float* dL_ddepth,
-                                float* rows, float* losses, hipStream_t st)
+                                float* rows, float* losses, hipStream_t st, const float* d_median)
 {
     const int npix = W * H;
     const int64_t nb = tracking_loss_rows(npix);
-    if (nb > 0)
-        hipLaunchKernelGGL(tracking_loss_kernel, dim3((unsigned)nb), dim3(kBlock), 0, st, npix, im, gt, depth, depth_sq, gt_depth, sil, use_sil,
-                           sil_thres, w_im, w_depth, dL_dim, dL_ddepth, rows);
+    if (nb > 0 && d_median)
+        hipLaunchKernelGGL((tracking_loss_kernel<true>), dim3((unsigned)nb), dim3(kBlock), 0, st, npix, im, gt, depth, depth_sq, gt_depth, sil, use_sil,
+                           sil_thres, w_im, w_depth, dL_dim, dL_ddepth, rows, d_median);
+    else if (nb > 0)
+        hipLaunchKernelGGL((tracking_loss_kernel<false>), dim3((unsigned)nb), dim3(kBlock), 0, st, npix, im, gt, depth, depth_sq, gt_depth, sil, use_sil,
+                           sil_thres, w_im, w_depth, dL_dim, dL_ddepth, rows, d_median);
     if (losses) hipLaunchKernelGGL(tracking_loss_finish_kernel, dim3(1), dim3(kBlock), 0, st, nb, rows, w_im, w_depth, losses);
     return hipGetLastError();
 }

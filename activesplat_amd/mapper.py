@@ -255,13 +255,14 @@ class SplatMapper:
             fused_path = cfg.get("fused_preprocess", False) and cfg["fused_render"] and not event
             in_backward = cfg.get("fused_adam", False) and fused_path
             # (fused_iteration IS the Adam-inside-the-backward form without autograd: it implies fused_adam whatever the config says)
-            direct = cfg.get("fused_iteration", False) and fused_path and cfg["fused_loss"] and mc["use_l1"] and not mc["ignore_outlier_depth_loss"]
+            direct = cfg.get("fused_iteration", False) and fused_path and cfg["fused_loss"] and mc["use_l1"]
             if direct:
                 # the whole iteration without autograd.  No event here, so prune_gaussians is a no-op by its own predicate (prune_event) and
                 # densify only accumulates this iteration's statistics; nothing holds a gradient afterwards, so step() / zero_grad() have
                 # nothing to do -- asserted, so that a parameter that starts receiving gradients (camera learning rates > 0) cannot be skipped
                 loss, self.variables, losses = M.mapping_iteration(self.params, self._data(it_color, it_depth, it_id), self.variables, it_id,
-                                                                   mc["loss_weights"], self.optimizer)
+                                                                   mc["loss_weights"], self.optimizer,
+                                                                   ignore_outlier_depth_loss=mc["ignore_outlier_depth_loss"])
                 if mc["use_gaussian_splatting_densification"]:
                     self.params, self.variables = O.densify(self.params, self.variables, self.optimizer, it, mc["densify_dict"])
                 if any(p.grad is not None for p in self.params.values()):

@@ -334,11 +334,53 @@ def _loss_scratch_done(key, ok):
         _LOSS_SCRATCH.pop(key, None)
 
 
+#: scratch of gs_depth_error_median per (device, stream): three histograms and a flag, cleared inside every call
+_MEDIAN_SCRATCH = {}
+
+
+def _median_scratch(lib, dev, W, H):
+    from . import _lib
+    if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+        return torch.empty(int(lib.gs_depth_error_median_scratch_bytes(W, H)), dtype=torch.uint8, device=dev)
+    key = (dev.index, _lib.stream_handle(dev))
+    buf = _MEDIAN_SCRATCH.get(key)
+    if buf is None:
+        while len(_MEDIAN_SCRATCH) >= 32:
+            _MEDIAN_SCRATCH.pop(next(iter(_MEDIAN_SCRATCH)))
+        buf = _MEDIAN_SCRATCH[key] = torch.empty(int(lib.gs_depth_error_median_scratch_bytes(W, H)), dtype=torch.uint8, device=dev)
+    return buf
+
+
+@torch.no_grad()
+def depth_error_median(depth, gt_depth, grid=None, out=None, scratch=None):
+    """torch.median of the depth error of ignore_outlier_depth_loss (splatam.py:220-228), ((gt_depth - depth).abs() * (gt_depth > 0)).median(),
+    as a DEVICE scalar, bit-identical to torch's: the lower median over ALL pixels (unmeasured ones count as zeros), NaN as soon as one error
+    is NaN.  gs_depth_error_median (csrc/loss.hip): an exact three-pass radix select over a grid of workgroups, no sort and no host wait.
+    depth, gt_depth: [1,H,W] (or [H,W]) float32 on one device.  grid: workgroups per pass (None: the library's choice for H W pixels; 1: a single
+    workgroup) -- for tests and measurements.  out ([] or [1] float32) / scratch (gs_depth_error_median_scratch_bytes): the caller's buffers."""
+    import ctypes as C
+    from . import _lib
+    lib = _lib.get()
+    H, W = int(depth.shape[-2]), int(depth.shape[-1])
+    dev = depth.device
+    d, g = depth.detach().contiguous().float(), gt_depth.detach().to(dev).contiguous().float()
+    if d.numel() != H * W or g.numel() != H * W:
+        raise ValueError("depth_error_median: depth and gt_depth must hold one H x W image each")
+    if out is None:
+        out = torch.empty((), dtype=torch.float32, device=dev)
+    if scratch is None:
+        scratch = _median_scratch(lib, dev, W, H)
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    _lib.check(lib.gs_depth_error_median_grid(W, H, p(d), p(g), p(scratch), p(out), 0 if grid is None else int(grid), _lib.stream_ptr(dev)))
+    return out
+
+
 class _FusedMappingLoss(torch.autograd.Function):
-    """gs_mapping_loss: value and gradients in two HIP launches (csrc/loss.hip)."""
+    """gs_mapping_loss: value and gradients in two HIP launches (csrc/loss.hip).  outlier (ignore_outlier_depth_loss): gs_depth_error_median,
+    then gs_mapping_loss_outlier -- the depth mask ANDed with err < 10 median, nothing through the median (the reference detaches the mask)."""
 
     @staticmethod
-    def forward(ctx, im, depth, depth_sq, gt_im, gt_depth, w_im, w_depth):
+    def forward(ctx, im, depth, depth_sq, gt_im, gt_depth, w_im, w_depth, outlier=False):
         import ctypes as C
         from . import _lib
         lib = _lib.get()
@@ -351,10 +393,15 @@ class _FusedMappingLoss(torch.autograd.Function):
         d_im, d_depth = grads[:3], grads[3:]
         st = _lib.stream_ptr(dev)
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        median = depth_error_median(depth_, gtd_) if outlier else None
         key, scratch, call = _loss_scratch(lib, dev, W, H)
         try:
-            _lib.check(lib.gs_mapping_loss(W, H, p(im_), p(gt_), p(depth_), p(dsq_), p(gtd_), float(w_im), float(w_depth), p(buf),
-                                           p(d_im), p(d_depth), p(scratch), call, st))
+            if outlier:
+                _lib.check(lib.gs_mapping_loss_outlier(W, H, p(im_), p(gt_), p(depth_), p(dsq_), p(gtd_), float(w_im), float(w_depth), p(buf),
+                                                       p(d_im), p(d_depth), p(scratch), call, p(median), st))
+            else:
+                _lib.check(lib.gs_mapping_loss(W, H, p(im_), p(gt_), p(depth_), p(dsq_), p(gtd_), float(w_im), float(w_depth), p(buf),
+                                               p(d_im), p(d_depth), p(scratch), call, st))
         except Exception:
             _loss_scratch_done(key, False)
             raise
@@ -369,18 +416,21 @@ class _FusedMappingLoss(torch.autograd.Function):
     def backward(ctx, g, _gl=None):
         (grads,) = ctx.saved_tensors
         if g is None:
-            return None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None
         u = _UNIT_GRADS.get((str(g.device), g.dtype))
         if u is not None and g.dim() == 0 and g.data_ptr() == u.data_ptr():
             gd = grads                           # the root gradient is the cached 1: no launch
         else:
             gd = g * grads                       # one launch for both gradients
-        return gd[:3], gd[3:], None, None, None, None, None
+        return gd[:3], gd[3:], None, None, None, None, None, None
 
 
-def fused_mapping_loss(im, depth, depth_sq, gt_im, gt_depth, loss_weights):
-    """(loss, {'im','depth','loss'}) with the reference's mapping-loss semantics, computed by the HIP library."""
-    loss, parts = _FusedMappingLoss.apply(im, depth, depth_sq, gt_im, gt_depth, loss_weights["im"], loss_weights["depth"])
+def fused_mapping_loss(im, depth, depth_sq, gt_im, gt_depth, loss_weights, ignore_outlier_depth_loss=False):
+    """(loss, {'im','depth','loss'}) with the reference's mapping-loss semantics, computed by the HIP library.  ignore_outlier_depth_loss: the
+    depth term runs over the pixels whose depth error is below 10 x its median (depth_error_median, on the device); when that leaves no pixel
+    (a median of 0 or NaN) the depth term and the loss are NaN, as torch's mean of nothing, dL/ddepth is zero and dL/dim the usual image."""
+    loss, parts = _FusedMappingLoss.apply(im, depth, depth_sq, gt_im, gt_depth, loss_weights["im"], loss_weights["depth"],
+                                          bool(ignore_outlier_depth_loss))
     return loss, {"im": parts[1], "depth": parts[2], "loss": loss}
 
 
@@ -394,7 +444,7 @@ def get_loss(params, curr_data, variables, iter_time_idx, loss_weights, use_sil_
                  matrix at every reference call site; means2D.grad then also carries the depth term (the
                  reference's densifier sees the colour pass only).
     fused_loss : the masked-L1 + L1 + SSIM loss and its gradients come from gs_mapping_loss (csrc/loss.hip) instead
-                 of ~40 torch kernels.
+                 of ~40 torch kernels; with ignore_outlier_depth_loss from gs_depth_error_median + gs_mapping_loss_outlier (no sort).
     fused_inputs : transform_to_frame + activations by gs_activate_* (csrc/activate.hip).
     accumulate_grads (with fused_inputs, for `loss.backward()` over a batch of keyframes): the activation backward ADDS its gradients to
                  the four per-Gaussian parameters' .grad in the kernel instead of handing them to autograd's accumulation passes; gradients
@@ -429,7 +479,7 @@ def get_loss(params, curr_data, variables, iter_time_idx, loss_weights, use_sil_
         m2d = torch.empty_like(params["means3D"], requires_grad=True)      # gradient carrier only (see fused_rendervar)
         # seen + the running max radius are written by the render's per-Gaussian kernel where the tensors allow it
         mx = variables["max_2D_radius"]
-        stats_in_render = not tracking and fused_loss and use_l1 and not ignore_outlier_depth_loss and mx.dtype == torch.float32 \
+        stats_in_render = not tracking and fused_loss and use_l1 and mx.dtype == torch.float32 \
             and mx.is_contiguous() and mx.device == params["means3D"].device and mx.numel() == params["means3D"].shape[0]
         seen = torch.empty(mx.numel(), dtype=torch.bool, device=mx.device) if stats_in_render else None
         im, radius, depth, _sil, depth_sq = render_rgbd_raw(curr_data["cam"], params["means3D"], m2d, params["logit_opacities"],
@@ -439,8 +489,8 @@ def get_loss(params, curr_data, variables, iter_time_idx, loss_weights, use_sil_
                                                              visibility=(mx, seen) if stats_in_render else None, camera=cam,
                                                              gaussians_grad=not tracking)
         variables["means2D"] = m2d
-        if fused_loss and use_l1 and not ignore_outlier_depth_loss and not tracking:
-            loss, weighted = fused_mapping_loss(im, depth, depth_sq, curr_data["im"], curr_data["depth"], loss_weights)
+        if fused_loss and use_l1 and not tracking:
+            loss, weighted = fused_mapping_loss(im, depth, depth_sq, curr_data["im"], curr_data["depth"], loss_weights, ignore_outlier_depth_loss)
             if stats_in_render:
                 variables["seen"] = seen
             else:
@@ -471,8 +521,8 @@ def get_loss(params, curr_data, variables, iter_time_idx, loss_weights, use_sil_
         depth_sq = depth_sil[2].unsqueeze(0)
     if rendervar is not None:
         variables["means2D"] = rendervar["means2D"]      # densification reads the colour pass' gradient only
-    if fused_loss and use_l1 and not ignore_outlier_depth_loss and not tracking:
-        loss, weighted = fused_mapping_loss(im, depth, depth_sq, curr_data["im"], curr_data["depth"], loss_weights)
+    if fused_loss and use_l1 and not tracking:
+        loss, weighted = fused_mapping_loss(im, depth, depth_sq, curr_data["im"], curr_data["depth"], loss_weights, ignore_outlier_depth_loss)
         from . import optim as O
         variables["seen"] = O.visibility_stats(radius, variables["max_2D_radius"])      # one launch: seen + max radius in place
         return loss, variables, weighted
@@ -523,14 +573,14 @@ class _DirectCtx:
 
 
 @torch.no_grad()
-def mapping_iteration(params, curr_data, variables, iter_time_idx, loss_weights, optimizer, pose7=None):
+def mapping_iteration(params, curr_data, variables, iter_time_idx, loss_weights, optimizer, pose7=None, ignore_outlier_depth_loss=False):
     """One whole mapping iteration of the reference's loop (src/mapper/splatam/__init__.py:470-480: get_loss, loss.backward(), optimizer.step(),
     optimizer.zero_grad) WITHOUT autograd: the four library calls of the fused path -- per-Gaussian forward on the parameters, render,
     fused loss, backward with the Adam step inside -- are issued one after the other by the very code get_loss(fused=True, fused_loss=True,
     fused_preprocess=True, fused_adam=optimizer) + loss.backward() runs, minus the graph, the engine's thread hand-over and the Function
     boundaries.  At the reference's 256 x 256 frames the iteration is bound by exactly that host time (GPU busy ~230 us, wall ~320 us through
     autograd).  Same parameters, moments and statistics afterwards.  For iterations without a prune / densify event (optim.densify_event /
-    prune_event) and the default loss options (use_l1, no outlier rejection, no bundle adjustment).
+    prune_event) and the loss options use_l1 without bundle adjustment; ignore_outlier_depth_loss as in get_loss(fused_loss=True).
     -> (loss, variables, {'im', 'depth', 'loss'}); variables['means2D'].grad, ['seen'] and ['max_2D_radius'] are updated as get_loss +
     backward leave them."""
     from . import rasterizer as R
@@ -553,7 +603,8 @@ def mapping_iteration(params, curr_data, variables, iter_time_idx, loss_weights,
         rctx, means, m2d, shs, colors, params["logit_opacities"], params["log_scales"], params["unnorm_rotations"], None, curr_data["cam"], True,
         (pose7, iso, False, (mx, seen), optimizer))
     lctx = _DirectCtx()
-    loss, parts = _FusedMappingLoss.forward(lctx, im, depth, depth_sq, curr_data["im"], curr_data["depth"], loss_weights["im"], loss_weights["depth"])
+    loss, parts = _FusedMappingLoss.forward(lctx, im, depth, depth_sq, curr_data["im"], curr_data["depth"], loss_weights["im"], loss_weights["depth"],
+                                             bool(ignore_outlier_depth_loss))
     grads = lctx.saved_tensors[0]                               # dL/dim [3,H,W] and dL/ddepth [1,H,W] for dL/dloss = 1
     out = R._RasterizeGaussians.backward(rctx, grads[:3], None, grads[3:], None, None)
     m2d.grad = out[1]
@@ -612,6 +663,9 @@ class TrackingState:
         self.grads = torch.empty(4, H, W, dtype=torch.float32, device=dev)          # dL/dim [3,H,W], dL/ddepth [1,H,W]
         self.loss_rows = torch.empty(int(lib.gs_tracking_loss_scratch_bytes(W, H)), dtype=torch.uint8, device=dev)
         self.pose_rows = torch.empty(int(lib.gs_pose_grad_scratch_bytes(P)), dtype=torch.uint8, device=dev)
+        # ignore_outlier_depth_loss: the select's histograms and the median of the iteration's depth error (a device scalar, never read by the host)
+        self.median_scratch = torch.empty(int(lib.gs_depth_error_median_scratch_bytes(W, H)), dtype=torch.uint8, device=dev)
+        self.median = torch.empty(1, dtype=torch.float32, device=dev)
         self.step = 0
 
     def begin(self, params, time_idx):
@@ -665,14 +719,14 @@ def tracking_iteration(params, curr_data, variables, time_idx, tracking_cfg, sta
     gs_tracking_loss (value and gradient images), the pose-only backward (gs_render_backward_raw_pose_dev), gs_tracking_step (loss and pose
     reductions, F.normalize's Jacobian, torch.optim.Adam on params['cam_*'][..., time_idx] in place, the best candidate).  `state`: a
     TrackingState of this frame (begin() called); history_row: an optional [10] device row {loss, depth, im, the 7 post-step values}.
-    use_l1 with ignore_outlier_depth_loss=False only (the outlier rule needs a median: track_frame(fused=False))."""
+    With cfg['ignore_outlier_depth_loss']: render, gs_depth_error_median, gs_tracking_loss_outlier (the mask ANDed with err < 10 median, the
+    colour mask always the tiled mask), then the same backward and step.  use_l1 only."""
     import ctypes as C
     from . import _lib
     from . import rasterizer as R
     cfg = tracking_cfg
-    if not cfg.get("use_l1", True) or cfg.get("ignore_outlier_depth_loss", False):
-        raise Exception("tracking_iteration: use_l1 without ignore_outlier_depth_loss only (the outlier rule's median stays on the torch loss: "
-                        "track_frame(fused=False))")
+    if not cfg.get("use_l1", True):
+        raise Exception("tracking_iteration: use_l1 only (track_frame(fused=False) runs the torch loss)")
     lib = _lib.get()
     rctx, (im, _radius, depth, sil, depth_sq) = tracking_render(params, curr_data, variables, time_idx)
     dev = state.device
@@ -682,8 +736,14 @@ def tracking_iteration(params, curr_data, variables, time_idx, tracking_cfg, sta
     use_sil = bool(cfg["use_sil_for_loss"])
     gt_im, gt_d = R._f32(curr_data["im"], dev), R._f32(curr_data["depth"], dev)
     g = state.grads
-    _lib.check(lib.gs_tracking_loss(state.W, state.H, p(im), p(gt_im), p(depth), p(depth_sq), p(gt_d), p(sil if use_sil else None), 1 if use_sil else 0,
-                                    float(cfg["sil_thres"]), float(lw["im"]), float(lw["depth"]), p(g[:3]), p(g[3:]), p(state.loss_rows), None, st))
+    if cfg.get("ignore_outlier_depth_loss", False):
+        depth_error_median(depth, gt_d, out=state.median, scratch=state.median_scratch)
+        _lib.check(lib.gs_tracking_loss_outlier(state.W, state.H, p(im), p(gt_im), p(depth), p(depth_sq), p(gt_d), p(sil if use_sil else None),
+                                                1 if use_sil else 0, float(cfg["sil_thres"]), float(lw["im"]), float(lw["depth"]), p(g[:3]), p(g[3:]),
+                                                p(state.loss_rows), None, p(state.median), st))
+    else:
+        _lib.check(lib.gs_tracking_loss(state.W, state.H, p(im), p(gt_im), p(depth), p(depth_sq), p(gt_d), p(sil if use_sil else None), 1 if use_sil else 0,
+                                        float(cfg["sil_thres"]), float(lw["im"]), float(lw["depth"]), p(g[:3]), p(g[3:]), p(state.loss_rows), None, st))
     R.backward_pose_dev(rctx, g[:3], g[3:], state.pose_rows)
     rots, trans = _pose_columns(params)
     state.step += 1

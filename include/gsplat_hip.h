@@ -181,7 +181,7 @@ const char* gs_version(void);
 /* Integer version of THIS binary interface: bumped whenever an entry point's argument list or a published record layout changes (e.g.
  * the seed argument of gs_densify_children, the 40-byte SH Jacobian record).  A host binding compares it with the GS_ABI_VERSION it was
  * written against before the first call, so that a stale prebuilt library fails at load time instead of misreading its arguments. */
-#define GS_ABI_VERSION 16
+#define GS_ABI_VERSION 17
 int32_t gs_abi_version(void);
 
 /* Optional per-stage timing (hipEvents recorded on the caller's stream around each stage's launches).
@@ -393,12 +393,41 @@ int gs_mapping_loss(int32_t width, int32_t height, const float* im, const float*
                     const float* depth_sq, const float* gt_depth, float w_im, float w_depth, float* losses,
                     float* dL_dim, float* dL_ddepth, void* scratch, int64_t persistent_call, gs_stream_t stream);
 
+/* ---- ignore_outlier_depth_loss (src/mapper/splatam/splatam.py:220-228), all in fp32 without FMA contraction ----
+ *   err    = |gt_depth - depth| * (gt_depth > 0)            (the product: NaN * 0 and inf * 0 are NaN, as in torch)
+ *   median = torch.median(err): element (n - 1) / 2 of the sorted errors of ALL n = width * height pixels -- unmeasured pixels count as zeros,
+ *            the LOWER of two middle values -- and NaN as soon as one err is NaN
+ *   keep   = err < 10 * median                              (strict; the product rounded to fp32 once)
+ * gs_depth_error_median writes the median to d_median (DEVICE, 1 float), bit-identical to torch's and from call to call: an exact radix
+ * select in three histogram passes (11 + 11 + 10 bits of the error's bit pattern), each ONE launch over a grid of workgroups (LDS histogram,
+ * then integer atomics into the pass' global histogram) and a one-workgroup launch that picks the value.  The workgroups of a pass re-derive
+ * the prefix of the pass before from its finished histogram: no workgroup waits for another inside a launch.  scratch:
+ * gs_depth_error_median_scratch_bytes bytes, cleared by a memset inside the call.  The grid is a function of width * height only
+ * (gs_depth_error_median_workgroups reports it); gs_depth_error_median_grid is the same call with the grid given, for tests and
+ * measurements (workgroups = 1: a single workgroup; 0: the automatic grid; at most 1024).  No state is kept between calls.
+ * The _outlier forms of the two losses take that scalar: their depth mask is the plain mask AND keep.  A median of 0 (half of the pixels
+ * unmeasured or exact) or NaN keeps nothing: gs_mapping_loss_outlier then gives a NaN depth term and loss (the mean of nothing), dL_ddepth all
+ * zero and the usual dL_dim; gs_tracking_loss_outlier gives zero sums and zero gradient images.  In gs_tracking_loss_outlier the colour mask
+ * is always the mask tiled to 3 channels (splatam.py:242), with or without use_sil_for_loss.  No gradient passes through the median.
+ * Everything else -- arguments, scratch protocol, row layout -- is gs_mapping_loss' / gs_tracking_loss'. */
+uint64_t gs_depth_error_median_scratch_bytes(int32_t width, int32_t height);
+int gs_depth_error_median(int32_t width, int32_t height, const float* depth, const float* gt_depth, void* scratch, float* d_median,
+                          gs_stream_t stream);
+int gs_depth_error_median_grid(int32_t width, int32_t height, const float* depth, const float* gt_depth, void* scratch, float* d_median,
+                               int32_t workgroups, gs_stream_t stream);
+int32_t gs_depth_error_median_workgroups(int32_t width, int32_t height);
+int gs_mapping_loss_outlier(int32_t width, int32_t height, const float* im, const float* gt_im, const float* depth,
+                            const float* depth_sq, const float* gt_depth, float w_im, float w_depth, float* losses,
+                            float* dL_dim, float* dL_ddepth, void* scratch, int64_t persistent_call, const float* d_median, gs_stream_t stream);
+
 /* ---- Camera tracking on the device (SplaTAM's per-frame pose optimisation; tracking loss src/mapper/splatam/splatam.py:220-249) ----
  * One iteration, no host round trip beyond the render's counters:
  *   gs_preprocess_forward_raw_dev -> gs_render_forward -> gs_tracking_loss -> gs_render_backward_raw_pose_dev -> gs_tracking_step
  * The pose lives in the caller's parameter tensors cam_unnorm_rots [1,4,T] and cam_trans [1,3,T] (contiguous fp32, DEVICE): column time_idx
  * (stride num_frames = T) is read in place by the kernels, the quaternion normalised as F.normalize does (x / max(|x|, 1e-12)), and the step
- * updates that column in place.  What stays on torch: ignore_outlier_depth_loss (a median), and tracking on the activation path. */
+ * updates that column in place.  With ignore_outlier_depth_loss the iteration is
+ *   ... -> gs_render_forward -> gs_depth_error_median -> gs_tracking_loss_outlier -> gs_render_backward_raw_pose_dev -> gs_tracking_step
+ * (same rows, same step).  What stays on torch: use_l1 = False, and tracking on the activation path. */
 
 /* Tracking loss, value and gradient in one pass (tracking=True, use_l1=True):
  *   mask  = (gt_depth > 0) & !isnan(depth) & !isnan(depth_sq - depth^2), & (silhouette > sil_thres) when use_sil_for_loss
@@ -412,6 +441,10 @@ uint64_t gs_tracking_loss_scratch_bytes(int32_t width, int32_t height);
 int gs_tracking_loss(int32_t width, int32_t height, const float* im, const float* gt_im, const float* depth, const float* depth_sq,
                      const float* gt_depth, const float* silhouette, int32_t use_sil_for_loss, float sil_thres, float w_im, float w_depth,
                      float* dL_dim, float* dL_ddepth, void* loss_rows, float* losses, gs_stream_t stream);
+/* the same with the outlier rule (see gs_depth_error_median above) */
+int gs_tracking_loss_outlier(int32_t width, int32_t height, const float* im, const float* gt_im, const float* depth, const float* depth_sq,
+                             const float* gt_depth, const float* silhouette, int32_t use_sil_for_loss, float sil_thres, float w_im, float w_depth,
+                             float* dL_dim, float* dL_ddepth, void* loss_rows, float* losses, const float* d_median, gs_stream_t stream);
 
 /* gs_preprocess_forward_raw with the pose read from device memory: cam_unnorm_rots[0, :, time_idx], cam_trans[0, :, time_idx] in place of
  * h_pose7 (everything else, the visibility statistics included, as gs_preprocess_forward_raw). */
