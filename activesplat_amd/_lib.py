@@ -62,7 +62,7 @@ SORT_AUTO, SORT_TILE_LDS, SORT_RADIX = 0, 1, 2
 
 # every symbol include/gsplat_hip.h declares (tests check the library exports all of them)
 #: the GS_ABI_VERSION of include/gsplat_hip.h this binding was written against (checked when a library is bound)
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 SYMBOLS = ("gs_abi_version", "gs_geom_layout", "gs_image_layout", "gs_bin_layout", "gs_backward_scratch_bytes", "gs_last_error",
            "gs_version", "gs_set_sort_path", "gs_set_forward_segments", "gs_set_half_quadrants", "gs_set_backward_chain", "gs_set_backward_chain_tickets", "gs_set_backward_chain_polls", "gs_async_status_word", "gs_async_status_clear", "gs_recorded_cut", "gs_set_backward_segments", "gs_preprocess_forward", "gs_preprocess_forward_raw", "gs_render_forward", "gs_render_backward", "gs_render_backward_raw", "gs_render_backward_raw_adam", "gs_adam_step", "gs_adam_step_multi",
@@ -77,7 +77,8 @@ SYMBOLS = ("gs_abi_version", "gs_geom_layout", "gs_image_layout", "gs_bin_layout
            "gs_preprocess_forward_topdown", "gs_render_forward_topdown", "gs_grid_dbscan_layout", "gs_grid_dbscan", "gs_high_loss_grid",
            "gs_cluster_hulls_layout", "gs_cluster_hulls",
            "gs_depth_error_median_scratch_bytes", "gs_depth_error_median", "gs_depth_error_median_grid", "gs_depth_error_median_workgroups",
-           "gs_mapping_loss_outlier", "gs_tracking_loss_outlier")
+           "gs_mapping_loss_outlier", "gs_tracking_loss_outlier",
+           "gs_depth_cloud", "gs_cloud_nearest_scratch_bytes", "gs_cloud_nearest", "gs_completion_row_scratch_bytes", "gs_completion_row")
 
 
 def _bind(lib):
@@ -170,6 +171,19 @@ def _bind(lib):
     lib.gs_render_backward_raw_pose_dev.argtypes = [C.POINTER(GsCamera), i32, i64] + [vp] * 6 + [vp, vp, i64, i64, i32] + [vp] * 7 + \
         [vp, i32, i32, vp, vp, vp]
     lib.gs_render_backward_raw_pose_dev.restype = C.c_int
+    # the completion / accuracy judge: (width, height, depth, h_intrinsics4, h_c2w12, points, valid, stream)
+    lib.gs_depth_cloud.argtypes = [i32, i32, vp, C.POINTER(f32), C.POINTER(f32), vp, vp, vp]
+    lib.gs_depth_cloud.restype = C.c_int
+    lib.gs_cloud_nearest_scratch_bytes.argtypes = [i64, i64]
+    lib.gs_cloud_nearest_scratch_bytes.restype = C.c_uint64
+    # (n_query, query, query_valid, n_points, points, points_valid, flags, out, scratch, stream)
+    lib.gs_cloud_nearest.argtypes = [i64, vp, vp, i64, vp, vp, i32, vp, vp, vp]
+    lib.gs_cloud_nearest.restype = C.c_int
+    lib.gs_completion_row_scratch_bytes.argtypes = []
+    lib.gs_completion_row_scratch_bytes.restype = C.c_uint64
+    # (n_samples, min_dist, n_acc, acc_dist, acc_valid, path_length, row6, scratch, stream)
+    lib.gs_completion_row.argtypes = [i64, vp, i64, vp, vp, C.c_double, vp, vp, vp]
+    lib.gs_completion_row.restype = C.c_int
     lib.gs_tracking_loss_scratch_bytes.argtypes = [i32, i32]
     lib.gs_tracking_loss_scratch_bytes.restype = C.c_uint64
     lib.gs_tracking_loss.argtypes = [i32, i32] + [vp] * 6 + [i32, f32, f32, f32] + [vp] * 4 + [vp]

@@ -1270,4 +1270,54 @@ int gs_keyframe_overlap(int32_t n_pts, const float* pts_world, int32_t n_keyfram
     return GS_OK;
 }
 
+int gs_depth_cloud(int32_t width, int32_t height, const float* depth, const float* h_intrinsics4, const float* h_c2w12, float* points,
+                   uint8_t* valid, gs_stream_t stream)
+{
+    if (width < 1 || height < 1 || width > 16384 || height > 16384)
+        return fail(GS_EINVAL, "gs_depth_cloud: image size out of range (1 <= width, height <= 16384)");
+    if (!depth || !h_intrinsics4 || !h_c2w12 || !points || !valid) return fail(GS_EINVAL, "gs_depth_cloud: null pointer");
+    // (written so that a NaN fails it)
+    if (!(fabsf(h_intrinsics4[0]) > 0.0f) || !(fabsf(h_intrinsics4[1]) > 0.0f))
+        return fail(GS_EINVAL, "gs_depth_cloud: fx and fy must not be zero");
+    hipError_t e = gs::launch_depth_cloud(width, height, depth, h_intrinsics4, h_c2w12, points, valid, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_depth_cloud: %s", hipGetErrorString(e));
+    return GS_OK;
+}
+
+static bool nearest_size_ok(int64_t n) { return n >= 0 && n <= ((int64_t)1 << 30); }
+
+uint64_t gs_cloud_nearest_scratch_bytes(int64_t n_query, int64_t n_points)
+{
+    if (!nearest_size_ok(n_query) || !nearest_size_ok(n_points)) return 0;
+    return align_up(gs::cloud_nearest_scratch_bytes(n_query, n_points) + 4);
+}
+
+int gs_cloud_nearest(int64_t n_query, const float* query, const uint8_t* query_valid, int64_t n_points, const float* points,
+                     const uint8_t* points_valid, int32_t flags, float* out, void* scratch, gs_stream_t stream)
+{
+    if (!nearest_size_ok(n_query) || !nearest_size_ok(n_points))
+        return fail(GS_EINVAL, "gs_cloud_nearest: size out of range (0 <= n_query, n_points <= 2^30)");
+    if (flags & ~(GS_NEAREST_ACCUMULATE | GS_NEAREST_ROOT)) return fail(GS_EINVAL, "gs_cloud_nearest: unknown flag");
+    if (n_query == 0) return GS_OK;
+    if (!query || !out || !scratch || (n_points > 0 && !points) || ((uintptr_t)scratch & 3))
+        return fail(GS_EINVAL, "gs_cloud_nearest: null pointer (only query_valid and points_valid may be null) or scratch not 4-byte aligned");
+    hipError_t e = gs::launch_cloud_nearest(n_query, query, query_valid, n_points, points, points_valid, flags, out, scratch, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_cloud_nearest: %s", hipGetErrorString(e));
+    return GS_OK;
+}
+
+uint64_t gs_completion_row_scratch_bytes(void) { return align_up(gs::completion_row_scratch_bytes()); }
+
+int gs_completion_row(int64_t n_samples, const float* min_dist, int64_t n_acc, const float* acc_dist, const uint8_t* acc_valid,
+                      double path_length, double* row6, void* scratch, gs_stream_t stream)
+{
+    if (n_samples < 1 || !nearest_size_ok(n_samples) || !nearest_size_ok(n_acc))
+        return fail(GS_EINVAL, "gs_completion_row: size out of range (1 <= n_samples <= 2^30, 0 <= n_acc <= 2^30)");
+    if (!min_dist || !row6 || !scratch || (n_acc > 0 && !acc_dist) || ((uintptr_t)scratch & 7) || ((uintptr_t)row6 & 7))
+        return fail(GS_EINVAL, "gs_completion_row: null pointer (only acc_valid may be null), or scratch / row6 not 8-byte aligned");
+    hipError_t e = gs::launch_completion_row(n_samples, min_dist, n_acc, acc_dist, acc_valid, path_length, row6, scratch, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_completion_row: %s", hipGetErrorString(e));
+    return GS_OK;
+}
+
 }  // extern "C"

@@ -199,4 +199,245 @@ hipError_t launch_keyframe_overlap(int n_pts, const float* pts, int n_kf, const 
     return hipGetLastError();
 }
 
+// ---- completion / accuracy judge (scripts/judges/eval_actions.py:33-40,139-152) ------------------------------------------------------
+// The reference builds two KD-trees per frame -- one over the frame's back-projected cloud, queried with the 200 000 mesh samples, one over the
+// samples, queried with the cloud -- keeps two running minima per sample and writes a row of six means per frame.  Here: the back-projection
+// (rgbd_to_pointcloud, src/utils/gui_utils.py:96-125, restated in include/gsplat_hip.h), an exact brute-force nearest-distance kernel for both
+// directions, and a fixed-order fp64 reduction of the row.  No atomics anywhere: a min is exact, the sums are trees, two calls give the same bits.
+struct CloudCam { float fx, fy, cx, cy; float c2w[12]; int W; };
+
+__global__ __launch_bounds__(kBlock) void depth_cloud_kernel(CloudCam c, int64_t npix, const float* __restrict__ depth, float* __restrict__ points,
+                                                              uint8_t* __restrict__ valid)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= npix) return;
+    // the uint16 millimetre image the reference hands to Open3D; written so that a NaN fails the test
+    const float q = truncf(depth[i] * 1000.0f);
+    const bool ok = q >= 1.0f && q <= 65535.0f;
+    float X = 0.0f, Y = 0.0f, Z = 0.0f;
+    if (ok) {
+        const int u = (int)(i % c.W), v = (int)(i / c.W);
+        const float z = q / 1000.0f;
+        const float x = ((float)u - c.cx) * z / c.fx;
+        const float y = ((float)v - c.cy) * z / c.fy;
+        X = c.c2w[0] * x + c.c2w[1] * y + c.c2w[2] * z + c.c2w[3];
+        Y = c.c2w[4] * x + c.c2w[5] * y + c.c2w[6] * z + c.c2w[7];
+        Z = c.c2w[8] * x + c.c2w[9] * y + c.c2w[10] * z + c.c2w[11];
+    }
+    points[3 * i + 0] = X; points[3 * i + 1] = Y; points[3 * i + 2] = Z;
+    valid[i] = ok ? 1 : 0;
+}
+
+hipError_t launch_depth_cloud(int W, int H, const float* depth, const float* k4, const float* c2w12, float* points, uint8_t* valid, hipStream_t st)
+{
+    const int64_t n = (int64_t)W * H;
+    CloudCam c;
+    c.fx = k4[0]; c.fy = k4[1]; c.cx = k4[2]; c.cy = k4[3]; c.W = W;
+    for (int i = 0; i < 12; ++i) c.c2w[i] = c2w12[i];
+    hipLaunchKernelGGL(depth_cloud_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, c, n, depth, points, valid);
+    return hipGetLastError();
+}
+
+// Nearest squared distance, brute force, N-body style: a lane keeps kNnQ queries and their running minima in registers, the workgroup stages
+// kNnTile streamed points in LDS and every lane reads each of them once (one broadcast ds_read_b128 per point and wavefront) for its kNnQ
+// queries: seven vector operations per pair (three differences, a product, two FMAs, a min) and nothing else in the loop -- and the first six of
+// them are packed fp32 instructions that serve two queries each (the loop compiles to 3 v_pk_add_f32, 1 v_pk_mul_f32, 2 v_pk_fma_f32 and one
+// v_min3_f32 per two pairs).  Written with the vector type on purpose: the scalar form is re-associated by the SLP vectoriser into a mix of packed
+// and plain instructions with register moves in the loop.  A packed instruction takes the time of two plain ones here, so this form and a
+// purely scalar one (measured with packed fp32 switched off for the kernel) run within 1.5 % of each other (profiles/completion_judge.txt).  The grid is
+// (blocks of kNnGroup queries) x (pieces of the streamed set): the pieces are sized so that both of the judge's directions -- 200 000 queries
+// against 16 384 points, and the reverse -- put about kNnWorkgroups workgroups on the chip: seven per CU, what the kernel's 72 registers let a CU
+// hold at once, so that no workgroup waits for another to finish.  Every workgroup writes the minima
+// of its piece to partial[piece][query]; the combine kernel takes the min over the pieces, which is exact in any order.
+// The arithmetic is the difference form: |q|^2 + |p|^2 - 2 q.p cancels at room coordinates (in fp32 it is wrong by more than the distance itself at
+// centimetre distances in a 6 m room).
+constexpr int kNnQ = 8;
+constexpr int kNnTile = 256;
+constexpr int kNnGroup = kBlock * kNnQ;
+constexpr int kNnWorkgroups = 7 * 256;
+constexpr int kNnMaxPieces = 2048;
+
+typedef float nn_f2 __attribute__((vector_size(8)));
+
+struct NnPlan { int64_t qblocks, pieces, chunk; };
+static NnPlan nn_plan(int64_t Q, int64_t M)
+{
+    NnPlan p;
+    p.qblocks = (Q + kNnGroup - 1) / kNnGroup;
+    int64_t pieces = p.qblocks > 0 ? kNnWorkgroups / p.qblocks : 1;
+    const int64_t most = (M + kNnTile - 1) / kNnTile;           // no piece shorter than one tile
+    if (pieces > most) pieces = most;
+    if (pieces > kNnMaxPieces) pieces = kNnMaxPieces;
+    if (pieces < 1) pieces = 1;
+    p.chunk = (M + pieces - 1) / pieces;
+    p.pieces = p.chunk > 0 ? (M + p.chunk - 1) / p.chunk : 1;   // (pieces that would start beyond M are not launched)
+    if (p.pieces < 1) p.pieces = 1;
+    return p;
+}
+
+uint64_t cloud_nearest_scratch_bytes(int64_t Q, int64_t M)
+{
+    const NnPlan p = nn_plan(Q, M);
+    return (uint64_t)p.pieces * (uint64_t)Q * 4u;
+}
+
+__global__ __launch_bounds__(kBlock) void cloud_nearest_kernel(int64_t Q, const float* __restrict__ query, int64_t M, const float* __restrict__ points,
+                                                                const uint8_t* __restrict__ pvalid, int64_t chunk, float* __restrict__ partial)
+{
+    __shared__ float4 s_pt[kNnTile];
+    const float inf = __uint_as_float(0x7f800000u);
+    const int64_t q0 = (int64_t)blockIdx.x * kNnGroup + threadIdx.x;
+    // two queries per register pair: the differences, the product and the two FMAs of a pair of queries are one packed fp32 instruction each
+    nn_f2 qx[kNnQ / 2], qy[kNnQ / 2], qz[kNnQ / 2];
+    float best[kNnQ];
+#pragma unroll
+    for (int j = 0; j < kNnQ; ++j) {
+        const int64_t q = q0 + (int64_t)j * kBlock;
+        const bool in = q < Q;
+        qx[j >> 1][j & 1] = in ? query[3 * q + 0] : 0.0f;
+        qy[j >> 1][j & 1] = in ? query[3 * q + 1] : 0.0f;
+        qz[j >> 1][j & 1] = in ? query[3 * q + 2] : 0.0f;
+        best[j] = inf;
+    }
+    const int64_t p0 = (int64_t)blockIdx.y * chunk;
+    const int64_t p1 = p0 + chunk < M ? p0 + chunk : M;
+    for (int64_t base = p0; base < p1; base += kNnTile) {
+        const int n = p1 - base < kNnTile ? (int)(p1 - base) : kNnTile;
+        __syncthreads();                                        // the tile before this one has been read by every wavefront
+        if ((int)threadIdx.x < n) {
+            const int64_t p = base + threadIdx.x;
+            // an invalid point sits at infinity: its distance to any finite query is inf, and a NaN (an infinite query) never wins an fminf
+            const bool ok = pvalid == nullptr || pvalid[p] != 0;
+            s_pt[threadIdx.x] = ok ? make_float4(points[3 * p + 0], points[3 * p + 1], points[3 * p + 2], 0.0f) : make_float4(inf, inf, inf, 0.0f);
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int k = 0; k < n; ++k) {
+            const float4 p = s_pt[k];
+#pragma unroll
+            for (int j = 0; j < kNnQ / 2; ++j) {
+                const nn_f2 dx = qx[j] - p.x, dy = qy[j] - p.y, dz = qz[j] - p.z;
+                const nn_f2 d = dx * dx + dy * dy + dz * dz;
+                best[2 * j] = fminf(best[2 * j], d[0]);
+                best[2 * j + 1] = fminf(best[2 * j + 1], d[1]);
+            }
+        }
+    }
+    float* row = partial + (int64_t)blockIdx.y * Q;
+#pragma unroll
+    for (int j = 0; j < kNnQ; ++j) {
+        const int64_t q = q0 + (int64_t)j * kBlock;
+        if (q < Q) row[q] = best[j];
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void cloud_nearest_combine_kernel(int64_t Q, int pieces, const float* __restrict__ partial,
+                                                                        const uint8_t* __restrict__ qvalid, int flags, float* __restrict__ out)
+{
+    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (q >= Q) return;
+    if (qvalid != nullptr && qvalid[q] == 0) return;            // an invalid query's output is left as it was
+    float m = partial[q];
+    for (int s = 1; s < pieces; ++s) m = fminf(m, partial[(int64_t)s * Q + q]);
+    if (flags & GS_NEAREST_ROOT) m = sqrtf(m);
+    if (flags & GS_NEAREST_ACCUMULATE) m = fminf(out[q], m);
+    out[q] = m;
+}
+
+hipError_t launch_cloud_nearest(int64_t Q, const float* query, const uint8_t* qvalid, int64_t M, const float* points, const uint8_t* pvalid,
+                                int flags, float* out, void* scratch, hipStream_t st)
+{
+    if (Q <= 0) return hipSuccess;
+    const NnPlan p = nn_plan(Q, M);
+    float* partial = (float*)scratch;
+    hipLaunchKernelGGL(cloud_nearest_kernel, dim3((unsigned)p.qblocks, (unsigned)p.pieces), dim3(kBlock), 0, st, Q, query, M, points, pvalid, p.chunk,
+                       partial);
+    hipLaunchKernelGGL(cloud_nearest_combine_kernel, dim3((unsigned)((Q + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, Q, (int)p.pieces,
+                       (const float*)partial, qvalid, flags, out);
+    return hipGetLastError();
+}
+
+// The judge's row (eval_actions.py:142-149).  Partial sums in fp64: every thread adds its elements in index order (stride = the grid), a pairwise
+// tree over the workgroup's kBlock partials in LDS, one record per workgroup; a second single-workgroup launch runs the same tree over the records.
+// The grid depends on the sizes alone, so the order of every addition is fixed.
+constexpr int kRowVals = 5;                 // sum min(1, d) | count d < 0.05 | sum d | sum of the accuracy distances | their count
+constexpr int kRowStride = 8;               // doubles per record
+constexpr int kRowGridMax = kBlock;         // the second launch reads one record per thread
+
+__device__ __forceinline__ void row_block_tree(double (&a)[kRowVals])
+{
+    __shared__ double s_row[kRowVals][kBlock];
+#pragma unroll
+    for (int k = 0; k < kRowVals; ++k) s_row[k][threadIdx.x] = a[k];
+    __syncthreads();
+    for (int h = kBlock / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) {
+#pragma unroll
+            for (int k = 0; k < kRowVals; ++k) s_row[k][threadIdx.x] += s_row[k][threadIdx.x + h];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < kRowVals; ++k) a[k] = s_row[k][0];
+}
+
+__global__ __launch_bounds__(kBlock) void completion_partial_kernel(int64_t N, const float* __restrict__ min_d, int64_t P, const float* __restrict__ acc_d,
+                                                                     const uint8_t* __restrict__ acc_valid, double* __restrict__ partial)
+{
+    double a[kRowVals] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < N; i += stride) {
+        const float d = min_d[i];
+        a[0] += (double)fminf(d, 1.0f);
+        a[1] += (double)d < 0.05 ? 1.0 : 0.0;                   // the fp32 distance widened, against the double 0.05
+        a[2] += (double)d;
+    }
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < P; i += stride) {
+        if (acc_valid == nullptr || acc_valid[i] != 0) { a[3] += (double)acc_d[i]; a[4] += 1.0; }
+    }
+    row_block_tree(a);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < kRowVals; ++k) partial[(int64_t)blockIdx.x * kRowStride + k] = a[k];
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void completion_finish_kernel(int records, const double* __restrict__ partial, int64_t N, double path_length,
+                                                                    double* __restrict__ row)
+{
+    double a[kRowVals] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if ((int)threadIdx.x < records) {
+#pragma unroll
+        for (int k = 0; k < kRowVals; ++k) a[k] = partial[(int64_t)threadIdx.x * kRowStride + k];
+    }
+    row_block_tree(a);
+    if (threadIdx.x != 0) return;
+    const double n = (double)N;
+    row[0] = a[0] / n;                      // completion error, capped at 1 m
+    row[1] = a[1] / n;                      // completion ratio (min(1, d) < 0.05 iff d < 0.05)
+    row[2] = a[2] / n;                      // ... uncapped: inf while a sample is unseen
+    row[3] = a[1] / n;
+    row[4] = path_length;
+    row[5] = a[3] / a[4];                   // accuracy of this frame; 0 / 0 = NaN for a frame without a valid pixel
+}
+
+static int completion_records(int64_t N, int64_t P)
+{
+    const int64_t most = N > P ? N : P;
+    const int64_t g = (most + 4 * kBlock - 1) / (4 * kBlock);   // at least four elements per thread before another workgroup is worth its launch
+    return g < 1 ? 1 : g > kRowGridMax ? kRowGridMax : (int)g;
+}
+
+uint64_t completion_row_scratch_bytes() { return (uint64_t)kRowGridMax * kRowStride * 8u; }
+
+hipError_t launch_completion_row(int64_t N, const float* min_d, int64_t P, const float* acc_d, const uint8_t* acc_valid, double path_length,
+                                 double* row, void* scratch, hipStream_t st)
+{
+    const int g = completion_records(N, P);
+    double* partial = (double*)scratch;
+    hipLaunchKernelGGL(completion_partial_kernel, dim3(g), dim3(kBlock), 0, st, N, min_d, P, acc_d, acc_valid, partial);
+    hipLaunchKernelGGL(completion_finish_kernel, dim3(1), dim3(kBlock), 0, st, g, (const double*)partial, N, path_length, row);
+    return hipGetLastError();
+}
+
 }  // namespace gs

@@ -878,6 +878,14 @@ hipError_t launch_grow(int W, int H, const float* rd, const float* sil, const fl
                        float* log_scales, uint32_t* d_counts, void* scratch, hipStream_t st);
 hipError_t launch_keyframe_overlap(int n_pts, const float* pts, int n_kf, const float* w2c, const float* k9, int W, int H, int edge,
                                    uint32_t* counts, hipStream_t st);
+// the completion / accuracy judge (grow.hip; the rules: include/gsplat_hip.h, gs_depth_cloud / gs_cloud_nearest / gs_completion_row)
+hipError_t launch_depth_cloud(int W, int H, const float* depth, const float* k4, const float* c2w12, float* points, uint8_t* valid, hipStream_t st);
+uint64_t cloud_nearest_scratch_bytes(int64_t Q, int64_t M);
+hipError_t launch_cloud_nearest(int64_t Q, const float* query, const uint8_t* qvalid, int64_t M, const float* points, const uint8_t* pvalid,
+                                int flags, float* out, void* scratch, hipStream_t st);
+uint64_t completion_row_scratch_bytes();
+hipError_t launch_completion_row(int64_t N, const float* min_d, int64_t P, const float* acc_d, const uint8_t* acc_valid, double path_length,
+                                 double* row, void* scratch, hipStream_t st);
 uint64_t compact_scratch_bytes(int64_t n);
 hipError_t launch_compact_index(int64_t n, const uint8_t* keep, uint32_t* src_index, uint32_t* d_count, void* scratch, hipStream_t st);
 hipError_t launch_gather_rows(int64_t n_out, int row_floats, const uint32_t* src_index, const float* src, float* dst, int64_t n_copy, hipStream_t st);

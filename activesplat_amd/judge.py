@@ -1,0 +1,244 @@
+"""ActiveSplat's own judge on the device: completion ratio / completion error / accuracy per step of a run.
+
+The reference replays a run offline (scripts/judges/eval_actions.py): for every frame it back-projects the sensor depth at the simulator's pose
+(`rgbd_to_pointcloud`, src/utils/gui_utils.py:96-125, depth scale 1000, depth max inf), builds a scipy KD-tree over that cloud and queries it with
+200 000 samples of the ground-truth mesh (:36-37), builds one over the samples and queries it with the cloud (:38-39), keeps two running minima
+per sample that start at 1 and at inf (:67-68, :142-143) and writes one row of six numbers per frame (:144-152).  It needs a process pool over
+all cores to finish.  Here the same answer is three library calls per frame (include/gsplat_hip.h states the rules):
+
+* `depth_cloud`        -- gs_depth_cloud: the back-projection, every pixel with a validity byte, no compaction;
+* `nearest_distances`  -- gs_cloud_nearest: exact brute-force nearest distances in the difference form; the public primitive ("how far is this
+                          point set from that one");
+* `CompletionJudge`    -- the running minima, one gs_completion_row per frame into a device table, nothing read back until `rows()`;
+* `map_distances`      -- the same two directions between the Gaussian map's centres and a point set.  NOT a reference quantity.
+
+The back-projection rule restates what Open3D's create_from_rgbd_image documents; it was NOT run against Open3D (not installed, not a
+dependency).  Frames: points, samples and poses must share one frame.  `SplatMapper.judge` feeds poses relative to frame 0's camera, so its
+samples must be given in that frame; transforming a mesh into it is the caller's work.
+
+There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import rasterizer as R
+
+NEAREST_ACCUMULATE, NEAREST_ROOT = 1, 2          # GS_NEAREST_* of include/gsplat_hip.h
+COLUMNS = ("completion", "completion_ratio", "completion_inf", "completion_ratio_inf", "path_length", "accuracy")   # eval_actions.py:149
+
+
+def _on(t, device):
+    """is tensor t on `device` (an index-less device names the current one of its type)"""
+    return t.device.type == device.type and (device.index is None or t.device.index is None or t.device.index == device.index)
+
+
+def _cloud(t, name, device=None, width=3):
+    """a contiguous fp32 [n, 3] tensor on `device` (the product path: a ROCm device), or an error that names the argument"""
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name} must be a torch tensor, got {type(t).__name__}")
+    if device is not None and not _on(t, device):
+        raise ValueError(f"{name} must be on {device}, got {t.device}")
+    R._require_rocm(t.device)
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, got {t.dtype}")
+    if t.dim() != 2 or t.shape[1] != width:
+        raise ValueError(f"{name} must have shape [n, {width}], got {list(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    return t.detach()
+
+
+def _valid(t, name, n, device):
+    """None, or n validity bytes (bool or uint8, contiguous) on `device`"""
+    if t is None:
+        return None
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name} must be a torch tensor or None, got {type(t).__name__}")
+    if not _on(t, device):
+        raise ValueError(f"{name} must be on {device}, got {t.device}")
+    if t.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"{name} must be uint8 or bool, got {t.dtype}")
+    if t.dim() != 1 or t.shape[0] != n:
+        raise ValueError(f"{name} must have shape [{n}], got {list(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+
+def _nearest(query, query_valid, points, points_valid, flags, out, scratch=None):
+    """gs_cloud_nearest on checked tensors; `scratch` is reused when it is large enough -> the scratch tensor"""
+    lib = _lib.get()
+    Q, M = int(query.shape[0]), int(points.shape[0])
+    need = int(lib.gs_cloud_nearest_scratch_bytes(Q, M))
+    if scratch is None or scratch.numel() < need:
+        scratch = torch.empty(need, dtype=torch.uint8, device=query.device)
+    _lib.check(lib.gs_cloud_nearest(Q, R._ptr(query), R._ptr(query_valid), M, R._ptr(points) if M else None, R._ptr(points_valid), int(flags),
+                                    R._ptr(out), R._ptr(scratch), _lib.stream_ptr(query.device)))
+    return scratch
+
+
+@torch.no_grad()
+def nearest_distances(query, points, query_valid=None, points_valid=None):
+    """For every row of `query` [Q, 3] the distance (not its square) to the nearest row of `points` [M, 3] -> [Q] float32 on the same device.
+    Exact brute force in the difference form, fp32.  `points_valid` [M]: rows with a 0 contribute nothing; `query_valid` [Q]: rows with a 0 get
+    +inf, as does every row when no point is valid.  Inputs: contiguous float32 device tensors.  No host synchronisation."""
+    q = _cloud(query, "query")
+    p = _cloud(points, "points", q.device)
+    qv = _valid(query_valid, "query_valid", q.shape[0], q.device)
+    pv = _valid(points_valid, "points_valid", p.shape[0], q.device)
+    out = torch.full((q.shape[0],), float("inf"), dtype=torch.float32, device=q.device)
+    _nearest(q, qv, p, pv, NEAREST_ROOT, out)
+    return out
+
+
+def _host_floats(a, name, shapes):
+    """a small host array from an array-like or a tensor (a device tensor is copied, which waits for the device: pass host values)"""
+    if torch.is_tensor(a):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a, dtype=np.float64)
+    if a.shape not in shapes:
+        raise ValueError(f"{name} must have shape {' or '.join(str(list(s)) for s in shapes)}, got {list(a.shape)}")
+    return a
+
+
+def _camera(intrinsics, c2w):
+    k = _host_floats(intrinsics, "intrinsics", ((3, 3), (4,)))
+    k4 = np.array([k[0, 0], k[1, 1], k[0, 2], k[1, 2]] if k.shape == (3, 3) else k, dtype=np.float32)
+    m = _host_floats(c2w, "c2w", ((4, 4), (3, 4)))
+    m12 = np.ascontiguousarray(m[:3].reshape(12), dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    return k4, m12, k4.ctypes.data_as(fp), m12.ctypes.data_as(fp)
+
+
+def _depth_image(depth, device=None):
+    if not torch.is_tensor(depth):
+        raise TypeError(f"depth must be a torch tensor, got {type(depth).__name__}")
+    if device is not None and not _on(depth, device):
+        raise ValueError(f"depth must be on {device}, got {depth.device}")
+    R._require_rocm(depth.device)
+    if depth.dtype != torch.float32:
+        raise ValueError(f"depth must be float32, got {depth.dtype}")
+    if depth.dim() == 3 and depth.shape[0] == 1:
+        depth = depth[0]
+    if depth.dim() != 2 or depth.numel() == 0:
+        raise ValueError(f"depth must have shape [H, W] or [1, H, W], got {list(depth.shape)}")
+    if not depth.is_contiguous():
+        raise ValueError("depth must be contiguous")
+    return depth.detach()
+
+
+@torch.no_grad()
+def depth_cloud(depth, intrinsics, c2w):
+    """Back-projection of a depth image [H, W] (float32 metres, device) -> (points [H W, 3] float32, valid [H W] uint8), pixel v * W + u at row
+    v * W + u: q = trunc(depth * 1000) in fp32 (the uint16 millimetre image the reference hands to Open3D), a pixel is valid iff 1 <= q <= 65535
+    (above that range the reference's cast would wrap; dropping is this build's choice), z = q / 1000, x = (u - cx) z / fx, y = (v - cy) z / fy,
+    point = R (x, y, z) + t.  `intrinsics`: 3 x 3 (or fx, fy, cx, cy) and `c2w`: 4 x 4 or 3 x 4 camera-to-world, HOST values.  Not run against
+    Open3D.  No host synchronisation."""
+    d = _depth_image(depth)
+    H, W = int(d.shape[0]), int(d.shape[1])
+    k4, m12, kp, mp = _camera(intrinsics, c2w)
+    points = torch.empty(H * W, 3, dtype=torch.float32, device=d.device)
+    valid = torch.empty(H * W, dtype=torch.uint8, device=d.device)
+    _lib.check(_lib.get().gs_depth_cloud(W, H, R._ptr(d), kp, mp, R._ptr(points), R._ptr(valid), _lib.stream_ptr(d.device)))
+    return points, valid
+
+
+class CompletionJudge:
+    """The running state of eval_actions.py for one run: `samples` [N, 3] (contiguous float32, on `device` when that is given) are the mesh
+    samples; every `add_frame` / `add_points` folds one frame's cloud into the per-sample minimum distance and appends one row
+      (mean min(1, d), share of min(1, d) < 0.05, mean d, share of d < 0.05, path length, mean accuracy distance of the frame)
+    to a table on the device.  The minima start at 1 (`min_distances`) and at inf (`min_distances_inf`), as the reference's two arrays do; one
+    buffer holds both, since min(1, .) of the second is the first at every step.  A frame without a valid pixel leaves the minima alone and
+    its accuracy is NaN (the reference would raise on the empty cloud).  Nothing waits for the device until `rows()`."""
+
+    def __init__(self, samples, device=None):
+        self.samples = _cloud(samples, "samples", torch.device(device) if device is not None else None)
+        if self.samples.shape[0] == 0:
+            raise ValueError("samples must hold at least one point")
+        self.device = self.samples.device
+        lib = _lib.get()
+        self._row_scratch = torch.empty(int(lib.gs_completion_row_scratch_bytes()), dtype=torch.uint8, device=self.device)
+        self._scratch = None
+        self._accuracy = None
+        self.reset()
+
+    def reset(self):
+        """forget every frame: minima back to inf (1 under the cap), no rows"""
+        self.min_distances_inf = torch.full((self.samples.shape[0],), float("inf"), dtype=torch.float32, device=self.device)
+        self._rows = torch.zeros(64, 6, dtype=torch.float64, device=self.device)
+        self.frames = 0
+
+    @property
+    def min_distances(self):
+        """the reference's capped array (starts at 1)"""
+        return self.min_distances_inf.clamp(max=1.0)
+
+    @torch.no_grad()
+    def add_points(self, points, path_length=0.0, valid=None):
+        """one frame given as a world-frame cloud `points` [P, 3] with optional validity bytes `valid` [P]"""
+        p = _cloud(points, "points", self.device)
+        v = _valid(valid, "valid", p.shape[0], self.device)
+        P = int(p.shape[0])
+        if self.frames == self._rows.shape[0]:
+            grown = torch.zeros(2 * self.frames, 6, dtype=torch.float64, device=self.device)
+            grown[:self.frames] = self._rows
+            self._rows = grown
+        if self._accuracy is None or self._accuracy.shape[0] < P:
+            self._accuracy = torch.empty(P, dtype=torch.float32, device=self.device)
+        # completion: every sample against this frame's cloud, folded into the running minimum; accuracy: every point against the samples
+        self._scratch = _nearest(self.samples, None, p, v, NEAREST_ROOT | NEAREST_ACCUMULATE, self.min_distances_inf, self._scratch)
+        if P:
+            self._scratch = _nearest(p, v, self.samples, None, NEAREST_ROOT, self._accuracy, self._scratch)
+        row = self._rows[self.frames]
+        _lib.check(_lib.get().gs_completion_row(int(self.samples.shape[0]), R._ptr(self.min_distances_inf), P, R._ptr(self._accuracy) if P else None,
+                                                R._ptr(v), float(path_length), R._ptr(row), R._ptr(self._row_scratch), _lib.stream_ptr(self.device)))
+        self.frames += 1
+
+    @torch.no_grad()
+    def add_frame(self, depth, intrinsics, c2w, path_length=0.0):
+        """one frame given as the sensor's depth image [H, W] and its camera-to-world pose (see `depth_cloud`)"""
+        points, valid = depth_cloud(_depth_image(depth, self.device), intrinsics, c2w)
+        self.add_points(points, path_length, valid)
+
+    def rows(self):
+        """[frames, 6] float64 on the host, the reference's column order (COLUMNS); ONE copy, which waits for the device"""
+        return self._rows[:self.frames].cpu().numpy()
+
+    def write(self, path):
+        """the reference's file (eval_actions.py:150-152): one line per frame, six values separated by blanks"""
+        with open(path, "w") as f:
+            for r in self.rows():
+                f.write(" ".join(str(float(v)) for v in r) + "\n")
+
+
+@torch.no_grad()
+def map_distances(params, samples, min_opacity=0.5):
+    """How far the Gaussian map is from a point set: one `nearest_distances`-style launch in each direction between `samples` [N, 3] and the
+    centres of the Gaussians with sigmoid(logit_opacities) >= min_opacity -> (mean distance from a sample to its nearest centre, share of the
+    samples within 0.05, mean distance from a kept centre to its nearest sample) as floats (one small copy).  No running state.  THIS BUILD'S
+    quantity: the reference judges the back-projected sensor frames (CompletionJudge), never the map."""
+    s = _cloud(samples, "samples")
+    if s.shape[0] == 0:
+        raise ValueError("samples must hold at least one point")
+    means = _cloud(params["means3D"], "params['means3D']", s.device)
+    logit = params["logit_opacities"].detach()
+    if not _on(logit, s.device) or logit.numel() != means.shape[0]:
+        raise ValueError(f"params['logit_opacities'] must hold one value per Gaussian on {s.device}")
+    keep = (torch.sigmoid(logit.reshape(-1).float()) >= float(min_opacity)).to(torch.uint8)
+    lib = _lib.get()
+    d = torch.full((s.shape[0],), float("inf"), dtype=torch.float32, device=s.device)
+    acc = torch.empty(means.shape[0], dtype=torch.float32, device=s.device)
+    scratch = _nearest(s, None, means, keep, NEAREST_ROOT, d)
+    if means.shape[0]:
+        _nearest(means, keep, s, None, NEAREST_ROOT, acc, scratch)
+    row = torch.zeros(6, dtype=torch.float64, device=s.device)
+    rs = torch.empty(int(lib.gs_completion_row_scratch_bytes()), dtype=torch.uint8, device=s.device)
+    _lib.check(lib.gs_completion_row(int(s.shape[0]), R._ptr(d), int(means.shape[0]), R._ptr(acc) if means.shape[0] else None, R._ptr(keep), 0.0,
+                                     R._ptr(row), R._ptr(rs), _lib.stream_ptr(s.device)))
+    r = row.cpu().numpy()
+    return float(r[2]), float(r[3]), float(r[5])

@@ -24,6 +24,8 @@ habitat).  It reproduces the CALL PATTERN and SCHEDULE of the hot loop, nothing 
                                   device too (visibility.high_loss_grid: the mask and its resize to one pixel per degree in one
                                   launch; visibility.grid_dbscan), and `high_loss_samples_pose_c2w` resolves the look target
                                   (__init__.py:216-250) from one small copy when it is first read
+  every frame, `judge` set      : the completion / accuracy judge of scripts/judges/eval_actions.py on the frame's sensor depth at its
+                                  ground-truth pose (judge.CompletionJudge.add_frame; rows are read when the caller asks for them)
 
 Inputs are already-resized frames (`color [3,H,W]` in 0..1, `depth [1,H,W]` metres, pose relative to frame 0 as
 quaternion (w,x,y,z) + translation of the w2c) -- the cv2 resize / PNG / manifest work of the reference is I/O
@@ -115,6 +117,11 @@ class SplatMapper:
         self.high_loss_grid = None          # float32 [vfov, hfov] of 0 / 1 (high_loss_target=True): the reference's non_presence_depth_mask_cv2 / 255
         self._high_loss_pending = None      # (host w2c or None, device w2c or None, GridClusters) of the most recent frame, until the pose is read
         self._high_loss_pose = None
+        #: a judge.CompletionJudge, or None (the default: nothing changes).  When set, run() hands every frame's sensor depth, the inverse of
+        #: the frame's INPUT pose (the ground-truth pose also when tracking is on: this is what the reference's judge replays) and
+        #: frame.get("path_length", 0.0) to judge.add_frame -- three library calls, no host wait.  The poses are relative to frame 0's
+        #: camera, so the judge's samples must be given in that frame; transforming a mesh into it is the caller's work.
+        self.judge = None
 
     @property
     def last_losses(self):
@@ -180,6 +187,9 @@ class SplatMapper:
         pos_h = torch.as_tensor(np.asarray(frame["position"], dtype=np.float32)).reshape(3).clone()
         self._pose_host[fid] = (quat_h, pos_h)
         quat, pos = quat_h.to(self.device), pos_h.to(self.device)
+        if self.judge is not None:
+            c2w = np.linalg.inv(self._w2c_host(quat_h, pos_h).numpy().astype(np.float64))
+            self.judge.add_frame(depth.reshape(depth.shape[-2], depth.shape[-1]).contiguous(), self._k_host, c2w, float(frame.get("path_length", 0.0)))
         tracked = self._tracking and fid > 0 and self.params is not None
         if tracked:
             # SplaTAM's tracking of this frame: constant-velocity start, then the tracking loop; the frame's own pose only goes to gt_w2c_all_frames

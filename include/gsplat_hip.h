@@ -181,7 +181,7 @@ const char* gs_version(void);
 /* Integer version of THIS binary interface: bumped whenever an entry point's argument list or a published record layout changes (e.g.
  * the seed argument of gs_densify_children, the 40-byte SH Jacobian record).  A host binding compares it with the GS_ABI_VERSION it was
  * written against before the first call, so that a stale prebuilt library fails at load time instead of misreading its arguments. */
-#define GS_ABI_VERSION 17
+#define GS_ABI_VERSION 18
 int32_t gs_abi_version(void);
 
 /* Optional per-stage timing (hipEvents recorded on the caller's stream around each stage's launches).
@@ -690,6 +690,47 @@ int gs_grow_gaussians(int32_t width, int32_t height, const float* render_depth, 
 int gs_keyframe_overlap(int32_t n_pts, const float* pts_world, int32_t n_keyframes, const float* w2c,
                         const float* h_intrinsics9, int32_t width, int32_t height, int32_t edge, uint32_t* counts,
                         gs_stream_t stream);
+
+/* ---- Completion / accuracy judge (ActiveSplat's own figure: scripts/judges/eval_actions.py:33-40,139-152) ----
+ * Per frame the reference back-projects the sensor depth (rgbd_to_pointcloud, src/utils/gui_utils.py:96-125, called with depth scale 1000 and
+ * depth max inf), builds a KD-tree over that cloud and queries it with 200 000 mesh samples, builds one over the samples and queries it with
+ * the cloud, keeps two running minima per sample (starting at 1 and at inf) and writes a row of six means.  The three calls below are those
+ * steps on the device; none of them waits for the host, none uses atomics, and two calls on the same inputs give the same bits.
+ *
+ * gs_depth_cloud: depth [height * width] fp32 metres, DEVICE; h_intrinsics4 = HOST {fx, fy, cx, cy}; h_c2w12 = HOST row-major 3x4
+ * camera-to-world.  Pixel i = v * width + u, all in fp32:
+ *   q = truncf(depth * 1000.0f)                  (the uint16 millimetre image the reference hands to Open3D)
+ *   valid[i] = q >= 1 && q <= 65535              (0, negative and NaN are dropped; so is q > 65535, where the reference's uint16 cast would wrap:
+ *                                                 dropping is THIS build's choice)
+ *   z = q / 1000.0f;  x = (u - cx) * z / fx;  y = (v - cy) * z / fy;  points[i] = R (x, y, z) + t
+ * points fp32 [height * width, 3] (0, 0, 0 where invalid), valid uint8 [height * width]; no compaction.  This restates what Open3D's
+ * create_from_rgbd_image documents; it was NOT run against Open3D.
+ *
+ * gs_cloud_nearest: for every query point the squared distance to the nearest of the n_points streamed points, exact brute force in the
+ * difference form (qx - px)^2 + (qy - py)^2 + (qz - pz)^2, fp32 (not |q|^2 + |p|^2 - 2 q.p, which cancels at room coordinates).  query
+ * [n_query, 3], points [n_points, 3] fp32 DEVICE; query_valid / points_valid: uint8 per row, nullable (null = all valid).  An invalid point
+ * contributes nothing; an invalid query's out[] entry is left untouched.  A query with no valid point gets +inf.  flags: GS_NEAREST_ROOT writes
+ * the distance instead of its square; GS_NEAREST_ACCUMULATE writes min(out[q], value) -- the running minimum of the judge.  The streamed set is
+ * split over workgroups and the partial minima are combined by a second launch (a min is exact in any order); scratch: DEVICE,
+ * gs_cloud_nearest_scratch_bytes(n_query, n_points) bytes, 4-byte aligned.  0 <= n_query, n_points <= 2^30.
+ *
+ * gs_completion_row: min_dist [n_samples] = the running minimum DISTANCES (inf where a sample has not been seen), acc_dist [n_acc] with the
+ * optional acc_valid bytes = this frame's accuracy distances.  Writes six doubles at the DEVICE address row6, the reference's columns:
+ *   0 mean of min(1, d)   1 share of min(1, d) < 0.05   2 mean of d (inf while a sample is unseen)   3 share of d < 0.05
+ *   4 path_length as passed   5 mean of the valid accuracy distances (NaN when there is none: the reference would raise on an empty cloud)
+ * The < 0.05 test is made on the fp32 distance widened to double against the double 0.05 (float32(0.05) is not below it).  Sums in fp64 in a
+ * fixed order: every thread adds its elements in index order, a pairwise tree per workgroup, the same tree over the workgroups' records in a
+ * second launch.  scratch: DEVICE, gs_completion_row_scratch_bytes() bytes, 8-byte aligned.  1 <= n_samples, 0 <= n_acc, both <= 2^30. */
+#define GS_NEAREST_ACCUMULATE 1
+#define GS_NEAREST_ROOT 2
+int gs_depth_cloud(int32_t width, int32_t height, const float* depth, const float* h_intrinsics4, const float* h_c2w12, float* points,
+                   uint8_t* valid, gs_stream_t stream);
+uint64_t gs_cloud_nearest_scratch_bytes(int64_t n_query, int64_t n_points);
+int gs_cloud_nearest(int64_t n_query, const float* query, const uint8_t* query_valid, int64_t n_points, const float* points,
+                     const uint8_t* points_valid, int32_t flags, float* out, void* scratch, gs_stream_t stream);
+uint64_t gs_completion_row_scratch_bytes(void);
+int gs_completion_row(int64_t n_samples, const float* min_dist, int64_t n_acc, const float* acc_dist, const uint8_t* acc_valid,
+                      double path_length, double* row6, void* scratch, gs_stream_t stream);
 
 #ifdef __cplusplus
 }
