@@ -30,7 +30,7 @@ import torch.nn.functional as F
 from .camera import setup_camera
 from .rasterizer import GaussianRasterizationSettings as Camera
 from .rasterizer import GaussianRasterizer as Renderer
-from .rasterizer import render_rgbd, render_rgbd_raw
+from .rasterizer import RawInputs, _DirectCtx, backward_direct, render_rgbd, render_rgbd_raw, render_rgbd_raw_direct
 
 _GAUSSIAN_KEYS = ("means3D", "rgb_colors", "unnorm_rotations", "logit_opacities", "log_scales")
 
@@ -557,21 +557,6 @@ def get_loss(params, curr_data, variables, iter_time_idx, loss_weights, use_sil_
     return loss, variables, weighted
 
 
-class _DirectCtx:
-    """Stands in for an autograd context when the Functions' forward / backward are called directly (mapping_iteration)."""
-    needs_input_grad = (True,) * 8 + (False,) * 3
-    saved_tensors = ()
-
-    def save_for_backward(self, *tensors):
-        self.saved_tensors = tensors
-
-    def mark_non_differentiable(self, *tensors):
-        pass
-
-    def set_materialize_grads(self, value):
-        pass
-
-
 @torch.no_grad()
 def mapping_iteration(params, curr_data, variables, iter_time_idx, loss_weights, optimizer, pose7=None, ignore_outlier_depth_loss=False):
     """One whole mapping iteration of the reference's loop (src/mapper/splatam/__init__.py:470-480: get_loss, loss.backward(), optimizer.step(),
@@ -583,7 +568,6 @@ def mapping_iteration(params, curr_data, variables, iter_time_idx, loss_weights,
     prune_event) and the loss options use_l1 without bundle adjustment; ignore_outlier_depth_loss as in get_loss(fused_loss=True).
     -> (loss, variables, {'im', 'depth', 'loss'}); variables['means2D'].grad, ['seen'] and ['max_2D_radius'] are updated as get_loss +
     backward leave them."""
-    from . import rasterizer as R
     if pose7 is None:
         q = F.normalize(params["cam_unnorm_rots"][..., iter_time_idx].detach()).reshape(4)
         pose7 = torch.cat([q, params["cam_trans"][..., iter_time_idx].detach().reshape(3)]).cpu().tolist()
@@ -598,16 +582,14 @@ def mapping_iteration(params, curr_data, variables, iter_time_idx, loss_weights,
     if shs is not None and int(shs.shape[1]) != 16:
         raise Exception("mapping_iteration: SH rows of 16 coefficients only")
     iso = int(params["log_scales"].shape[1]) == 1
-    rctx = _DirectCtx()
-    im, radius, depth, _sil, depth_sq = R._RasterizeGaussians.forward(
-        rctx, means, m2d, shs, colors, params["logit_opacities"], params["log_scales"], params["unnorm_rotations"], None, curr_data["cam"], True,
-        (pose7, iso, False, (mx, seen), optimizer))
+    rctx, (im, radius, depth, _sil, depth_sq) = render_rgbd_raw_direct(
+        curr_data["cam"], means, m2d, params["logit_opacities"], params["log_scales"], params["unnorm_rotations"],
+        RawInputs(pose7, iso, visibility=(mx, seen), adam=optimizer), shs=shs, colors_precomp=colors)
     lctx = _DirectCtx()
     loss, parts = _FusedMappingLoss.forward(lctx, im, depth, depth_sq, curr_data["im"], curr_data["depth"], loss_weights["im"], loss_weights["depth"],
                                              bool(ignore_outlier_depth_loss))
     grads = lctx.saved_tensors[0]                               # dL/dim [3,H,W] and dL/ddepth [1,H,W] for dL/dloss = 1
-    out = R._RasterizeGaussians.backward(rctx, grads[:3], None, grads[3:], None, None)
-    m2d.grad = out[1]
+    m2d.grad = backward_direct(rctx, grads[:3], grads[3:])[1]
     variables["means2D"] = m2d
     variables["seen"] = seen
     return loss, variables, {"im": parts[1], "depth": parts[2], "loss": loss}
@@ -693,7 +675,6 @@ def tracking_render(params, curr_data, variables, time_idx):
     params['cam_trans'][..., time_idx] on the device (gs_preprocess_forward_raw_dev), then the render.  variables['max_2D_radius'] and ['seen']
     are updated in the kernel, as get_loss(tracking=True) updates them.  -> (ctx for rasterizer.backward_pose_dev, (im, radius, depth,
     silhouette, depth_sq))."""
-    from . import rasterizer as R
     rots, trans = _pose_columns(params)
     mx = variables["max_2D_radius"]
     means = params["means3D"]
@@ -705,10 +686,10 @@ def tracking_render(params, curr_data, variables, time_idx):
     seen = torch.empty(mx.numel(), dtype=torch.bool, device=mx.device)
     m2d = torch.empty_like(means)
     iso = int(params["log_scales"].shape[1]) == 1
-    rctx = _DirectCtx()
-    out = R._RasterizeGaussians.forward(
-        rctx, means, m2d, shs, None if shs is not None else params["rgb_colors"], params["logit_opacities"], params["log_scales"],
-        params["unnorm_rotations"], None, curr_data["cam"], True, (None, iso, False, (mx, seen), None, False, (rots, trans, int(time_idx))))
+    rctx, out = render_rgbd_raw_direct(
+        curr_data["cam"], means, m2d, params["logit_opacities"], params["log_scales"], params["unnorm_rotations"],
+        RawInputs(None, iso, visibility=(mx, seen), gaussians_grad=False, device_pose=(rots, trans, int(time_idx))),
+        shs=shs, colors_precomp=None if shs is not None else params["rgb_colors"])
     variables["seen"] = seen
     return rctx, out
 

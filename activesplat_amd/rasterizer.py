@@ -21,6 +21,7 @@ All compute is in libgsplat_hip.so through the C ABI of include/gsplat_hip.h; th
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes as C
 import threading
@@ -144,6 +145,118 @@ def _camera(rs: GaussianRasterizationSettings, device, sh_coeffs: int):
     return cam, keep
 
 
+def _capture_target():
+    """The dict the innermost capture() block of this thread publishes into, or None outside one."""
+    caps = getattr(_tls, "captures", None)
+    return caps[-1] if caps else None
+
+
+#: what every frame launch starts from: the current stream (object -- None on the emulated build --, handle, c_void_p), the size-only
+#: layouts, the fresh workspaces and the host counter pair
+_Frame = collections.namedtuple("_Frame", "device cur st_handle st gl il scratch_bytes geom image radii d_num h_num")
+
+
+def _begin_frame(lib, device, P, W, H, image_bytes=None):
+    """image_bytes: None = the whole image layout, else a function of the layout -> bytes (topdown_maps uses its first region only)."""
+    cur = torch.cuda.current_stream(device) if device.type == "cuda" else None     # ONE lookup per call (~6 us each)
+    st_handle = int(cur.cuda_stream) if cur is not None else 0
+    gl, il, scratch_bytes = _frame_layouts(lib, P, W, H)
+    return _Frame(device, cur, st_handle, C.c_void_p(st_handle), gl, il, scratch_bytes,
+                  torch.empty(gl.total_bytes, dtype=torch.uint8, device=device),
+                  torch.empty(il.total_bytes if image_bytes is None else image_bytes(il), dtype=torch.uint8, device=device),
+                  torch.empty(P, dtype=torch.int32, device=device), torch.empty(2, dtype=torch.int32, device=device),
+                  _host_counters(device, st_handle) if cur is not None else torch.zeros(2, dtype=torch.int32))
+
+
+def _capacity_guess(key):
+    """(pair capacity, tile-list capacity) for the optimistic launch of `key`'s next frame; None: size it from the exact counts."""
+    if key is None or not optimistic:
+        return None
+    with _capacity_lock:
+        return _capacity.get(key)
+
+
+def _capacity_update(key, D, max_tile):
+    with _capacity_lock:
+        old = _capacity.get(key, (0, 0))                    # monotone: views that alternate settle on the largest
+        if len(_capacity) >= 64 and key not in _capacity:   # P changes with every densify / growth step: keep the table small
+            _capacity.pop(next(iter(_capacity)))
+        # (the tile-list bound only selects kernels and LDS variants: a tight margin keeps a 2 M-Gaussian frame -- lists of up to 4.8 k keys --
+        # inside the one-workgroup bucket sort's 5632-key class; a list that outgrows it costs one exact re-launch)
+        _capacity[key] = (max(old[0], int(D * 1.25) + 4096), max(old[1], max_tile + max_tile // 16 + 64))
+
+
+def _record_launch(key, guess, hit, D, max_tile, P):
+    """The bookkeeping of one finished frame launch.  key = None (render_views): an exact-size launch outside the capacity table -- no
+    hit or miss is counted and nothing is stored (the atlas picks its segment count from the capacities)."""
+    if key is not None:
+        if hit:
+            last_stats["optimistic_hits"] = last_stats.get("optimistic_hits", 0) + 1
+        else:
+            last_stats["optimistic_misses"] = last_stats.get("optimistic_misses", 0) + (1 if guess is not None else 0)
+        _capacity_update(key, D, max_tile)
+    last_stats["num_rendered"], last_stats["P"], last_stats["max_tile_instances"] = D, P, max_tile
+
+
+def _render_at(lib, frame, W, H, launch, cap_d, cap_tile, bl=None):
+    if bl is None:
+        bl = _lib.GsBinLayout(); _lib.check(lib.gs_bin_layout(cap_d, cap_tile, W, H, C.byref(bl)))
+    binning = torch.empty(bl.total_bytes, dtype=torch.uint8, device=frame.device)
+    point_list = torch.empty(max(cap_d, 1), dtype=torch.int32, device=frame.device)
+    launch(cap_d, cap_tile, binning, point_list)
+    return bl, binning, point_list
+
+
+def _bin_and_render(lib, frame, key, P, W, H, launch, segmented_ok=False):
+    """Everything between "the per-Gaussian call is enqueued" and "the render that stands is known"; launch(cap_d, cap_tile, binning,
+    point_list) issues the caller's one gs_render_forward* call.  -> (D, max_tile, bl, binning, point_list).
+
+    Optimistic launch: the binning workspace is sized from the previous frame of this `key` (+25 %), the whole render is enqueued BEHIND
+    the counting kernels, and only then does the host wait for the two counters -- the GPU keeps working through what used to be an idle
+    gap (host wake-up + allocation + launch).  A frame whose true counts exceed the guess is re-launched with exact sizes (the render
+    calls are capacity-safe and idempotent)."""
+    cur, h_num = frame.cur, frame.h_num
+    done = None
+    guess = _capacity_guess(key)
+    if guess is not None:
+        if cur is not None:
+            ev = torch.cuda.Event()
+            ev.record(cur)
+        bl_g = _lib.GsBinLayout(); _lib.check(lib.gs_bin_layout(guess[0], guess[1], W, H, C.byref(bl_g)))
+        # Never optimistic where the capacities would CHOOSE the algorithm.  segmented_ok=False (the rasteriser): the segmented compositing of
+        # few-tile images is switched on, and its segment count set, by the tile-list bound -- an inflated guess would make the image depend on
+        # the call history; such frames take the exact launch, whose choice follows the true counts.  segmented_ok=True (topdown_maps): there
+        # is no segmented top-down kernel, the streams kernel serves every tile count (DESIGN.md section 5), so the bound decides nothing.
+        if bl_g.path == 1 and (segmented_ok or bl_g.segments <= 1):
+            done = _render_at(lib, frame, W, H, launch, guess[0], guess[1], bl_g)
+        if cur is not None:
+            ev.synchronize()                                # counters are on the host; the render is still in flight
+    elif cur is not None:
+        cur.synchronize()                                   # no guess (first frame of a stream, exact-size callers): D sizes the binning buffers
+    D = int(h_num[0].item()) & 0xFFFFFFFF
+    max_tile = int(h_num[1].item()) & 0xFFFFFFFF
+    hit = done is not None and D <= guess[0] and max_tile <= guess[1]
+    if not hit:
+        done = _render_at(lib, frame, W, H, launch, D, max_tile)
+    _record_launch(key, guess, hit, D, max_tile, P)
+    return (D, max_tile) + done
+
+
+class RawInputs(NamedTuple):
+    """What the raw-parameter forward (render_rgbd_raw, render_rgbd_raw_direct) needs besides the tensors."""
+    pose7: object                   # host (qw,qx,qy,qz,tx,ty,tz) of the frame's relative w2c; None with device_pose
+    isotropic: bool                 # log_scales is [P,1]
+    accumulate: bool = False        # the backward adds into the leaves' .grad
+    visibility: object = None       # (max_2D_radius [P] float32, seen [P] bool), written by the forward kernel
+    adam: object = None             # the optim.GaussianAdam whose step rides in the backward kernel
+    gaussians_grad: bool = True     # False: the pose-only backward of tracking
+    device_pose: object = None      # (cam_unnorm_rots [1,4,T], cam_trans [1,3,T], t): the kernels read column t in place
+
+
+#: what the raw backward keeps of the forward's RawInputs: pose = (c_float * 7), None with a device pose; logit = the opacity parameters
+_RawCtx = collections.namedtuple("_RawCtx", "pose iso accumulate logit")
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """fused=False: the reference contract (color differentiable; radii, depth, opacity not).
     fused=True : one pass also yields the reference's SECOND raster pass -- depth (differentiable), silhouette
@@ -152,10 +265,10 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, rs, fused=False, raw=None,
                 cam_rot=None, cam_trans=None):
-        """raw = (pose7, isotropic, accumulate): means3D / opacities / scales / rotations are the mapper's PARAMETERS (world-frame means, logit
+        """raw = RawInputs: means3D / opacities / scales / rotations are the mapper's PARAMETERS (world-frame means, logit
         opacities, log scales, unnormalised quaternions); frame transform + activations run inside the per-Gaussian kernels (render_rgbd_raw).
-        cam_rot [4] / cam_trans [3] (raw only): device tensors whose VALUES are pose7; the backward returns dL/d of them (raw[5] False: of them
-        only -- the pose-only backward of tracking)."""
+        cam_rot [4] / cam_trans [3] (raw only): device tensors whose VALUES are pose7; the backward returns dL/d of them (gaussians_grad False:
+        of them only -- the pose-only backward of tracking)."""
         lib = _lib.get()
         device = means3D.device
         leaves = (means3D, opacities, scales, rotations, colors_precomp)     # (raw + accumulate: the backward adds into these tensors' .grad)
@@ -170,44 +283,35 @@ class _RasterizeGaussians(torch.autograd.Function):
         M = 0 if shs is None else int(shs.shape[1])
         cam, keep = _camera(rs, device, M)
         W, H = int(rs.image_width), int(rs.image_height)
-        cur = torch.cuda.current_stream(device) if device.type == "cuda" else None     # ONE lookup per call (~6 us each)
-        st_handle = int(cur.cuda_stream) if cur is not None else 0
-        st = C.c_void_p(st_handle)
-
-        gl, il, scratch_bytes = _frame_layouts(lib, P, W, H)
-        geom = torch.empty(gl.total_bytes, dtype=torch.uint8, device=device)
-        image = torch.empty(il.total_bytes, dtype=torch.uint8, device=device)
-        radii = torch.empty(P, dtype=torch.int32, device=device)
-        d_num = torch.empty(2, dtype=torch.int32, device=device)
-        h_num = _host_counters(device, st_handle) if device.type == "cuda" else torch.zeros(2, dtype=torch.int32)
+        fr = _begin_frame(lib, device, P, W, H)
+        st, geom, image, radii = fr.st, fr.geom, fr.image, fr.radii
         # camera-pose gradient (render_rgbd_raw(camera=...)): (pose_only, shape of cam_rot, shape of cam_trans)
         pose_req = None
         if raw is not None and cam_rot is not None and (cam_rot.requires_grad or cam_trans.requires_grad):
-            pose_req = (len(raw) > 5 and not raw[5], cam_rot.shape, cam_trans.shape)
+            pose_req = (not raw.gaussians_grad, cam_rot.shape, cam_trans.shape)
         ctx.pose_req = pose_req
         ctx.cam_inputs = cam_rot is not None         # the backward then owes autograd two more entries (None when the camera is frozen)
         want_bwd = 1 if any(ctx.needs_input_grad[:8]) or pose_req is not None else 0
         pose = None
-        devpose = raw[6] if raw is not None and len(raw) > 6 else None
-        ctx.devpose = devpose
-        if devpose is not None:
+        ctx.devpose = raw.device_pose if raw is not None else None
+        if raw is not None:
+            iso = 1 if raw.isotropic else 0
+            vis_max, vis_seen = raw.visibility if raw.visibility is not None else (None, None)
+            tail = (_ptr(vis_max), _ptr(vis_seen), _ptr(radii), _ptr(geom), _ptr(image), _ptr(fr.d_num), _ptr(fr.h_num), want_bwd, st)
+        if ctx.devpose is not None:
             # tracking (mapping.tracking_iteration): the pose is read by the kernels from cam_unnorm_rots[0, :, t] / cam_trans[0, :, t] in place
-            rots_p, trans_p, t_idx = devpose
-            vis_max, vis_seen = raw[3] if raw[3] is not None else (None, None)
+            rots_p, trans_p, t_idx = ctx.devpose
             _lib.check(lib.gs_preprocess_forward_raw_dev(C.byref(cam), P, _ptr(means3D), _ptr(shs), _ptr(colors_precomp), _ptr(opacities),
                                                          _ptr(scales), _ptr(rotations), _ptr(rots_p), _ptr(trans_p), int(rots_p.shape[-1]),
-                                                         int(t_idx), 1 if raw[1] else 0, _ptr(vis_max), _ptr(vis_seen), _ptr(radii), _ptr(geom),
-                                                         _ptr(image), _ptr(d_num), _ptr(h_num), want_bwd, st))
+                                                         int(t_idx), iso, *tail))
         elif raw is not None:
-            pose = (C.c_float * 7)(*[float(v) for v in raw[0]])
-            vis_max, vis_seen = raw[3] if len(raw) > 3 and raw[3] is not None else (None, None)
+            pose = (C.c_float * 7)(*[float(v) for v in raw.pose7])
             _lib.check(lib.gs_preprocess_forward_raw(C.byref(cam), P, _ptr(means3D), _ptr(shs), _ptr(colors_precomp), _ptr(opacities),
-                                                     _ptr(scales), _ptr(rotations), pose, 1 if raw[1] else 0, _ptr(vis_max), _ptr(vis_seen),
-                                                     _ptr(radii), _ptr(geom), _ptr(image), _ptr(d_num), _ptr(h_num), want_bwd, st))
+                                                     _ptr(scales), _ptr(rotations), pose, iso, *tail))
         else:
             _lib.check(lib.gs_preprocess_forward(C.byref(cam), P, _ptr(means3D), _ptr(shs), _ptr(colors_precomp),
                                                  _ptr(opacities), _ptr(scales), _ptr(rotations), _ptr(cov3D_precomp),
-                                                 _ptr(radii), _ptr(geom), _ptr(image), _ptr(d_num), _ptr(h_num), want_bwd, st))
+                                                 _ptr(radii), _ptr(geom), _ptr(image), _ptr(fr.d_num), _ptr(fr.h_num), want_bwd, st))
         color = torch.empty(3, H, W, dtype=torch.float32, device=device)
         depth = torch.empty(1, H, W, dtype=torch.float32, device=device)
         opacity = torch.empty(1, H, W, dtype=torch.float32, device=device)
@@ -216,67 +320,26 @@ class _RasterizeGaussians(torch.autograd.Function):
         # forward zero-fills them as a side job instead of a fill launch in front of the backward
         scratch = None
         if want_bwd and P > 0:
-            scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=device)
+            scratch = torch.empty(fr.scratch_bytes, dtype=torch.uint8, device=device)
 
-        def render(cap_d, cap_tile):
-            bl_ = _lib.GsBinLayout(); _lib.check(lib.gs_bin_layout(cap_d, cap_tile, W, H, C.byref(bl_)))
-            binning_ = torch.empty(bl_.total_bytes, dtype=torch.uint8, device=device)
-            plist_ = torch.empty(max(cap_d, 1), dtype=torch.int32, device=device)
+        def launch(cap_d, cap_tile, binning_, plist_):
             _lib.check(lib.gs_render_forward(C.byref(cam), P, cap_d, cap_tile, _ptr(geom), _ptr(binning_), _ptr(plist_), _ptr(image),
                                              _ptr(color), _ptr(depth), _ptr(opacity), _ptr(depth_sq), _ptr(scratch), st))
-            return bl_, binning_, plist_
 
-        # Optimistic launch: the binning workspace is sized from the previous frame of this (P, W, H) stream (+25 %), the
-        # whole render is enqueued BEHIND the counting kernels, and only then does the host wait for the two counters --
-        # the GPU keeps working through what used to be an idle gap (host wake-up + allocation + launch).  A frame whose
-        # true counts exceed the guess is re-launched with exact sizes (gs_render_forward is capacity-safe and idempotent).
-        done = None
-        key = (P, W, H, device.index)
-        with _capacity_lock:
-            guess = _capacity.get(key) if optimistic else None
-        if guess is not None:
-            if device.type == "cuda":
-                ev = torch.cuda.Event()
-                ev.record(cur)
-            bl_g = _lib.GsBinLayout(); _lib.check(lib.gs_bin_layout(guess[0], guess[1], W, H, C.byref(bl_g)))
-            # (never optimistic where the capacities would CHOOSE the algorithm: the segmented compositing of few-tile images is switched on, and
-            # its segment count set, by the tile-list bound -- an inflated guess would make the image depend on the call history; such frames
-            # take the exact launch, whose choice follows the true counts)
-            if bl_g.path == 1 and bl_g.segments <= 1:
-                done = render(*guess)
-            if device.type == "cuda":
-                ev.synchronize()                                # counters are on the host; the render is still in flight
-        elif device.type == "cuda":
-            cur.synchronize()                                    # first frame of a stream: D sizes the binning buffers
-        D = int(h_num[0].item()) & 0xFFFFFFFF
-        max_tile = int(h_num[1].item()) & 0xFFFFFFFF
-        if done is not None and D <= guess[0] and max_tile <= guess[1]:
-            bl, binning, point_list = done
-            last_stats["optimistic_hits"] = last_stats.get("optimistic_hits", 0) + 1
-        else:
-            bl, binning, point_list = render(D, max_tile)
-            last_stats["optimistic_misses"] = last_stats.get("optimistic_misses", 0) + (1 if guess is not None else 0)
-        with _capacity_lock:
-            old = _capacity.get(key, (0, 0))                    # monotone: views that alternate settle on the largest
-            if len(_capacity) >= 64 and key not in _capacity:   # P changes with every densify / growth step: keep the table small
-                _capacity.pop(next(iter(_capacity)))
-            # (the tile-list bound only selects kernels and LDS variants: a tight margin keeps a 2 M-Gaussian frame -- lists of up to 4.8 k keys --
-            # inside the one-workgroup bucket sort's 5632-key class; a list that outgrows it costs one exact re-launch)
-            _capacity[key] = (max(old[0], int(D * 1.25) + 4096), max(old[1], max_tile + max_tile // 16 + 64))
-        last_stats["num_rendered"], last_stats["P"], last_stats["max_tile_instances"] = D, P, max_tile
+        D, max_tile, bl, binning, point_list = _bin_and_render(lib, fr, (P, W, H, device.index), P, W, H, launch)
         ctx.rs, ctx.D, ctx.keep, ctx.fused, ctx.cam = rs, D, keep, fused, cam      # the backward reuses the camera block
         ctx.scratch, ctx.scratch_clean, ctx.sh_jac = scratch, scratch is not None, want_bwd
         ctx.has = (shs is not None, colors_precomp is not None, scales is not None, rotations is not None,
                    cov3D_precomp is not None)
-        ctx.raw = None if raw is None else (pose, 1 if raw[1] else 0, bool(raw[2]), opacities)
+        ctx.raw = None if raw is None else _RawCtx(pose, iso, bool(raw.accumulate), opacities)
         # in-kernel accumulation only into the very tensors the caller passed (a converted copy has no .grad to add to)
-        adam = raw[4] if raw is not None and len(raw) > 4 else None
-        same = raw is not None and (raw[2] or adam is not None) and all(a is b for a, b in zip(leaves, (means3D, opacities, scales, rotations, colors_precomp)))
+        adam = raw.adam if raw is not None else None
+        same = raw is not None and (raw.accumulate or adam is not None) and all(a is b for a, b in zip(leaves, (means3D, opacities, scales, rotations, colors_precomp)))
         ctx.leaves = leaves if same else None
         ctx.adam = None
         if adam is not None:
             # the optimiser step inside the backward kernel: it updates the caller's parameter tensors in place
-            if raw[2]:
+            if raw.accumulate:
                 raise Exception("render_rgbd_raw: adam= and accumulate_grads= exclude each other")
             if pose_req is not None:
                 raise Exception("render_rgbd_raw: adam= and a differentiable camera exclude each other (the library has no pose-gradient form of the "
@@ -284,9 +347,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             if not same or (shs is not None and shs is not shs_in):
                 raise Exception("render_rgbd_raw(adam=...): the parameters must be contiguous, 16-byte aligned fp32 tensors on the device (they are updated in place)")
             ctx.adam = (adam, leaves[:4] + (shs_in if shs_in is not None else leaves[4],))
-        caps = getattr(_tls, "captures", None)
-        if caps:
-            caps[-1].update(geom=geom, image=image, binning=binning, point_list=point_list, gl=gl, il=il, bl=bl, D=D, P=P, W=W, H=H)
+        cap = _capture_target()
+        if cap is not None:
+            cap.update(geom=geom, image=image, binning=binning, point_list=point_list, gl=fr.gl, il=fr.il, bl=bl, D=D, P=P, W=W, H=H)
         e = torch.empty(0, device=device)
         ctx.save_for_backward(means3D, shs if shs is not None else e, colors_precomp if colors_precomp is not None else e,
                               scales if scales is not None else e, rotations if rotations is not None else e,
@@ -318,58 +381,52 @@ class _RasterizeGaussians(torch.autograd.Function):
             grad_color = torch.zeros(3, int(ctx.rs.image_height), int(ctx.rs.image_width), device=device)
         grad_color = _f32(grad_color, device)
         grad_depth = _f32(grad_depth, device) if (ctx.fused and grad_depth is not None) else None
-        scratch, clean = ctx.scratch, ctx.scratch_clean
-        if scratch is None:
-            scratch, clean = torch.empty(int(lib.gs_backward_scratch_bytes(P)), dtype=torch.uint8, device=device), False
-        ctx.scratch, ctx.scratch_clean = None, False     # released with this launch (64 B x P); a second backward through the same graph
-                                                         # takes a fresh buffer plus a memset
-        if ctx.raw is not None and ctx.adam is not None:
-            # single-keyframe step: Adam on the five per-Gaussian tensors rides in the per-Gaussian backward kernel (no gradient tensors)
+        scratch, clean = _take_scratch(ctx, lib, P, device)
+        z = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)  # noqa: E731  (kernel writes every row)
+        pose_req = getattr(ctx, "pose_req", None)
+        d_m2d = z(P, 3)
+        if ctx.raw is not None:
             if ctx.adam == "stepped":
                 # (retain_graph + a second backward through this render would apply the optimiser step twice, on already-stepped parameters)
                 raise RuntimeError("render_rgbd_raw(adam=...): this render's backward has already applied its optimiser step; a second backward "
                                    "through the same graph is refused -- render again, or use accumulate_grads / a separate optimizer.step()")
-            pose, iso, _acc, logit = ctx.raw
-            d_m2d = torch.empty(P, 3, dtype=torch.float32, device=device)
-            opt, tensors = ctx.adam
-            desc = opt.backward_step_descriptors(tensors)                 # (validates, then advances the step counters ...; a refusal here
-            ctx.adam = "stepped"                                          # leaves counters AND this graph as they were: the caller may retry)
-            try:
-                _lib.check(lib.gs_render_backward_raw_adam(
-                    C.byref(cam), P, ctx.D, _ptr(means3D), _ptr(shs if has_sh else None), _ptr(colors if has_col else None), _ptr(logit),
-                    _ptr(scales), _ptr(rots), pose, iso, _ptr(radii), _ptr(geom), _ptr(point_list), _ptr(image), _ptr(grad_color),
-                    _ptr(grad_depth), _ptr(d_m2d), _ptr(scratch), 1 if clean else 0, int(ctx.sh_jac), desc, _stream(device)))
-            except Exception:
-                opt.rollback_backward_step(tensors)                       # (... which a launch that did not happen must not keep)
-                ctx.adam = (opt, tensors)
-                raise
-            # the parameters changed in place behind autograd's back: bump their version counters, so that any other graph that saved them
-            # (a regulariser on the same parameters, a second keyframe rendered before this backward) fails loudly in ITS backward instead of
-            # differentiating through stepped values -- and note that such a branch gets no rasteriser gradient from this render
-            torch.autograd.graph.increment_version([t for t in tensors if t is not None])
-            return None, d_m2d, None, None, None, None, None, None, None, None, None
-        z = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)  # noqa: E731  (kernel writes every row)
-        d_m2d, d_m3d, d_op = z(P, 3), z(P, 3), z(P, 1)
+            rc = ctx.raw
+            # what every raw backward call starts with, has in its middle (after `accumulate` / before the parameter gradients) and ends on
+            head = (C.byref(cam), P, ctx.D, _ptr(means3D), _ptr(shs if has_sh else None), _ptr(colors if has_col else None), _ptr(rc.logit),
+                    _ptr(scales), _ptr(rots), rc.pose, rc.iso)
+            mid = (_ptr(radii), _ptr(geom), _ptr(point_list), _ptr(image), _ptr(grad_color), _ptr(grad_depth), _ptr(d_m2d))
+            scr = (_ptr(scratch), 1 if clean else 0, int(ctx.sh_jac))
+            if ctx.adam is not None:
+                # single-keyframe step: Adam on the five per-Gaussian tensors rides in the per-Gaussian backward kernel (no gradient tensors)
+                opt, tensors = ctx.adam
+                desc = opt.backward_step_descriptors(tensors)                 # (validates, then advances the step counters ...; a refusal here
+                ctx.adam = "stepped"                                          # leaves counters AND this graph as they were: the caller may retry)
+                try:
+                    _lib.check(lib.gs_render_backward_raw_adam(*head, *mid, *scr, desc, _stream(device)))
+                except Exception:
+                    opt.rollback_backward_step(tensors)                       # (... which a launch that did not happen must not keep)
+                    ctx.adam = (opt, tensors)
+                    raise
+                # the parameters changed in place behind autograd's back: bump their version counters, so that any other graph that saved them
+                # (a regulariser on the same parameters, a second keyframe rendered before this backward) fails loudly in ITS backward instead of
+                # differentiating through stepped values -- and note that such a branch gets no rasteriser gradient from this render
+                torch.autograd.graph.increment_version([t for t in tensors if t is not None])
+                return None, d_m2d, None, None, None, None, None, None, None, None, None
+            if pose_req is not None:
+                d_pose = z(7)
+                pscr = torch.empty(int(lib.gs_pose_grad_scratch_bytes(P)), dtype=torch.uint8, device=device)
+                pose_tail = (d_pose[:4].view(pose_req[1]), d_pose[4:].view(pose_req[2]))
+                if pose_req[0]:
+                    # tracking: the pose gradient only -- no parameter gradient is formed (gs_render_backward_raw_pose, pose_only = 1)
+                    _lib.check(lib.gs_render_backward_raw_pose(*head, 0, *mid, None, None, None, None, None, None, *scr, 1, _ptr(d_pose), _ptr(pscr),
+                                                               _stream(device)))
+                    return (None, d_m2d) + (None,) * 9 + pose_tail
+        d_m3d, d_op = z(P, 3), z(P, 1)
         d_col = z(P, 3) if has_col else None
         d_shs = z(P, M, 3) if has_sh else None
-        d_sc = z(P, 3) if has_sc else None
         d_rot = z(P, 4) if has_rot else None
-        d_cov = z(P, 6) if has_cov else None
-        pose_req = getattr(ctx, "pose_req", None)
-        if ctx.raw is not None and pose_req is not None and pose_req[0]:
-            # tracking: the pose gradient only -- no parameter gradient is formed (gs_render_backward_raw_pose, pose_only = 1)
-            pose, iso, _acc, logit = ctx.raw
-            d_pose = z(7)
-            pscr = torch.empty(int(lib.gs_pose_grad_scratch_bytes(P)), dtype=torch.uint8, device=device)
-            _lib.check(lib.gs_render_backward_raw_pose(
-                C.byref(cam), P, ctx.D, _ptr(means3D), _ptr(shs if has_sh else None), _ptr(colors if has_col else None), _ptr(logit),
-                _ptr(scales), _ptr(rots), pose, iso, 0, _ptr(radii), _ptr(geom), _ptr(point_list), _ptr(image), _ptr(grad_color),
-                _ptr(grad_depth), _ptr(d_m2d), None, None, None, None, None, None, _ptr(scratch), 1 if clean else 0, int(ctx.sh_jac), 1,
-                _ptr(d_pose), _ptr(pscr), _stream(device)))
-            return (None, d_m2d) + (None,) * 9 + (d_pose[:4].view(pose_req[1]), d_pose[4:].view(pose_req[2]))
         if ctx.raw is not None:
-            pose, iso, accumulate, logit = ctx.raw
-            d_sc = z(P, 1 if iso else 3)                  # (gradients w.r.t. the parameters: log scales are [P,1] for an isotropic map)
+            d_sc = z(P, 1 if rc.iso else 3)               # (gradients w.r.t. the parameters: log scales are [P,1] for an isotropic map)
             # accumulate: add into the leaves' .grad inside the kernel (what autograd would do with the results in separate passes);
             # leaves = (means3D, logit opacities, log scales, rotations, colours)
             leaves, acc, into = ctx.leaves, 0, None
@@ -385,17 +442,12 @@ class _RasterizeGaussians(torch.autograd.Function):
                 d_m3d, d_op, d_sc, d_rot = into[0], into[1], into[2], into[3]
                 if has_col:
                     d_col = into[4]
-            args = (C.byref(cam), P, ctx.D, _ptr(means3D), _ptr(shs if has_sh else None), _ptr(colors if has_col else None), _ptr(logit),
-                    _ptr(scales), _ptr(rots), pose, iso, acc, _ptr(radii), _ptr(geom), _ptr(point_list), _ptr(image), _ptr(grad_color),
-                    _ptr(grad_depth), _ptr(d_m2d), _ptr(d_m3d), _ptr(d_op), _ptr(d_col), _ptr(d_shs), _ptr(d_sc), _ptr(d_rot),
-                    _ptr(scratch), 1 if clean else 0, int(ctx.sh_jac))
+            args = (*head, acc, *mid, _ptr(d_m3d), _ptr(d_op), _ptr(d_col), _ptr(d_shs), _ptr(d_sc), _ptr(d_rot), *scr)
             tail = ()
             if pose_req is not None:
                 # bundle adjustment: the same launch also reduces the camera-pose gradient (parameter gradients bit-identical to the plain call)
-                d_pose = z(7)
-                pscr = torch.empty(int(lib.gs_pose_grad_scratch_bytes(P)), dtype=torch.uint8, device=device)
                 _lib.check(lib.gs_render_backward_raw_pose(*args, 0, _ptr(d_pose), _ptr(pscr), _stream(device)))
-                tail = (d_pose[:4].view(pose_req[1]), d_pose[4:].view(pose_req[2]))
+                tail = pose_tail
             else:
                 _lib.check(lib.gs_render_backward_raw(*args, _stream(device)))
             if into is not None:
@@ -405,6 +457,8 @@ class _RasterizeGaussians(torch.autograd.Function):
                             x.grad = t
                 return (None, d_m2d, d_shs, None, None, None, None, None, None, None, None) + tail
             return (d_m3d, d_m2d, d_shs, d_col, d_op, d_sc, d_rot, None, None, None, None) + tail
+        d_sc = z(P, 3) if has_sc else None
+        d_cov = z(P, 6) if has_cov else None
         _lib.check(lib.gs_render_backward(
             C.byref(cam), P, ctx.D, _ptr(means3D), _ptr(shs if has_sh else None), _ptr(colors if has_col else None),
             _ptr(scales if has_sc else None), _ptr(rots if has_rot else None), _ptr(cov3Dp if has_cov else None),
@@ -414,8 +468,47 @@ class _RasterizeGaussians(torch.autograd.Function):
         return d_m3d, d_m2d, d_shs, d_col, d_op, d_sc, d_rot, d_cov, None, None, None
 
 
+class _DirectCtx:
+    """Stands in for an autograd context when a Function's forward / backward is called directly (render_rgbd_raw_direct, mapping.mapping_iteration)."""
+    # one entry per input of _RasterizeGaussians.forward: the eight tensor inputs it asks about, then rs, fused, raw and the camera pair
+    needs_input_grad = (True,) * 8 + (False,) * (_RasterizeGaussians.forward.__code__.co_argcount - 1 - 8)
+    saved_tensors = ()
+
+    def save_for_backward(self, *tensors):
+        self.saved_tensors = tensors
+
+    def mark_non_differentiable(self, *tensors):
+        pass
+
+    def set_materialize_grads(self, value):
+        pass
+
+
+def render_rgbd_raw_direct(rs, means3D, means2D, logit_opacities, log_scales, unnorm_rotations, raw, shs=None, colors_precomp=None):
+    """render_rgbd_raw's forward without autograd (raw: RawInputs) -> (ctx for backward_direct / backward_pose_dev, (color, radii, depth,
+    silhouette, depth_sq)); the caller has checked what render_rgbd_raw checks."""
+    ctx = _DirectCtx()
+    return ctx, _RasterizeGaussians.forward(ctx, means3D, means2D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, None, rs,
+                                            True, raw)
+
+
+def backward_direct(ctx, grad_color, grad_depth):
+    """The backward of a render_rgbd_raw_direct forward -> the Function's gradient tuple ([1] is dL/dmeans2D)."""
+    return _RasterizeGaussians._backward(ctx, grad_color, grad_depth)
+
+
+def _take_scratch(ctx, lib, P, device):
+    """-> (scratch, clean): the forward's zero-filled gradient records, or a dirty buffer of its own.  Released with this launch (64 B x P); a
+    second backward through the same graph takes a fresh buffer plus a memset."""
+    scratch, clean = ctx.scratch, ctx.scratch_clean
+    if scratch is None:
+        scratch, clean = torch.empty(int(lib.gs_backward_scratch_bytes(P)), dtype=torch.uint8, device=device), False
+    ctx.scratch, ctx.scratch_clean = None, False
+    return scratch, clean
+
+
 def backward_pose_dev(ctx, grad_color, grad_depth, pose_scratch, d_pose=None):
-    """The pose-only backward of a render whose forward read the pose from the device (raw[6], mapping.tracking_iteration):
+    """The pose-only backward of a render whose forward read the pose from the device (RawInputs.device_pose, mapping.tracking_iteration):
     gs_render_backward_raw_pose_dev.  The per-workgroup pose rows go to pose_scratch (gs_pose_grad_scratch_bytes(P) bytes); d_pose [7] (optional)
     receives dL/d(qw,qx,qy,qz,tx,ty,tz) of the normalised column.  -> dL/dmeans2D [P,3]."""
     lib = _lib.get()
@@ -423,12 +516,9 @@ def backward_pose_dev(ctx, grad_color, grad_depth, pose_scratch, d_pose=None):
     has_sh, has_col = ctx.has[0], ctx.has[1]
     device = means3D.device
     P = int(means3D.shape[0])
-    _pose, iso, _acc, logit = ctx.raw
+    iso, logit = ctx.raw.iso, ctx.raw.logit
     rots_p, trans_p, t_idx = ctx.devpose
-    scratch, clean = ctx.scratch, ctx.scratch_clean
-    if scratch is None:
-        scratch, clean = torch.empty(int(lib.gs_backward_scratch_bytes(P)), dtype=torch.uint8, device=device), False
-    ctx.scratch, ctx.scratch_clean = None, False
+    scratch, clean = _take_scratch(ctx, lib, P, device)
     d_m2d = torch.empty(P, 3, dtype=torch.float32, device=device)
     _lib.check(lib.gs_render_backward_raw_pose_dev(
         C.byref(ctx.cam), P, ctx.D, _ptr(means3D), _ptr(shs if has_sh else None), _ptr(colors if has_col else None), _ptr(logit), _ptr(scales),
@@ -449,7 +539,7 @@ def _frontend_apply(means3D, means2D, shs, colors_precomp, opacities, scales, ro
     """The drop-in forward through the C++ front-end; None when this call is not one for it (then the Python twin takes it)."""
     if not use_frontend or _lib.emulated() or means3D.device.type != "cuda":
         return None
-    caps = getattr(_tls, "captures", None)
+    cap = _capture_target()
     from . import _frontend
     _lib.get()                                          # (the HIP library itself missing: raises -- there is no CPU path)
     ext = _frontend.get_or_none()                       # (no g++ / torch headers on this box: ONE warning, then the Python twin -- the same library calls)
@@ -458,31 +548,21 @@ def _frontend_apply(means3D, means2D, shs, colors_precomp, opacities, scales, ro
     device = means3D.device
     P, W, H = int(means3D.shape[0]), int(rs.image_width), int(rs.image_height)
     key = (P, W, H, device.index)
-    with _capacity_lock:
-        guess = _capacity.get(key) if optimistic else None
+    guess = _capacity_guess(key)
     out, D, max_tile, hit, state, off = ext.rasterize(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, rs.bg,
                                                       rs.viewmatrix, rs.projmatrix, rs.campos, W, H, float(rs.tanfovx), float(rs.tanfovy),
                                                       float(rs.scale_modifier), int(rs.sh_degree), bool(fused), guess[0] if guess else 0,
-                                                      guess[1] if guess else 0, bool(caps))
-    if caps:
+                                                      guess[1] if guess else 0, cap is not None)
+    if cap is not None:
         # capture(): views of the one workspace (and of the exact re-render's buffers after a miss), under the names the Python twin publishes
         lib = _lib.get()
         gl, il, _ = _frame_layouts(lib, P, W, H)
         ws, binning, plist2 = state
         cap_d, cap_tile = (guess if hit else (D, max_tile))
         bl = _lib.GsBinLayout(); _lib.check(lib.gs_bin_layout(cap_d, cap_tile, W, H, C.byref(bl)))
-        caps[-1].update(geom=ws[off[0]:off[0] + off[1]], image=ws[off[2]:off[2] + off[3]], gl=gl, il=il, bl=bl, D=D, P=P, W=W, H=H, binning=binning,
-                        point_list=ws[off[4]:off[4] + 4 * off[5]].view(torch.int32) if hit else plist2)
-    if hit:
-        last_stats["optimistic_hits"] = last_stats.get("optimistic_hits", 0) + 1
-    else:
-        last_stats["optimistic_misses"] = last_stats.get("optimistic_misses", 0) + (1 if guess is not None else 0)
-    with _capacity_lock:
-        old = _capacity.get(key, (0, 0))
-        if len(_capacity) >= 64 and key not in _capacity:
-            _capacity.pop(next(iter(_capacity)))
-        _capacity[key] = (max(old[0], int(D * 1.25) + 4096), max(old[1], max_tile + max_tile // 16 + 64))
-    last_stats["num_rendered"], last_stats["P"], last_stats["max_tile_instances"] = D, P, max_tile
+        cap.update(geom=ws[off[0]:off[0] + off[1]], image=ws[off[2]:off[2] + off[3]], gl=gl, il=il, bl=bl, D=D, P=P, W=W, H=H, binning=binning,
+                   point_list=ws[off[4]:off[4] + 4 * off[5]].view(torch.int32) if hit else plist2)
+    _record_launch(key, guess, hit, D, max_tile, P)     # (the C++ front-end decides hits itself; the bookkeeping is the twin's)
     return tuple(out)
 
 
@@ -560,7 +640,7 @@ def render_rgbd_raw(raster_settings, means3D, means2D, logit_opacities, log_scal
         if not gaussians_grad:
             raise Exception("render_rgbd_raw: gaussians_grad=False is the pose-only backward: it needs camera=(cam_rot, cam_trans)")
         return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, None,
-                                         raster_settings, True, (pose7, iso, accumulate_grads, visibility, adam))
+                                         raster_settings, True, RawInputs(pose7, iso, accumulate=accumulate_grads, visibility=visibility, adam=adam))
     cam_rot, cam_trans = camera
     if cam_rot.numel() != 4 or cam_trans.numel() != 3:
         raise Exception("render_rgbd_raw: camera = (cam_rot with 4 values, cam_trans with 3)")
@@ -575,7 +655,8 @@ def render_rgbd_raw(raster_settings, means3D, means2D, logit_opacities, log_scal
                                                                                       d(log_scales), d(unnorm_rotations))
         accumulate_grads = False
     return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, None,
-                                     raster_settings, True, (pose7, iso, accumulate_grads, visibility, None, gaussians_grad), cam_rot, cam_trans)
+                                     raster_settings, True, RawInputs(pose7, iso, accumulate=accumulate_grads, visibility=visibility, gaussians_grad=gaussians_grad),
+                                     cam_rot, cam_trans)
 
 
 class GaussianRasterizer(nn.Module):
@@ -643,29 +724,20 @@ def render_views(settings_list, means3D, opacities, shs=None, colors_precomp=Non
     pv, aw, stride = C.c_int32(), C.c_int32(), C.c_int32()
     _lib.check(lib.gs_atlas_layout(P, W, V, C.byref(pv), C.byref(aw), C.byref(stride)))
     Pv, AW, S = pv.value, aw.value, stride.value
-    st_handle = _lib.stream_handle(device)
-    st = C.c_void_p(st_handle)
-    gl = _lib.GsGeomLayout(); _lib.check(lib.gs_geom_layout(Pv, AW, H, C.byref(gl)))
-    il = _lib.GsImageLayout(); _lib.check(lib.gs_image_layout(AW, H, C.byref(il)))
-    geom = torch.empty(gl.total_bytes, dtype=torch.uint8, device=device)
-    image = torch.empty(il.total_bytes, dtype=torch.uint8, device=device)
-    radii = torch.empty(max(Pv, 1), dtype=torch.int32, device=device)
-    d_num = torch.empty(2, dtype=torch.int32, device=device)
-    h_num = _host_counters(device, st_handle) if device.type == "cuda" else torch.zeros(2, dtype=torch.int32)
+    fr = _begin_frame(lib, device, max(Pv, 1), AW, H)
+    geom, image, radii, st = fr.geom, fr.image, fr.radii, fr.st
     _lib.check(lib.gs_preprocess_forward(C.byref(cam), P, _ptr(means3D), _ptr(shs), _ptr(colors_precomp), _ptr(opacities), _ptr(scales),
-                                         _ptr(rotations), _ptr(cov3D_precomp), _ptr(radii), _ptr(geom), _ptr(image), _ptr(d_num), _ptr(h_num), 0, st))
-    if device.type == "cuda":
-        torch.cuda.current_stream(device).synchronize()      # D and the longest tile list size the binning workspace
-    D, max_tile = int(h_num[0].item()) & 0xFFFFFFFF, int(h_num[1].item()) & 0xFFFFFFFF
-    bl = _lib.GsBinLayout(); _lib.check(lib.gs_bin_layout(D, max_tile, AW, H, C.byref(bl)))
-    binning = torch.empty(bl.total_bytes, dtype=torch.uint8, device=device)
-    plist = torch.empty(max(D, 1), dtype=torch.int32, device=device)
+                                         _ptr(rotations), _ptr(cov3D_precomp), _ptr(radii), _ptr(geom), _ptr(image), _ptr(fr.d_num), _ptr(fr.h_num), 0, st))
     color = torch.empty(3, H, AW, dtype=torch.float32, device=device)
     depth = torch.empty(1, H, AW, dtype=torch.float32, device=device)
     opacity = torch.empty(1, H, AW, dtype=torch.float32, device=device)
-    _lib.check(lib.gs_render_forward(C.byref(cam), P, D, max_tile, _ptr(geom), _ptr(binning), _ptr(plist), _ptr(image),
-                                     _ptr(color), _ptr(depth), _ptr(opacity), None, None, st))
-    last_stats["num_rendered"], last_stats["P"], last_stats["max_tile_instances"] = D, P, max_tile
+
+    def launch(cap_d, cap_tile, binning, plist):
+        _lib.check(lib.gs_render_forward(C.byref(cam), P, cap_d, cap_tile, _ptr(geom), _ptr(binning), _ptr(plist), _ptr(image),
+                                         _ptr(color), _ptr(depth), _ptr(opacity), None, None, st))
+
+    # key = None: always at exact size and outside the capacity table (D and the longest tile list size the binning workspace)
+    _bin_and_render(lib, fr, None, P, AW, H, launch)
     if return_atlas:
         return color, depth, opacity, S
     rows = Pv // V

@@ -15,6 +15,7 @@ synchronisation is the one every render needs for its instance counters.  There 
 from __future__ import annotations
 
 import ctypes as C
+import operator
 from typing import NamedTuple
 
 import numpy as np
@@ -26,6 +27,8 @@ from .camera import setup_camera
 
 #: `free = opacity <= 0.4` (visualizer.py:948), compared in fp32 inside the blend kernel
 FREE_OPACITY_THRESHOLD = 0.4
+#: bytes of the image state a tick needs: everything in front of the layout's final_T region
+_TILE_RANGES_ONLY = operator.attrgetter("final_T")
 
 
 class TopdownMaps(NamedTuple):
@@ -88,62 +91,23 @@ def topdown_maps(params, cam, upper, lower, scale_modifier=0.01):
     iso = 1 if log_scales.shape[1] == 1 else 0
     gcam, keep = R._camera(cam, device, 0)
     W, H = int(cam.image_width), int(cam.image_height)
-    cur = torch.cuda.current_stream(device) if device.type == "cuda" else None
-    st_handle = int(cur.cuda_stream) if cur is not None else 0
-    st = C.c_void_p(st_handle)
-    gl, il, _ = R._frame_layouts(lib, P, W, H)
-    caps = getattr(R._tls, "captures", None)
-    geom = torch.empty(gl.total_bytes, dtype=torch.uint8, device=device)
+    cap = R._capture_target()
     # (only the tile ranges of the image state are used -- its first region; a capture gets the whole layout so that it decodes as usual)
-    image = torch.empty(il.total_bytes if caps else il.final_T, dtype=torch.uint8, device=device)
-    radii = torch.empty(P, dtype=torch.int32, device=device)
-    d_num = torch.empty(2, dtype=torch.int32, device=device)
-    h_num = R._host_counters(device, st_handle) if device.type == "cuda" else torch.zeros(2, dtype=torch.int32)
+    fr = R._begin_frame(lib, device, P, W, H, image_bytes=None if cap is not None else _TILE_RANGES_ONLY)
+    geom, image, radii, st = fr.geom, fr.image, fr.radii, fr.st
     _lib.check(lib.gs_preprocess_forward_topdown(C.byref(gcam), P, R._ptr(means3D), R._ptr(colors), R._ptr(logit), R._ptr(log_scales), R._ptr(rots),
-                                                 iso, upper, lower, R._ptr(radii), R._ptr(geom), R._ptr(image), R._ptr(d_num), R._ptr(h_num), st))
+                                                 iso, upper, lower, R._ptr(radii), R._ptr(geom), R._ptr(image), R._ptr(fr.d_num), R._ptr(fr.h_num), st))
     free_opacity = torch.empty(H, W, dtype=torch.float32, device=device)
     free_bin = torch.empty(H, W, dtype=torch.uint8, device=device)
     vis_rgb = torch.empty(H, W, 3, dtype=torch.uint8, device=device)
     vis_bin = torch.empty(H, W, dtype=torch.uint8, device=device)
 
-    def render(cap_d, cap_tile):
-        bl_ = _lib.GsBinLayout(); _lib.check(lib.gs_bin_layout(cap_d, cap_tile, W, H, C.byref(bl_)))
-        binning_ = torch.empty(bl_.total_bytes, dtype=torch.uint8, device=device)
-        plist_ = torch.empty(max(cap_d, 1), dtype=torch.int32, device=device)
+    def launch(cap_d, cap_tile, binning_, plist_):
         _lib.check(lib.gs_render_forward_topdown(C.byref(gcam), P, cap_d, cap_tile, R._ptr(geom), R._ptr(binning_), R._ptr(plist_), R._ptr(image),
                                                  R._ptr(free_opacity), R._ptr(free_bin), R._ptr(vis_rgb), R._ptr(vis_bin), st))
-        return bl_, binning_, plist_
 
-    # the rasteriser's optimistic launch (rasterizer.py): capacities from the previous tick of this (P, W, H) stream, the render enqueued behind
-    # the counting kernels, and only then the wait for the two counters -- the one host synchronisation of a render; a tick whose true counts
-    # exceed the guess is launched again with exact sizes (gs_render_forward_topdown is capacity-safe and idempotent)
-    done = None
-    key = ("topdown", P, W, H, device.index)
-    with R._capacity_lock:
-        guess = R._capacity.get(key) if R.optimistic else None
-    if guess is not None:
-        if cur is not None:
-            ev = torch.cuda.Event()
-            ev.record(cur)
-        bl_g = _lib.GsBinLayout(); _lib.check(lib.gs_bin_layout(guess[0], guess[1], W, H, C.byref(bl_g)))
-        if bl_g.path == 1:
-            done = render(*guess)
-        if cur is not None:
-            ev.synchronize()
-    elif cur is not None:
-        cur.synchronize()
-    D = int(h_num[0].item()) & 0xFFFFFFFF
-    max_tile = int(h_num[1].item()) & 0xFFFFFFFF
-    if done is not None and D <= guess[0] and max_tile <= guess[1]:
-        bl, binning, point_list = done
-    else:
-        bl, binning, point_list = render(D, max_tile)
-    with R._capacity_lock:
-        old = R._capacity.get(key, (0, 0))
-        if len(R._capacity) >= 64 and key not in R._capacity:
-            R._capacity.pop(next(iter(R._capacity)))
-        R._capacity[key] = (max(old[0], int(D * 1.25) + 4096), max(old[1], max_tile + max_tile // 16 + 64))
-    R.last_stats["num_rendered"], R.last_stats["P"], R.last_stats["max_tile_instances"] = D, P, max_tile
-    if caps:
-        caps[-1].update(geom=geom, image=image, binning=binning, point_list=point_list, gl=gl, il=il, bl=bl, D=D, P=P, W=W, H=H, radii=radii)
+    # the rasteriser's optimistic launch with a capacity stream of its own: the one host synchronisation of a tick is the wait for its two counters
+    D, _max_tile, bl, binning, point_list = R._bin_and_render(lib, fr, ("topdown", P, W, H, device.index), P, W, H, launch, segmented_ok=True)
+    if cap is not None:
+        cap.update(geom=geom, image=image, binning=binning, point_list=point_list, gl=fr.gl, il=fr.il, bl=bl, D=D, P=P, W=W, H=H, radii=radii)
     return TopdownMaps(free_opacity, free_bin, vis_rgb, vis_bin)

@@ -1489,3 +1489,88 @@ def check_segmented_forward(device, oracle32):
         den = np.linalg.norm(b[k])
         if den > 0:
             assert np.linalg.norm(a[k] - b[k]) / den < 1e-4, k
+
+
+def check_render_views_leaves_the_capacity_table_alone(device, N=2000, W=48, H=40):
+    """render_views launches at exact size outside the capacity table (the atlas picks its segment count from the capacities, so a stored
+    guess would make a panorama depend on the call history): R._capacity and the hit / miss counters are what they were before the call,
+    the call twice gives the same bits, and the three views are those of three single-view exact-size calls: bit for bit in the view whose
+    atlas slot starts at column 0 and in every view's radii.  The other views are NOT bit-identical to a single-view render, before this helper
+    existed or after: a pixel's x is offset by its view's slot, so fp32 rounds pixel - mean differently (measured here on the emulated
+    kernels, the same figures with and without the shared launch helper: colour up to 1.4e-6, depth 7.2e-6, opacity 1.6e-6 apart).  They
+    are held to the bound that tests/test_lookaround.py (batched against batched=False) and cluster_cases.check_look_around_nodes already
+    pin for exactly this difference: atol 1e-5, depth atol 2e-5 / rtol 1e-5."""
+    from activesplat_amd import GaussianRasterizer, rasterizer as R
+    views = [util.scene(N, W, H, seed=4, device=device, w2c=util.pose(yaw, t))[0] for yaw, t in ((0.0, (0.0, 0.0, 0.0)), (0.35, (0.1, 0.0, 0.2)),
+                                                                                                  (-0.4, (-0.2, 0.05, 0.4)))]
+    _, rv = util.scene(N, W, H, seed=4, device=device)
+    was = R.optimistic
+    try:
+        R.optimistic = False
+        single = [[t.clone() for t in GaussianRasterizer(raster_settings=rs)(means2D=None, **rv)] for rs in views]
+        R.optimistic = True
+        R._capacity.clear()
+        R._capacity[("sentinel",)] = (7, 9)
+        R.last_stats["optimistic_hits"], R.last_stats["optimistic_misses"] = 5, 3
+        with torch.no_grad():
+            got = R.render_views(views, **rv)
+            again = R.render_views(views, **rv)
+        assert R._capacity == {("sentinel",): (7, 9)}, R._capacity
+        assert (R.last_stats["optimistic_hits"], R.last_stats["optimistic_misses"]) == (5, 3)
+        assert R.last_stats["P"] == N and R.last_stats["num_rendered"] > 0
+        worst = 0.0
+        for v, (g, a, ref) in enumerate(zip(got, again, single)):
+            assert g[0].shape == (3, H, W) and g[1].shape == (N,)
+            for x, y in zip(g, a):
+                assert torch.equal(x, y), v                      # (no dependence on the call history)
+            worst = max([worst] + [float((x.float() - y.float()).abs().max()) for x, y in zip(g, ref)])
+        print(f"[render_views] largest difference between a view of the atlas and its single-view render: {worst:.3e}")
+        for v, (g, ref) in enumerate(zip(got, single)):
+            assert torch.equal(g[1], ref[1]) and int((ref[1] > 0).sum()) > 0, v           # radii: every view, exactly
+            if v == 0:
+                assert all(torch.equal(x, y) for x, y in zip(g, ref))
+            else:
+                assert torch.allclose(g[0], ref[0], atol=1e-5) and torch.allclose(g[3], ref[3], atol=1e-5), v
+                assert torch.allclose(g[2], ref[2], atol=2e-5, rtol=1e-5), v
+    finally:
+        R.optimistic = was
+        R._capacity.clear()
+        R.last_stats.pop("optimistic_hits", None); R.last_stats.pop("optimistic_misses", None)
+
+
+def check_raw_inputs_by_name(device, N=500, W=48, H=40):
+    """render_rgbd_raw (autograd) and the direct entry (render_rgbd_raw_direct + backward_direct, what mapping_iteration calls) are the same
+    launches: equal outputs, equal dL/dmeans2D.  And the three exclusions of the raw inputs still raise with their messages."""
+    import pytest
+    from activesplat_amd import rasterizer as R
+    from activesplat_amd import synthetic as syn
+    from activesplat_amd.camera import setup_camera
+    p = {k: v.to(device) for k, v in syn.make_params(N, W, H, seed=9).items()}
+    cam = setup_camera(W, H, syn.intrinsics(W, H), np.eye(4), device=device)
+    pose = [0.9950042, 0.0, 0.0998334, 0.0, 0.03, -0.02, 0.05]
+    g = torch.Generator().manual_seed(4)
+    dLc, dLd = torch.randn(3, H, W, generator=g).to(device), torch.randn(1, H, W, generator=g).to(device)
+    args = (p["means3D"], p["logit_opacities"], p["log_scales"], p["unnorm_rotations"])
+    iso = int(p["log_scales"].shape[1]) == 1
+    m2d = torch.empty_like(p["means3D"], requires_grad=True)
+    a = R.render_rgbd_raw(cam, args[0], m2d, *args[1:], pose, colors_precomp=p["rgb_colors"])
+    ((a[0] * dLc).sum() + (a[2] * dLd).sum()).backward()
+    with torch.no_grad():
+        ctx, b = R.render_rgbd_raw_direct(cam, args[0], torch.empty_like(p["means3D"]), *args[1:], R.RawInputs(pose, iso), colors_precomp=p["rgb_colors"])
+        d_m2d = R.backward_direct(ctx, dLc, dLd)[1]
+    assert int((a[1] > 0).sum()) > N // 4
+    for x, y in zip(a, b):
+        assert torch.equal(x, y)
+    print(f"[raw inputs] |dL/dmeans2D| autograd - direct: {float((m2d.grad - d_m2d).abs().max()):.3e} of {float(d_m2d.abs().max()):.3e}")
+    if device == "cpu":
+        assert torch.equal(m2d.grad, d_m2d)
+    else:                                                            # (two runs of the device's atomics: sums in a different order)
+        assert float((m2d.grad.double() - d_m2d.double()).norm() / d_m2d.double().norm().clamp_min(1e-30)) < 1e-5
+    raw = lambda **kw: R.render_rgbd_raw(cam, args[0], torch.empty_like(p["means3D"]), *args[1:], pose, colors_precomp=p["rgb_colors"], **kw)  # noqa: E731
+    camera = (torch.tensor(pose[:4], device=device, requires_grad=True), torch.tensor(pose[4:], device=device, requires_grad=True))
+    with pytest.raises(Exception, match="adam= and accumulate_grads= exclude each other"):
+        raw(adam=object(), accumulate_grads=True)
+    with pytest.raises(Exception, match="adam= and a differentiable camera exclude each other"):
+        raw(adam=object(), camera=camera)
+    with pytest.raises(Exception, match=r"gaussians_grad=False is the pose-only backward: it needs camera=\(cam_rot, cam_trans\)"):
+        raw(gaussians_grad=False)

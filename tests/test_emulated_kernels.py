@@ -176,6 +176,21 @@ def test_emulated_optimistic_launch_hit_and_miss_equal_exact_launch(emu):
     pc.check_optimistic_tile_list_growth(emu)
 
 
+def test_emulated_render_views_leaves_the_capacity_table_alone(emu):
+    pc.check_render_views_leaves_the_capacity_table_alone(emu)
+
+
+def test_emulated_raw_inputs_by_name_and_the_direct_entry(emu):
+    import ctypes
+    omp = ctypes.CDLL("libgomp.so.1")
+    before = omp.omp_get_max_threads()
+    omp.omp_set_num_threads(1)                  # (one thread: the emulated atomics then sum in one order, and equal means equal)
+    try:
+        pc.check_raw_inputs_by_name(emu)
+    finally:
+        omp.omp_set_num_threads(before)
+
+
 def test_emulated_densification_statistics_kernels(emu):
     from activesplat_amd import optim as O
     g0 = torch.Generator().manual_seed(8)

@@ -233,6 +233,14 @@ def test_optimistic_launch_hit_and_miss_equal_exact_launch(hip):
     pc.check_optimistic_tile_list_growth(hip)
 
 
+def test_render_views_leaves_the_capacity_table_alone(hip):
+    pc.check_render_views_leaves_the_capacity_table_alone(hip)
+
+
+def test_raw_inputs_by_name_and_the_direct_entry(hip):
+    pc.check_raw_inputs_by_name(hip)
+
+
 @pytest.mark.parametrize("frontend", [True, False], ids=["frontend", "python-twin"])
 def test_render_does_not_depend_on_the_capacity_history(hip, frontend):
     """Round-5 sweep, seeds 130045 / 130237: a small image whose longest tile list sits just under 8192 (7753 / 7885).  The second render of the

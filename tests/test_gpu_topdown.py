@@ -51,3 +51,7 @@ def test_topdown_maps_twice_on_one_stream_take_the_optimistic_launch(hip):
 
 def test_mapper_topdown_maps(hip):
     tc.check_mapper(hip)
+
+
+def test_topdown_optimistic_launch_hits_and_misses_reproduce_the_exact_maps(hip):
+    tc.check_optimistic_launch(hip)

@@ -97,3 +97,7 @@ def test_emulated_topdown_maps_equal_the_two_pass_composition(emu, N, W, H, iso)
 
 def test_emulated_mapper_topdown_maps(emu):
     tc.check_mapper(emu)
+
+
+def test_emulated_topdown_optimistic_launch_hits_and_misses_reproduce_the_exact_maps(emu):
+    tc.check_optimistic_launch(emu)

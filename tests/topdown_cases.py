@@ -402,3 +402,37 @@ def check_mapper(device, frames=3, W=64, H=48):
     ff, uf = float(got.free_map_binary.float().mean()), float(got.visible_map_binary.float().mean())
     print(f"[topdown mapper] {m3.shape[0]} Gaussians after {frames} frames: {ff * 100:.1f} % free, {uf * 100:.1f} % unseen")
     assert 0.0 < ff < 1.0 and 0.0 < uf < 1.0
+
+
+def check_optimistic_launch(device, N=3000, W=120, H=150, raise_log_scales=8.0):
+    """The twin of parity_cases.check_optimistic_launch for the top-down route: a tick's binning workspace is sized from the previous tick of its
+    (P, W, H) stream.  An exact launch, a hit, a miss (the same map with its log scales raised by 8: 4 490 -> 60 429 tile instances on
+    the emulated kernels against a stored guess of 9 708, re-launched with exact sizes), a hit at the grown capacity and a hit with a much larger capacity than needed must all reproduce the
+    exactly-sized maps bit for bit, and the route counts its hits and misses like the rasteriser's own."""
+    params = scene_params(N, W, H, device)
+    cam = camera(W, H, device)
+    small = lambda: TD.topdown_maps(params, cam, *BAND)                                  # noqa: E731
+    big = dict(params, log_scales=params["log_scales"] + raise_log_scales)
+    large = lambda: TD.topdown_maps(big, cam, *BAND)                                     # noqa: E731
+    was = R.optimistic
+    try:
+        R.optimistic = False
+        exact_small, exact_large = small(), large()
+        R.optimistic = True
+        R._capacity.clear()
+        R.last_stats.pop("optimistic_hits", None); R.last_stats.pop("optimistic_misses", None)
+        got = [small(), small()]                 # no guess yet: exact; then a hit
+        assert R.last_stats.get("optimistic_hits", 0) == 1 and R.last_stats.get("optimistic_misses", 0) == 0
+        d_guess = R._capacity[("topdown", N, W, H, params["means3D"].device.index)][0]
+        got.append(large())                      # miss: D grows far beyond 1.25 x + 4096
+        print(f"[topdown optimistic] stored guess {d_guess}, tile instances of the large tick {R.last_stats['num_rendered']}")
+        assert R.last_stats["num_rendered"] > d_guess and R.last_stats["optimistic_misses"] == 1
+        got += [large(), small()]                # hit at the grown capacity; hit with a much larger capacity than needed
+        assert R.last_stats["optimistic_hits"] == 3 and R.last_stats["optimistic_misses"] == 1
+        for step, (m, ref) in enumerate(zip(got, (exact_small, exact_small, exact_large, exact_large, exact_small))):
+            for k in m._fields:
+                assert torch.equal(getattr(m, k), getattr(ref, k)), (step, k)
+        assert not torch.equal(exact_small.visible_rgb, exact_large.visible_rgb)
+    finally:
+        R.optimistic = was
+        R._capacity.clear()
