@@ -53,6 +53,11 @@ class GsDbscanLayout(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("total_bytes", "mask_bits", "core_bits", "root_bits", "word_prefix", "parent", "root", "row_range")]
 
 
+class GsEvalLayout(C.Structure):
+    _fields_ = [("total_bytes", C.c_uint64), ("ms_ssim_defined", C.c_int32), ("levels", C.c_int32), ("level_width", C.c_int32 * 5),
+                ("level_height", C.c_int32 * 5)]
+
+
 class GsHullLayout(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("total_bytes", "cluster_status")]
 
@@ -62,7 +67,7 @@ SORT_AUTO, SORT_TILE_LDS, SORT_RADIX = 0, 1, 2
 
 # every symbol include/gsplat_hip.h declares (tests check the library exports all of them)
 #: the GS_ABI_VERSION of include/gsplat_hip.h this binding was written against (checked when a library is bound)
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 SYMBOLS = ("gs_abi_version", "gs_geom_layout", "gs_image_layout", "gs_bin_layout", "gs_backward_scratch_bytes", "gs_last_error",
            "gs_version", "gs_set_sort_path", "gs_set_forward_segments", "gs_set_half_quadrants", "gs_set_backward_chain", "gs_set_backward_chain_tickets", "gs_set_backward_chain_polls", "gs_async_status_word", "gs_async_status_clear", "gs_recorded_cut", "gs_set_backward_segments", "gs_preprocess_forward", "gs_preprocess_forward_raw", "gs_render_forward", "gs_render_backward", "gs_render_backward_raw", "gs_render_backward_raw_adam", "gs_adam_step", "gs_adam_step_multi",
@@ -78,7 +83,8 @@ SYMBOLS = ("gs_abi_version", "gs_geom_layout", "gs_image_layout", "gs_bin_layout
            "gs_cluster_hulls_layout", "gs_cluster_hulls",
            "gs_depth_error_median_scratch_bytes", "gs_depth_error_median", "gs_depth_error_median_grid", "gs_depth_error_median_workgroups",
            "gs_mapping_loss_outlier", "gs_tracking_loss_outlier",
-           "gs_depth_cloud", "gs_cloud_nearest_scratch_bytes", "gs_cloud_nearest", "gs_completion_row_scratch_bytes", "gs_completion_row")
+           "gs_depth_cloud", "gs_cloud_nearest_scratch_bytes", "gs_cloud_nearest", "gs_completion_row_scratch_bytes", "gs_completion_row",
+           "gs_eval_frame_layout", "gs_eval_frame")
 
 
 def _bind(lib):
@@ -184,6 +190,11 @@ def _bind(lib):
     # (n_samples, min_dist, n_acc, acc_dist, acc_valid, path_length, row6, scratch, stream)
     lib.gs_completion_row.argtypes = [i64, vp, i64, vp, vp, C.c_double, vp, vp, vp]
     lib.gs_completion_row.restype = C.c_int
+    # map-quality evaluation: (width, height, flags, layout); (width, height, im, depth, silhouette, gt_im, gt_depth, sil_thres, flags, row8, scratch, stream)
+    lib.gs_eval_frame_layout.argtypes = [i32, i32, i32, C.POINTER(GsEvalLayout)]
+    lib.gs_eval_frame_layout.restype = C.c_int
+    lib.gs_eval_frame.argtypes = [i32, i32, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp]
+    lib.gs_eval_frame.restype = C.c_int
     lib.gs_tracking_loss_scratch_bytes.argtypes = [i32, i32]
     lib.gs_tracking_loss_scratch_bytes.restype = C.c_uint64
     lib.gs_tracking_loss.argtypes = [i32, i32] + [vp] * 6 + [i32, f32, f32, f32] + [vp] * 4 + [vp]

@@ -1320,4 +1320,41 @@ int gs_completion_row(int64_t n_samples, const float* min_dist, int64_t n_acc, c
     return GS_OK;
 }
 
+static int eval_plan_checked(const char* who, int32_t width, int32_t height, int32_t flags, gs::EvalPlan& p)
+{
+    if (width < 1 || height < 1 || width > 16384 || height > 16384) return fail(GS_EINVAL, "%s: image size out of range (1 <= width, height <= 16384)", who);
+    if (flags & ~(GS_EVAL_SIL_MASK | GS_EVAL_IMAGE_VALID_MASK | GS_EVAL_SSIM | GS_EVAL_MS_SSIM)) return fail(GS_EINVAL, "%s: unknown flag", who);
+    if (!gs::eval_plan(width, height, flags, p))
+        return fail(GS_EINVAL, "%s: GS_EVAL_MS_SSIM needs min(width, height) > 160 (five scales of an 11-tap valid window)", who);
+    return GS_OK;
+}
+
+int gs_eval_frame_layout(int32_t width, int32_t height, int32_t flags, GsEvalLayout* layout)
+{
+    if (!layout) return fail(GS_EINVAL, "gs_eval_frame_layout: null pointer");
+    gs::EvalPlan p;
+    // (the layout call answers "is MS-SSIM defined here" instead of refusing: the plan is made without that flag when it is not)
+    const bool ms_ok = width >= 1 && height >= 1 && (width < height ? width : height) > 160;
+    const int rc = eval_plan_checked("gs_eval_frame_layout", width, height, ms_ok ? flags : (flags & ~GS_EVAL_MS_SSIM), p);
+    if (rc != GS_OK) return rc;
+    layout->total_bytes = align_up(p.total_bytes);
+    layout->ms_ssim_defined = p.ms_defined;
+    layout->levels = p.levels;
+    for (int l = 0; l < 5; l++) { layout->level_width[l] = p.w[l]; layout->level_height[l] = p.h[l]; }
+    return GS_OK;
+}
+
+int gs_eval_frame(int32_t width, int32_t height, const float* im, const float* depth, const float* silhouette, const float* gt_im,
+                  const float* gt_depth, float sil_thres, int32_t flags, double* row, void* scratch, gs_stream_t stream)
+{
+    gs::EvalPlan p;
+    const int rc = eval_plan_checked("gs_eval_frame", width, height, flags, p);
+    if (rc != GS_OK) return rc;
+    if (!im || !depth || !silhouette || !gt_im || !gt_depth || !row || !scratch || ((uintptr_t)scratch & 7) || ((uintptr_t)row & 7))
+        return fail(GS_EINVAL, "gs_eval_frame: null pointer, or scratch / row not 8-byte aligned");
+    hipError_t e = gs::launch_eval_frame(p, im, depth, silhouette, gt_im, gt_depth, sil_thres, flags, row, scratch, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_eval_frame: %s", hipGetErrorString(e));
+    return GS_OK;
+}
+
 }  // extern "C"

@@ -886,6 +886,17 @@ hipError_t launch_cloud_nearest(int64_t Q, const float* query, const uint8_t* qv
 uint64_t completion_row_scratch_bytes();
 hipError_t launch_completion_row(int64_t N, const float* min_d, int64_t P, const float* acc_d, const uint8_t* acc_valid, double path_length,
                                  double* row, void* scratch, hipStream_t st);
+// map-quality evaluation of one frame (loss.hip; the rules: include/gsplat_hip.h, gs_eval_frame).  One plan for the layout call, the launches and
+// the finish kernel: level sizes, workgroup records per pass, offsets of the records (in doubles) and of the pooled images (in bytes)
+struct EvalPlan {
+    int w[5], h[5], levels, ms_defined;
+    int sums_records, same_tiles, ms_tiles[5];
+    int64_t same_off, ms_off[5];
+    uint64_t image_off[5], total_bytes;
+};
+bool eval_plan(int W, int H, int flags, EvalPlan& p);          // false: MS-SSIM asked for a size where it is undefined
+hipError_t launch_eval_frame(const EvalPlan& p, const float* im, const float* depth, const float* sil, const float* gt, const float* gt_depth,
+                             float sil_thres, int flags, double* row, void* scratch, hipStream_t st);
 uint64_t compact_scratch_bytes(int64_t n);
 hipError_t launch_compact_index(int64_t n, const uint8_t* keep, uint32_t* src_index, uint32_t* d_count, void* scratch, hipStream_t st);
 hipError_t launch_gather_rows(int64_t n_out, int row_floats, const uint32_t* src_index, const float* src, float* dst, int64_t n_copy, hipStream_t st);

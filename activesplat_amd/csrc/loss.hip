@@ -482,4 +482,319 @@ hipError_t launch_tracking_loss(int W, int H, const float* im, const float* gt, 
     return hipGetLastError();
 }
 
+// ---- map-quality evaluation of one frame (gs_eval_frame; the rules: include/gsplat_hip.h) ----
+// The reference's report_progress (src/mapper/splatam/utils/eval_helpers.py:211-245) and eval (:464-508) on one rendered frame: PSNR, the two depth
+// errors, SSIM with the loss' own window (same padding, slam_external.py:66-97) and the 5-scale MS-SSIM of the package eval imports (valid
+// window).  No float atomics and nothing read across workgroups inside a launch: every kernel writes one fp64 record per workgroup, and
+// eval_finish_kernel (one workgroup) adds all records in a fixed order -- thread t takes records t, t + 256, ... in index order, then a pairwise tree
+// in LDS -- so a row has the same bits on every run.
+//   eval_sums_kernel        : per-channel sum (d im)^2, sum |d depth| valid, sum (d depth)^2 valid, count of gt_depth > 0; the terms are fp32 (two
+//                             roundings each), the accumulation fp64
+//   eval_ssim_kernel<V, R>  : loss_stats_kernel's tile + halo in LDS, separable 11-tap passes, CENTRED moments; per workgroup the sums of the ssim and
+//                             cs maps of its 16 x 16 outputs.  V: valid window (no padding, output (w - 10) x (h - 10)), else zero padding 5.
+//                             R: level 0 -- reads the frame itself and applies the masks on load (no masked copy of the frame exists)
+//   eval_pool_kernel<R>     : avg_pool2d(kernel 2, padding = size % 2) of both images: the zero padding counts, the divisor is always 4
+// the reference's window to the bit: exp(-(i - 5)^2 / 4.5) rounded to fp32 and normalised in fp32 (slam_external.py:54-56).  Its taps sum to
+// 1 - 3.1e-8; kWin above (eight printed digits) is up to one ulp per tap away, which moves an SSIM by some 1e-7: enough to matter to a metric
+// that is compared at 1e-6, so the evaluation kernels carry their own copy and the loss keeps its constants
+__device__ __constant__ float kEvalWin[11] = {1.028380124e-03f, 7.598758209e-03f, 3.600077331e-02f, 1.093606874e-01f, 2.130055279e-01f, 2.660117149e-01f,
+                                              2.130055279e-01f, 1.093606874e-01f, 3.600077331e-02f, 7.598758209e-03f, 1.028380124e-03f};
+constexpr float kEvalWinDeficit = 6.2398611e-08f;         // 1 - (sum of kEvalWin)^2
+constexpr int kEvalSums = 6;                // doubles per record of the sums pass (padded to 8)
+constexpr int kEvalRecord = 8;
+
+__device__ __forceinline__ float eval_image_mask(size_t o, const float* __restrict__ gt_depth, const float* __restrict__ sil, float sil_thres, int flags)
+{
+    float m = 1.0f;
+    if (flags & GS_EVAL_IMAGE_VALID_MASK) m *= gt_depth[o] > 0.0f ? 1.0f : 0.0f;
+    if (flags & GS_EVAL_SIL_MASK) m *= sil[o] > sil_thres ? 1.0f : 0.0f;
+    return m;
+}
+
+// pairwise tree over the workgroup's kBlock values of each of K sums (s_tree: K * kBlock doubles of LDS); every thread gets the totals
+template <int K>
+__device__ __forceinline__ void eval_block_tree(double (&a)[K], double* s_tree)
+{
+    const int tid = threadIdx.x;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) s_tree[k * kBlock + tid] = a[k];
+    __syncthreads();
+    for (int h = kBlock / 2; h > 0; h >>= 1) {
+        if (tid < h) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) s_tree[k * kBlock + tid] += s_tree[k * kBlock + tid + h];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) a[k] = s_tree[k * kBlock];
+}
+
+__global__ __launch_bounds__(kBlock) void eval_sums_kernel(int64_t npix, const float* __restrict__ im, const float* __restrict__ depth,
+                                                           const float* __restrict__ sil, const float* __restrict__ gt,
+                                                           const float* __restrict__ gt_depth, float sil_thres, int flags,
+                                                           double* __restrict__ partial)
+{
+    __shared__ double s_tree[kEvalSums * kBlock];
+    double a[kEvalSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < npix; i += stride) {
+        const float g = gt_depth[i];
+        const float valid = g > 0.0f ? 1.0f : 0.0f;
+        const float presence = (flags & GS_EVAL_SIL_MASK) ? (sil[i] > sil_thres ? 1.0f : 0.0f) : 1.0f;       // strict, as the reference's mask
+        const float m = (flags & GS_EVAL_IMAGE_VALID_MASK) ? presence * valid : presence;
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            const float d = (im[ch * npix + i] - gt[ch * npix + i]) * m;       // (im m - gt m of the reference, m in {0, 1}: the same float)
+            const float sq = d * d;
+            a[ch] += (double)sq;
+        }
+        const float dd = (depth[i] - g) * presence;        // products, not selects: a NaN under a zero mask stays a NaN, as in torch
+        const float l1 = fabsf(dd) * valid, l2 = dd * dd;
+        a[3] += (double)l1;
+        a[4] += (double)(l2 * valid);
+        a[5] += (double)valid;
+    }
+    eval_block_tree<kEvalSums>(a, s_tree);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < kEvalSums; ++k) partial[(int64_t)blockIdx.x * kEvalRecord + k] = a[k];
+    }
+}
+
+// partial: [3][tiles][2] doubles = (sum of 1 - ssim, sum of 1 - cs) over the workgroup's outputs
+template <bool kValid, bool kRaw>
+__global__ __launch_bounds__(kBlock) void eval_ssim_kernel(int W, int H, const float* __restrict__ x, const float* __restrict__ y,
+                                                           const float* __restrict__ gt_depth, const float* __restrict__ sil, float sil_thres,
+                                                           int flags, double* __restrict__ partial)
+{
+    __shared__ float s_x[kLP][kLP + 1];
+    __shared__ float s_y[kLP][kLP + 1];
+    __shared__ float s_h[5][kLP][kLT + 1];
+    __shared__ double s_tree[2 * kBlock];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int x0 = blockIdx.x * kLT, y0 = blockIdx.y * kLT;
+    const int OW = kValid ? W - 2 * kLH : W, OH = kValid ? H - 2 * kLH : H;
+    const int off = kValid ? 0 : kLH;                       // staged element (r, c) is input pixel (y0 + r - off, x0 + c - off)
+    const bool inside = x0 + tx < OW && y0 + ty < OH;
+    const size_t HW = (size_t)W * H;
+    const int ch = blockIdx.z;
+    constexpr int kStage = (kLP * kLP + kBlock - 1) / kBlock;
+    float vx[kStage], vy[kStage];
+    // the pivot of the centred moments: the target at the tile's first output pixel (x0 < OW <= W, y0 < OH <= H)
+    const size_t po = (size_t)y0 * W + x0;
+    const float pivot = y[ch * HW + po] * (kRaw ? eval_image_mask(po, gt_depth, sil, sil_thres, flags) : 1.0f);
+#pragma unroll
+    for (int it = 0; it < kStage; it++) {
+        const int e = tid + it * kBlock;
+        const int r = e / kLP, c = e - r * kLP;
+        const int gx = x0 + c - off, gy = y0 + r - off;
+        const bool in = e < kLP * kLP && gx >= 0 && gx < W && gy >= 0 && gy < H;
+        const size_t p = (size_t)(in ? gy : 0) * W + (in ? gx : 0);
+        const float m = kRaw ? eval_image_mask(p, gt_depth, sil, sil_thres, flags) : 1.0f;
+        vx[it] = x[ch * HW + p] * m; vy[it] = y[ch * HW + p] * m;
+        if (!in) { vx[it] = 0.f; vy[it] = 0.f; }
+    }
+#pragma unroll
+    for (int it = 0; it < kStage; it++) {
+        const int e = tid + it * kBlock;
+        if (e < kLP * kLP) { const int r = e / kLP, c = e - r * kLP; s_x[r][c] = vx[it] - pivot; s_y[r][c] = vy[it] - pivot; }
+    }
+    __syncthreads();
+    for (int e = tid; e < kLP * kLT; e += kBlock) {
+        const int r = e / kLT, c = e - r * kLT;
+        float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, dd = 0.f;
+#pragma unroll
+        for (int k = 0; k < 11; k++) {
+            const float w = kEvalWin[k], xv = s_x[r][c + k], yv = s_y[r][c + k], dv = xv - yv;
+            a += w * xv; b += w * yv; aa += w * xv * xv; bb += w * yv * yv; dd += w * dv * dv;
+        }
+        s_h[0][r][c] = a; s_h[1][r][c] = b; s_h[2][r][c] = aa; s_h[3][r][c] = bb; s_h[4][r][c] = dd;
+    }
+    __syncthreads();
+    float n1 = 0.f, n2 = 0.f, e11 = 0.f, e22 = 0.f, edd = 0.f;
+#pragma unroll
+    for (int k = 0; k < 11; k++) {
+        const float w = kEvalWin[k];
+        n1 += w * s_h[0][ty + k][tx]; n2 += w * s_h[1][ty + k][tx]; e11 += w * s_h[2][ty + k][tx];
+        e22 += w * s_h[3][ty + k][tx]; edd += w * s_h[4][ty + k][tx];
+    }
+    double a[2] = {0.0, 0.0};
+    if (inside) {
+        // as in loss_stats_kernel: 1 - cs = var(x - y) / B2 and 1 - ssim = (B1 var(x - y) + A2 (mu1 - mu2)^2) / (B1 B2), both exactly 0 for x == y
+        const float c1 = 0.0001f, c2 = 0.0009f;
+        const float dm = n1 - n2, vd = edd - dm * dm;
+        const float m1 = n1 + pivot, m2 = n2 + pivot;
+        // kEvalWin's taps sum to 1 - 3.1e-8, the 2-D window to S = 1 - kEvalWinDeficit, and the reference's sum w x^2 - (sum w x)^2 is not
+        // shift-invariant then: with x = x' + c it is the centred variance + 2 c (1 - S) sum w x' + c^2 S (1 - S).  The last term is 1.5e-8
+        // against variances of a few 1e-3 -- 1e-6 of an SSIM of 0.8 -- so the centred sums get it back.  (var(x - y) has no such term.)
+        const float shift = 2.f * pivot * kEvalWinDeficit * ((n1 + n2) + pivot * (1.0f - kEvalWinDeficit));
+        const float B2 = ((e11 - n1 * n1) + (e22 - n2 * n2) + shift) + c2, A2 = B2 - vd;
+        const float B1 = m1 * m1 + m2 * m2 + c1;
+        a[0] = (double)((B1 * vd + A2 * (dm * dm)) / (B1 * B2));        // what is summed is 1 - value: small terms, not values near 1
+        a[1] = (double)(vd / B2);
+    }
+    eval_block_tree<2>(a, s_tree);
+    if (tid == 0) {
+        double* out = partial + ((size_t)ch * gridDim.x * gridDim.y + (size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2;
+        out[0] = a[0]; out[1] = a[1];
+    }
+}
+
+template <bool kRaw>
+__global__ __launch_bounds__(kBlock) void eval_pool_kernel(int W, int H, int W2, int H2, const float* __restrict__ x, const float* __restrict__ y,
+                                                           const float* __restrict__ gt_depth, const float* __restrict__ sil, float sil_thres,
+                                                           int flags, float* __restrict__ ox, float* __restrict__ oy)
+{
+    const int64_t n2 = (int64_t)W2 * H2;
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= 3 * n2) return;
+    const int ch = (int)(i / n2);
+    const int64_t q = i - ch * n2;
+    const int oyi = (int)(q / W2), oxi = (int)(q - (int64_t)oyi * W2);
+    const int bx = 2 * oxi - (W & 1), by = 2 * oyi - (H & 1);
+    const size_t HW = (size_t)W * H;
+    float sx = 0.f, sy = 0.f;
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            const int gx = bx + k, gy = by + j;
+            if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+                const size_t p = (size_t)gy * W + gx;
+                const float m = kRaw ? eval_image_mask(p, gt_depth, sil, sil_thres, flags) : 1.0f;
+                sx += x[ch * HW + p] * m; sy += y[ch * HW + p] * m;
+            }
+        }
+    ox[i] = sx * 0.25f; oy[i] = sy * 0.25f;
+}
+
+// a thread's share of the `records` doubles at part[r * stride]: its records in index order
+__device__ __forceinline__ double eval_thread_sum(const double* __restrict__ part, int64_t records, int stride)
+{
+    double a = 0.0;
+    for (int64_t r = threadIdx.x; r < records; r += kBlock) a += part[r * stride];
+    return a;
+}
+
+// All totals of a row in ONE tree: 6 sums, 3 same-window SSIM sums, 15 MS-SSIM sums.  (A tree per total -- 24 trees, some 240 barriers -- took
+// 33 us of a 96 us call at 256 x 256; the additions of every total and their order are the same here.)
+constexpr int kEvalTotals = kEvalSums + 3 + 15;
+
+__global__ __launch_bounds__(kBlock) void eval_finish_kernel(EvalPlan p, int flags, const double* __restrict__ partial, double* __restrict__ row)
+{
+    __shared__ double s_tree[kEvalTotals * kBlock];
+    double s[kEvalTotals];
+#pragma unroll
+    for (int k = 0; k < kEvalSums; ++k) s[k] = eval_thread_sum(partial + k, p.sums_records, kEvalRecord);
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        s[kEvalSums + ch] = (flags & GS_EVAL_SSIM) ? eval_thread_sum(partial + p.same_off + (int64_t)ch * p.same_tiles * 2, p.same_tiles, 2) : 0.0;
+#pragma unroll
+        for (int l = 0; l < 5; l++)       // levels 0-3 contribute cs (the second double of a record), level 4 ssim
+            s[kEvalSums + 3 + ch * 5 + l] = (flags & GS_EVAL_MS_SSIM)
+                ? eval_thread_sum(partial + p.ms_off[l] + (int64_t)ch * p.ms_tiles[l] * 2 + (l < 4 ? 1 : 0), p.ms_tiles[l], 2) : 0.0;
+    }
+    eval_block_tree<kEvalTotals>(s, s_tree);
+    if (threadIdx.x != 0) return;
+    const double nan = __builtin_nan("");
+    const double npix = (double)p.w[0] * (double)p.h[0];
+    double psnr = 0.0;
+    for (int ch = 0; ch < 3; ch++) psnr += 20.0 * log10(1.0 / sqrt(s[ch] / npix));          // calc_psnr(...).mean(): the mean of three values in dB
+    double ssim = nan, ms = nan;
+    if (flags & GS_EVAL_SSIM) ssim = 1.0 - ((s[kEvalSums] + s[kEvalSums + 1]) + s[kEvalSums + 2]) / (3.0 * npix);      // (what was summed is 1 - value)
+    if (flags & GS_EVAL_MS_SSIM) {
+        const double wgt[5] = {0.0448, 0.2856, 0.3001, 0.2363, 0.1333};
+        ms = 0.0;
+        for (int ch = 0; ch < 3; ch++) {
+            double prod = 1.0;
+            for (int l = 0; l < 5; l++) {
+                // the spatial mean over the valid window's outputs, clamped at 0
+                const double n = (double)(p.w[l] - 2 * kLH) * (double)(p.h[l] - 2 * kLH);
+                const double t = 1.0 - s[kEvalSums + 3 + ch * 5 + l] / n;
+                prod *= pow(t > 0.0 ? t : 0.0, wgt[l]);
+            }
+            ms += prod;
+        }
+        ms /= 3.0;
+    }
+    row[0] = psnr / 3.0;
+    row[1] = s[3] / s[5];            // the reference's "Depth RMSE": sum sqrt(d^2) valid / sum valid -- the L1 error again
+    row[2] = s[3] / s[5];
+    row[3] = ssim;
+    row[4] = ms;
+    row[5] = s[5];
+    row[6] = sqrt(s[4] / s[5]);      // the root of the mean square (not a reference quantity)
+    row[7] = 0.0;
+}
+
+static int eval_tiles(int w, int h, bool valid)
+{
+    const int ow = valid ? w - 2 * kLH : w, oh = valid ? h - 2 * kLH : h;
+    return ((ow + kLT - 1) / kLT) * ((oh + kLT - 1) / kLT);
+}
+
+bool eval_plan(int W, int H, int flags, EvalPlan& p)
+{
+    p = EvalPlan();
+    p.w[0] = W; p.h[0] = H;
+    p.ms_defined = (W < H ? W : H) > 160 ? 1 : 0;           // (11 - 1) * 2^4: the smallest side must leave an 11-tap window at level 4
+    p.levels = 1;
+    const int64_t npix = (int64_t)W * H;
+    const int64_t g = (npix + 4 * kBlock - 1) / (4 * kBlock);
+    p.sums_records = (int)(g > kBlock ? kBlock : g);
+    int64_t d = (int64_t)p.sums_records * kEvalRecord;       // doubles so far
+    if (flags & GS_EVAL_SSIM) { p.same_tiles = eval_tiles(W, H, false); p.same_off = d; d += (int64_t)p.same_tiles * 6; }
+    if (flags & GS_EVAL_MS_SSIM) {
+        if (!p.ms_defined) return false;
+        p.levels = 5;
+        for (int l = 0; l < 5; l++) {
+            if (l) { p.w[l] = p.w[l - 1] / 2 + (p.w[l - 1] & 1); p.h[l] = p.h[l - 1] / 2 + (p.h[l - 1] & 1); }
+            p.ms_tiles[l] = eval_tiles(p.w[l], p.h[l], true); p.ms_off[l] = d; d += (int64_t)p.ms_tiles[l] * 6;
+        }
+    }
+    uint64_t bytes = (uint64_t)d * 8u;
+    for (int l = 1; l < p.levels; l++) { p.image_off[l] = bytes; bytes += (uint64_t)6 * p.w[l] * p.h[l] * sizeof(float); }
+    p.total_bytes = bytes;
+    return true;
+}
+
+hipError_t launch_eval_frame(const EvalPlan& p, const float* im, const float* depth, const float* sil, const float* gt, const float* gt_depth,
+                             float sil_thres, int flags, double* row, void* scratch, hipStream_t st)
+{
+    const int W = p.w[0], H = p.h[0];
+    double* partial = (double*)scratch;
+    hipLaunchKernelGGL(eval_sums_kernel, dim3(p.sums_records), dim3(kBlock), 0, st, (int64_t)W * H, im, depth, sil, gt, gt_depth, sil_thres, flags,
+                       partial);
+    if (flags & GS_EVAL_SSIM)
+        hipLaunchKernelGGL((eval_ssim_kernel<false, true>), dim3((W + kLT - 1) / kLT, (H + kLT - 1) / kLT, 3), dim3(kBlock), 0, st, W, H, im, gt,
+                           gt_depth, sil, sil_thres, flags, partial + p.same_off);
+    if (flags & GS_EVAL_MS_SSIM) {
+        const float *x = im, *y = gt;
+        for (int l = 0; l < 5; l++) {
+            const int w = p.w[l], h = p.h[l];
+            const dim3 grid((w - 2 * kLH + kLT - 1) / kLT, (h - 2 * kLH + kLT - 1) / kLT, 3);
+            if (l == 0)
+                hipLaunchKernelGGL((eval_ssim_kernel<true, true>), grid, dim3(kBlock), 0, st, w, h, x, y, gt_depth, sil, sil_thres, flags,
+                                   partial + p.ms_off[l]);
+            else
+                hipLaunchKernelGGL((eval_ssim_kernel<true, false>), grid, dim3(kBlock), 0, st, w, h, x, y, gt_depth, sil, sil_thres, flags,
+                                   partial + p.ms_off[l]);
+            if (l == 4) break;
+            const int w2 = p.w[l + 1], h2 = p.h[l + 1];
+            float* ox = (float*)((char*)scratch + p.image_off[l + 1]);
+            float* oy = ox + (size_t)3 * w2 * h2;
+            const unsigned nb = (unsigned)(((int64_t)3 * w2 * h2 + kBlock - 1) / kBlock);
+            if (l == 0)
+                hipLaunchKernelGGL((eval_pool_kernel<true>), dim3(nb), dim3(kBlock), 0, st, w, h, w2, h2, x, y, gt_depth, sil, sil_thres, flags, ox, oy);
+            else
+                hipLaunchKernelGGL((eval_pool_kernel<false>), dim3(nb), dim3(kBlock), 0, st, w, h, w2, h2, x, y, gt_depth, sil, sil_thres, flags, ox, oy);
+            x = ox; y = oy;
+        }
+    }
+    hipLaunchKernelGGL(eval_finish_kernel, dim3(1), dim3(kBlock), 0, st, p, flags, (const double*)partial, row);
+    return hipGetLastError();
+}
+
 }  // namespace gs

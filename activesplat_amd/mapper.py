@@ -24,6 +24,9 @@ habitat).  It reproduces the CALL PATTERN and SCHEDULE of the hot loop, nothing 
                                   device too (visibility.high_loss_grid: the mask and its resize to one pixel per degree in one
                                   launch; visibility.grid_dbscan), and `high_loss_samples_pose_c2w` resolves the look target
                                   (__init__.py:216-250) from one small copy when it is first read
+  frame 0 and frames with (id+1) % report_global_progress_every == 0, when they ran iterations, `report_progress` on
+                                : report_progress(mapping=True) of the frame (__init__.py:499-505): PSNR, "Depth RMSE", depth L1 -- one render and
+                                  one library call into the table `progress` (evaluate.MapEvaluator; rows are read when the caller asks for them)
   every frame, `judge` set      : the completion / accuracy judge of scripts/judges/eval_actions.py on the frame's sensor depth at its
                                   ground-truth pose (judge.CompletionJudge.add_frame; rows are read when the caller asks for them)
 
@@ -65,6 +68,9 @@ DEFAULT_CONFIG = dict(
     high_loss_samples=True,  # the per-frame no-grad render of get_high_loss_samples (__init__.py:184-258) before mapping a frame
     high_loss_target=False,  # ... and the rest of get_high_loss_samples on the device (gs_high_loss_grid + gs_grid_dbscan): the look target of the
                              # frame is then `SplatMapper.high_loss_samples_pose_c2w`, resolved from one small copy when it is read
+    report_progress=False,   # report_progress(mapping=True) after the iterations of frame 0 and of every report_global_progress_every-th frame
+                             # (eval_helpers.py:153-264): one row of `SplatMapper.progress` per reported frame.  Off: run() issues what it issued without the key
+    report_global_progress_every=100,
     cluster_invisibility_threshold=25,   # config/datasets/gibson.json:60
     high_loss_fov=(90, 90),  # (hfov, vfov) of get_high_loss_samples: the grid has one pixel per degree
     mapping=dict(
@@ -122,6 +128,9 @@ class SplatMapper:
         #: frame.get("path_length", 0.0) to judge.add_frame -- three library calls, no host wait.  The poses are relative to frame 0's
         #: camera, so the judge's samples must be given in that frame; transforming a mesh into it is the caller's work.
         self.judge = None
+        #: evaluate.MapEvaluator of the reported frames (config report_progress; None until the first report) and their frame ids
+        self.progress = None
+        self.progress_frames = []
 
     @property
     def last_losses(self):
@@ -302,6 +311,8 @@ class SplatMapper:
         if iter_per_frame > 0:
             self.stats["frames"] += 1
             self.stats["frame_time"] += time.perf_counter() - t_frame
+            if cfg.get("report_progress", False) and (fid == 0 or (fid + 1) % int(cfg["report_global_progress_every"]) == 0):
+                self.report_progress(fid, color, depth)
         with torch.no_grad():
             # the simulator's pose when the caller hands one over (run_raw), the pose written into the camera parameters otherwise
             # (tracking: the frame's own pose -- the parameters hold the estimate)
@@ -312,6 +323,28 @@ class SplatMapper:
                 self.keyframe_list.append({"id": fid, "est_w2c": self._w2c(fid), "color": color, "depth": depth})
             self.gt_w2c_all_frames.append(gt_w2c)
         return self.params
+
+    @torch.no_grad()
+    def report_progress(self, fid, color, depth):
+        """report_progress(mapping=True) of frame `fid` (eval_helpers.py:211-245: no silhouette mask, images not masked by the depth): one fused render
+        at the frame's pose column and one gs_eval_frame into `progress`.  Only enqueues work."""
+        from . import evaluate as E
+        if self.progress is None:
+            every = max(1, int(self.cfg["report_global_progress_every"]))
+            self.progress = E.MapEvaluator(self.W, self.H, int(self.cfg["step_num"]) // every + 2, device=self.device)
+        host = self._pose_host.get(int(fid)) if self._poses_fixed else None      # (an optimised pose is read from the parameters: one small copy)
+        pose7 = None if host is None else [float(v) for v in F.normalize(host[0].view(1, 4)).view(4).tolist()] + [float(v) for v in host[1].tolist()]
+        im, rdepth, sil = E.render_frame(self.params, self.cam, fid, pose7)
+        self.progress.add_frame(im.contiguous(), rdepth.contiguous(), sil.contiguous(), color.contiguous(), depth.contiguous(),
+                                self.cfg["mapping"]["sil_thres"], sil_mask=False, image_valid_mask=False, ssim=False, ms_ssim=False)
+        self.progress_frames.append(int(fid))
+
+    def evaluate(self, frames, eval_every=1, ssim=True, ms_ssim=True):
+        """The reference's end-of-run `eval` of this mapper's map over `frames` (evaluate.evaluate_map) -> its dict."""
+        from . import evaluate as E
+        mc = self.cfg["mapping"]
+        return E.evaluate_map(self.params, frames, self._k_host, self.first_frame_w2c, mc["sil_thres"], self.cfg["mapping_iters"],
+                              mc["add_new_gaussians"], eval_every=eval_every, ssim=ssim, ms_ssim=ms_ssim)
 
     @torch.no_grad()
     def high_loss_step(self, view_w2c, gt_depth, tracked=False):

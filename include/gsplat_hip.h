@@ -181,7 +181,7 @@ const char* gs_version(void);
 /* Integer version of THIS binary interface: bumped whenever an entry point's argument list or a published record layout changes (e.g.
  * the seed argument of gs_densify_children, the 40-byte SH Jacobian record).  A host binding compares it with the GS_ABI_VERSION it was
  * written against before the first call, so that a stale prebuilt library fails at load time instead of misreading its arguments. */
-#define GS_ABI_VERSION 18
+#define GS_ABI_VERSION 19
 int32_t gs_abi_version(void);
 
 /* Optional per-stage timing (hipEvents recorded on the caller's stream around each stage's launches).
@@ -731,6 +731,50 @@ int gs_cloud_nearest(int64_t n_query, const float* query, const uint8_t* query_v
 uint64_t gs_completion_row_scratch_bytes(void);
 int gs_completion_row(int64_t n_samples, const float* min_dist, int64_t n_acc, const float* acc_dist, const uint8_t* acc_valid,
                       double path_length, double* row6, void* scratch, gs_stream_t stream);
+
+/* ---- Map-quality evaluation of one frame (report_progress, src/mapper/splatam/utils/eval_helpers.py:211-245, and eval, :464-508) ----
+ * im / gt_im [3, height, width], depth / silhouette / gt_depth [height, width]: fp32, DEVICE, contiguous.  The reference's two masks are applied on
+ * load: valid = gt_depth > 0, presence = silhouette > sil_thres (strict).  flags:
+ *   GS_EVAL_SIL_MASK          image and depth differences are multiplied by presence (eval with mapping_iters == 0 and no new Gaussians;
+ *                             report_progress(tracking=True))
+ *   GS_EVAL_IMAGE_VALID_MASK  both images are multiplied by valid (eval does, report_progress does not)
+ *   GS_EVAL_SSIM              column 3,  GS_EVAL_MS_SSIM  column 4 (a column whose flag is off is NaN)
+ * Writes eight doubles at the DEVICE address row (8-byte aligned); with D = (depth - gt_depth) [presence], N = width * height:
+ *   0 psnr           the MEAN of the three per-channel values 20 log10(1 / sqrt(mse_c)), mse_c = sum (im_c - gt_c)^2 [masks] / N
+ *                    (calc_psnr(...).mean(), slam_external.py: not the PSNR of the mean error)
+ *   1 depth_rmse     the reference's "Depth RMSE": sum sqrt(D^2) valid / sum valid.  This IS the mean absolute error -- the root is taken per
+ *                    pixel -- and equals column 2 in every mode; it is kept because the reference writes both files (rmse.txt, l1.txt)
+ *   2 depth_l1       sum |D| valid / sum valid
+ *   3 ssim           the mean SSIM map of the masked pair with the mapping loss' window (calc_ssim, slam_external.py:66-97: 11 taps, sigma 1.5,
+ *                    zero padding 5, C1 = 0.01^2, C2 = 0.03^2)
+ *   4 ms_ssim        the five-scale MS-SSIM of the masked pair to the PUBLISHED definition of the package the reference imports (not installed
+ *                    here, so this column is not pinned to it): the same window as a VALID convolution; cs = (2 s12 + C2) / (s1 + s2 + C2),
+ *                    ssim = (2 m1 m2 + C1) / (m1^2 + m2^2 + C1) cs; per channel the spatial means, clamped at 0; levels 0-3 contribute cs, level 4
+ *                    ssim, with the powers 0.0448, 0.2856, 0.3001, 0.2363, 0.1333; the product, then the mean over the channels.  Between levels:
+ *                    2 x 2 mean pooling with zero padding size % 2 on each axis, the padding counted (divisor 4), size n -> n / 2 + n % 2.
+ *                    Defined for min(width, height) > 160
+ *   5 valid_pixels   the count of gt_depth > 0
+ *   6 depth_rmse_l2  sqrt(sum D^2 valid / sum valid): the root of the mean square.  NOT a reference quantity
+ *   7 reserved, 0
+ * Every term is formed in fp32 and added in fp64; no float atomics; every final sum is a fixed-order reduction (one record per workgroup, one
+ * finishing workgroup), so two calls on the same inputs give the same bits.  Divisions are IEEE, as torch's: no valid pixel gives NaN in columns
+ * 1, 2 and 6, identical images give +inf dB.  LPIPS is not provided.
+ * gs_eval_frame_layout fills the layout for (width, height, flags): scratch bytes, the level sizes, and whether MS-SSIM is defined for the size.
+ * scratch: DEVICE, total_bytes bytes, 8-byte aligned.  1 <= width, height <= 16384; GS_EVAL_MS_SSIM on a size where it is undefined, an unknown
+ * flag or a null pointer is GS_EINVAL and nothing is launched. */
+#define GS_EVAL_SIL_MASK 1
+#define GS_EVAL_IMAGE_VALID_MASK 2
+#define GS_EVAL_SSIM 4
+#define GS_EVAL_MS_SSIM 8
+typedef struct GsEvalLayout {
+    uint64_t total_bytes;
+    int32_t ms_ssim_defined;      /* min(width, height) > 160 */
+    int32_t levels;               /* 5 with GS_EVAL_MS_SSIM, else 1 */
+    int32_t level_width[5], level_height[5];
+} GsEvalLayout;
+int gs_eval_frame_layout(int32_t width, int32_t height, int32_t flags, GsEvalLayout* layout);
+int gs_eval_frame(int32_t width, int32_t height, const float* im, const float* depth, const float* silhouette, const float* gt_im,
+                  const float* gt_depth, float sil_thres, int32_t flags, double* row, void* scratch, gs_stream_t stream);
 
 #ifdef __cplusplus
 }
