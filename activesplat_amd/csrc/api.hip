@@ -1251,6 +1251,7 @@ int gs_grow_gaussians(int32_t width, int32_t height, const float* render_depth, 
     if (width <= 0 || height <= 0 || !render_depth || !silhouette || !gt_depth || !color || !h_intrinsics4 || !h_c2w12 ||
         !out_means3D || !out_rgb_colors || !out_unnorm_rotations || !out_logit_opacities || !out_log_scales || !d_counts || !scratch)
         return fail(GS_EINVAL, "gs_grow_gaussians: bad argument");
+    if ((int64_t)width * height >= ((int64_t)1 << 31)) return fail(GS_EINVAL, "gs_grow_gaussians: bad image size");     // (the median select's 32-bit rank)
     hipError_t e = gs::launch_grow(width, height, render_depth, silhouette, gt_depth, color, h_intrinsics4, h_c2w12, sil_thres,
                                    isotropic != 0, out_means3D, out_rgb_colors, out_unnorm_rotations, out_logit_opacities,
                                    out_log_scales, d_counts, scratch, (hipStream_t)stream);

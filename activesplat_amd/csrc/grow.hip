@@ -7,9 +7,10 @@
 //      non_presence = sil < thr  |  (render > gt  &  err > 2 median(err)  &  sil > thr  &  gt < 5)
 //    every non_presence pixel with valid depth becomes a Gaussian: mean = c2w * ((u-cx)/fx z, (v-cy)/fy z, z), colour =
 //    pixel RGB, rotation (1,0,0,0), logit opacity 0, log scale = log(sqrt((z / ((fx+fy)/2))^2)).  The reference does this
-//    with ~40 torch launches, a device-wide sort for the median and boolean-mask gathers; here: one single-workgroup radix
-//    select (the image is only H*W <= a few 100k values), one mask kernel, the ordered compaction of compact.hip and one
-//    row-emitting kernel.  Row order = row-major pixel order, as boolean-mask indexing yields.
+//    with ~40 torch launches, a device-wide sort for the median and boolean-mask gathers; here: the exact radix
+//    select of the median that the loss' outlier rejection uses (loss.hip, a grid of workgroups), one mask kernel,
+//    the ordered compaction of compact.hip and one row-emitting kernel.  Row order = row-major pixel order, as
+//    boolean-mask indexing yields.
 // 2. keyframe_selection_overlap's scoring loop (src/mapper/splatam/utils/keyframe_selection.py:62-86): for every keyframe,
 //    the number of sampled world points that project inside its image with a 20 px border -- one workgroup per keyframe
 //    instead of ~12 torch launches and a blocking .sum() each.
@@ -17,61 +18,9 @@
 
 namespace gs {
 
-constexpr int kSelectThreads = 1024;
-constexpr int kSelectBins = 2048;
-
-__device__ __forceinline__ float depth_error(const float* __restrict__ gt, const float* __restrict__ rd, int64_t i)
-{
-    const float g = gt[i];
-    return fabsf(g - rd[i]) * (g > 0.0f ? 1.0f : 0.0f);
-}
-
-// torch.median of a flat tensor = the LOWER median, element (n-1)/2 of the sorted values.  err >= 0, so the order of the
-// floats is the order of their bit patterns: three histogram passes (11 + 11 + 10 bits) pin the value exactly.
-// NaN rule: torch.median propagates NaN -- if ANY error is NaN (a NaN in either depth image, or inf * 0 where gt <= 0) the median is NaN,
-// `err > 2 median` is false everywhere and only the silhouette candidates remain.  The first pass raises a flag for it (a NaN's bit pattern
-// would otherwise be counted as the largest value and a finite median come out).
-__global__ __launch_bounds__(kSelectThreads) void grow_median_kernel(int64_t n, const float* __restrict__ gt,
-                                                                      const float* __restrict__ rd, float* __restrict__ d_median)
-{
-    __shared__ uint32_t s_hist[kSelectBins];
-    __shared__ uint32_t s_prefix, s_mask;
-    __shared__ uint64_t s_k;
-    __shared__ uint32_t s_nan;
-    const int tid = threadIdx.x;
-    if (tid == 0) { s_prefix = 0u; s_mask = 0u; s_k = (uint64_t)((n - 1) / 2); s_nan = 0u; }
-    const int shifts[3] = {21, 10, 0};
-    const int widths[3] = {11, 11, 10};
-    for (int pass = 0; pass < 3; ++pass) {
-        for (int b = tid; b < kSelectBins; b += kSelectThreads) s_hist[b] = 0u;
-        __syncthreads();
-        const uint32_t prefix = s_prefix, mask = s_mask;
-        const int sh = shifts[pass];
-        const uint32_t bm = (1u << widths[pass]) - 1u;
-        for (int64_t i = tid; i < n; i += kSelectThreads) {
-            const float err = depth_error(gt, rd, i);
-            if (pass == 0 && err != err) s_nan = 1u;           // (every writer stores the same value)
-            const uint32_t bits = __float_as_uint(err);
-            if ((bits & mask) == prefix) atomicAdd(&s_hist[(bits >> sh) & bm], 1u);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            uint64_t k = s_k;
-            uint32_t b = 0;
-            for (; b < bm; ++b) {
-                const uint32_t c = s_hist[b];
-                if (k < c) break;
-                k -= c;
-            }
-            s_k = k;
-            s_prefix = prefix | (b << sh);
-            s_mask = mask | (bm << sh);
-        }
-        __syncthreads();
-    }
-    if (tid == 0) *d_median = s_nan ? __uint_as_float(0x7fc00000u) : __uint_as_float(s_prefix);
-}
-
+// The median of err: torch.median of a flat tensor = the LOWER median, propagating NaN -- the exact select of loss.hip (launch_depth_error_median,
+// shared with the loss' outlier rejection; depth_error itself is in gs_common.h).  If ANY error is NaN (a NaN in either depth image, or
+// inf * 0 where gt <= 0) the median is NaN, `err > 2 median` is false everywhere and only the silhouette candidates remain.
 __global__ __launch_bounds__(kBlock) void grow_mask_kernel(int64_t n, const float* __restrict__ gt, const float* __restrict__ rd,
                                                             const float* __restrict__ sil, const float* __restrict__ d_median,
                                                             float sil_thres, uint8_t* __restrict__ keep, uint32_t* __restrict__ d_candidates)
@@ -80,8 +29,7 @@ __global__ __launch_bounds__(kBlock) void grow_mask_kernel(int64_t n, const floa
     bool cand = false, take = false;
     if (i < n) {
         const float g = gt[i], r = rd[i], s = sil[i];
-        const float err = fabsf(g - r) * (g > 0.0f ? 1.0f : 0.0f);
-        const bool behind = (r > g) && (err > 2.0f * d_median[0]);
+        const bool behind = (r > g) && (depth_error(g, r) > 2.0f * d_median[0]);
         cand = (s < sil_thres) || (behind && (s > sil_thres) && (g < 5.0f));
         take = cand && (g > 0.0f);
         keep[i] = take ? 1 : 0;
@@ -129,8 +77,9 @@ __global__ __launch_bounds__(kBlock) void grow_rows_kernel(GrowCam c, int64_t np
 }
 
 uint64_t grow_scratch_bytes(int64_t npix)
-{   // keep mask | index list | median | compaction block sums
-    return (uint64_t)((npix + 255) / 256 * 256) + (uint64_t)npix * 4 + 256 + 64 * 64 + compact_scratch_bytes(npix) + 256;
+{   // keep mask | index list | median | candidate counters | the select's histograms | compaction block sums
+    return (uint64_t)((npix + 255) / 256 * 256) + (uint64_t)npix * 4 + 256 + 64 * 64 + (uint64_t)kMedianScratchWords * 4 +
+           compact_scratch_bytes(npix) + 256;
 }
 
 hipError_t launch_grow(int W, int H, const float* rd, const float* sil, const float* gt, const float* color, const float* k4,
@@ -142,10 +91,12 @@ hipError_t launch_grow(int W, int H, const float* rd, const float* sil, const fl
     uint32_t* index = (uint32_t*)(keep + (n + 255) / 256 * 256);
     float* med = (float*)(index + n);
     uint32_t* slots = (uint32_t*)(med + 64);                 // 64 lines of candidate counters
-    void* cscr = (void*)(slots + 64 * 16);
+    uint32_t* hists = slots + 64 * 16;
+    void* cscr = (void*)(hists + kMedianScratchWords);
     hipError_t e = hipMemsetAsync(slots, 0, 64 * 64, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(grow_median_kernel, dim3(1), dim3(kSelectThreads), 0, st, n, gt, rd, med);
+    e = launch_depth_error_median(n, rd, gt, hists, med, 0, st);
+    if (e != hipSuccess) return e;
     const int nb = (int)((n + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(grow_mask_kernel, dim3(nb), dim3(kBlock), 0, st, n, gt, rd, sil, (const float*)med, sil_thres, keep, slots);
     hipLaunchKernelGGL(grow_sum_slots_kernel, dim3(1), dim3(kWave), 0, st, (const uint32_t*)slots, d_counts);
@@ -357,33 +308,17 @@ hipError_t launch_cloud_nearest(int64_t Q, const float* query, const uint8_t* qv
     return hipGetLastError();
 }
 
-// The judge's row (eval_actions.py:142-149).  Partial sums in fp64: every thread adds its elements in index order (stride = the grid), a pairwise
-// tree over the workgroup's kBlock partials in LDS, one record per workgroup; a second single-workgroup launch runs the same tree over the records.
+// The judge's row (eval_actions.py:142-149).  Partial sums in fp64: every thread adds its elements in index order (stride = the grid), the pairwise
+// tree of gs_common.h over the workgroup's kBlock partials, one record per workgroup; a second single-workgroup launch runs the same tree over the records.
 // The grid depends on the sizes alone, so the order of every addition is fixed.
 constexpr int kRowVals = 5;                 // sum min(1, d) | count d < 0.05 | sum d | sum of the accuracy distances | their count
 constexpr int kRowStride = 8;               // doubles per record
 constexpr int kRowGridMax = kBlock;         // the second launch reads one record per thread
 
-__device__ __forceinline__ void row_block_tree(double (&a)[kRowVals])
-{
-    __shared__ double s_row[kRowVals][kBlock];
-#pragma unroll
-    for (int k = 0; k < kRowVals; ++k) s_row[k][threadIdx.x] = a[k];
-    __syncthreads();
-    for (int h = kBlock / 2; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) {
-#pragma unroll
-            for (int k = 0; k < kRowVals; ++k) s_row[k][threadIdx.x] += s_row[k][threadIdx.x + h];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int k = 0; k < kRowVals; ++k) a[k] = s_row[k][0];
-}
-
 __global__ __launch_bounds__(kBlock) void completion_partial_kernel(int64_t N, const float* __restrict__ min_d, int64_t P, const float* __restrict__ acc_d,
                                                                      const uint8_t* __restrict__ acc_valid, double* __restrict__ partial)
 {
+    __shared__ double s_tree[kRowVals][kBlock];
     double a[kRowVals] = {0.0, 0.0, 0.0, 0.0, 0.0};
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < N; i += stride) {
@@ -395,7 +330,7 @@ __global__ __launch_bounds__(kBlock) void completion_partial_kernel(int64_t N, c
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < P; i += stride) {
         if (acc_valid == nullptr || acc_valid[i] != 0) { a[3] += (double)acc_d[i]; a[4] += 1.0; }
     }
-    row_block_tree(a);
+    block_tree_sum(a, s_tree);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < kRowVals; ++k) partial[(int64_t)blockIdx.x * kRowStride + k] = a[k];
@@ -405,12 +340,13 @@ __global__ __launch_bounds__(kBlock) void completion_partial_kernel(int64_t N, c
 __global__ __launch_bounds__(kBlock) void completion_finish_kernel(int records, const double* __restrict__ partial, int64_t N, double path_length,
                                                                     double* __restrict__ row)
 {
+    __shared__ double s_tree[kRowVals][kBlock];
     double a[kRowVals] = {0.0, 0.0, 0.0, 0.0, 0.0};
     if ((int)threadIdx.x < records) {
 #pragma unroll
         for (int k = 0; k < kRowVals; ++k) a[k] = partial[(int64_t)threadIdx.x * kRowStride + k];
     }
-    row_block_tree(a);
+    block_tree_sum(a, s_tree);
     if (threadIdx.x != 0) return;
     const double n = (double)N;
     row[0] = a[0] / n;                      // completion error, capped at 1 m

@@ -314,27 +314,50 @@ __device__ __forceinline__ void pose_grad_finish_block(int64_t nrows, const Pose
     out[4] = (float)t[0]; out[5] = (float)t[1]; out[6] = (float)t[2];
 }
 
+// ---- fixed-order fp64 sums: the same bits on every run ----
+// A thread's share of `records` values at part[r * stride]: thread t adds records t, t + kBlock, ... in index order.
+__device__ __forceinline__ double strided_record_sum(const double* __restrict__ part, int64_t records, int stride)
+{
+    double a = 0.0;
+    for (int64_t r = threadIdx.x; r < records; r += kBlock) a += part[r * stride];
+    return a;
+}
+
+// Pairwise tree over the workgroup's kBlock values of each of K sums: halving from kBlock / 2, element t += element t + h.  Every thread of the
+// workgroup calls and gets the totals.  No barrier in front: a caller whose s_tree is still being read as something else puts one there.
+template <int K>
+__device__ __forceinline__ void block_tree_sum(double (&a)[K], double (&s_tree)[K][kBlock])
+{
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < K; ++k) s_tree[k][tid] = a[k];
+    __syncthreads();
+    for (int h = kBlock / 2; h > 0; h >>= 1) {
+        if (tid < h) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) s_tree[k][tid] += s_tree[k][tid + h];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) a[k] = s_tree[k][0];
+}
+
 // Tracking loss (loss.hip): one row of kTrackRow partial sums per workgroup -- {sum of masked |gt_depth - depth|, sum of |gt_im - im| over the
-// colour mask} -- reduced by tracking_loss_reduce in fp64, in a fixed order (thread t adds rows t, t + kBlock, ...; then a pairwise tree over the
-// kBlock partials in LDS), and weighted as the reference weights them in fp32: out = {w_depth d + w_im c, w_depth d, w_im c} (thread 0 only).
-// Every thread of the workgroup must call it.
+// colour mask} -- reduced by tracking_loss_reduce in fp64 in the fixed order above, and weighted as the reference weights them in fp32:
+// out = {w_depth d + w_im c, w_depth d, w_im c} (thread 0 only).  Every thread of the workgroup must call it.
 constexpr int kTrackRow = 2;
 __device__ __forceinline__ void tracking_loss_reduce(int64_t nrows, const float* __restrict__ rows, float w_im, float w_depth, float (&out)[3])
 {
-    __shared__ double s_l[kTrackRow][kBlock];
-    double a = 0.0, b = 0.0;
-    for (int64_t r = threadIdx.x; r < nrows; r += kBlock) { a += (double)rows[r * kTrackRow]; b += (double)rows[r * kTrackRow + 1]; }
-    s_l[0][threadIdx.x] = a; s_l[1][threadIdx.x] = b;
-    __syncthreads();
-    for (int h = kBlock / 2; h > 0; h >>= 1) {
-        if (threadIdx.x < h) { s_l[0][threadIdx.x] += s_l[0][threadIdx.x + h]; s_l[1][threadIdx.x] += s_l[1][threadIdx.x + h]; }
-        __syncthreads();
-    }
+    __shared__ double s_tree[kTrackRow][kBlock];
+    double s[kTrackRow] = {0.0, 0.0};
+    // (strided_record_sum's order for both columns in ONE pass: a row is one 8-byte load)
+    for (int64_t r = threadIdx.x; r < nrows; r += kBlock) { s[0] += (double)rows[r * kTrackRow]; s[1] += (double)rows[r * kTrackRow + 1]; }
+    block_tree_sum(s, s_tree);
     if (threadIdx.x != 0) return;
-    const double d = s_l[0][0], c = s_l[1][0];
     {
 #pragma clang fp contract(off)
-        const float wd = (float)d * w_depth, wc = (float)c * w_im;
+        const float wd = (float)s[0] * w_depth, wc = (float)s[1] * w_im;
         out[0] = wd + wc; out[1] = wd; out[2] = wc;
     }
 }
@@ -825,7 +848,15 @@ hipError_t launch_mapping_loss(int W, int H, const float* im, const float* gt, c
                                const float* gt_depth, float w_im, float w_depth, float* losses, float* dL_dim,
                                float* dL_ddepth, float* scratch, int64_t persistent_call, hipStream_t st, const float* d_median = nullptr);
 // (d_median != nullptr in the two launches above: the ignore_outlier_depth_loss instantiations, fed by the select below)
-// exact lower median of |gt_depth - depth| * (gt_depth > 0) over a grid of workgroups (loss.hip): three histograms of kMedianBins counts + the NaN flag
+// The depth error of ignore_outlier_depth_loss (splatam.py:220-228) and of map growth (:344-345): |gt - render| * (gt > 0).  The PRODUCT, not a
+// select: NaN * 0 and inf * 0 are NaN, as in torch, and torch.median hands a NaN on.  fp32 without contraction: what is compared with a multiple
+// of the median is torch's value, bit for bit.
+__device__ __forceinline__ float depth_error(float g, float d)
+{
+#pragma clang fp contract(off)
+    return fabsf(g - d) * (g > 0.0f ? 1.0f : 0.0f);
+}
+// its exact lower median over a grid of workgroups (loss.hip; the loss' outlier rejection and map growth): three histograms of kMedianBins counts + the NaN flag
 constexpr int kMedianBins = 2048;
 constexpr int kMedianScratchWords = 3 * kMedianBins + 16;
 constexpr int kMedianChunk = 2048;          // the automatic grid: one workgroup per kMedianChunk pixels, at most kMedianAutoGrid of them

@@ -71,20 +71,20 @@ __device__ __forceinline__ void acc_totals(const float* __restrict__ acc, float*
 // ---- ignore_outlier_depth_loss (src/mapper/splatam/splatam.py:220-228) ----
 //   err = |gt_depth - depth| * (gt_depth > 0),  keep = err < 10 * median(err)   (strict; torch.median over ALL pixels: the lower median, NaN as
 //   soon as one err is NaN).  The median is a DEVICE scalar of gs_depth_error_median; the kOutlier instantiations of the three loss kernels AND
-//   `keep` into their depth mask.  A median of 0 or NaN keeps nothing.  fp32 without contraction: the decision is torch's, bit for bit.
-__device__ __forceinline__ float outlier_depth_error(float g, float d)
-{
-#pragma clang fp contract(off)
-    return fabsf(g - d) * (g > 0.0f ? 1.0f : 0.0f);        // (the product: NaN * 0 and inf * 0 are NaN, as in torch)
-}
+//   `keep` into their depth mask.  A median of 0 or NaN keeps nothing.  err is depth_error (gs_common.h); fp32 without contraction: the decision is
+//   torch's, bit for bit.
 __device__ __forceinline__ bool outlier_keep(float g, float d, float median)
 {
 #pragma clang fp contract(off)
-    return outlier_depth_error(g, d) < 10.0f * median;
+    return depth_error(g, d) < 10.0f * median;
 }
+// the depth mask of the three loss kernels (splatam.py:231-234): a sensor depth, and neither the rendered depth nor its uncertainty a NaN
+__device__ __forceinline__ bool depth_measured(float g, float d, float unc) { return g > 0.0f && d == d && unc == unc; }
 
-// Exact select of the depth error's lower median over a GRID of workgroups.  err >= +0, so the floats order as their bit patterns do: three
-// passes over 11 + 11 + 10 bits pin the value (grow.hip's rule).  One launch per pass: a workgroup histograms its pixels in LDS and adds its
+// Exact select of the depth error's lower median (element (n - 1) / 2 of the sorted values) over a GRID of workgroups; map growth (grow.hip) calls it
+// too.  err >= +0, so the floats order as their bit patterns do: three passes over 11 + 11 + 10 bits pin the value.  A NaN's bit pattern would be
+// counted as the largest value and a finite median come out: the first pass raises a flag for it, and the pick returns NaN.
+// One launch per pass: a workgroup histograms its pixels in LDS and adds its
 // non-zero bins to the pass' global histogram with integer atomics (order-independent: the same bits on every run).  The workgroups of pass p + 1
 // each re-derive the prefix of pass p from that FINISHED histogram -- nothing is handed from workgroup to workgroup inside a launch, the
 // kernel boundary is the only synchronisation -- and a one-workgroup launch resolves the third pass.  A grid of 1 is the same code.
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(kMedThreads) void depth_median_kernel(int64_t n, co
     bool saw_nan = false;
     const int64_t stride = (int64_t)gridDim.x * kMedThreads;
     for (int64_t i = (int64_t)blockIdx.x * kMedThreads + tid; i < n; i += stride) {
-        const float err = outlier_depth_error(gt_depth[i], depth[i]);
+        const float err = depth_error(gt_depth[i], depth[i]);
         if (kPass == 0 && err != err) saw_nan = true;
         const uint32_t bits = __float_as_uint(err);
         if ((bits & p.mask) == p.prefix) atomicAdd(&s_hist[(bits >> sh) & bm], 1u);
@@ -196,6 +196,59 @@ hipError_t launch_depth_error_median(int64_t n, const float* depth, const float*
     return hipGetLastError();
 }
 
+// The window moments of one 16 x 16 output tile, shared by the loss and the evaluation: the tile + halo of two images staged in LDS minus one
+// pivot, then the separable 11-tap passes over the five CENTRED moments (of x' = x - pivot, y' = y - pivot: means, second moments and the mean of
+// (x' - y')^2).  load(p, x, y) reads both images at pixel offset p = row * W + column.  kValid: valid window (staged element (r, c) is input
+// pixel (y0 + r, x0 + c)), else zero padding kLH (pixel (y0 + r - kLH, x0 + c - kLH); the padding becomes -pivot).  Every thread of the
+// workgroup calls; thread (tx, ty) gets the moments of output (x0 + tx, y0 + ty), and s_x / s_y stay staged for the caller.
+struct SsimMoments { float n1, n2, e11, e22, edd; };
+
+template <bool kValid, typename Load>
+__device__ __forceinline__ SsimMoments ssim_tile_moments(const float (&window)[11], int W, int H, int x0, int y0, float pivot, Load load,
+                                                         float (&s_x)[kLP][kLP + 1], float (&s_y)[kLP][kLP + 1], float (&s_h)[5][kLP][kLT + 1])
+{
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int off = kValid ? 0 : kLH;
+    // the tile + halo: 676 values of each image, three per thread.  ALL loads are issued before the first LDS store: as a loop with a store
+    // behind each load the staging was three dependent memory round trips -- 5 of a wavefront's 6.8 us (round 6, rocprofv3 SQ_WAVE_CYCLES)
+    constexpr int kStage = (kLP * kLP + kBlock - 1) / kBlock;
+    float vx[kStage], vy[kStage];
+#pragma unroll
+    for (int it = 0; it < kStage; it++) {
+        const int e = tid + it * kBlock;
+        const int r = e / kLP, c = e - r * kLP;
+        const int gx = x0 + c - off, gy = y0 + r - off;
+        const bool in = e < kLP * kLP && gx >= 0 && gx < W && gy >= 0 && gy < H;
+        load((size_t)(in ? gy : 0) * W + (in ? gx : 0), vx[it], vy[it]);
+        if (!in) { vx[it] = 0.f; vy[it] = 0.f; }
+    }
+#pragma unroll
+    for (int it = 0; it < kStage; it++) {
+        const int e = tid + it * kBlock;
+        if (e < kLP * kLP) { const int r = e / kLP, c = e - r * kLP; s_x[r][c] = vx[it] - pivot; s_y[r][c] = vy[it] - pivot; }
+    }
+    __syncthreads();
+    for (int e = tid; e < kLP * kLT; e += kBlock) {       // horizontal pass: 26 rows x 16 columns
+        const int r = e / kLT, c = e - r * kLT;
+        float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, dd = 0.f;
+#pragma unroll
+        for (int k = 0; k < 11; k++) {
+            const float w = window[k], xv = s_x[r][c + k], yv = s_y[r][c + k], dv = xv - yv;
+            a += w * xv; b += w * yv; aa += w * xv * xv; bb += w * yv * yv; dd += w * dv * dv;
+        }
+        s_h[0][r][c] = a; s_h[1][r][c] = b; s_h[2][r][c] = aa; s_h[3][r][c] = bb; s_h[4][r][c] = dd;
+    }
+    __syncthreads();
+    SsimMoments m = {0.f, 0.f, 0.f, 0.f, 0.f};             // centred: n = mu - pivot
+#pragma unroll
+    for (int k = 0; k < 11; k++) {                         // vertical pass
+        const float w = window[k];
+        m.n1 += w * s_h[0][ty + k][tx]; m.n2 += w * s_h[1][ty + k][tx]; m.e11 += w * s_h[2][ty + k][tx];
+        m.e22 += w * s_h[3][ty + k][tx]; m.edd += w * s_h[4][ty + k][tx];
+    }
+    return m;
+}
+
 template <bool kOutlier>
 __global__ __launch_bounds__(kBlock) void loss_stats_kernel(int W, int H, const float* __restrict__ im,
                                                             const float* __restrict__ gt, const float* __restrict__ depth,
@@ -215,45 +268,10 @@ __global__ __launch_bounds__(kBlock) void loss_stats_kernel(int W, int H, const 
     float sum_ssim = 0.f, sum_l1 = 0.f;         // (sum_ssim: of 1 - SSIM)
     const int ch = blockIdx.z;                  // one colour channel per workgroup: 3x the workgroups, a third of the serial chain
     {
-        // the tile + halo: 676 values of each image, three per thread.  ALL loads are issued before the first LDS store: as a loop with a store
-        // behind each load the staging was three dependent memory round trips -- 5 of a wavefront's 6.8 us (round 6, rocprofv3 SQ_WAVE_CYCLES)
-        constexpr int kStage = (kLP * kLP + kBlock - 1) / kBlock;
-        float vx[kStage], vy[kStage];
         const float pivot = gt[ch * HW + (size_t)y0 * W + x0];          // (x0 < W and y0 < H for every workgroup of the grid)
-#pragma unroll
-        for (int it = 0; it < kStage; it++) {
-            const int e = tid + it * kBlock;
-            const int r = e / kLP, c = e - r * kLP;
-            const int gx = x0 + c - kLH, gy = y0 + r - kLH;
-            const bool in = e < kLP * kLP && gx >= 0 && gx < W && gy >= 0 && gy < H;
-            const size_t o = ch * HW + (size_t)(in ? gy : 0) * W + (in ? gx : 0);
-            vx[it] = im[o]; vy[it] = gt[o];
-            if (!in) { vx[it] = 0.f; vy[it] = 0.f; }
-        }
-#pragma unroll
-        for (int it = 0; it < kStage; it++) {
-            const int e = tid + it * kBlock;
-            if (e < kLP * kLP) { const int r = e / kLP, c = e - r * kLP; s_x[r][c] = vx[it] - pivot; s_y[r][c] = vy[it] - pivot; }
-        }
-        __syncthreads();
-        for (int e = tid; e < kLP * kLT; e += kBlock) {       // horizontal pass: 26 rows x 16 columns
-            const int r = e / kLT, c = e - r * kLT;
-            float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, dd = 0.f;
-#pragma unroll
-            for (int k = 0; k < 11; k++) {
-                const float w = kWin[k], xv = s_x[r][c + k], yv = s_y[r][c + k], dv = xv - yv;
-                a += w * xv; b += w * yv; aa += w * xv * xv; bb += w * yv * yv; dd += w * dv * dv;
-            }
-            s_h[0][r][c] = a; s_h[1][r][c] = b; s_h[2][r][c] = aa; s_h[3][r][c] = bb; s_h[4][r][c] = dd;
-        }
-        __syncthreads();
-        float n1 = 0.f, n2 = 0.f, e11 = 0.f, e22 = 0.f, edd = 0.f;           // centred: n = mu - pivot
-#pragma unroll
-        for (int k = 0; k < 11; k++) {                         // vertical pass
-            const float w = kWin[k];
-            n1 += w * s_h[0][ty + k][tx]; n2 += w * s_h[1][ty + k][tx]; e11 += w * s_h[2][ty + k][tx];
-            e22 += w * s_h[3][ty + k][tx]; edd += w * s_h[4][ty + k][tx];
-        }
+        const SsimMoments mo = ssim_tile_moments<false>(kWin, W, H, x0, y0, pivot,
+                                                        [&](size_t p, float& x, float& y) { x = im[ch * HW + p]; y = gt[ch * HW + p]; }, s_x, s_y, s_h);
+        const float n1 = mo.n1, n2 = mo.n2, e11 = mo.e11, e22 = mo.e22, edd = mo.edd;
         if (inside) {
             const float c1 = 0.0001f, c2 = 0.0009f;
             const float dm = n1 - n2, vd = edd - dm * dm;                    // mu1 - mu2, var(x - y)
@@ -275,7 +293,7 @@ __global__ __launch_bounds__(kBlock) void loss_stats_kernel(int W, int H, const 
         const size_t o = (size_t)py * W + px;
         const float d = depth[o], g = gt_depth[o];
         const float unc = depth_sq ? depth_sq[o] - d * d : 0.f;
-        bool m = g > 0.f && d == d && unc == unc;
+        bool m = depth_measured(g, d, unc);
         if (kOutlier) m = m && outlier_keep(g, d, d_median[0]);
         if (m) { sum_d = fabsf(g - d); cnt = 1.f; }
     }
@@ -365,7 +383,7 @@ __global__ __launch_bounds__(kBlock) void loss_grad_kernel(int W, int H, const f
         const size_t o = (size_t)py * W + px;
         const float d = depth[o], g = gt_depth[o];
         const float unc = depth_sq ? depth_sq[o] - d * d : 0.f;
-        bool m = g > 0.f && d == d && unc == unc;
+        bool m = depth_measured(g, d, unc);
         if (kOutlier) m = m && outlier_keep(g, d, d_median[0]);
         const float diff = d - g;
         const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
@@ -432,7 +450,7 @@ __global__ __launch_bounds__(kBlock) void tracking_loss_kernel(int npix, const f
     if (i < npix) {
         const float d = depth[i], gd = gt_depth[i];
         const float unc = depth_sq[i] - d * d;
-        bool m = gd > 0.f && !__builtin_isnan(d) && !__builtin_isnan(unc);
+        bool m = depth_measured(gd, d, unc);
         if (kOutlier) m = m && outlier_keep(gd, d, d_median[0]);
         if (use_sil) m = m && sil[i] > sil_thres;
         const float ed = gd - d;
@@ -486,11 +504,11 @@ hipError_t launch_tracking_loss(int W, int H, const float* im, const float* gt, 
 // The reference's report_progress (src/mapper/splatam/utils/eval_helpers.py:211-245) and eval (:464-508) on one rendered frame: PSNR, the two depth
 // errors, SSIM with the loss' own window (same padding, slam_external.py:66-97) and the 5-scale MS-SSIM of the package eval imports (valid
 // window).  No float atomics and nothing read across workgroups inside a launch: every kernel writes one fp64 record per workgroup, and
-// eval_finish_kernel (one workgroup) adds all records in a fixed order -- thread t takes records t, t + 256, ... in index order, then a pairwise tree
-// in LDS -- so a row has the same bits on every run.
+// eval_finish_kernel (one workgroup) adds all records in the fixed order of gs_common.h (strided_record_sum, block_tree_sum), so a row has the same
+// bits on every run.
 //   eval_sums_kernel        : per-channel sum (d im)^2, sum |d depth| valid, sum (d depth)^2 valid, count of gt_depth > 0; the terms are fp32 (two
 //                             roundings each), the accumulation fp64
-//   eval_ssim_kernel<V, R>  : loss_stats_kernel's tile + halo in LDS, separable 11-tap passes, CENTRED moments; per workgroup the sums of the ssim and
+//   eval_ssim_kernel<V, R>  : loss_stats_kernel's moment pass (ssim_tile_moments) with its own window table; per workgroup the sums of the ssim and
 //                             cs maps of its 16 x 16 outputs.  V: valid window (no padding, output (w - 10) x (h - 10)), else zero padding 5.
 //                             R: level 0 -- reads the frame itself and applies the masks on load (no masked copy of the frame exists)
 //   eval_pool_kernel<R>     : avg_pool2d(kernel 2, padding = size % 2) of both images: the zero padding counts, the divisor is always 4
@@ -511,32 +529,12 @@ __device__ __forceinline__ float eval_image_mask(size_t o, const float* __restri
     return m;
 }
 
-// pairwise tree over the workgroup's kBlock values of each of K sums (s_tree: K * kBlock doubles of LDS); every thread gets the totals
-template <int K>
-__device__ __forceinline__ void eval_block_tree(double (&a)[K], double* s_tree)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) s_tree[k * kBlock + tid] = a[k];
-    __syncthreads();
-    for (int h = kBlock / 2; h > 0; h >>= 1) {
-        if (tid < h) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) s_tree[k * kBlock + tid] += s_tree[k * kBlock + tid + h];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) a[k] = s_tree[k * kBlock];
-}
-
 __global__ __launch_bounds__(kBlock) void eval_sums_kernel(int64_t npix, const float* __restrict__ im, const float* __restrict__ depth,
                                                            const float* __restrict__ sil, const float* __restrict__ gt,
                                                            const float* __restrict__ gt_depth, float sil_thres, int flags,
                                                            double* __restrict__ partial)
 {
-    __shared__ double s_tree[kEvalSums * kBlock];
+    __shared__ double s_tree[kEvalSums][kBlock];
     double a[kEvalSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < npix; i += stride) {
@@ -556,7 +554,7 @@ __global__ __launch_bounds__(kBlock) void eval_sums_kernel(int64_t npix, const f
         a[4] += (double)(l2 * valid);
         a[5] += (double)valid;
     }
-    eval_block_tree<kEvalSums>(a, s_tree);
+    block_tree_sum(a, s_tree);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < kEvalSums; ++k) partial[(int64_t)blockIdx.x * kEvalRecord + k] = a[k];
@@ -572,54 +570,22 @@ __global__ __launch_bounds__(kBlock) void eval_ssim_kernel(int W, int H, const f
     __shared__ float s_x[kLP][kLP + 1];
     __shared__ float s_y[kLP][kLP + 1];
     __shared__ float s_h[5][kLP][kLT + 1];
-    __shared__ double s_tree[2 * kBlock];
+    __shared__ double s_tree[2][kBlock];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int x0 = blockIdx.x * kLT, y0 = blockIdx.y * kLT;
     const int OW = kValid ? W - 2 * kLH : W, OH = kValid ? H - 2 * kLH : H;
-    const int off = kValid ? 0 : kLH;                       // staged element (r, c) is input pixel (y0 + r - off, x0 + c - off)
     const bool inside = x0 + tx < OW && y0 + ty < OH;
     const size_t HW = (size_t)W * H;
     const int ch = blockIdx.z;
-    constexpr int kStage = (kLP * kLP + kBlock - 1) / kBlock;
-    float vx[kStage], vy[kStage];
     // the pivot of the centred moments: the target at the tile's first output pixel (x0 < OW <= W, y0 < OH <= H)
     const size_t po = (size_t)y0 * W + x0;
     const float pivot = y[ch * HW + po] * (kRaw ? eval_image_mask(po, gt_depth, sil, sil_thres, flags) : 1.0f);
-#pragma unroll
-    for (int it = 0; it < kStage; it++) {
-        const int e = tid + it * kBlock;
-        const int r = e / kLP, c = e - r * kLP;
-        const int gx = x0 + c - off, gy = y0 + r - off;
-        const bool in = e < kLP * kLP && gx >= 0 && gx < W && gy >= 0 && gy < H;
-        const size_t p = (size_t)(in ? gy : 0) * W + (in ? gx : 0);
-        const float m = kRaw ? eval_image_mask(p, gt_depth, sil, sil_thres, flags) : 1.0f;
-        vx[it] = x[ch * HW + p] * m; vy[it] = y[ch * HW + p] * m;
-        if (!in) { vx[it] = 0.f; vy[it] = 0.f; }
-    }
-#pragma unroll
-    for (int it = 0; it < kStage; it++) {
-        const int e = tid + it * kBlock;
-        if (e < kLP * kLP) { const int r = e / kLP, c = e - r * kLP; s_x[r][c] = vx[it] - pivot; s_y[r][c] = vy[it] - pivot; }
-    }
-    __syncthreads();
-    for (int e = tid; e < kLP * kLT; e += kBlock) {
-        const int r = e / kLT, c = e - r * kLT;
-        float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, dd = 0.f;
-#pragma unroll
-        for (int k = 0; k < 11; k++) {
-            const float w = kEvalWin[k], xv = s_x[r][c + k], yv = s_y[r][c + k], dv = xv - yv;
-            a += w * xv; b += w * yv; aa += w * xv * xv; bb += w * yv * yv; dd += w * dv * dv;
-        }
-        s_h[0][r][c] = a; s_h[1][r][c] = b; s_h[2][r][c] = aa; s_h[3][r][c] = bb; s_h[4][r][c] = dd;
-    }
-    __syncthreads();
-    float n1 = 0.f, n2 = 0.f, e11 = 0.f, e22 = 0.f, edd = 0.f;
-#pragma unroll
-    for (int k = 0; k < 11; k++) {
-        const float w = kEvalWin[k];
-        n1 += w * s_h[0][ty + k][tx]; n2 += w * s_h[1][ty + k][tx]; e11 += w * s_h[2][ty + k][tx];
-        e22 += w * s_h[3][ty + k][tx]; edd += w * s_h[4][ty + k][tx];
-    }
+    const SsimMoments mo = ssim_tile_moments<kValid>(kEvalWin, W, H, x0, y0, pivot,
+                                                     [&](size_t p, float& vx, float& vy) {
+                                                         const float m = kRaw ? eval_image_mask(p, gt_depth, sil, sil_thres, flags) : 1.0f;
+                                                         vx = x[ch * HW + p] * m; vy = y[ch * HW + p] * m;
+                                                     }, s_x, s_y, s_h);
+    const float n1 = mo.n1, n2 = mo.n2, e11 = mo.e11, e22 = mo.e22, edd = mo.edd;
     double a[2] = {0.0, 0.0};
     if (inside) {
         // as in loss_stats_kernel: 1 - cs = var(x - y) / B2 and 1 - ssim = (B1 var(x - y) + A2 (mu1 - mu2)^2) / (B1 B2), both exactly 0 for x == y
@@ -635,7 +601,7 @@ __global__ __launch_bounds__(kBlock) void eval_ssim_kernel(int W, int H, const f
         a[0] = (double)((B1 * vd + A2 * (dm * dm)) / (B1 * B2));        // what is summed is 1 - value: small terms, not values near 1
         a[1] = (double)(vd / B2);
     }
-    eval_block_tree<2>(a, s_tree);
+    block_tree_sum(a, s_tree);
     if (tid == 0) {
         double* out = partial + ((size_t)ch * gridDim.x * gridDim.y + (size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2;
         out[0] = a[0]; out[1] = a[1];
@@ -670,33 +636,25 @@ __global__ __launch_bounds__(kBlock) void eval_pool_kernel(int W, int H, int W2,
     ox[i] = sx * 0.25f; oy[i] = sy * 0.25f;
 }
 
-// a thread's share of the `records` doubles at part[r * stride]: its records in index order
-__device__ __forceinline__ double eval_thread_sum(const double* __restrict__ part, int64_t records, int stride)
-{
-    double a = 0.0;
-    for (int64_t r = threadIdx.x; r < records; r += kBlock) a += part[r * stride];
-    return a;
-}
-
 // All totals of a row in ONE tree: 6 sums, 3 same-window SSIM sums, 15 MS-SSIM sums.  (A tree per total -- 24 trees, some 240 barriers -- took
 // 33 us of a 96 us call at 256 x 256; the additions of every total and their order are the same here.)
 constexpr int kEvalTotals = kEvalSums + 3 + 15;
 
 __global__ __launch_bounds__(kBlock) void eval_finish_kernel(EvalPlan p, int flags, const double* __restrict__ partial, double* __restrict__ row)
 {
-    __shared__ double s_tree[kEvalTotals * kBlock];
+    __shared__ double s_tree[kEvalTotals][kBlock];
     double s[kEvalTotals];
 #pragma unroll
-    for (int k = 0; k < kEvalSums; ++k) s[k] = eval_thread_sum(partial + k, p.sums_records, kEvalRecord);
+    for (int k = 0; k < kEvalSums; ++k) s[k] = strided_record_sum(partial + k, p.sums_records, kEvalRecord);
 #pragma unroll
     for (int ch = 0; ch < 3; ch++) {
-        s[kEvalSums + ch] = (flags & GS_EVAL_SSIM) ? eval_thread_sum(partial + p.same_off + (int64_t)ch * p.same_tiles * 2, p.same_tiles, 2) : 0.0;
+        s[kEvalSums + ch] = (flags & GS_EVAL_SSIM) ? strided_record_sum(partial + p.same_off + (int64_t)ch * p.same_tiles * 2, p.same_tiles, 2) : 0.0;
 #pragma unroll
         for (int l = 0; l < 5; l++)       // levels 0-3 contribute cs (the second double of a record), level 4 ssim
             s[kEvalSums + 3 + ch * 5 + l] = (flags & GS_EVAL_MS_SSIM)
-                ? eval_thread_sum(partial + p.ms_off[l] + (int64_t)ch * p.ms_tiles[l] * 2 + (l < 4 ? 1 : 0), p.ms_tiles[l], 2) : 0.0;
+                ? strided_record_sum(partial + p.ms_off[l] + (int64_t)ch * p.ms_tiles[l] * 2 + (l < 4 ? 1 : 0), p.ms_tiles[l], 2) : 0.0;
     }
-    eval_block_tree<kEvalTotals>(s, s_tree);
+    block_tree_sum(s, s_tree);
     if (threadIdx.x != 0) return;
     const double nan = __builtin_nan("");
     const double npix = (double)p.w[0] * (double)p.h[0];

@@ -676,7 +676,8 @@ int gs_high_loss_grid(int32_t width, int32_t height, const float* render_depth, 
  * row-major pixel order.  log_scales is [rows,1] when isotropic != 0, else [rows,3].
  * NaN rule: the median of the depth error is torch.median's -- the lower median, and NaN as soon as ONE error is NaN (a NaN pixel in
  * render_depth or gt_depth, or an infinite render_depth where gt_depth <= 0).  `error > 2 median` is then false for every pixel and only
- * the silhouette test (silhouette < sil_thres) flags pixels. */
+ * the silhouette test (silhouette < sil_thres) flags pixels.  The median is gs_depth_error_median's select (its histograms are part of the
+ * scratch); width * height < 2^31 as there, else GS_EINVAL. */
 uint64_t gs_grow_scratch_bytes(int32_t width, int32_t height);
 int gs_grow_gaussians(int32_t width, int32_t height, const float* render_depth, const float* silhouette,
                       const float* gt_depth, const float* color, const float* h_intrinsics4, const float* h_c2w12,

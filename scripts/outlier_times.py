@@ -14,6 +14,8 @@ call.  All learning rates are zero, so the poses and the map -- and with them th
                mapping.track_frame(fused=False) with the option (TRACK_ITERS iterations per call, reported per iteration)
     mapping    one mapping iteration: mapping.mapping_iteration with the option off and on, and the route the option had before:
                get_loss(fused=True, fused_preprocess=True, ignore_outlier_depth_loss=True) with the torch loss, backward, optimizer.step()
+    growth     mapping.grow_rows (gs_grow_gaussians: the same select, mask, compaction, rows, and the call's one host read of the counts) on a
+               frame of that size, no map.  Timed call by call with device events (timed_by_events); a block's figure is the median of its calls
 """
 import json
 import math
@@ -27,7 +29,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 SIZES = ((200_000, 256, 256), (500_000, 640, 480))
-SECTIONS = ("median", "tracking", "mapping")
+SECTIONS = ("median", "tracking", "mapping", "growth")
+GROWTH_CALLS = 200                                 # event-timed calls per block of the growth section
 GRIDS = (1, 2, 4, 8, 16, 32, 64, 128, 256)
 CHILD_LIMIT = 420                                  # seconds per child
 WINDOW, ROUNDS, WARM = float(os.environ.get("WINDOW", 0.3)), int(os.environ.get("ROUNDS", 5)), int(os.environ.get("WARM", 5))
@@ -60,6 +63,40 @@ def timed_alternately(variants, per_call=None):
             ts[name].append((time.perf_counter() - t0) / (calls[name] * per_call.get(name, 1)) * 1e3)
     return {name: dict(ms_median=round(statistics.median(v), 4), ms_min=round(min(v), 4), ms_max=round(max(v), 4), calls_per_block=calls[name],
                        blocks=len(v)) for name, v in ts.items()}
+
+
+def timed_by_events(variants, calls=GROWTH_CALLS):
+    """As timed_alternately, for calls that end in a host read: a pair of device events around every call, a block = the median of `calls`."""
+    import torch
+    for step in variants.values():
+        for _ in range(WARM):
+            step()
+    ts = {name: [] for name in variants}
+    for _ in range(ROUNDS):
+        for name, step in variants.items():
+            pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(calls)]
+            for a, b in pairs:
+                a.record()
+                step()
+                b.record()
+            torch.cuda.synchronize()
+            ts[name].append(statistics.median(a.elapsed_time(b) for a, b in pairs))
+    return {name: dict(ms_median=round(statistics.median(v), 4), ms_min=round(min(v), 4), ms_max=round(max(v), 4), calls_per_block=calls,
+                       blocks=len(v)) for name, v in ts.items()}
+
+
+def growth_step(W, H):
+    """-> a call of mapping.grow_rows on depth_pair's frame: a silhouette with ~9 % below the threshold, a camera at the origin."""
+    import numpy as np
+    import torch
+    from activesplat_amd import mapping as M
+    from activesplat_amd import synthetic as syn
+    g = torch.Generator().manual_seed(5)
+    d, gt = [x[0].cuda() for x in depth_pair(H, W)]
+    sil = (1.0 - 0.6 * torch.rand(H, W, generator=g) ** 2).cuda()
+    color = torch.rand(3, H, W, generator=g).cuda()
+    K = syn.intrinsics(W, H)
+    return lambda: M.grow_rows(d, sil, gt, color, K, np.eye(4), 0.5, "isotropic")
 
 
 def depth_pair(H, W, seed=0):
@@ -138,6 +175,11 @@ def child(section, n, W, H):
             assert torch.equal(out.cpu().view(torch.int32), want.cpu().reshape(1).view(torch.int32)), (grid, float(out), float(want))
             extra[name] = dict(grid=grid or auto, chosen=not grid)
         say(timed_alternately(variants), **extra)
+        return
+    if section == "growth":
+        name, step = "grow_rows (gs_grow_gaussians)", growth_step(W, H)
+        rows, n_cand = step()
+        say(timed_by_events({name: step}), **{name: dict(candidates=n_cand, rows=int(rows["means3D"].shape[0]))})
         return
     params, curr, variables, t = scene(n, W, H)
     if section == "tracking":

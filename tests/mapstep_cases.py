@@ -148,7 +148,7 @@ def check_mapping_loss(device, H, W, kind, all_invalid=False):
 # =====================================================================================================================================
 # B. gs_grow_gaussians
 # =====================================================================================================================================
-GROW_FRAMES = [(1, 1), (1, 2), (7, 9), (8, 9), (33, 47), (160, 120)]
+GROW_FRAMES = [(1, 1), (1, 2), (7, 9), (8, 9), (33, 47), (160, 120), (32, 64), (1, 2049)]      # the last two: at, and one pixel past, a kMedianChunk boundary of the select
 GROW_VARIANTS = ("random", "all_gt_zero", "ties", "shared_high_bits", "inf_render", "nan_render", "nan_gt")
 SIL_THRES = 0.5
 
