@@ -67,7 +67,7 @@ SORT_AUTO, SORT_TILE_LDS, SORT_RADIX = 0, 1, 2
 
 # every symbol include/gsplat_hip.h declares (tests check the library exports all of them)
 #: the GS_ABI_VERSION of include/gsplat_hip.h this binding was written against (checked when a library is bound)
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 SYMBOLS = ("gs_abi_version", "gs_geom_layout", "gs_image_layout", "gs_bin_layout", "gs_backward_scratch_bytes", "gs_last_error",
            "gs_version", "gs_set_sort_path", "gs_set_forward_segments", "gs_set_half_quadrants", "gs_set_backward_chain", "gs_set_backward_chain_tickets", "gs_set_backward_chain_polls", "gs_async_status_word", "gs_async_status_clear", "gs_recorded_cut", "gs_set_backward_segments", "gs_preprocess_forward", "gs_preprocess_forward_raw", "gs_render_forward", "gs_render_backward", "gs_render_backward_raw", "gs_render_backward_raw_adam", "gs_adam_step", "gs_adam_step_multi",
@@ -84,7 +84,7 @@ SYMBOLS = ("gs_abi_version", "gs_geom_layout", "gs_image_layout", "gs_bin_layout
            "gs_depth_error_median_scratch_bytes", "gs_depth_error_median", "gs_depth_error_median_grid", "gs_depth_error_median_workgroups",
            "gs_mapping_loss_outlier", "gs_tracking_loss_outlier",
            "gs_depth_cloud", "gs_cloud_nearest_scratch_bytes", "gs_cloud_nearest", "gs_completion_row_scratch_bytes", "gs_completion_row",
-           "gs_eval_frame_layout", "gs_eval_frame")
+           "gs_eval_frame_layout", "gs_eval_frame", "gs_frame_ingest")
 
 
 def _bind(lib):
@@ -195,6 +195,9 @@ def _bind(lib):
     lib.gs_eval_frame_layout.restype = C.c_int
     lib.gs_eval_frame.argtypes = [i32, i32, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp]
     lib.gs_eval_frame.restype = C.c_int
+    # frame ingest: (width, height, image, depth, level_value, n_out, h_sizes (host int32 pairs), color0, depth0, color1, depth1, stream)
+    lib.gs_frame_ingest.argtypes = [i32, i32, vp, vp, vp, i32, C.POINTER(i32), vp, vp, vp, vp, vp]
+    lib.gs_frame_ingest.restype = C.c_int
     lib.gs_tracking_loss_scratch_bytes.argtypes = [i32, i32]
     lib.gs_tracking_loss_scratch_bytes.restype = C.c_uint64
     lib.gs_tracking_loss.argtypes = [i32, i32] + [vp] * 6 + [i32, f32, f32, f32] + [vp] * 4 + [vp]

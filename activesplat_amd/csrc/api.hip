@@ -1271,6 +1271,23 @@ int gs_keyframe_overlap(int32_t n_pts, const float* pts_world, int32_t n_keyfram
     return GS_OK;
 }
 
+int gs_frame_ingest(int32_t width, int32_t height, const uint8_t* image, const float* depth, const float* level_value, int32_t n_out,
+                    const int32_t* h_sizes, float* color0, float* depth0, float* color1, float* depth1, gs_stream_t stream)
+{
+    if (n_out < 1 || n_out > 2) return fail(GS_EINVAL, "gs_frame_ingest: n_out must be 1 or 2");
+    if (!image || !depth || !level_value || !h_sizes || !color0 || !depth0 || (n_out == 2 && (!color1 || !depth1)))
+        return fail(GS_EINVAL, "gs_frame_ingest: null pointer");
+    if (width < 1 || height < 1 || width > 16384 || height > 16384)
+        return fail(GS_EINVAL, "gs_frame_ingest: source size out of range (1 <= width, height <= 16384)");
+    for (int k = 0; k < 2 * n_out; ++k)
+        if (h_sizes[k] < 1 || h_sizes[k] > 16384) return fail(GS_EINVAL, "gs_frame_ingest: output size out of range (1 <= W, H <= 16384)");
+    float* const colors[2] = {color0, color1};
+    float* const depths[2] = {depth0, depth1};
+    hipError_t e = gs::launch_frame_ingest(width, height, image, depth, level_value, n_out, h_sizes, colors, depths, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_frame_ingest: %s", hipGetErrorString(e));
+    return GS_OK;
+}
+
 int gs_depth_cloud(int32_t width, int32_t height, const float* depth, const float* h_intrinsics4, const float* h_c2w12, float* points,
                    uint8_t* valid, gs_stream_t stream)
 {

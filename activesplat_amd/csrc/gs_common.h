@@ -909,6 +909,9 @@ hipError_t launch_grow(int W, int H, const float* rd, const float* sil, const fl
                        float* log_scales, uint32_t* d_counts, void* scratch, hipStream_t st);
 hipError_t launch_keyframe_overlap(int n_pts, const float* pts, int n_kf, const float* w2c, const float* k9, int W, int H, int edge,
                                    uint32_t* counts, hipStream_t st);
+// frame ingest (grow.hip; the rules: include/gsplat_hip.h, gs_frame_ingest): sizes = n_out HOST (W, H) pairs, one launch for all outputs
+hipError_t launch_frame_ingest(int w, int h, const uint8_t* image, const float* depth, const float* level_value, int n_out, const int* sizes,
+                               float* const* colors, float* const* depths, hipStream_t st);
 // the completion / accuracy judge (grow.hip; the rules: include/gsplat_hip.h, gs_depth_cloud / gs_cloud_nearest / gs_completion_row)
 hipError_t launch_depth_cloud(int W, int H, const float* depth, const float* k4, const float* c2w12, float* points, uint8_t* valid, hipStream_t st);
 uint64_t cloud_nearest_scratch_bytes(int64_t Q, int64_t M);

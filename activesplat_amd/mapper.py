@@ -64,6 +64,9 @@ DEFAULT_CONFIG = dict(
                              # (mapping.mapping_iteration; needs fused_render, fused_loss, fused_preprocess; event iterations take the usual path)
     fused_growth=False,      # add_new_gaussians: one forward + gs_grow_gaussians
     fused_tracking=False,    # tracking (tracking.use_gt_poses=False): mapping.track_frame's HIP loop (tracking_iteration) instead of the reference pattern
+    device_ingest=False,     # run_raw: the raw frame goes up once through pinned buffers and gs_frame_ingest writes both resolutions (ingest.FrameIngest)
+                             # instead of two host resizes and pageable copies; the frame's pose floats travel with it and the keyframe decision is
+                             # made on the host pose.  The same frame tensors, bit for bit; a frame whose image is not uint8 takes the host path
     fused_keyframes=True,    # (accepted for older configs; no effect: the keyframe overlap scores always come from gs_keyframe_overlap, one launch)
     high_loss_samples=True,  # the per-frame no-grad render of get_high_loss_samples (__init__.py:184-258) before mapping a frame
     high_loss_target=False,  # ... and the rest of get_high_loss_samples on the device (gs_high_loss_grid + gs_grid_dbscan): the look target of the
@@ -131,6 +134,7 @@ class SplatMapper:
         #: evaluate.MapEvaluator of the reported frames (config report_progress; None until the first report) and their frame ids
         self.progress = None
         self.progress_frames = []
+        self._ingest = None                 # ingest.FrameIngest of the current source size (device_ingest=True; built on first use)
 
     @property
     def last_losses(self):
@@ -195,7 +199,10 @@ class SplatMapper:
         quat_h = torch.as_tensor(np.asarray(frame["quat"], dtype=np.float32)).reshape(4).clone()
         pos_h = torch.as_tensor(np.asarray(frame["position"], dtype=np.float32)).reshape(3).clone()
         self._pose_host[fid] = (quat_h, pos_h)
-        quat, pos = quat_h.to(self.device), pos_h.to(self.device)
+        if "quat_device" in frame and "position_device" in frame:      # (run_raw with device_ingest: already uploaded with the frame)
+            quat, pos = frame["quat_device"], frame["position_device"]
+        else:
+            quat, pos = quat_h.to(self.device), pos_h.to(self.device)
         if self.judge is not None:
             c2w = np.linalg.inv(self._w2c_host(quat_h, pos_h).numpy().astype(np.float64))
             self.judge.add_frame(depth.reshape(depth.shape[-2], depth.shape[-1]).contiguous(), self._k_host, c2w, float(frame.get("path_length", 0.0)))
@@ -316,9 +323,17 @@ class SplatMapper:
         with torch.no_grad():
             # the simulator's pose when the caller hands one over (run_raw), the pose written into the camera parameters otherwise
             # (tracking: the frame's own pose -- the parameters hold the estimate)
-            gt_w2c = torch.as_tensor(np.asarray(frame["gt_w2c"]), dtype=torch.float32, device=self.device) if "gt_w2c" in frame \
-                else (self._w2c_host(quat_h, pos_h).to(self.device) if self._tracking else self._w2c(fid))
-            pose_ok = bool(torch.isfinite(gt_w2c).all())
+            pose_ok = None
+            if cfg.get("device_ingest", False) and ("gt_w2c" in frame or self._tracking or self._poses_fixed):
+                # the pose is known on the host: the same decision from the host values, without reading the device
+                gt_host = torch.as_tensor(np.asarray(frame["gt_w2c"]), dtype=torch.float32) if "gt_w2c" in frame else self._w2c_host(quat_h, pos_h)
+                pose_ok = bool(torch.isfinite(gt_host).all())
+                gt_w2c = frame["gt_w2c_device"].clone() if "gt_w2c_device" in frame else gt_host.to(self.device)
+            else:
+                gt_w2c = torch.as_tensor(np.asarray(frame["gt_w2c"]), dtype=torch.float32, device=self.device) if "gt_w2c" in frame \
+                    else (self._w2c_host(quat_h, pos_h).to(self.device) if self._tracking else self._w2c(fid))
+            if pose_ok is None:
+                pose_ok = bool(torch.isfinite(gt_w2c).all())
             if (fid == 0 or (fid + 1) % cfg["keyframe_every"] == 0 or fid == cfg["step_num"] - 2) and pose_ok:
                 self.keyframe_list.append({"id": fid, "est_w2c": self._w2c(fid), "color": color, "depth": depth})
             self.gt_w2c_all_frames.append(gt_w2c)
@@ -378,6 +393,8 @@ class SplatMapper:
         quat (w,x,y,z) / position are the tracker's camera parameters for this frame (the reference skips tracking and
         writes the simulator's, :400-405)."""
         gt_w2c, self.first_abs_pose = FR.gt_w2c_from_pose(X_WV, self.first_abs_pose)
+        if self.cfg.get("device_ingest", False) and getattr(image, "dtype", None) in (np.uint8, torch.uint8):
+            return self.run(self._ingest_raw(image, depth, gt_w2c, frame_id, quat, position))
         color, d = FR.to_mapping_tensors(image, depth, self.W, self.H, self.device)
         fac = float(self.cfg.get("densify_downscale_factor", 1))
         frame = {"id": frame_id, "color": color, "depth": d, "quat": quat, "position": position, "gt_w2c": gt_w2c}
@@ -385,6 +402,21 @@ class SplatMapper:
             frame["densify_color"], frame["densify_depth"] = FR.to_mapping_tensors(image, depth, int(self.W / fac), int(self.H / fac),
                                                                                    self.device)
         return self.run(frame)
+
+    def _ingest_raw(self, image, depth, gt_w2c, frame_id, quat, position):
+        """run_raw's frame dict with device_ingest: one upload and one launch for both resolutions (ingest.FrameIngest)."""
+        from . import ingest as IN
+        h, w = int(image.shape[0]), int(image.shape[1])
+        fac = float(self.cfg.get("densify_downscale_factor", 1))
+        sizes = [(self.W, self.H)] + ([(int(self.W / fac), int(self.H / fac))] if fac != 1 else [])
+        if self._ingest is None or (self._ingest.w, self._ingest.h) != (w, h) or self._ingest.sizes != sizes:
+            self._ingest = IN.FrameIngest(w, h, sizes, self.device)
+        outs, quat_d, pos_d, gt_d = self._ingest.put(image, depth, quat, position, gt_w2c)
+        frame = {"id": frame_id, "color": outs[0][0], "depth": outs[0][1], "quat": quat, "position": position, "gt_w2c": gt_w2c,
+                 "quat_device": quat_d, "position_device": pos_d, "gt_w2c_device": gt_d}
+        if len(outs) == 2:
+            frame["densify_color"], frame["densify_depth"] = outs[1]
+        return frame
 
     # -- hand-off (reference: q_main2vis.put(GaussianPacket(...)) __init__.py:536-542; post_processing :544-578) ----
     def packet(self, c2w=None):

@@ -181,7 +181,7 @@ const char* gs_version(void);
 /* Integer version of THIS binary interface: bumped whenever an entry point's argument list or a published record layout changes (e.g.
  * the seed argument of gs_densify_children, the 40-byte SH Jacobian record).  A host binding compares it with the GS_ABI_VERSION it was
  * written against before the first call, so that a stale prebuilt library fails at load time instead of misreading its arguments. */
-#define GS_ABI_VERSION 19
+#define GS_ABI_VERSION 20
 int32_t gs_abi_version(void);
 
 /* Optional per-stage timing (hipEvents recorded on the caller's stream around each stage's launches).
@@ -691,6 +691,33 @@ int gs_grow_gaussians(int32_t width, int32_t height, const float* render_depth, 
 int gs_keyframe_overlap(int32_t n_pts, const float* pts_world, int32_t n_keyframes, const float* w2c,
                         const float* h_intrinsics9, int32_t width, int32_t height, int32_t edge, uint32_t* counts,
                         gs_stream_t stream);
+
+/* ---- Frame ingest (the pre-processing of a sensor frame, src/mapper/splatam/__init__.py:341-376) ----
+ * The raw frame resized to n_out (1 or 2) resolutions -- the mapping and the densification resolution -- in ONE launch.  image: uint8
+ * [height * width * 3], interleaved RGB; depth: fp32 [height * width]; level_value: fp32 [256]; all DEVICE.  h_sizes: HOST, n_out pairs
+ * (W_k, H_k).  Output k: color_k fp32 [3 * H_k * W_k], PLANAR, and depth_k fp32 [H_k * W_k], DEVICE (color1 / depth1 are ignored when n_out
+ * is 1).  No atomics, no scratch, nothing depends on scheduling: two calls on the same inputs give the same bits.
+ *
+ * Colour (cv2.resize(INTER_LINEAR)'s sampling, as activesplat_amd/frames.py resize_linear restates it), in fp64, EVERY operation rounded on its
+ * own.  Per axis, destination sample d of n_dst from n_src:
+ *   r = double(n_src) / double(n_dst);  c = (d + 0.5) * r - 0.5;  i0 = floor(c);  f = c - i0;  taps clamp(i0), clamp(i0 + 1) into [0, n_src - 1]
+ * and per channel, with the taps a b (upper row) and c d (lower row):
+ *   top = a * (1 - fx) + b * fx;  bot = c * (1 - fx) + d * fx;  o = top * (1 - fy) + bot * fy;  level = clamp(floor(o + 0.5), 0, 255)
+ * The value written is level_value[level].  The table is an argument, not level / 255.0f, so that the caller decides what a grey level is: the
+ * binding fills it with the operations its host path applies (uint8 -> float, / 255, by torch on the same device) and the loop receives the bits
+ * it would have received from there.  Equal sizes reproduce the source levels (f = 0 on both axes).
+ * UNPINNED: the product build of the kernel's file allows FMA contraction; the kernel switches it off for itself.  The host-emulated test
+ * build compiles every file without contraction, so no test can tell whether the product kernel contracts: a contraction could move a level
+ * only where o + 0.5 lies within an ulp of an integer.  It is right by construction (the pragma), not by a test.
+ * cv2 itself was NOT run against this rule; its uint8 path quantises the interpolation weights to 11 bits, which can move a result by one level.
+ *
+ * Depth (cv2.resize(INTER_NEAREST); frames.py resize_nearest): source row min((int)floor(double(y) * (double(height) / double(H_k))),
+ * height - 1), likewise for the column, in fp64 -- NOT (y * height) / H_k in integers, which picks another row for some size pairs (2 -> 98
+ * is one).  The 32-bit pattern is copied: NaN payloads, +-inf, -0, negatives and denormals pass through unchanged.
+ *
+ * Supported: 1 <= width, height, W_k, H_k <= 16384, n_out in {1, 2}; anything else, or a null pointer, is GS_EINVAL before any launch. */
+int gs_frame_ingest(int32_t width, int32_t height, const uint8_t* image, const float* depth, const float* level_value, int32_t n_out,
+                    const int32_t* h_sizes, float* color0, float* depth0, float* color1, float* depth1, gs_stream_t stream);
 
 /* ---- Completion / accuracy judge (ActiveSplat's own figure: scripts/judges/eval_actions.py:33-40,139-152) ----
  * Per frame the reference back-projects the sensor depth (rgbd_to_pointcloud, src/utils/gui_utils.py:96-125, called with depth scale 1000 and
