@@ -65,30 +65,184 @@ class GsHullLayout(C.Structure):
 SORT_AUTO, SORT_TILE_LDS, SORT_RADIX = 0, 1, 2
 
 
-# every symbol include/gsplat_hip.h declares (tests check the library exports all of them)
 #: the GS_ABI_VERSION of include/gsplat_hip.h this binding was written against (checked when a library is bound)
 ABI_VERSION = 20
 
-SYMBOLS = ("gs_abi_version", "gs_geom_layout", "gs_image_layout", "gs_bin_layout", "gs_backward_scratch_bytes", "gs_last_error",
-           "gs_version", "gs_set_sort_path", "gs_set_forward_segments", "gs_set_half_quadrants", "gs_set_backward_chain", "gs_set_backward_chain_tickets", "gs_set_backward_chain_polls", "gs_async_status_word", "gs_async_status_clear", "gs_recorded_cut", "gs_set_backward_segments", "gs_preprocess_forward", "gs_preprocess_forward_raw", "gs_render_forward", "gs_render_backward", "gs_render_backward_raw", "gs_render_backward_raw_adam", "gs_adam_step", "gs_adam_step_multi",
-           "gs_profile_enable", "gs_profile_stage_count", "gs_profile_stage_name", "gs_profile_collect",
-           "gs_compact_scratch_bytes", "gs_compact_index", "gs_gather_rows", "gs_mapping_loss_scratch_bytes", "gs_mapping_loss", "gs_activate_forward", "gs_activate_backward", "gs_activate_backward_accumulate",
-           "gs_grow_scratch_bytes", "gs_grow_gaussians", "gs_keyframe_overlap", "gs_visibility_stats", "gs_accumulate_grad2d",
-           "gs_gather_rows_zero_tail", "gs_densify_classify", "gs_densify_children", "gs_atlas_layout",
-           "gs_pack_columns", "gs_adam_rows", "gs_unpack_columns", "gs_compact3_scratch_bytes", "gs_compact_index3",
-           "gs_pose_grad_scratch_bytes", "gs_render_backward_raw_pose", "gs_activate_backward_pose",
-           "gs_tracking_loss_scratch_bytes", "gs_tracking_loss", "gs_preprocess_forward_raw_dev", "gs_render_backward_raw_pose_dev",
-           "gs_tracking_state_bytes", "gs_tracking_begin", "gs_tracking_step",
-           "gs_preprocess_forward_topdown", "gs_render_forward_topdown", "gs_grid_dbscan_layout", "gs_grid_dbscan", "gs_high_loss_grid",
-           "gs_cluster_hulls_layout", "gs_cluster_hulls",
-           "gs_depth_error_median_scratch_bytes", "gs_depth_error_median", "gs_depth_error_median_grid", "gs_depth_error_median_workgroups",
-           "gs_mapping_loss_outlier", "gs_tracking_loss_outlier",
-           "gs_depth_cloud", "gs_cloud_nearest_scratch_bytes", "gs_cloud_nearest", "gs_completion_row_scratch_bytes", "gs_completion_row",
-           "gs_eval_frame_layout", "gs_eval_frame", "gs_frame_ingest")
+vp, i32, u32, i64, u64, f32, f64, cint = C.c_void_p, C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_int
+
+# every symbol include/gsplat_hip.h declares -> (restype, argtypes), in the header's order, each under its parameter names (tests check the library
+# exports all of them and that return type, parameter count and every parameter's class agree with the header's prototype)
+BINDINGS = {
+    # (P, view_width, num_views, virtual_P, atlas_width, view_stride)
+    "gs_atlas_layout": (cint, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+    # (P, width, height, out)
+    "gs_geom_layout": (cint, [i32, i32, i32, C.POINTER(GsGeomLayout)]),
+    # (width, height, out)
+    "gs_image_layout": (cint, [i32, i32, C.POINTER(GsImageLayout)]),
+    # (D, max_tile_instances, width, height, out)
+    "gs_bin_layout": (cint, [i64, u32, i32, i32, C.POINTER(GsBinLayout)]),
+    # (path)
+    "gs_set_sort_path": (cint, [i32]),
+    # (on)
+    "gs_set_forward_segments": (cint, [i32]),
+    # (max_tiles)
+    "gs_set_half_quadrants": (cint, [i32]),
+    # (pieces, min_tiles)
+    "gs_set_backward_chain": (cint, [i32, i32]),
+    # (on)
+    "gs_set_backward_chain_tickets": (cint, [i32]),
+    # (polls)
+    "gs_set_backward_chain_polls": (cint, [i32]),
+    # (host_word)
+    "gs_async_status_word": (cint, [C.POINTER(C.POINTER(u32))]),
+    # ()
+    "gs_async_status_clear": (cint, []),
+    # (target, nearest, level)
+    "gs_recorded_cut": (cint, [u32, C.POINTER(u32), C.POINTER(i32)]),
+    # (segments)
+    "gs_set_backward_segments": (cint, [i32]),
+    # (P)
+    "gs_backward_scratch_bytes": (u64, [i32]),
+    # ()
+    "gs_last_error": (C.c_char_p, []),
+    # ()
+    "gs_version": (C.c_char_p, []),
+    # ()
+    "gs_abi_version": (i32, []),
+    # (on)
+    "gs_profile_enable": (cint, [i32]),
+    # ()
+    "gs_profile_stage_count": (i32, []),
+    # (stage)
+    "gs_profile_stage_name": (C.c_char_p, [i32]),
+    # (ms_sum, calls, n_stages)
+    "gs_profile_collect": (cint, [vp, vp, i32]),
+    # (cam, P, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii, geom_state, image_state, d_counts, h_counts, want_backward, stream)
+    "gs_preprocess_forward": (cint, [C.POINTER(GsCamera), i32] + [vp] * 12 + [i32, vp]),
+    # (cam, P, D, max_tile_instances, geom_state, bin_state, point_list, image_state, out_color, out_depth, out_opacity, out_depth_sq, backward_scratch, stream)
+    "gs_render_forward": (cint, [C.POINTER(GsCamera), i32, i64, u32] + [vp] * 10),
+    # (cam, P, D, means3D, shs, colors_precomp, scales, rotations, cov3D_precomp, radii, geom_state, point_list, image_state, dL_dcolor, dL_ddepth, dL_dmeans2D, dL_dmeans3D, dL_dopacities, dL_dcolors_precomp, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, scratch, scratch_zeroed, have_sh_jacobian, stream)
+    "gs_render_backward": (cint, [C.POINTER(GsCamera), i32, i64] + [vp] * 21 + [i32, i32, vp]),
+    # (cam, P, means3D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, h_pose7, isotropic, max_2D_radius, seen, radii, geom_state, image_state, d_counts, h_counts, want_backward, stream)
+    "gs_preprocess_forward_raw": (cint, [C.POINTER(GsCamera), i32] + [vp] * 7 + [i32] + [vp] * 7 + [i32, vp]),
+    # (cam, P, D, means3D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, h_pose7, isotropic, accumulate, radii, geom_state, point_list, image_state, dL_dcolor, dL_ddepth, dL_dmeans2D, dL_dmeans3D, dL_dlogit_opacities, dL_dcolors_precomp, dL_dshs, dL_dlog_scales, dL_dunnorm_rotations, scratch, scratch_zeroed, have_sh_jacobian, stream)
+    "gs_render_backward_raw": (cint, [C.POINTER(GsCamera), i32, i64] + [vp] * 7 + [i32, i32] + [vp] * 14 + [i32, i32, vp]),
+    # (P)
+    "gs_pose_grad_scratch_bytes": (u64, [i32]),
+    # (cam, P, D, means3D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, h_pose7, isotropic, accumulate, radii, geom_state, point_list, image_state, dL_dcolor, dL_ddepth, dL_dmeans2D, dL_dmeans3D, dL_dlogit_opacities, dL_dcolors_precomp, dL_dshs, dL_dlog_scales, dL_dunnorm_rotations, scratch, scratch_zeroed, have_sh_jacobian, pose_only, dL_dpose7, pose_scratch, stream)
+    "gs_render_backward_raw_pose": (cint, [C.POINTER(GsCamera), i32, i64] + [vp] * 7 + [i32, i32] + [vp] * 14 + [i32, i32, i32, vp, vp, vp]),
+    # (n, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, stream)
+    "gs_adam_step": (cint, [i64] + [vp] * 4 + [f64] * 4 + [i32, vp]),
+    # (count, tensors, stream)
+    "gs_adam_step_multi": (cint, [i32, C.POINTER(GsAdamTensor), vp]),
+    # (cam, P, D, means3D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, h_pose7, isotropic, radii, geom_state, point_list, image_state, dL_dcolor, dL_ddepth, dL_dmeans2D, scratch, scratch_zeroed, have_sh_jacobian, adam5, stream)
+    "gs_render_backward_raw_adam": (cint, [C.POINTER(GsCamera), i32, i64] + [vp] * 7 + [i32] + [vp] * 8 + [i32, i32, C.POINTER(GsAdamTensor), vp]),
+    # (count, tensors, n, n_padded, flat, stream)
+    "gs_pack_columns": (cint, [i32, C.POINTER(GsRowTensor), i64, i64, vp, vp]),
+    # (count, tensors, row_lo, n_valid, n_rows, grad_shard, out_shard, stream)
+    "gs_adam_rows": (cint, [i32, C.POINTER(GsRowTensor), i64, i64, i64, vp, vp, vp]),
+    # (count, tensors, n, flat, stream)
+    "gs_unpack_columns": (cint, [i32, C.POINTER(GsRowTensor), i64, vp, vp]),
+    # (P, isotropic, h_pose7, means3D, unnorm_rotations, logit_opacities, log_scales, out_means3D, out_rotations, out_opacities, out_scales, stream)
+    "gs_activate_forward": (cint, [i32, i32] + [vp] * 10),
+    # (P, isotropic, h_pose7, unnorm_rotations, out_opacities, out_scales, g_means3D, g_rotations, g_opacities, g_scales, d_means3D, d_unnorm_rotations, d_logit_opacities, d_log_scales, stream)
+    "gs_activate_backward": (cint, [i32, i32] + [vp] * 13),
+    # (P, isotropic, h_pose7, unnorm_rotations, out_opacities, out_scales, g_means3D, g_rotations, g_opacities, g_scales, d_means3D, d_unnorm_rotations, d_logit_opacities, d_log_scales, stream)
+    "gs_activate_backward_accumulate": (cint, [i32, i32] + [vp] * 13),
+    # (P, isotropic, h_pose7, means3D, unnorm_rotations, out_opacities, out_scales, g_means3D, g_rotations, g_opacities, g_scales, d_means3D, d_unnorm_rotations, d_logit_opacities, d_log_scales, accumulate, pose_only, dL_dpose7, pose_scratch, stream)
+    "gs_activate_backward_pose": (cint, [i32, i32] + [vp] * 13 + [i32, i32, vp, vp, vp]),
+    # (width, height)
+    "gs_mapping_loss_scratch_bytes": (u64, [i32, i32]),
+    # (width, height, im, gt_im, depth, depth_sq, gt_depth, w_im, w_depth, losses, dL_dim, dL_ddepth, scratch, persistent_call, stream)
+    "gs_mapping_loss": (cint, [i32, i32] + [vp] * 5 + [f32, f32] + [vp] * 4 + [i64, vp]),
+    # (width, height)
+    "gs_depth_error_median_scratch_bytes": (u64, [i32, i32]),
+    # (width, height, depth, gt_depth, scratch, d_median, stream)
+    "gs_depth_error_median": (cint, [i32, i32] + [vp] * 5),
+    # (width, height, depth, gt_depth, scratch, d_median, workgroups, stream)
+    "gs_depth_error_median_grid": (cint, [i32, i32] + [vp] * 4 + [i32, vp]),
+    # (width, height)
+    "gs_depth_error_median_workgroups": (i32, [i32, i32]),
+    # (width, height, im, gt_im, depth, depth_sq, gt_depth, w_im, w_depth, losses, dL_dim, dL_ddepth, scratch, persistent_call, d_median, stream)
+    "gs_mapping_loss_outlier": (cint, [i32, i32] + [vp] * 5 + [f32, f32] + [vp] * 4 + [i64, vp, vp]),
+    # (width, height)
+    "gs_tracking_loss_scratch_bytes": (u64, [i32, i32]),
+    # (width, height, im, gt_im, depth, depth_sq, gt_depth, silhouette, use_sil_for_loss, sil_thres, w_im, w_depth, dL_dim, dL_ddepth, loss_rows, losses, stream)
+    "gs_tracking_loss": (cint, [i32, i32] + [vp] * 6 + [i32, f32, f32, f32] + [vp] * 5),
+    # (width, height, im, gt_im, depth, depth_sq, gt_depth, silhouette, use_sil_for_loss, sil_thres, w_im, w_depth, dL_dim, dL_ddepth, loss_rows, losses, d_median, stream)
+    "gs_tracking_loss_outlier": (cint, [i32, i32] + [vp] * 6 + [i32, f32, f32, f32] + [vp] * 6),
+    # (cam, P, means3D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, cam_unnorm_rots, cam_trans, num_frames, time_idx, isotropic, max_2D_radius, seen, radii, geom_state, image_state, d_counts, h_counts, want_backward, stream)
+    "gs_preprocess_forward_raw_dev": (cint, [C.POINTER(GsCamera), i32] + [vp] * 8 + [i64, i64, i32] + [vp] * 7 + [i32, vp]),
+    # (cam, P, means3D, colors_precomp, logit_opacities, log_scales, unnorm_rotations, isotropic, band_upper, band_lower, radii, geom_state, image_state, d_counts, h_counts, stream)
+    "gs_preprocess_forward_topdown": (cint, [C.POINTER(GsCamera), i32] + [vp] * 5 + [i32, f32, f32] + [vp] * 6),
+    # (cam, P, D, max_tile_instances, geom_state, bin_state, point_list, image_state, free_opacity, free_map_binary, visible_rgb, visible_map_binary, stream)
+    "gs_render_forward_topdown": (cint, [C.POINTER(GsCamera), i32, i64, u32] + [vp] * 9),
+    # (cam, P, D, means3D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, cam_unnorm_rots, cam_trans, num_frames, time_idx, isotropic, radii, geom_state, point_list, image_state, dL_dcolor, dL_ddepth, dL_dmeans2D, scratch, scratch_zeroed, have_sh_jacobian, dL_dpose7, pose_scratch, stream)
+    "gs_render_backward_raw_pose_dev": (cint, [C.POINTER(GsCamera), i32, i64] + [vp] * 8 + [i64, i64, i32] + [vp] * 8 + [i32, i32, vp, vp, vp]),
+    # ()
+    "gs_tracking_state_bytes": (u64, []),
+    # (cam_unnorm_rots, cam_trans, num_frames, time_idx, state, stream)
+    "gs_tracking_begin": (cint, [vp, vp, i64, i64, vp, vp]),
+    # (P, pose_scratch, width, height, loss_rows, w_im, w_depth, cam_unnorm_rots, cam_trans, num_frames, time_idx, lr_rot, lr_trans, step, state, history_row, stream)
+    "gs_tracking_step": (cint, [i32, vp, i32, i32, vp, f32, f32, vp, vp, i64, i64, f64, f64, i32, vp, vp, vp]),
+    # (n)
+    "gs_compact_scratch_bytes": (u64, [i64]),
+    # (n, keep, src_index, d_count, scratch, stream)
+    "gs_compact_index": (cint, [i64] + [vp] * 5),
+    # (n_out, row_floats, src_index, src, dst, stream)
+    "gs_gather_rows": (cint, [i64, i32] + [vp] * 4),
+    # (n_out, n_copy, row_floats, src_index, src, dst, stream)
+    "gs_gather_rows_zero_tail": (cint, [i64, i64, i32] + [vp] * 4),
+    # (N, scale_dim, log_scales, logit_opacities, grad_accum, denom, d_scene_radius, grad_thresh, opacity_thresh, remove_big, num_to_split_into, keep_orig, keep_clone, keep_child, split_mask, stream)
+    "gs_densify_classify": (cint, [i32, i32] + [vp] * 5 + [f32, f32, i32, i32] + [vp] * 5),
+    # (n_child, scale_dim, num_to_split_into, unnorm_rotations, samples, seed, means3D, log_scales, stream)
+    "gs_densify_children": (cint, [i32, i32, i32, vp, vp, u64, vp, vp, vp]),
+    # (n)
+    "gs_compact3_scratch_bytes": (u64, [i64]),
+    # (n, keep_a, keep_b, keep_c, repeat_c, src_index, d_counts, scratch, stream)
+    "gs_compact_index3": (cint, [i64, vp, vp, vp, i32] + [vp] * 4),
+    # (P, radii, seen, max_2D_radius, stream)
+    "gs_visibility_stats": (cint, [i32] + [vp] * 4),
+    # (P, means2D_grad, seen, grad_accum, denom, stream)
+    "gs_accumulate_grad2d": (cint, [i32] + [vp] * 5),
+    # (B, H, W, max_clusters, out)
+    "gs_grid_dbscan_layout": (cint, [i32] * 4 + [C.POINTER(GsDbscanLayout)]),
+    # (B, H, W, values, row_stride, image_stride, threshold, complement, eps, min_samples, max_clusters, workspace, labels, n_clusters, table, sum_value, total, stream)
+    "gs_grid_dbscan": (cint, [i32, i32, i32, vp, i64, i64, f32] + [i32] * 4 + [vp] * 7),
+    # (B, H, W, max_clusters, max_points, out)
+    "gs_cluster_hulls_layout": (cint, [i32] * 5 + [C.POINTER(GsHullLayout)]),
+    # (B, H, W, labels, depth, row_stride, image_stride, n_clusters, sum_value, max_clusters, footprint_rows, kh, kw, skip_depth, x_scale, y_scale, max_points, workspace, volume, n_points, contour_xy, sum_volume, sum_invisibility, status, stream)
+    "gs_cluster_hulls": (cint, [i32, i32, i32, vp, vp, i64, i64, vp, vp, i32, C.POINTER(u32), i32, i32, f32, f64, f64, i32] + [vp] * 8),
+    # (width, height, render_depth, opacity, gt_depth, depth_err_thres, opacity_thres, grid_width, grid_height, mask_full, grid, stream)
+    "gs_high_loss_grid": (cint, [i32, i32, vp, vp, vp, f32, f32, i32, i32, vp, vp, vp]),
+    # (width, height)
+    "gs_grow_scratch_bytes": (u64, [i32, i32]),
+    # (width, height, render_depth, silhouette, gt_depth, color, h_intrinsics4, h_c2w12, sil_thres, isotropic, out_means3D, out_rgb_colors, out_unnorm_rotations, out_logit_opacities, out_log_scales, d_counts, scratch, stream)
+    "gs_grow_gaussians": (cint, [i32, i32] + [vp] * 6 + [f32, i32] + [vp] * 8),
+    # (n_pts, pts_world, n_keyframes, w2c, h_intrinsics9, width, height, edge, counts, stream)
+    "gs_keyframe_overlap": (cint, [i32, vp, i32, vp, vp, i32, i32, i32, vp, vp]),
+    # (width, height, image, depth, level_value, n_out, h_sizes, color0, depth0, color1, depth1, stream)
+    "gs_frame_ingest": (cint, [i32, i32, vp, vp, vp, i32, C.POINTER(i32)] + [vp] * 5),
+    # (width, height, depth, h_intrinsics4, h_c2w12, points, valid, stream)
+    "gs_depth_cloud": (cint, [i32, i32, vp, C.POINTER(f32), C.POINTER(f32), vp, vp, vp]),
+    # (n_query, n_points)
+    "gs_cloud_nearest_scratch_bytes": (u64, [i64, i64]),
+    # (n_query, query, query_valid, n_points, points, points_valid, flags, out, scratch, stream)
+    "gs_cloud_nearest": (cint, [i64, vp, vp, i64, vp, vp, i32, vp, vp, vp]),
+    # ()
+    "gs_completion_row_scratch_bytes": (u64, []),
+    # (n_samples, min_dist, n_acc, acc_dist, acc_valid, path_length, row6, scratch, stream)
+    "gs_completion_row": (cint, [i64, vp, i64, vp, vp, f64, vp, vp, vp]),
+    # (width, height, flags, layout)
+    "gs_eval_frame_layout": (cint, [i32, i32, i32, C.POINTER(GsEvalLayout)]),
+    # (width, height, im, depth, silhouette, gt_im, gt_depth, sil_thres, flags, row, scratch, stream)
+    "gs_eval_frame": (cint, [i32, i32] + [vp] * 5 + [f32, i32, vp, vp, vp]),
+}
+
+SYMBOLS = tuple(BINDINGS)
 
 
 def _bind(lib):
-    vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
     # a stale prebuilt library (another round's .so, an old emulated build) must fail HERE, not misread pointers later
     try:
         lib.gs_abi_version.restype = i32
@@ -98,189 +252,9 @@ def _bind(lib):
     if have != ABI_VERSION:
         raise RuntimeError(f"{getattr(lib, '_name', 'library')}: C ABI version {have}, this binding needs {ABI_VERSION} (include/gsplat_hip.h "
                            "GS_ABI_VERSION) -- rebuild it: python -c 'import __graft_entry__ as g; g.build()'")
-    lib.gs_geom_layout.argtypes = [i32, i32, i32, C.POINTER(GsGeomLayout)]
-    lib.gs_atlas_layout.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
-    lib.gs_atlas_layout.restype = C.c_int
-    lib.gs_set_sort_path.argtypes = [i32]
-    lib.gs_set_sort_path.restype = C.c_int
-    lib.gs_set_forward_segments.argtypes = [i32]
-    lib.gs_set_half_quadrants.argtypes = [i32]
-    lib.gs_set_half_quadrants.restype = C.c_int
-    lib.gs_set_backward_chain.argtypes = [i32, i32]
-    lib.gs_set_backward_chain.restype = C.c_int
-    lib.gs_set_backward_segments.argtypes = [i32]
-    lib.gs_set_backward_segments.restype = C.c_int
-    lib.gs_set_backward_chain_tickets.argtypes = [i32]
-    lib.gs_set_backward_chain_tickets.restype = C.c_int
-    lib.gs_set_backward_chain_polls.argtypes = [i32]
-    lib.gs_set_backward_chain_polls.restype = C.c_int
-    lib.gs_async_status_clear.argtypes = []
-    lib.gs_async_status_clear.restype = C.c_int
-    lib.gs_async_status_word.argtypes = [C.POINTER(C.POINTER(C.c_uint32))]
-    lib.gs_async_status_word.restype = C.c_int
-    lib.gs_recorded_cut.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(i32)]
-    lib.gs_recorded_cut.restype = C.c_int
-    lib.gs_set_forward_segments.restype = C.c_int
-    lib.gs_image_layout.argtypes = [i32, i32, C.POINTER(GsImageLayout)]
-    lib.gs_bin_layout.argtypes = [i64, C.c_uint32, i32, i32, C.POINTER(GsBinLayout)]
-    lib.gs_backward_scratch_bytes.argtypes = [i32]
-    lib.gs_backward_scratch_bytes.restype = C.c_uint64
-    lib.gs_last_error.restype = C.c_char_p
-    lib.gs_version.restype = C.c_char_p
-    lib.gs_preprocess_forward.argtypes = [C.POINTER(GsCamera), i32] + [vp] * 7 + [vp, vp, vp, vp, vp, i32, vp]
-    lib.gs_render_forward.argtypes = [C.POINTER(GsCamera), i32, i64, C.c_uint32] + [vp] * 8 + [vp, vp]
-    lib.gs_render_backward.argtypes = [C.POINTER(GsCamera), i32, i64] + [vp] * 6 + [vp] * 6 + [vp] * 8 + [vp, i32, i32, vp]
-    # (cam, P, means3D, shs, colors, logit, log_scales, unnorm_rot, h_pose7, isotropic, max_2D_radius, seen, radii, geom, image, d_counts, h_counts, want_backward, stream)
-    lib.gs_preprocess_forward_raw.argtypes = [C.POINTER(GsCamera), i32] + [vp] * 6 + [vp, i32] + [vp, vp] + [vp] * 5 + [i32, vp]
-    # (cam, P, D, means3D, shs, colors, logit, log_scales, unnorm_rot, h_pose7, isotropic, accumulate, radii, geom, point_list, image,
-    #  dL_dcolor, dL_ddepth, 7 gradient outputs, scratch, scratch_zeroed, have_sh_jacobian, stream)
-    lib.gs_render_backward_raw.argtypes = [C.POINTER(GsCamera), i32, i64] + [vp] * 6 + [vp, i32, i32] + [vp] * 4 + [vp] * 2 + [vp] * 7 + [vp, i32, i32, vp]
-    # (cam, P, D, means3D, shs, colors, logit, log_scales, unnorm_rot, h_pose7, isotropic, radii, geom, point_list, image, dL_dcolor, dL_ddepth,
-    #  dL_dmeans2D, scratch, scratch_zeroed, have_sh_jacobian, adam5, stream)
-    lib.gs_render_backward_raw_adam.argtypes = [C.POINTER(GsCamera), i32, i64] + [vp] * 6 + [vp, i32] + [vp] * 4 + [vp] * 2 + [vp] + [vp, i32, i32] + \
-        [C.POINTER(GsAdamTensor), vp]
-    lib.gs_render_backward_raw_adam.restype = C.c_int
-    # gs_render_backward_raw's arguments, then pose_only, dL_dpose7, pose_scratch, stream
-    lib.gs_render_backward_raw_pose.argtypes = [C.POINTER(GsCamera), i32, i64] + [vp] * 6 + [vp, i32, i32] + [vp] * 4 + [vp] * 2 + [vp] * 7 + \
-        [vp, i32, i32, i32, vp, vp, vp]
-    lib.gs_render_backward_raw_pose.restype = C.c_int
-    # top-down maps: (cam, P, means3D, colors, logit, log_scales, unnorm_rot, isotropic, band_upper, band_lower, radii, geom, image, d_counts,
-    #  h_counts, stream)
-    lib.gs_preprocess_forward_topdown.argtypes = [C.POINTER(GsCamera), i32] + [vp] * 5 + [i32, f32, f32] + [vp] * 5 + [vp]
-    lib.gs_preprocess_forward_topdown.restype = C.c_int
-    # (cam, P, D, max_tile_instances, geom, binning, point_list, image, free_opacity, free_map_binary, visible_rgb, visible_map_binary, stream)
-    lib.gs_render_forward_topdown.argtypes = [C.POINTER(GsCamera), i32, i64, C.c_uint32] + [vp] * 8 + [vp]
-    lib.gs_render_forward_topdown.restype = C.c_int
-    # (B, H, W, max_clusters, layout)
-    lib.gs_grid_dbscan_layout.argtypes = [i32, i32, i32, i32, C.POINTER(GsDbscanLayout)]
-    lib.gs_grid_dbscan_layout.restype = C.c_int
-    # (B, H, W, values, row_stride, image_stride, threshold, complement, eps, min_samples, max_clusters, workspace, labels, n_clusters, table,
-    #  sum_value, total, stream)
-    lib.gs_grid_dbscan.argtypes = [i32, i32, i32, vp, i64, i64, f32, i32, i32, i32, i32] + [vp] * 6 + [vp]
-    lib.gs_grid_dbscan.restype = C.c_int
-    # (B, H, W, max_clusters, max_points, layout)
-    lib.gs_cluster_hulls_layout.argtypes = [i32, i32, i32, i32, i32, C.POINTER(GsHullLayout)]
-    lib.gs_cluster_hulls_layout.restype = C.c_int
-    # (B, H, W, labels, depth, row_stride, image_stride, n_clusters, sum_value, max_clusters, footprint_rows (host uint32[kh]), kh, kw, skip_depth,
-    #  x_scale, y_scale, max_points, workspace, volume, n_points, contour_xy, sum_volume, sum_invisibility, status, stream)
-    lib.gs_cluster_hulls.argtypes = [i32, i32, i32, vp, vp, i64, i64, vp, vp, i32, C.POINTER(C.c_uint32), i32, i32, f32, C.c_double, C.c_double, i32] + [vp] * 7 + [vp]
-    lib.gs_cluster_hulls.restype = C.c_int
-    # (width, height, render_depth, opacity, gt_depth, depth_err_thres, opacity_thres, grid_width, grid_height, mask_full, grid, stream)
-    lib.gs_high_loss_grid.argtypes = [i32, i32, vp, vp, vp, f32, f32, i32, i32, vp, vp, vp]
-    lib.gs_high_loss_grid.restype = C.c_int
-    # tracking: (cam, P, means3D, shs, colors, logit, log_scales, unnorm_rot, cam_unnorm_rots, cam_trans, num_frames, time_idx, isotropic,
-    #  max_2D_radius, seen, radii, geom, image, d_counts, h_counts, want_backward, stream)
-    lib.gs_preprocess_forward_raw_dev.argtypes = [C.POINTER(GsCamera), i32] + [vp] * 6 + [vp, vp, i64, i64, i32] + [vp] * 7 + [i32, vp]
-    lib.gs_preprocess_forward_raw_dev.restype = C.c_int
-    # (cam, P, D, means3D, shs, colors, logit, log_scales, unnorm_rot, cam_unnorm_rots, cam_trans, num_frames, time_idx, isotropic, radii, geom,
-    #  point_list, image, dL_dcolor, dL_ddepth, dL_dmeans2D, scratch, scratch_zeroed, have_sh_jacobian, dL_dpose7, pose_scratch, stream)
-    lib.gs_render_backward_raw_pose_dev.argtypes = [C.POINTER(GsCamera), i32, i64] + [vp] * 6 + [vp, vp, i64, i64, i32] + [vp] * 7 + \
-        [vp, i32, i32, vp, vp, vp]
-    lib.gs_render_backward_raw_pose_dev.restype = C.c_int
-    # the completion / accuracy judge: (width, height, depth, h_intrinsics4, h_c2w12, points, valid, stream)
-    lib.gs_depth_cloud.argtypes = [i32, i32, vp, C.POINTER(f32), C.POINTER(f32), vp, vp, vp]
-    lib.gs_depth_cloud.restype = C.c_int
-    lib.gs_cloud_nearest_scratch_bytes.argtypes = [i64, i64]
-    lib.gs_cloud_nearest_scratch_bytes.restype = C.c_uint64
-    # (n_query, query, query_valid, n_points, points, points_valid, flags, out, scratch, stream)
-    lib.gs_cloud_nearest.argtypes = [i64, vp, vp, i64, vp, vp, i32, vp, vp, vp]
-    lib.gs_cloud_nearest.restype = C.c_int
-    lib.gs_completion_row_scratch_bytes.argtypes = []
-    lib.gs_completion_row_scratch_bytes.restype = C.c_uint64
-    # (n_samples, min_dist, n_acc, acc_dist, acc_valid, path_length, row6, scratch, stream)
-    lib.gs_completion_row.argtypes = [i64, vp, i64, vp, vp, C.c_double, vp, vp, vp]
-    lib.gs_completion_row.restype = C.c_int
-    # map-quality evaluation: (width, height, flags, layout); (width, height, im, depth, silhouette, gt_im, gt_depth, sil_thres, flags, row8, scratch, stream)
-    lib.gs_eval_frame_layout.argtypes = [i32, i32, i32, C.POINTER(GsEvalLayout)]
-    lib.gs_eval_frame_layout.restype = C.c_int
-    lib.gs_eval_frame.argtypes = [i32, i32, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp]
-    lib.gs_eval_frame.restype = C.c_int
-    # frame ingest: (width, height, image, depth, level_value, n_out, h_sizes (host int32 pairs), color0, depth0, color1, depth1, stream)
-    lib.gs_frame_ingest.argtypes = [i32, i32, vp, vp, vp, i32, C.POINTER(i32), vp, vp, vp, vp, vp]
-    lib.gs_frame_ingest.restype = C.c_int
-    lib.gs_tracking_loss_scratch_bytes.argtypes = [i32, i32]
-    lib.gs_tracking_loss_scratch_bytes.restype = C.c_uint64
-    lib.gs_tracking_loss.argtypes = [i32, i32] + [vp] * 6 + [i32, f32, f32, f32] + [vp] * 4 + [vp]
-    lib.gs_tracking_loss.restype = C.c_int
-    lib.gs_tracking_loss_outlier.argtypes = [i32, i32] + [vp] * 6 + [i32, f32, f32, f32] + [vp] * 4 + [vp, vp]       # (..., d_median, stream)
-    lib.gs_tracking_loss_outlier.restype = C.c_int
-    lib.gs_tracking_state_bytes.argtypes = []
-    lib.gs_tracking_state_bytes.restype = C.c_uint64
-    lib.gs_tracking_begin.argtypes = [vp, vp, i64, i64, vp, vp]
-    lib.gs_tracking_begin.restype = C.c_int
-    lib.gs_tracking_step.argtypes = [i32, vp, i32, i32, vp, f32, f32, vp, vp, i64, i64, C.c_double, C.c_double, i32, vp, vp, vp]
-    lib.gs_tracking_step.restype = C.c_int
-    lib.gs_pose_grad_scratch_bytes.argtypes = [i32]
-    lib.gs_pose_grad_scratch_bytes.restype = C.c_uint64
-    lib.gs_preprocess_forward_raw.restype = C.c_int
-    lib.gs_render_backward_raw.restype = C.c_int
-    lib.gs_adam_step.argtypes = [i64, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, i32, vp]
-    lib.gs_adam_step_multi.argtypes = [i32, C.POINTER(GsAdamTensor), vp]
-    lib.gs_profile_enable.argtypes = [i32]
-    lib.gs_profile_stage_count.restype = i32
-    lib.gs_profile_stage_name.argtypes = [i32]
-    lib.gs_profile_stage_name.restype = C.c_char_p
-    lib.gs_profile_collect.argtypes = [vp, vp, i32]
-    lib.gs_profile_collect.restype = C.c_int
-    lib.gs_activate_forward.argtypes = [i32, i32] + [vp] * 9 + [vp]
-    lib.gs_activate_forward.restype = C.c_int
-    lib.gs_activate_backward.argtypes = [i32, i32] + [vp] * 12 + [vp]
-    lib.gs_activate_backward.restype = C.c_int
-    lib.gs_activate_backward_accumulate.argtypes = [i32, i32] + [vp] * 12 + [vp]
-    lib.gs_activate_backward_accumulate.restype = C.c_int
-    # (P, isotropic, h_pose7, means3D, unnorm_rot, out_op, out_scales, 4 gradients in, 4 out, accumulate, pose_only, dL_dpose7, pose_scratch, stream)
-    lib.gs_activate_backward_pose.argtypes = [i32, i32] + [vp] * 13 + [i32, i32, vp, vp, vp]
-    lib.gs_activate_backward_pose.restype = C.c_int
-    lib.gs_mapping_loss_scratch_bytes.argtypes = [i32, i32]
-    lib.gs_mapping_loss_scratch_bytes.restype = C.c_uint64
-    lib.gs_mapping_loss.argtypes = [i32, i32, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, i64, vp]
-    lib.gs_mapping_loss.restype = C.c_int
-    lib.gs_mapping_loss_outlier.argtypes = [i32, i32, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, i64, vp, vp]    # (..., d_median, stream)
-    lib.gs_mapping_loss_outlier.restype = C.c_int
-    lib.gs_depth_error_median_scratch_bytes.argtypes = [i32, i32]
-    lib.gs_depth_error_median_scratch_bytes.restype = C.c_uint64
-    lib.gs_depth_error_median.argtypes = [i32, i32, vp, vp, vp, vp, vp]
-    lib.gs_depth_error_median.restype = C.c_int
-    lib.gs_depth_error_median_grid.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp]      # (..., workgroups, stream)
-    lib.gs_depth_error_median_grid.restype = C.c_int
-    lib.gs_depth_error_median_workgroups.argtypes = [i32, i32]
-    lib.gs_depth_error_median_workgroups.restype = i32
-    lib.gs_compact_scratch_bytes.argtypes = [i64]
-    lib.gs_compact_scratch_bytes.restype = C.c_uint64
-    lib.gs_compact_index.argtypes = [i64, vp, vp, vp, vp, vp]
-    lib.gs_compact_index.restype = C.c_int
-    lib.gs_gather_rows.argtypes = [i64, i32, vp, vp, vp, vp]
-    lib.gs_gather_rows.restype = C.c_int
-    lib.gs_gather_rows_zero_tail.argtypes = [i64, i64, i32, vp, vp, vp, vp]
-    lib.gs_gather_rows_zero_tail.restype = C.c_int
-    lib.gs_densify_classify.argtypes = [i32, i32, vp, vp, vp, vp, vp, f32, f32, i32, i32, vp, vp, vp, vp, vp]
-    lib.gs_densify_classify.restype = C.c_int
-    lib.gs_densify_children.argtypes = [i32, i32, i32, vp, vp, C.c_uint64, vp, vp, vp]
-    lib.gs_compact3_scratch_bytes.argtypes = [i64]
-    lib.gs_compact3_scratch_bytes.restype = C.c_uint64
-    lib.gs_compact_index3.argtypes = [i64, vp, vp, vp, i32, vp, vp, vp, vp]
-    lib.gs_compact_index3.restype = C.c_int
-    lib.gs_densify_children.restype = C.c_int
-    lib.gs_grow_scratch_bytes.argtypes = [i32, i32]
-    lib.gs_grow_scratch_bytes.restype = C.c_uint64
-    lib.gs_grow_gaussians.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.gs_grow_gaussians.restype = C.c_int
-    lib.gs_keyframe_overlap.argtypes = [i32, vp, i32, vp, vp, i32, i32, i32, vp, vp]
-    lib.gs_keyframe_overlap.restype = C.c_int
-    lib.gs_visibility_stats.argtypes = [i32, vp, vp, vp, vp]
-    lib.gs_visibility_stats.restype = C.c_int
-    lib.gs_accumulate_grad2d.argtypes = [i32, vp, vp, vp, vp, vp]
-    lib.gs_accumulate_grad2d.restype = C.c_int
-    lib.gs_adam_step_multi.restype = C.c_int
-    lib.gs_pack_columns.argtypes = [i32, C.POINTER(GsRowTensor), i64, i64, vp, vp]
-    lib.gs_pack_columns.restype = C.c_int
-    lib.gs_adam_rows.argtypes = [i32, C.POINTER(GsRowTensor), i64, i64, i64, vp, vp, vp]
-    lib.gs_adam_rows.restype = C.c_int
-    lib.gs_unpack_columns.argtypes = [i32, C.POINTER(GsRowTensor), i64, vp, vp]
-    lib.gs_unpack_columns.restype = C.c_int
-    for n in ("gs_geom_layout", "gs_image_layout", "gs_bin_layout", "gs_preprocess_forward", "gs_render_forward",
-              "gs_render_backward", "gs_adam_step"):
-        getattr(lib, n).restype = C.c_int
+    for name, (restype, argtypes) in BINDINGS.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     return lib
 
 

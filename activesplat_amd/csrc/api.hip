@@ -17,6 +17,14 @@ int fail(int code, const char* fmt, const char* a = "")
     return code;
 }
 
+// GS_OK, or the recorded GS_ELAUNCH failure "who: [what ]<the runtime's text>"
+int launched(const char* who, const char* what, hipError_t e)
+{
+    if (e == hipSuccess) return GS_OK;
+    snprintf(g_err, sizeof(g_err), "%s: %s%s%s", who, what, *what ? " " : "", hipGetErrorString(e));
+    return GS_ELAUNCH;
+}
+
 // adam.hip and the Adam inside the per-Gaussian backward reinterpret these pointers as float4*
 bool adam_aligned16(const void* p, const void* g, const void* m, const void* v)
 {
@@ -76,6 +84,13 @@ int tile_bits(int tiles)
     return b;
 }
 
+int32_t tiles_across(int32_t pixels) { return (pixels + gs::kTile - 1) / gs::kTile; }
+uint64_t tiles_of(int32_t width, int32_t height) { return (uint64_t)tiles_across(width) * tiles_across(height); }
+// multi-view atlas: every view padded to whole tiles; V x (P rounded up to whole 256-row blocks) virtual Gaussians (one view: nothing padded)
+int32_t atlas_view_stride(int32_t view_width, int32_t V) { return V > 1 ? tiles_across(view_width) * gs::kTile : view_width; }
+int32_t blocks_of(int32_t P) { return (P + gs::kBlock - 1) / gs::kBlock; }
+int32_t virtual_rows(int32_t P, int32_t V) { return V > 1 ? V * blocks_of(P) * gs::kBlock : P; }
+
 bool make_cam(const GsCamera* c, gs::Cam& k)
 {
     if (!c || c->image_width <= 0 || c->image_height <= 0 || !c->bg || !c->viewmatrix || !c->projmatrix) return false;
@@ -83,9 +98,9 @@ bool make_cam(const GsCamera* c, gs::Cam& k)
     if (c->num_views < 0 || c->num_views > 64) return false;
     k.V = c->num_views > 1 ? c->num_views : 1;
     k.Wv = c->image_width; k.H = c->image_height;
-    k.gxv = (k.Wv + gs::kTile - 1) / gs::kTile;
-    k.gx = k.V * k.gxv; k.gy = (k.H + gs::kTile - 1) / gs::kTile;
-    k.W = k.V > 1 ? k.gx * gs::kTile : k.Wv;               // atlas: every view padded to whole tiles
+    k.gxv = tiles_across(k.Wv);
+    k.gx = k.V * k.gxv; k.gy = tiles_across(k.H);
+    k.W = k.V * atlas_view_stride(k.Wv, k.V);
     k.nbv = 0;                                             // set by virtual_count()
     if (k.gx >= 65536 || k.gy >= 65536) return false;
     k.tanfovx = c->tanfovx; k.tanfovy = c->tanfovy;
@@ -98,11 +113,11 @@ bool make_cam(const GsCamera* c, gs::Cam& k)
     return true;
 }
 
-// rows of the per-Gaussian state: P for one view; V x (P rounded up to whole 256-row blocks) virtual Gaussians for an atlas
+// rows of the per-Gaussian state: P for one view; the atlas's virtual Gaussians
 int32_t virtual_count(gs::Cam& k, int32_t P)
 {
-    k.nbv = (P + gs::kBlock - 1) / gs::kBlock;
-    return k.V > 1 ? k.V * k.nbv * gs::kBlock : P;
+    k.nbv = blocks_of(P);
+    return virtual_rows(P, k.V);
 }
 
 gs::GeomPtrs carve_geom(void* base, int32_t P, const gs::Cam& k)
@@ -247,10 +262,9 @@ int gs_set_forward_segments(int32_t on)
 int gs_atlas_layout(int32_t P, int32_t view_width, int32_t num_views, int32_t* virtual_P, int32_t* atlas_width, int32_t* view_stride)
 {
     if (P < 0 || view_width <= 0 || num_views < 1 || num_views > 64) return fail(GS_EINVAL, "gs_atlas_layout: bad argument");
-    const int32_t gxv = (view_width + gs::kTile - 1) / gs::kTile;
-    const int32_t stride = num_views > 1 ? gxv * gs::kTile : view_width;
-    if (virtual_P) *virtual_P = num_views > 1 ? num_views * ((P + gs::kBlock - 1) / gs::kBlock) * gs::kBlock : P;
-    if (atlas_width) *atlas_width = num_views > 1 ? num_views * stride : view_width;
+    const int32_t stride = atlas_view_stride(view_width, num_views);
+    if (virtual_P) *virtual_P = virtual_rows(P, num_views);
+    if (atlas_width) *atlas_width = num_views * stride;
     if (view_stride) *view_stride = stride;
     return GS_OK;
 }
@@ -260,7 +274,7 @@ int gs_geom_layout(int32_t P, int32_t width, int32_t height, GsGeomLayout* out)
     if (!out || P < 0 || width <= 0 || height <= 0) return fail(GS_EINVAL, "gs_geom_layout: bad argument");
     const uint64_t n = (uint64_t)(P > 0 ? P : 1);
     const uint64_t nb = (n + gs::kBlock - 1) / gs::kBlock;
-    const uint64_t tiles = (uint64_t)((width + gs::kTile - 1) / gs::kTile) * ((height + gs::kTile - 1) / gs::kTile);
+    const uint64_t tiles = tiles_of(width, height);
     const uint64_t rows = (n + 1023) / 1024;   // sized for the smallest binning chunk
     uint64_t o = 0;
     out->geom = o; o = align_up(o + n * GS_GEOM_FLOATS * 4);
@@ -280,7 +294,7 @@ int gs_geom_layout(int32_t P, int32_t width, int32_t height, GsGeomLayout* out)
 int gs_image_layout(int32_t width, int32_t height, GsImageLayout* out)
 {
     if (!out || width <= 0 || height <= 0) return fail(GS_EINVAL, "gs_image_layout: bad argument");
-    const uint64_t tiles = (uint64_t)((width + gs::kTile - 1) / gs::kTile) * ((height + gs::kTile - 1) / gs::kTile);
+    const uint64_t tiles = tiles_of(width, height);
     const uint64_t hw = (uint64_t)width * height;
     uint64_t o = 0;
     out->ranges = o; o = align_up(o + tiles * 8);
@@ -297,7 +311,7 @@ int gs_image_layout(int32_t width, int32_t height, GsImageLayout* out)
 int gs_bin_layout(int64_t D, uint32_t max_tile_instances, int32_t width, int32_t height, GsBinLayout* out)
 {
     if (!out || D < 0 || width <= 0 || height <= 0) return fail(GS_EINVAL, "gs_bin_layout: bad argument");
-    const int tiles = ((width + gs::kTile - 1) / gs::kTile) * ((height + gs::kTile - 1) / gs::kTile);
+    const int tiles = (int)tiles_of(width, height);
     const uint64_t n = (uint64_t)(D > 0 ? D : 1);
     memset(out, 0, sizeof(*out));
     out->path = (uint64_t)choose_path(tiles, max_tile_instances);
@@ -333,27 +347,28 @@ int gs_bin_layout(int64_t D, uint32_t max_tile_instances, int32_t width, int32_t
 
 uint64_t gs_backward_scratch_bytes(int32_t P) { return align_up((uint64_t)(P > 0 ? P : 1) * gs::kGradStride * 4); }
 
-static bool set_input_activation(gs::Cam& k, const float* h_pose7, int32_t isotropic, int32_t accumulate)
+// raw-parameter mode (Cam::act) is on for every pose source but POSE_NONE
+static void set_input_activation(gs::Cam& k, const gs::PoseRequest& pose, int32_t isotropic, int32_t accumulate)
 {
-    k.act = k.act_iso = k.act_accumulate = 0;
-    if (!h_pose7) return true;
-    k.act = 1; k.act_iso = isotropic != 0; k.act_accumulate = accumulate != 0;
-    for (int c = 0; c < 4; c++) k.act_q[c] = h_pose7[c];
-    for (int c = 0; c < 3; c++) k.act_t[c] = h_pose7[4 + c];
-    return k.V == 1;
+    // the frame transform of the kernels that take it from the camera block: the host's pose, or the world frame (CamBand: the view matrix is the
+    // whole camera; CamDP: the kernels overwrite it with the device column)
+    static const float world[7] = {1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const float* p = pose.source == gs::POSE_HOST ? pose.pose7 : world;
+    k.act = pose.source != gs::POSE_NONE;
+    k.act_iso = k.act && isotropic != 0; k.act_accumulate = k.act && accumulate != 0;
+    for (int c = 0; c < 4; c++) k.act_q[c] = p[c];
+    for (int c = 0; c < 3; c++) k.act_t[c] = p[4 + c];
 }
 
 // the device-resident pose of the tracking entry points (gs::CamDP)
-struct DevPose { const float* q; const float* t; int64_t stride; };
-
-static bool dev_pose(const float* cam_unnorm_rots, const float* cam_trans, int64_t num_frames, int64_t time_idx, DevPose& dp)
+static bool dev_pose(const float* cam_unnorm_rots, const float* cam_trans, int64_t num_frames, int64_t time_idx, gs::DevPose& dp)
 {
     if (!cam_unnorm_rots || !cam_trans || num_frames < 1 || time_idx < 0 || time_idx >= num_frames) return false;
     dp.q = cam_unnorm_rots + time_idx; dp.t = cam_trans + time_idx; dp.stride = num_frames;
     return true;
 }
 
-static gs::CamDP with_dev_pose(const gs::Cam& k, const DevPose& dp)
+static gs::CamDP with_dev_pose(const gs::Cam& k, const gs::DevPose& dp)
 {
     gs::CamDP kd;
     static_cast<gs::Cam&>(kd) = k;
@@ -361,68 +376,78 @@ static gs::CamDP with_dev_pose(const gs::Cam& k, const DevPose& dp)
     return kd;
 }
 
-static int preprocess_forward_impl(const GsCamera* cam, int32_t P, const float* means3D, const float* shs,
-                                   const float* colors_precomp, const float* opacities, const float* scales,
-                                   const float* rotations, const float* cov3D_precomp, int32_t* radii, void* geom_state,
-                                   void* image_state, uint32_t* d_counts, uint32_t* h_counts, int32_t want_backward, gs_stream_t stream,
-                                   const float* h_pose7, int32_t isotropic, float* max_2D_radius, uint8_t* seen, const DevPose* dp = nullptr,
-                                   const float* band = nullptr)
+// one per-Gaussian forward, as its entry point describes it (what an entry point does not have stays zero)
+struct ForwardCall {
+    int32_t P;
+    gs::GaussianInputs in;
+    gs::PoseRequest pose;
+    int32_t isotropic;
+    float* max_2D_radius; uint8_t* seen;        // raw-parameter mode: the mapper's visibility statistics
+    int32_t* radii;
+    void* geom_state; void* image_state;
+    uint32_t* d_counts; uint32_t* h_counts;
+    int32_t want_backward;
+};
+
+static int preprocess_forward_impl(const GsCamera* cam, const ForwardCall& c, gs_stream_t stream)
 {
+    const gs::GaussianInputs& in = c.in;
+    const int32_t P = c.P;
     gs::Cam k;
     if (!make_cam(cam, k)) return fail(GS_EINVAL, "gs_preprocess_forward: invalid camera settings");
-    if (!set_input_activation(k, h_pose7, isotropic, 0)) return fail(GS_EINVAL, "gs_preprocess_forward_raw: one view only");
-    if (k.act && (cov3D_precomp || (shs && k.sh_coeffs != 16)))
+    set_input_activation(k, c.pose, c.isotropic, 0);
+    if (k.act && k.V != 1) return fail(GS_EINVAL, "gs_preprocess_forward_raw: one view only");
+    if (k.act && (in.cov3D || (in.shs && k.sh_coeffs != 16)))
         return fail(GS_EINVAL, "gs_preprocess_forward_raw: scale / rotation parameters with colours or 16-coefficient SH rows only");
-    if (P < 0 || !geom_state || !image_state || !d_counts) return fail(GS_EINVAL, "gs_preprocess_forward: null state pointer");
-    if (P > 0 && (!means3D || !opacities || !radii)) return fail(GS_EINVAL, "gs_preprocess_forward: null input pointer");
-    if ((shs == nullptr) == (colors_precomp == nullptr) && P > 0)
+    if (P < 0 || !c.geom_state || !c.image_state || !c.d_counts) return fail(GS_EINVAL, "gs_preprocess_forward: null state pointer");
+    if (P > 0 && (!in.means3D || !in.opac || !c.radii)) return fail(GS_EINVAL, "gs_preprocess_forward: null input pointer");
+    if ((in.shs == nullptr) == (in.colors == nullptr) && P > 0)
         return fail(GS_EINVAL, "Please provide excatly one of either SHs or precomputed colors!");
-    const bool have_sr = scales != nullptr && rotations != nullptr;
-    if (P > 0 && (have_sr == (cov3D_precomp != nullptr) || ((scales != nullptr) != (rotations != nullptr))))
+    const bool have_sr = in.scales != nullptr && in.rots != nullptr;
+    if (P > 0 && (have_sr == (in.cov3D != nullptr) || ((in.scales != nullptr) != (in.rots != nullptr))))
         return fail(GS_EINVAL, "Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!");
-    if (shs && (k.sh_degree < 0 || k.sh_degree > 3 || k.sh_coeffs < (k.sh_degree + 1) * (k.sh_degree + 1) || k.sh_coeffs > 16 || !k.campos))
+    if (in.shs && (k.sh_degree < 0 || k.sh_degree > 3 || k.sh_coeffs < (k.sh_degree + 1) * (k.sh_degree + 1) || k.sh_coeffs > 16 || !k.campos))
         return fail(GS_EINVAL, "gs_preprocess_forward: sh_degree / sh_coeffs / campos inconsistent");
     hipStream_t st = (hipStream_t)stream;
     const int32_t Pv = virtual_count(k, P);
-    gs::GeomPtrs gp = carve_geom(geom_state, Pv, k);
-    if (!(want_backward && shs)) gp.sh_jac = nullptr;        // written only for SH inputs whose backward will follow
-    gp.vis_max = k.act ? max_2D_radius : nullptr; gp.vis_seen = k.act ? seen : nullptr;
+    gs::GeomPtrs gp = carve_geom(c.geom_state, Pv, k);
+    if (!(c.want_backward && in.shs)) gp.sh_jac = nullptr;        // written only for SH inputs whose backward will follow
+    gp.vis_max = k.act ? c.max_2D_radius : nullptr; gp.vis_seen = k.act ? c.seen : nullptr;
     GsImageLayout IL; gs_image_layout(k.W, k.H, &IL);
-    uint2* ranges = (uint2*)((char*)image_state + IL.ranges);
+    uint2* ranges = (uint2*)((char*)c.image_state + IL.ranges);
     const int tiles = k.gx * k.gy;
     hipError_t e;
     {
         ScopedStage ps(ST_PREPROCESS, st);
-        if (band) {                             // the planner's top-down maps: raw parameters + height band {upper, lower}
+        if (c.pose.source == gs::POSE_BAND) {   // the planner's top-down maps: raw parameters + height band
             gs::CamBand kb;
             static_cast<gs::Cam&>(kb) = k;
-            kb.band_upper = band[0]; kb.band_lower = band[1];
-            e = gs::launch_preprocess_forward_band(kb, P, means3D, colors_precomp, opacities, scales, rotations, radii, gp, st);
-        } else if (dp)
-            e = gs::launch_preprocess_forward_dev(with_dev_pose(k, *dp), P, means3D, shs, colors_precomp, opacities, scales, rotations, radii, gp, st);
+            kb.band_upper = c.pose.band_upper; kb.band_lower = c.pose.band_lower;
+            e = gs::launch_preprocess_forward(kb, P, in, c.radii, gp, st);
+        } else if (c.pose.source == gs::POSE_DEVICE)
+            e = gs::launch_preprocess_forward(with_dev_pose(k, c.pose.dev), P, in, c.radii, gp, st);
         else
-            e = gs::launch_preprocess_forward(k, P, means3D, shs, colors_precomp, opacities, scales, rotations,
-                                              cov3D_precomp, radii, gp, d_counts, st);
+            e = gs::launch_preprocess_forward(k, P, in, c.radii, gp, st);
     }
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_preprocess_forward: %s", hipGetErrorString(e));
+    if (int rc = launched("gs_preprocess_forward", "", e)) return rc;
     bool mirrored = false;
     if (tiles <= gs::kMaxLdsTiles) {          // tile counting: ranges, D and the largest tile list
         // if h_counts is mapped pinned host memory the scan kernel stores the counters there itself (no copy engine hop)
         uint32_t* host_dev = nullptr;
-        if (h_counts && hipHostGetDevicePointer((void**)&host_dev, h_counts, 0) != hipSuccess) { host_dev = nullptr; (void)hipGetLastError(); }
+        if (c.h_counts && hipHostGetDevicePointer((void**)&host_dev, c.h_counts, 0) != hipSuccess) { host_dev = nullptr; (void)hipGetLastError(); }
         mirrored = host_dev != nullptr;
         ScopedStage ps(ST_TILE_COUNT, st);
-        e = gs::launch_tile_count(k, Pv, gp, gp.tile_total, gp.tile_base, ranges, d_counts, host_dev, st);
-        if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_preprocess_forward: tile count %s", hipGetErrorString(e));
+        e = gs::launch_tile_count(k, Pv, gp, gp.tile_total, gp.tile_base, ranges, c.d_counts, host_dev, st);
+        if (int rc = launched("gs_preprocess_forward", "tile count", e)) return rc;
     } else {                                   // too many tiles for the LDS histogram: radix path, counts = {D, 2^32-1}
-        e = gs::launch_scan_block_sums(Pv, gp, d_counts, st);
-        if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_preprocess_forward: scan %s", hipGetErrorString(e));
-        e = hipMemsetAsync(d_counts + 1, 0xff, sizeof(uint32_t), st);
-        if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_preprocess_forward: memset %s", hipGetErrorString(e));
+        e = gs::launch_scan_block_sums(Pv, gp, c.d_counts, st);
+        if (int rc = launched("gs_preprocess_forward", "scan", e)) return rc;
+        e = hipMemsetAsync(c.d_counts + 1, 0xff, sizeof(uint32_t), st);
+        if (int rc = launched("gs_preprocess_forward", "memset", e)) return rc;
     }
-    if (h_counts && !mirrored) {
-        e = hipMemcpyAsync(h_counts, d_counts, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_preprocess_forward: D2H %s", hipGetErrorString(e));
+    if (c.h_counts && !mirrored) {
+        e = hipMemcpyAsync(c.h_counts, c.d_counts, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+        if (int rc = launched("gs_preprocess_forward", "D2H", e)) return rc;
     }
     return GS_OK;
 }
@@ -432,8 +457,11 @@ int gs_preprocess_forward(const GsCamera* cam, int32_t P, const float* means3D, 
                           const float* rotations, const float* cov3D_precomp, int32_t* radii, void* geom_state,
                           void* image_state, uint32_t* d_counts, uint32_t* h_counts, int32_t want_backward, gs_stream_t stream)
 {
-    return preprocess_forward_impl(cam, P, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii, geom_state,
-                                   image_state, d_counts, h_counts, want_backward, stream, nullptr, 0, nullptr, nullptr);
+    ForwardCall c{};
+    c.in.means3D = means3D; c.in.shs = shs; c.in.colors = colors_precomp; c.in.opac = opacities; c.in.scales = scales; c.in.rots = rotations;
+    c.in.cov3D = cov3D_precomp; c.P = P;
+    c.radii = radii; c.geom_state = geom_state; c.image_state = image_state; c.d_counts = d_counts; c.h_counts = h_counts; c.want_backward = want_backward;
+    return preprocess_forward_impl(cam, c, stream);
 }
 
 int gs_preprocess_forward_raw(const GsCamera* cam, int32_t P, const float* means3D, const float* shs, const float* colors_precomp,
@@ -442,8 +470,11 @@ int gs_preprocess_forward_raw(const GsCamera* cam, int32_t P, const float* means
                               void* image_state, uint32_t* d_counts, uint32_t* h_counts, int32_t want_backward, gs_stream_t stream)
 {
     if (!h_pose7) return fail(GS_EINVAL, "gs_preprocess_forward_raw: null pose");
-    return preprocess_forward_impl(cam, P, means3D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, nullptr, radii,
-                                   geom_state, image_state, d_counts, h_counts, want_backward, stream, h_pose7, isotropic, max_2D_radius, seen);
+    ForwardCall c{};
+    c.in.means3D = means3D; c.in.shs = shs; c.in.colors = colors_precomp; c.in.opac = logit_opacities; c.in.scales = log_scales; c.in.rots = unnorm_rotations;
+    c.P = P; c.pose.source = gs::POSE_HOST; c.pose.pose7 = h_pose7; c.isotropic = isotropic; c.max_2D_radius = max_2D_radius; c.seen = seen;
+    c.radii = radii; c.geom_state = geom_state; c.image_state = image_state; c.d_counts = d_counts; c.h_counts = h_counts; c.want_backward = want_backward;
+    return preprocess_forward_impl(cam, c, stream);
 }
 
 int gs_preprocess_forward_raw_dev(const GsCamera* cam, int32_t P, const float* means3D, const float* shs, const float* colors_precomp,
@@ -452,20 +483,15 @@ int gs_preprocess_forward_raw_dev(const GsCamera* cam, int32_t P, const float* m
                                   float* max_2D_radius, uint8_t* seen, int32_t* radii, void* geom_state, void* image_state, uint32_t* d_counts,
                                   uint32_t* h_counts, int32_t want_backward, gs_stream_t stream)
 {
-    DevPose dp;
-    if (!dev_pose(cam_unnorm_rots, cam_trans, num_frames, time_idx, dp))
+    ForwardCall c{};
+    c.pose.source = gs::POSE_DEVICE;
+    if (!dev_pose(cam_unnorm_rots, cam_trans, num_frames, time_idx, c.pose.dev))
         return fail(GS_EINVAL, "gs_preprocess_forward_raw_dev: null pose columns or time index outside [0, num_frames)");
     if (P > 0 && (!log_scales || !unnorm_rotations)) return fail(GS_EINVAL, "gs_preprocess_forward_raw_dev: null scale / rotation parameters");
-    const float ident[7] = {1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};          // (sets the raw-parameter mode; the kernels read the pose themselves)
-    return preprocess_forward_impl(cam, P, means3D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, nullptr, radii,
-                                   geom_state, image_state, d_counts, h_counts, want_backward, stream, ident, isotropic, max_2D_radius, seen, &dp);
-}
-
-static int fail_at(const char* who, const char* what, hipError_t e)
-{
-    char buf[160];
-    snprintf(buf, sizeof buf, "%s: %s %s", who, what, hipGetErrorString(e));
-    return fail(GS_ELAUNCH, "%s", buf);
+    c.in.means3D = means3D; c.in.shs = shs; c.in.colors = colors_precomp; c.in.opac = logit_opacities; c.in.scales = log_scales; c.in.rots = unnorm_rotations;
+    c.P = P; c.isotropic = isotropic; c.max_2D_radius = max_2D_radius; c.seen = seen;
+    c.radii = radii; c.geom_state = geom_state; c.image_state = image_state; c.d_counts = d_counts; c.h_counts = h_counts; c.want_backward = want_backward;
+    return preprocess_forward_impl(cam, c, stream);
 }
 
 // binning + depth sort of one forward (the tile lists behind `ranges` / point_list): shared by gs_render_forward and gs_render_forward_topdown
@@ -478,31 +504,31 @@ static int bin_tile_lists(const char* who, const gs::Cam& k, int32_t P, int64_t 
             ScopedStage ps(ST_TILE_SCATTER_SORT, st);
             e = gs::launch_tile_scatter_sort(k, P, gp, gp.tile_base, ranges, max_tile_instances,
                                              (unsigned long long*)(bb + BL.pairs), (unsigned long long*)(bb + BL.pairs_alt), point_list, (uint32_t)D, st);
-            if (e != hipSuccess) return fail_at(who, "tile scatter/sort", e);
+            if (int rc = launched(who, "tile scatter/sort", e)) return rc;
         }
     } else {
         e = hipMemsetAsync(ranges, 0, (size_t)k.gx * k.gy * 8, st);
-        if (e != hipSuccess) return fail_at(who, "memset", e);
+        if (int rc = launched(who, "memset", e)) return rc;
         if (k.gx * k.gy <= gs::kMaxLdsTiles) {   // per-Gaussian offsets were not needed before the sync: scan them now
             e = gs::launch_scan_block_sums(P, gp, gp.block_sums + (P + gs::kBlock - 1) / gs::kBlock, st);
-            if (e != hipSuccess) return fail_at(who, "scan", e);
+            if (int rc = launched(who, "scan", e)) return rc;
         }
         if (D == 0) {   // nothing visible: the emitter still writes the (all-zero) scan offsets
             e = gs::launch_emit(k, P, gp, nullptr, nullptr, st);
-            if (e != hipSuccess) return fail_at(who, "emit", e);
+            if (int rc = launched(who, "emit", e)) return rc;
         } else {
             uint64_t* ku = (uint64_t*)(bb + BL.keys_unsorted); uint32_t* vu = (uint32_t*)(bb + BL.vals_unsorted);
             uint64_t* ks = (uint64_t*)(bb + BL.keys_sorted);
             { ScopedStage ps(ST_EMIT, st); e = gs::launch_emit(k, P, gp, ku, vu, st); }
-            if (e != hipSuccess) return fail_at(who, "emit", e);
+            if (int rc = launched(who, "emit", e)) return rc;
             const int end_bit = 32 + tile_bits(k.gx * k.gy);
             {
                 ScopedStage ps(ST_SORT, st);
                 e = gs::sort_pairs(bb + BL.sort_temp, (size_t)(BL.total_bytes - BL.sort_temp), ku, ks, vu, point_list, D, end_bit, st);
             }
-            if (e != hipSuccess) return fail_at(who, "sort", e);
+            if (int rc = launched(who, "sort", e)) return rc;
             { ScopedStage ps(ST_RANGES, st); e = gs::launch_ranges(D, ks, ranges, st); }
-            if (e != hipSuccess) return fail_at(who, "ranges", e);
+            if (int rc = launched(who, "ranges", e)) return rc;
         }
     }
     return GS_OK;
@@ -528,18 +554,11 @@ int gs_render_forward(const GsCamera* cam, int32_t P, int64_t D, uint32_t max_ti
     GsBinLayout BL; gs_bin_layout(D, max_tile_instances, k.W, k.H, &BL);
     char* bb = (char*)bin_state;
     if (int rc = bin_tile_lists("gs_render_forward", k, P, D, max_tile_instances, gp, ranges, BL, bb, point_list, st)) return rc;
-    hipError_t e;
-    {
-        ScopedStage ps(ST_BLEND_FWD, st);
-        e = gs::launch_blend_forward(k, ranges, point_list, gp.geom, out_color, out_depth, out_opacity,
-                                     (float*)(ib + IL.final_T), (uint32_t*)(ib + IL.n_contrib), out_depth_sq,
-                                     BL.path == GS_SORT_TILE_LDS ? (uint32_t)D : 0xffffffffu, (int)BL.segments,
-                                     BL.segments > 1 ? (float*)(bb + BL.seg_T) : nullptr,
-                                     (float*)(ib + IL.split_state), (uint32_t)P,
-                                     (float*)backward_scratch, st);
-    }
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_forward: blend %s", hipGetErrorString(e));
-    return GS_OK;
+    ScopedStage ps(ST_BLEND_FWD, st);
+    return launched("gs_render_forward", "blend", gs::launch_blend_forward(k, ranges, point_list, gp.geom, out_color, out_depth, out_opacity,
+                    (float*)(ib + IL.final_T), (uint32_t*)(ib + IL.n_contrib), out_depth_sq, BL.path == GS_SORT_TILE_LDS ? (uint32_t)D : 0xffffffffu,
+                    (int)BL.segments, BL.segments > 1 ? (float*)(bb + BL.seg_T) : nullptr, (float*)(ib + IL.split_state), (uint32_t)P,
+                    (float*)backward_scratch, st));
 }
 
 int gs_preprocess_forward_topdown(const GsCamera* cam, int32_t P, const float* means3D, const float* colors_precomp, const float* logit_opacities,
@@ -550,10 +569,11 @@ int gs_preprocess_forward_topdown(const GsCamera* cam, int32_t P, const float* m
     if (P > 0 && (!colors_precomp || !log_scales || !unnorm_rotations))
         return fail(GS_EINVAL, "gs_preprocess_forward_topdown: null colour / scale / rotation parameters");
     if (band_upper != band_upper || band_lower != band_lower) return fail(GS_EINVAL, "gs_preprocess_forward_topdown: NaN height band");
-    const float ident[7] = {1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};          // the parameters are rendered in the world frame: the view matrix is the camera
-    const float band[2] = {band_upper, band_lower};
-    return preprocess_forward_impl(cam, P, means3D, nullptr, colors_precomp, logit_opacities, log_scales, unnorm_rotations, nullptr, radii,
-                                   geom_state, image_state, d_counts, h_counts, 0, stream, ident, isotropic, nullptr, nullptr, nullptr, band);
+    ForwardCall c{};
+    c.in.means3D = means3D; c.in.colors = colors_precomp; c.in.opac = logit_opacities; c.in.scales = log_scales; c.in.rots = unnorm_rotations;
+    c.P = P; c.pose.source = gs::POSE_BAND; c.pose.band_upper = band_upper; c.pose.band_lower = band_lower; c.isotropic = isotropic;
+    c.radii = radii; c.geom_state = geom_state; c.image_state = image_state; c.d_counts = d_counts; c.h_counts = h_counts;
+    return preprocess_forward_impl(cam, c, stream);
 }
 
 int gs_render_forward_topdown(const GsCamera* cam, int32_t P, int64_t D, uint32_t max_tile_instances, void* geom_state, void* bin_state,
@@ -576,113 +596,112 @@ int gs_render_forward_topdown(const GsCamera* cam, int32_t P, int64_t D, uint32_
     uint2* ranges = (uint2*)((char*)image_state + IL.ranges);
     GsBinLayout BL; gs_bin_layout(D, max_tile_instances, k.W, k.H, &BL);
     if (int rc = bin_tile_lists("gs_render_forward_topdown", k, P, D, max_tile_instances, gp, ranges, BL, (char*)bin_state, point_list, st)) return rc;
-    hipError_t e;
-    {
-        ScopedStage ps(ST_BLEND_FWD, st);
-        e = gs::launch_blend_topdown(k, ranges, point_list, gp.geom, free_opacity, free_map_binary, visible_rgb, visible_map_binary,
-                                     BL.path == GS_SORT_TILE_LDS ? (uint32_t)D : 0xffffffffu, (uint32_t)P, st);
-    }
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_forward_topdown: blend %s", hipGetErrorString(e));
-    return GS_OK;
+    ScopedStage ps(ST_BLEND_FWD, st);
+    return launched("gs_render_forward_topdown", "blend", gs::launch_blend_topdown(k, ranges, point_list, gp.geom, free_opacity, free_map_binary, visible_rgb,
+                    visible_map_binary, BL.path == GS_SORT_TILE_LDS ? (uint32_t)D : 0xffffffffu, (uint32_t)P, st));
 }
 
-static int render_backward_impl(const GsCamera* cam, int32_t P, int64_t D, const float* means3D, const float* shs,
-                                const float* colors_precomp, const float* scales, const float* rotations,
-                                const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
-                                const uint32_t* point_list, const void* image_state, const float* dL_dcolor,
-                                const float* dL_ddepth, float* dL_dmeans2D, float* dL_dmeans3D, float* dL_dopacities, float* dL_dcolors_precomp,
-                                float* dL_dshs, float* dL_dscales, float* dL_drotations, float* dL_dcov3D, void* scratch,
-                                int32_t scratch_zeroed, int32_t have_sh_jacobian, gs_stream_t stream, const float* logit,
-                                const float* h_pose7, int32_t isotropic, int32_t accumulate, const GsAdamTensor* adam5 = nullptr,
-                                int32_t pose_mode = 0, float* dL_dpose7 = nullptr, void* pose_scratch = nullptr, const DevPose* dp = nullptr)
+// one backward, as its entry point describes it (what an entry point does not have stays zero)
+struct BackwardCall {
+    int32_t P;
+    int64_t D;
+    gs::GaussianBackward g;      // in, out and radii from the entry point; the rest from render_backward_impl
+    gs::PoseRequest pose;
+    int32_t isotropic, accumulate;
+    const void* geom_state; const uint32_t* point_list; const void* image_state;
+    const float* dL_dcolor; const float* dL_ddepth;
+    void* scratch; int32_t scratch_zeroed, have_sh_jacobian;
+    const GsAdamTensor* adam5;
+};
+
+static int render_backward_impl(const GsCamera* cam, const BackwardCall& c, gs_stream_t stream)
 {
+    gs::GaussianBackward g = c.g;
+    const gs::GaussianInputs& in = g.in;
+    const gs::GaussianGrads& out = g.out;
+    const gs::PoseRequest& pose = c.pose;
+    const int32_t P = c.P;
+    const bool pose_only = pose.grad == gs::POSE_GRAD_ONLY;
     gs::Cam k;
     if (!make_cam(cam, k)) return fail(GS_EINVAL, "gs_render_backward: invalid camera settings");
-    if (!set_input_activation(k, h_pose7, isotropic, accumulate)) return fail(GS_EINVAL, "gs_render_backward_raw: one view only");
-    if (k.act && (!logit || cov3D_precomp || (shs && k.sh_coeffs != 16)))
+    set_input_activation(k, pose, c.isotropic, pose_only ? 0 : c.accumulate);       // (pose only: no parameter gradient is written, nothing to add to)
+    if (k.act && k.V != 1) return fail(GS_EINVAL, "gs_render_backward_raw: one view only");
+    if (k.act && (!in.opac || in.cov3D || (in.shs && k.sh_coeffs != 16)))
         return fail(GS_EINVAL, "gs_render_backward_raw: scale / rotation parameters with colours or 16-coefficient SH rows only");
     if (k.V > 1) return fail(GS_EINVAL, "gs_render_backward: multi-view atlas renders are forward-only");
-    if (P < 0 || D < 0 || !geom_state || !image_state || !dL_dcolor || !scratch)
+    if (P < 0 || c.D < 0 || !c.geom_state || !c.image_state || !c.dL_dcolor || !c.scratch)
         return fail(GS_EINVAL, "gs_render_backward: null pointer");
-    if (pose_mode && (!k.act || adam5 || (!dL_dpose7 && !dp) || !pose_scratch))
+    if (pose.grad && (!k.act || c.adam5 || (!pose.dL_dpose7 && pose.source != gs::POSE_DEVICE) || !pose.pose_scratch))
         return fail(GS_EINVAL, "gs_render_backward_raw_pose: raw-parameter mode with a pose-gradient output and its scratch only");
-    if (dp && pose_mode != 2) return fail(GS_EINVAL, "gs_render_backward_raw_pose_dev: the pose-only backward only");
+    if (pose.source == gs::POSE_DEVICE && !pose_only) return fail(GS_EINVAL, "gs_render_backward_raw_pose_dev: the pose-only backward only");
     if (P == 0) {
-        if (pose_mode && dL_dpose7) {
-            const hipError_t e0 = hipMemsetAsync(dL_dpose7, 0, 7 * sizeof(float), (hipStream_t)stream);
-            if (e0 != hipSuccess) return fail(GS_ELAUNCH, "gs_render_backward_raw_pose: memset %s", hipGetErrorString(e0));
-        }
+        if (pose.grad && pose.dL_dpose7)
+            return launched("gs_render_backward_raw_pose", "memset", hipMemsetAsync(pose.dL_dpose7, 0, 7 * sizeof(float), (hipStream_t)stream));
         return GS_OK;
     }
-    const bool pose_only = pose_mode == 2;
     gs::FusedAdam fa{};
-    if (adam5) {
+    if (c.adam5) {
         // the optimiser step inside the per-Gaussian kernel: the five descriptors must describe the very tensors this call reads
-        if (!k.act || accumulate) return fail(GS_EINVAL, "gs_render_backward_raw_adam: raw-parameter mode without accumulation only");
-        if (!means3D || !radii || !dL_dmeans2D || !scales || !rotations || (shs == nullptr) == (colors_precomp == nullptr))
+        if (!k.act || c.accumulate) return fail(GS_EINVAL, "gs_render_backward_raw_adam: raw-parameter mode without accumulation only");
+        if (!in.means3D || !g.radii || !out.dmeans2D || !in.scales || !in.rots || (in.shs == nullptr) == (in.colors == nullptr))
             return fail(GS_EINVAL, "gs_render_backward_raw_adam: null input/output pointer");
-        if (shs && !have_sh_jacobian) return fail(GS_EINVAL, "gs_render_backward_raw_adam: SH rows need the forward's saved Jacobian (have_sh_jacobian = 1)");
-        const float* par[5] = {means3D, logit, scales, rotations, shs ? shs : colors_precomp};
-        const int64_t width[5] = {3, 1, isotropic ? 1 : 3, 4, shs ? 48 : 3};
+        if (in.shs && !c.have_sh_jacobian) return fail(GS_EINVAL, "gs_render_backward_raw_adam: SH rows need the forward's saved Jacobian (have_sh_jacobian = 1)");
+        const float* par[5] = {in.means3D, in.opac, in.scales, in.rots, in.shs ? in.shs : in.colors};
+        const int64_t width[5] = {3, 1, c.isotropic ? 1 : 3, 4, in.shs ? 48 : 3};
         for (int t = 0; t < 5; ++t) {
-            const GsAdamTensor& a = adam5[t];
+            const GsAdamTensor& a = c.adam5[t];
             if (a.param != par[t] || !a.exp_avg || !a.exp_avg_sq || a.step < 1 || a.n != width[t] * (int64_t)P)
                 return fail(GS_EINVAL, "gs_render_backward_raw_adam: descriptor of %s does not describe the input tensor (param / moments / n / step)",
                             t == 0 ? "means3D" : t == 1 ? "logit_opacities" : t == 2 ? "log_scales" : t == 3 ? "unnorm_rotations" : "the colours");
             // the kernel reads and writes the rotation rows, and the SH rows, of parameter and moments as float4
-            if (P > 0 && (t == 3 || (t == 4 && shs)) && !adam_aligned16(a.param, a.param, a.exp_avg, a.exp_avg_sq))
+            if (P > 0 && (t == 3 || (t == 4 && in.shs)) && !adam_aligned16(a.param, a.param, a.exp_avg, a.exp_avg_sq))
                 return fail_adam_alignment("gs_render_backward_raw_adam", t);
             fa.p[t] = a.param; fa.m[t] = a.exp_avg; fa.v[t] = a.exp_avg_sq;
             fa.c[t] = gs::adam_coef(a.lr, a.beta1, a.beta2, a.eps, a.step);
         }
         fa.fail = gs::chain_fail_word();
+        g.adam = &fa;
     } else if (pose_only) {
         // (tracking: no parameter gradient is formed; the colour / SH inputs are still read)
-        if (!means3D || !radii || !dL_dmeans2D || !scales || !rotations || (shs == nullptr) == (colors_precomp == nullptr))
+        if (!in.means3D || !g.radii || !out.dmeans2D || !in.scales || !in.rots || (in.shs == nullptr) == (in.colors == nullptr))
             return fail(GS_EINVAL, "gs_render_backward_raw_pose: null input/output pointer");
     } else {
-        if (!means3D || !radii || !dL_dmeans2D || !dL_dmeans3D || !dL_dopacities)
+        if (!in.means3D || !g.radii || !out.dmeans2D || !out.dmeans3D || !out.dopac)
             return fail(GS_EINVAL, "gs_render_backward: null input/output pointer");
-        if (shs ? !dL_dshs : !dL_dcolors_precomp) return fail(GS_EINVAL, "gs_render_backward: missing colour gradient output");
-        if (cov3D_precomp ? !dL_dcov3D : (!scales || !rotations || !dL_dscales || !dL_drotations))
+        if (in.shs ? !out.dshs : !out.dcolors) return fail(GS_EINVAL, "gs_render_backward: missing colour gradient output");
+        if (in.cov3D ? !out.dcov3D : (!in.scales || !in.rots || !out.dscales || !out.drots))
             return fail(GS_EINVAL, "gs_render_backward: missing covariance inputs/outputs");
     }
     hipStream_t st = (hipStream_t)stream;
-    gs::GeomPtrs gp = carve_geom(const_cast<void*>(geom_state), P, k);
+    gs::GeomPtrs gp = carve_geom(const_cast<void*>(c.geom_state), P, k);
     GsImageLayout IL; gs_image_layout(k.W, k.H, &IL);
-    const char* ib = (const char*)image_state;
-    float* grad2d = (float*)scratch;
-    hipError_t e = scratch_zeroed ? hipSuccess : hipMemsetAsync(grad2d, 0, (size_t)P * gs::kGradStride * 4, st);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_backward: memset %s", hipGetErrorString(e));
-    if (D > 0) {
+    const char* ib = (const char*)c.image_state;
+    float* grad2d = (float*)c.scratch;
+    hipError_t e = c.scratch_zeroed ? hipSuccess : hipMemsetAsync(grad2d, 0, (size_t)P * gs::kGradStride * 4, st);
+    if (int rc = launched("gs_render_backward", "memset", e)) return rc;
+    if (c.D > 0) {
         ScopedStage ps(ST_BLEND_BWD, st);
-        e = gs::launch_blend_backward(k, (const uint2*)(ib + IL.ranges), point_list, gp.geom,
+        e = gs::launch_blend_backward(k, (const uint2*)(ib + IL.ranges), c.point_list, gp.geom,
                                       (const float*)(ib + IL.split_state),
                                       (const float*)(ib + IL.final_T),
-                                      (const uint32_t*)(ib + IL.n_contrib), dL_dcolor, dL_ddepth, grad2d, st);
-        if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_backward: blend %s", hipGetErrorString(e));
+                                      (const uint32_t*)(ib + IL.n_contrib), c.dL_dcolor, c.dL_ddepth, grad2d, st);
+        if (int rc = launched("gs_render_backward", "blend", e)) return rc;
     }
+    g.clamped = gp.clamped; g.sh_jac = (in.shs && c.have_sh_jacobian) ? gp.sh_jac : nullptr; g.grad2d = grad2d;
     {
         ScopedStage ps(ST_PREPROCESS_BWD, st);
-        if (dp)
-            e = gs::launch_preprocess_backward_pose_dev(with_dev_pose(k, *dp), P, means3D, shs, scales, rotations, radii, gp.clamped,
-                                                        (shs && have_sh_jacobian) ? gp.sh_jac : nullptr, grad2d, dL_dmeans2D, logit,
-                                                        (float*)pose_scratch, st);
-        else
-            e = gs::launch_preprocess_backward(k, P, means3D, shs, scales, rotations, cov3D_precomp, radii, gp.clamped, (shs && have_sh_jacobian) ? gp.sh_jac : nullptr, grad2d,
-                                               dL_dmeans2D, dL_dmeans3D, dL_dopacities, dL_dcolors_precomp, dL_dshs, dL_dscales,
-                                               dL_drotations, dL_dcov3D, logit, adam5 ? &fa : nullptr, st, pose_mode, (float*)pose_scratch);
+        if (pose.source == gs::POSE_DEVICE) e = gs::launch_preprocess_backward(with_dev_pose(k, pose.dev), P, g, pose, st);
+        else e = gs::launch_preprocess_backward(k, P, g, pose, st);
     }
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_backward: preprocess %s", hipGetErrorString(e));
-    if (dp) {
-        if (dL_dpose7) {
-            e = gs::launch_pose_grad_finish_dev(gs::pose_rows_count(P), dp->q, dp->stride, (const float*)pose_scratch, dL_dpose7, st);
-            if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_backward_raw_pose_dev: pose reduction %s", hipGetErrorString(e));
-        }
-    } else if (pose_mode) {
-        e = gs::launch_pose_grad_finish(gs::pose_rows_count(P), h_pose7, (const float*)pose_scratch, dL_dpose7, st);
-        if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_render_backward_raw_pose: pose reduction %s", hipGetErrorString(e));
-    }
+    if (int rc = launched("gs_render_backward", "preprocess", e)) return rc;
+    const int64_t pose_rows = gs::pose_rows_count(P);
+    if (pose.source == gs::POSE_DEVICE) {
+        if (pose.dL_dpose7)
+            return launched("gs_render_backward_raw_pose_dev", "pose reduction", gs::launch_pose_grad_finish_dev(pose_rows, pose.dev.q, pose.dev.stride,
+                            (const float*)pose.pose_scratch, pose.dL_dpose7, st));
+    } else if (pose.grad)
+        return launched("gs_render_backward_raw_pose", "pose reduction", gs::launch_pose_grad_finish(pose_rows, pose.pose7, (const float*)pose.pose_scratch,
+                        pose.dL_dpose7, st));
     return GS_OK;
 }
 
@@ -694,9 +713,14 @@ int gs_render_backward(const GsCamera* cam, int32_t P, int64_t D, const float* m
                        float* dL_dshs, float* dL_dscales, float* dL_drotations, float* dL_dcov3D, void* scratch,
                        int32_t scratch_zeroed, int32_t have_sh_jacobian, gs_stream_t stream)
 {
-    return render_backward_impl(cam, P, D, means3D, shs, colors_precomp, scales, rotations, cov3D_precomp, radii, geom_state, point_list,
-                                image_state, dL_dcolor, dL_ddepth, dL_dmeans2D, dL_dmeans3D, dL_dopacities, dL_dcolors_precomp, dL_dshs,
-                                dL_dscales, dL_drotations, dL_dcov3D, scratch, scratch_zeroed, have_sh_jacobian, stream, nullptr, nullptr, 0, 0);
+    BackwardCall c{};
+    c.P = P; c.D = D;
+    c.g.in.means3D = means3D; c.g.in.shs = shs; c.g.in.colors = colors_precomp; c.g.in.scales = scales; c.g.in.rots = rotations; c.g.in.cov3D = cov3D_precomp;
+    c.g.radii = radii; c.geom_state = geom_state; c.point_list = point_list; c.image_state = image_state; c.dL_dcolor = dL_dcolor; c.dL_ddepth = dL_ddepth;
+    c.g.out.dmeans2D = dL_dmeans2D; c.g.out.dmeans3D = dL_dmeans3D; c.g.out.dopac = dL_dopacities; c.g.out.dcolors = dL_dcolors_precomp;
+    c.g.out.dshs = dL_dshs; c.g.out.dscales = dL_dscales; c.g.out.drots = dL_drotations; c.g.out.dcov3D = dL_dcov3D;
+    c.scratch = scratch; c.scratch_zeroed = scratch_zeroed; c.have_sh_jacobian = have_sh_jacobian;
+    return render_backward_impl(cam, c, stream);
 }
 
 int gs_render_backward_raw(const GsCamera* cam, int32_t P, int64_t D, const float* means3D, const float* shs, const float* colors_precomp,
@@ -707,10 +731,14 @@ int gs_render_backward_raw(const GsCamera* cam, int32_t P, int64_t D, const floa
                            float* dL_dunnorm_rotations, void* scratch, int32_t scratch_zeroed, int32_t have_sh_jacobian, gs_stream_t stream)
 {
     if (!h_pose7 || (P > 0 && !logit_opacities)) return fail(GS_EINVAL, "gs_render_backward_raw: null pose / opacity parameters");
-    return render_backward_impl(cam, P, D, means3D, shs, colors_precomp, log_scales, unnorm_rotations, nullptr, radii, geom_state, point_list,
-                                image_state, dL_dcolor, dL_ddepth, dL_dmeans2D, dL_dmeans3D, dL_dlogit_opacities, dL_dcolors_precomp, dL_dshs,
-                                dL_dlog_scales, dL_dunnorm_rotations, nullptr, scratch, scratch_zeroed, have_sh_jacobian, stream,
-                                logit_opacities, h_pose7, isotropic, accumulate);
+    BackwardCall c{};
+    c.g.in.means3D = means3D; c.g.in.shs = shs; c.g.in.colors = colors_precomp; c.g.in.opac = logit_opacities; c.g.in.scales = log_scales; c.g.in.rots = unnorm_rotations;
+    c.P = P; c.D = D; c.pose.source = gs::POSE_HOST; c.pose.pose7 = h_pose7; c.isotropic = isotropic; c.accumulate = accumulate;
+    c.g.radii = radii; c.geom_state = geom_state; c.point_list = point_list; c.image_state = image_state; c.dL_dcolor = dL_dcolor; c.dL_ddepth = dL_ddepth;
+    c.g.out.dmeans2D = dL_dmeans2D; c.g.out.dmeans3D = dL_dmeans3D; c.g.out.dopac = dL_dlogit_opacities; c.g.out.dcolors = dL_dcolors_precomp;
+    c.g.out.dshs = dL_dshs; c.g.out.dscales = dL_dlog_scales; c.g.out.drots = dL_dunnorm_rotations;
+    c.scratch = scratch; c.scratch_zeroed = scratch_zeroed; c.have_sh_jacobian = have_sh_jacobian;
+    return render_backward_impl(cam, c, stream);
 }
 
 uint64_t gs_pose_grad_scratch_bytes(int32_t P) { return align_up((uint64_t)gs::pose_rows_count(P > 0 ? P : 1) * gs::kPoseAcc * 4); }
@@ -725,10 +753,15 @@ int gs_render_backward_raw_pose(const GsCamera* cam, int32_t P, int64_t D, const
 {
     if (!h_pose7 || (P > 0 && !logit_opacities)) return fail(GS_EINVAL, "gs_render_backward_raw_pose: null pose / opacity parameters");
     if (!dL_dpose7 || !pose_scratch) return fail(GS_EINVAL, "gs_render_backward_raw_pose: null pose-gradient output or scratch");
-    return render_backward_impl(cam, P, D, means3D, shs, colors_precomp, log_scales, unnorm_rotations, nullptr, radii, geom_state, point_list,
-                                image_state, dL_dcolor, dL_ddepth, dL_dmeans2D, dL_dmeans3D, dL_dlogit_opacities, dL_dcolors_precomp, dL_dshs,
-                                dL_dlog_scales, dL_dunnorm_rotations, nullptr, scratch, scratch_zeroed, have_sh_jacobian, stream,
-                                logit_opacities, h_pose7, isotropic, pose_only ? 0 : accumulate, nullptr, pose_only ? 2 : 1, dL_dpose7, pose_scratch);
+    BackwardCall c{};
+    c.g.in.means3D = means3D; c.g.in.shs = shs; c.g.in.colors = colors_precomp; c.g.in.opac = logit_opacities; c.g.in.scales = log_scales; c.g.in.rots = unnorm_rotations;
+    c.P = P; c.D = D; c.pose.source = gs::POSE_HOST; c.pose.pose7 = h_pose7; c.isotropic = isotropic; c.accumulate = accumulate;
+    c.pose.grad = pose_only ? gs::POSE_GRAD_ONLY : gs::POSE_GRAD_WITH_PARAMS; c.pose.dL_dpose7 = dL_dpose7; c.pose.pose_scratch = pose_scratch;
+    c.g.radii = radii; c.geom_state = geom_state; c.point_list = point_list; c.image_state = image_state; c.dL_dcolor = dL_dcolor; c.dL_ddepth = dL_ddepth;
+    c.g.out.dmeans2D = dL_dmeans2D; c.g.out.dmeans3D = dL_dmeans3D; c.g.out.dopac = dL_dlogit_opacities; c.g.out.dcolors = dL_dcolors_precomp;
+    c.g.out.dshs = dL_dshs; c.g.out.dscales = dL_dlog_scales; c.g.out.drots = dL_dunnorm_rotations;
+    c.scratch = scratch; c.scratch_zeroed = scratch_zeroed; c.have_sh_jacobian = have_sh_jacobian;
+    return render_backward_impl(cam, c, stream);
 }
 
 int gs_render_backward_raw_pose_dev(const GsCamera* cam, int32_t P, int64_t D, const float* means3D, const float* shs, const float* colors_precomp,
@@ -738,16 +771,18 @@ int gs_render_backward_raw_pose_dev(const GsCamera* cam, int32_t P, int64_t D, c
                                     const float* dL_dcolor, const float* dL_ddepth, float* dL_dmeans2D, void* scratch, int32_t scratch_zeroed,
                                     int32_t have_sh_jacobian, float* dL_dpose7, void* pose_scratch, gs_stream_t stream)
 {
-    DevPose dp;
-    if (!dev_pose(cam_unnorm_rots, cam_trans, num_frames, time_idx, dp))
+    BackwardCall c{};
+    c.pose.source = gs::POSE_DEVICE;
+    if (!dev_pose(cam_unnorm_rots, cam_trans, num_frames, time_idx, c.pose.dev))
         return fail(GS_EINVAL, "gs_render_backward_raw_pose_dev: null pose columns or time index outside [0, num_frames)");
     if (P > 0 && !logit_opacities) return fail(GS_EINVAL, "gs_render_backward_raw_pose_dev: null opacity parameters");
     if (!pose_scratch) return fail(GS_EINVAL, "gs_render_backward_raw_pose_dev: null pose scratch");
-    const float ident[7] = {1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    return render_backward_impl(cam, P, D, means3D, shs, colors_precomp, log_scales, unnorm_rotations, nullptr, radii, geom_state, point_list,
-                                image_state, dL_dcolor, dL_ddepth, dL_dmeans2D, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                scratch, scratch_zeroed, have_sh_jacobian, stream, logit_opacities, ident, isotropic, 0, nullptr, 2, dL_dpose7,
-                                pose_scratch, &dp);
+    c.g.in.means3D = means3D; c.g.in.shs = shs; c.g.in.colors = colors_precomp; c.g.in.opac = logit_opacities; c.g.in.scales = log_scales; c.g.in.rots = unnorm_rotations;
+    c.P = P; c.D = D; c.isotropic = isotropic; c.pose.grad = gs::POSE_GRAD_ONLY; c.pose.dL_dpose7 = dL_dpose7; c.pose.pose_scratch = pose_scratch;
+    c.g.radii = radii; c.geom_state = geom_state; c.point_list = point_list; c.image_state = image_state; c.dL_dcolor = dL_dcolor; c.dL_ddepth = dL_ddepth;
+    c.g.out.dmeans2D = dL_dmeans2D;
+    c.scratch = scratch; c.scratch_zeroed = scratch_zeroed; c.have_sh_jacobian = have_sh_jacobian;
+    return render_backward_impl(cam, c, stream);
 }
 
 uint64_t gs_tracking_loss_scratch_bytes(int32_t width, int32_t height)
@@ -756,49 +791,49 @@ uint64_t gs_tracking_loss_scratch_bytes(int32_t width, int32_t height)
     return align_up((uint64_t)gs::tracking_loss_rows(n) * gs::kTrackRow * 4);
 }
 
+// d_median: the outlier rejection of gs_tracking_loss_outlier (`who` then requires it)
+static int tracking_loss_impl(const char* who, bool outlier, int32_t width, int32_t height, const float* im, const float* gt_im, const float* depth,
+                              const float* depth_sq, const float* gt_depth, const float* silhouette, int32_t use_sil_for_loss, float sil_thres, float w_im,
+                              float w_depth, float* dL_dim, float* dL_ddepth, void* loss_rows, float* losses, const float* d_median, gs_stream_t stream)
+{
+    if (width <= 0 || height <= 0 || (int64_t)width * height >= ((int64_t)1 << 31)) return fail(GS_EINVAL, "%s: bad image size", who);
+    if (!im || !gt_im || !depth || !depth_sq || !gt_depth || !dL_dim || !dL_ddepth || !loss_rows || (outlier && !d_median) || (use_sil_for_loss && !silhouette))
+        return fail(GS_EINVAL, "%s: null pointer", who);
+    return launched(who, "", gs::launch_tracking_loss(width, height, im, gt_im, depth, depth_sq, gt_depth, silhouette, use_sil_for_loss != 0, sil_thres, w_im,
+                    w_depth, dL_dim, dL_ddepth, (float*)loss_rows, losses, (hipStream_t)stream, d_median));
+}
+
 int gs_tracking_loss(int32_t width, int32_t height, const float* im, const float* gt_im, const float* depth, const float* depth_sq,
                      const float* gt_depth, const float* silhouette, int32_t use_sil_for_loss, float sil_thres, float w_im, float w_depth,
                      float* dL_dim, float* dL_ddepth, void* loss_rows, float* losses, gs_stream_t stream)
 {
-    if (width <= 0 || height <= 0 || (int64_t)width * height >= ((int64_t)1 << 31)) return fail(GS_EINVAL, "gs_tracking_loss: bad image size");
-    if (!im || !gt_im || !depth || !depth_sq || !gt_depth || !dL_dim || !dL_ddepth || !loss_rows || (use_sil_for_loss && !silhouette))
-        return fail(GS_EINVAL, "gs_tracking_loss: null pointer");
-    const hipError_t e = gs::launch_tracking_loss(width, height, im, gt_im, depth, depth_sq, gt_depth, silhouette, use_sil_for_loss != 0, sil_thres,
-                                                  w_im, w_depth, dL_dim, dL_ddepth, (float*)loss_rows, losses, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_tracking_loss: %s", hipGetErrorString(e));
-    return GS_OK;
+    return tracking_loss_impl("gs_tracking_loss", false, width, height, im, gt_im, depth, depth_sq, gt_depth, silhouette, use_sil_for_loss, sil_thres, w_im,
+                              w_depth, dL_dim, dL_ddepth, loss_rows, losses, nullptr, stream);
 }
 
 int gs_tracking_loss_outlier(int32_t width, int32_t height, const float* im, const float* gt_im, const float* depth, const float* depth_sq,
                              const float* gt_depth, const float* silhouette, int32_t use_sil_for_loss, float sil_thres, float w_im, float w_depth,
                              float* dL_dim, float* dL_ddepth, void* loss_rows, float* losses, const float* d_median, gs_stream_t stream)
 {
-    if (width <= 0 || height <= 0 || (int64_t)width * height >= ((int64_t)1 << 31)) return fail(GS_EINVAL, "gs_tracking_loss_outlier: bad image size");
-    if (!im || !gt_im || !depth || !depth_sq || !gt_depth || !dL_dim || !dL_ddepth || !loss_rows || !d_median || (use_sil_for_loss && !silhouette))
-        return fail(GS_EINVAL, "gs_tracking_loss_outlier: null pointer");
-    const hipError_t e = gs::launch_tracking_loss(width, height, im, gt_im, depth, depth_sq, gt_depth, silhouette, use_sil_for_loss != 0, sil_thres,
-                                                  w_im, w_depth, dL_dim, dL_ddepth, (float*)loss_rows, losses, (hipStream_t)stream, d_median);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_tracking_loss_outlier: %s", hipGetErrorString(e));
-    return GS_OK;
+    return tracking_loss_impl("gs_tracking_loss_outlier", true, width, height, im, gt_im, depth, depth_sq, gt_depth, silhouette, use_sil_for_loss, sil_thres,
+                              w_im, w_depth, dL_dim, dL_ddepth, loss_rows, losses, d_median, stream);
 }
 
 uint64_t gs_tracking_state_bytes(void) { return align_up((uint64_t)gs::kTrackState * 4); }
 
 int gs_tracking_begin(const float* cam_unnorm_rots, const float* cam_trans, int64_t num_frames, int64_t time_idx, void* state, gs_stream_t stream)
 {
-    DevPose dp;
+    gs::DevPose dp;
     if (!dev_pose(cam_unnorm_rots, cam_trans, num_frames, time_idx, dp) || !state)
         return fail(GS_EINVAL, "gs_tracking_begin: null pointer or time index outside [0, num_frames)");
-    const hipError_t e = gs::launch_tracking_begin(dp.q, dp.t, dp.stride, (float*)state, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_tracking_begin: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_tracking_begin", "", gs::launch_tracking_begin(dp.q, dp.t, dp.stride, (float*)state, (hipStream_t)stream));
 }
 
 int gs_tracking_step(int32_t P, const void* pose_scratch, int32_t width, int32_t height, const void* loss_rows, float w_im, float w_depth,
                      float* cam_unnorm_rots, float* cam_trans, int64_t num_frames, int64_t time_idx, double lr_rot, double lr_trans, int32_t step,
                      void* state, float* history_row, gs_stream_t stream)
 {
-    DevPose dp;
+    gs::DevPose dp;
     if (!dev_pose(cam_unnorm_rots, cam_trans, num_frames, time_idx, dp) || !state || !loss_rows || (P > 0 && !pose_scratch))
         return fail(GS_EINVAL, "gs_tracking_step: null pointer or time index outside [0, num_frames)");
     if (P < 0 || width <= 0 || height <= 0 || step < 1) return fail(GS_EINVAL, "gs_tracking_step: bad size or step (the first step is 1)");
@@ -809,11 +844,9 @@ int gs_tracking_step(int32_t P, const void* pose_scratch, int32_t width, int32_t
     c.one_m_b1 = (float)(1.0 - b1); c.b2 = (float)b2; c.one_m_b2 = (float)(1.0 - b2); c.bc2_sqrt = (float)pow(bc2, 0.5); c.eps = (float)1e-8;
     c.neg_step_size[0] = (float)(-(lr_rot / bc1)); c.neg_step_size[1] = (float)(-(lr_trans / bc1));
     const int64_t npix = (int64_t)width * height;
-    const hipError_t e = gs::launch_tracking_step(gs::pose_rows_count(P), (const float*)pose_scratch, gs::tracking_loss_rows(npix), (const float*)loss_rows,
-                                                  w_im, w_depth, cam_unnorm_rots + time_idx, cam_trans + time_idx, num_frames, c, (float*)state,
-                                                  history_row, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_tracking_step: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_tracking_step", "", gs::launch_tracking_step(gs::pose_rows_count(P), (const float*)pose_scratch, gs::tracking_loss_rows(npix),
+                    (const float*)loss_rows, w_im, w_depth, cam_unnorm_rots + time_idx, cam_trans + time_idx, num_frames, c, (float*)state, history_row,
+                    (hipStream_t)stream));
 }
 
 int gs_render_backward_raw_adam(const GsCamera* cam, int32_t P, int64_t D, const float* means3D, const float* shs, const float* colors_precomp,
@@ -823,9 +856,13 @@ int gs_render_backward_raw_adam(const GsCamera* cam, int32_t P, int64_t D, const
                                 int32_t scratch_zeroed, int32_t have_sh_jacobian, const GsAdamTensor* adam5, gs_stream_t stream)
 {
     if (!h_pose7 || !adam5 || (P > 0 && !logit_opacities)) return fail(GS_EINVAL, "gs_render_backward_raw_adam: null pose / opacity parameters / descriptors");
-    return render_backward_impl(cam, P, D, means3D, shs, colors_precomp, log_scales, unnorm_rotations, nullptr, radii, geom_state, point_list,
-                                image_state, dL_dcolor, dL_ddepth, dL_dmeans2D, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                scratch, scratch_zeroed, have_sh_jacobian, stream, logit_opacities, h_pose7, isotropic, 0, adam5);
+    BackwardCall c{};
+    c.g.in.means3D = means3D; c.g.in.shs = shs; c.g.in.colors = colors_precomp; c.g.in.opac = logit_opacities; c.g.in.scales = log_scales; c.g.in.rots = unnorm_rotations;
+    c.P = P; c.D = D; c.pose.source = gs::POSE_HOST; c.pose.pose7 = h_pose7; c.isotropic = isotropic; c.adam5 = adam5;
+    c.g.radii = radii; c.geom_state = geom_state; c.point_list = point_list; c.image_state = image_state; c.dL_dcolor = dL_dcolor; c.dL_ddepth = dL_ddepth;
+    c.g.out.dmeans2D = dL_dmeans2D;
+    c.scratch = scratch; c.scratch_zeroed = scratch_zeroed; c.have_sh_jacobian = have_sh_jacobian;
+    return render_backward_impl(cam, c, stream);
 }
 
 int gs_adam_step(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, double lr,
@@ -835,13 +872,8 @@ int gs_adam_step(int64_t n, float* param, const float* grad, float* exp_avg, flo
     if (n > 0 && (!param || !grad || !exp_avg || !exp_avg_sq)) return fail(GS_EINVAL, "gs_adam_step: null pointer");
     if (n > 0 && !adam_aligned16(param, grad, exp_avg, exp_avg_sq))
         return fail_adam_alignment("gs_adam_step", 0);
-    hipError_t e;
-    {
-        ScopedStage ps(ST_ADAM, (hipStream_t)stream);
-        e = gs::launch_adam(n, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, (hipStream_t)stream);
-    }
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_adam_step: %s", hipGetErrorString(e));
-    return GS_OK;
+    ScopedStage ps(ST_ADAM, (hipStream_t)stream);
+    return launched("gs_adam_step", "", gs::launch_adam(n, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, (hipStream_t)stream));
 }
 
 int gs_adam_step_multi(int32_t count, const GsAdamTensor* tensors, gs_stream_t stream)
@@ -855,13 +887,8 @@ int gs_adam_step_multi(int32_t count, const GsAdamTensor* tensors, gs_stream_t s
         if (t.n > 0 && !adam_aligned16(t.param, t.grad, t.exp_avg, t.exp_avg_sq))
             return fail_adam_alignment("gs_adam_step_multi", i);
     }
-    hipError_t e;
-    {
-        ScopedStage sc(ST_ADAM, (hipStream_t)stream);
-        e = gs::launch_adam_multi(count, tensors, (hipStream_t)stream);
-    }
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_adam_step_multi: %s", hipGetErrorString(e));
-    return GS_OK;
+    ScopedStage sc(ST_ADAM, (hipStream_t)stream);
+    return launched("gs_adam_step_multi", "", gs::launch_adam_multi(count, tensors, (hipStream_t)stream));
 }
 
 static int rows_args_ok(int32_t count, const GsRowTensor* t, int mode)
@@ -880,9 +907,7 @@ static int rows_args_ok(int32_t count, const GsRowTensor* t, int mode)
 int gs_pack_columns(int32_t count, const GsRowTensor* tensors, int64_t n, int64_t n_padded, float* flat, gs_stream_t stream)
 {
     if (!rows_args_ok(count, tensors, 0) || n < 0 || n_padded < n || (n_padded > 0 && !flat)) return fail(GS_EINVAL, "gs_pack_columns: bad argument");
-    hipError_t e = gs::launch_rows(0, count, tensors, 0, n, n_padded, nullptr, flat, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_pack_columns: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_pack_columns", "", gs::launch_rows(0, count, tensors, 0, n, n_padded, nullptr, flat, (hipStream_t)stream));
 }
 
 int gs_adam_rows(int32_t count, const GsRowTensor* tensors, int64_t row_lo, int64_t n_valid, int64_t n_rows, const float* grad_shard,
@@ -890,21 +915,14 @@ int gs_adam_rows(int32_t count, const GsRowTensor* tensors, int64_t row_lo, int6
 {
     if (!rows_args_ok(count, tensors, 2) || row_lo < 0 || n_valid < 0 || n_rows < n_valid || (n_rows > 0 && !grad_shard))
         return fail(GS_EINVAL, "gs_adam_rows: bad argument");
-    hipError_t e;
-    {
-        ScopedStage sc(ST_ADAM, (hipStream_t)stream);
-        e = gs::launch_rows(2, count, tensors, row_lo, n_valid, n_rows, grad_shard, out_shard, (hipStream_t)stream);
-    }
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_adam_rows: %s", hipGetErrorString(e));
-    return GS_OK;
+    ScopedStage sc(ST_ADAM, (hipStream_t)stream);
+    return launched("gs_adam_rows", "", gs::launch_rows(2, count, tensors, row_lo, n_valid, n_rows, grad_shard, out_shard, (hipStream_t)stream));
 }
 
 int gs_unpack_columns(int32_t count, const GsRowTensor* tensors, int64_t n, const float* flat, gs_stream_t stream)
 {
     if (!rows_args_ok(count, tensors, 1) || n < 0 || (n > 0 && !flat)) return fail(GS_EINVAL, "gs_unpack_columns: bad argument");
-    hipError_t e = gs::launch_rows(1, count, tensors, 0, n, n, flat, nullptr, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_unpack_columns: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_unpack_columns", "", gs::launch_rows(1, count, tensors, 0, n, n, flat, nullptr, (hipStream_t)stream));
 }
 
 int gs_activate_forward(int32_t P, int32_t isotropic, const float* h_pose7, const float* means3D, const float* unnorm_rotations,
@@ -914,10 +932,20 @@ int gs_activate_forward(int32_t P, int32_t isotropic, const float* h_pose7, cons
     if (P < 0 || !h_pose7 || (P > 0 && (!means3D || !unnorm_rotations || !logit_opacities || !log_scales || !out_means3D ||
                                         !out_rotations || !out_opacities || !out_scales)))
         return fail(GS_EINVAL, "gs_activate_forward: bad argument");
-    hipError_t e = gs::launch_activate_forward(P, isotropic, h_pose7, means3D, unnorm_rotations, logit_opacities, log_scales,
-                                               out_means3D, out_rotations, out_opacities, out_scales, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_activate_forward: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_activate_forward", "", gs::launch_activate_forward(P, isotropic, h_pose7, means3D, unnorm_rotations, logit_opacities, log_scales,
+                    out_means3D, out_rotations, out_opacities, out_scales, (hipStream_t)stream));
+}
+
+static int activate_backward_impl(const char* who, int accumulate, int32_t P, int32_t isotropic, const float* h_pose7, const float* unnorm_rotations,
+                                  const float* out_opacities, const float* out_scales, const float* g_means3D, const float* g_rotations,
+                                  const float* g_opacities, const float* g_scales, float* d_means3D, float* d_unnorm_rotations, float* d_logit_opacities,
+                                  float* d_log_scales, gs_stream_t stream)
+{
+    if (P < 0 || !h_pose7 || (P > 0 && (!unnorm_rotations || !out_opacities || !out_scales || !d_means3D || !d_unnorm_rotations ||
+                                        !d_logit_opacities || !d_log_scales)))
+        return fail(GS_EINVAL, "%s: bad argument", who);
+    return launched(who, "", gs::launch_activate_backward(P, isotropic, h_pose7, unnorm_rotations, out_opacities, out_scales, g_means3D, g_rotations,
+                    g_opacities, g_scales, d_means3D, d_unnorm_rotations, d_logit_opacities, d_log_scales, accumulate, (hipStream_t)stream));
 }
 
 int gs_activate_backward(int32_t P, int32_t isotropic, const float* h_pose7, const float* unnorm_rotations, const float* out_opacities,
@@ -925,14 +953,8 @@ int gs_activate_backward(int32_t P, int32_t isotropic, const float* h_pose7, con
                          const float* g_scales, float* d_means3D, float* d_unnorm_rotations, float* d_logit_opacities,
                          float* d_log_scales, gs_stream_t stream)
 {
-    if (P < 0 || !h_pose7 || (P > 0 && (!unnorm_rotations || !out_opacities || !out_scales || !d_means3D || !d_unnorm_rotations ||
-                                        !d_logit_opacities || !d_log_scales)))
-        return fail(GS_EINVAL, "gs_activate_backward: bad argument");
-    hipError_t e = gs::launch_activate_backward(P, isotropic, h_pose7, unnorm_rotations, out_opacities, out_scales, g_means3D, g_rotations,
-                                                g_opacities, g_scales, d_means3D, d_unnorm_rotations, d_logit_opacities, d_log_scales, 0,
-                                                (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_activate_backward: %s", hipGetErrorString(e));
-    return GS_OK;
+    return activate_backward_impl("gs_activate_backward", 0, P, isotropic, h_pose7, unnorm_rotations, out_opacities, out_scales, g_means3D, g_rotations,
+                                  g_opacities, g_scales, d_means3D, d_unnorm_rotations, d_logit_opacities, d_log_scales, stream);
 }
 
 int gs_activate_backward_accumulate(int32_t P, int32_t isotropic, const float* h_pose7, const float* unnorm_rotations, const float* out_opacities,
@@ -940,14 +962,8 @@ int gs_activate_backward_accumulate(int32_t P, int32_t isotropic, const float* h
                                     const float* g_scales, float* d_means3D, float* d_unnorm_rotations, float* d_logit_opacities,
                                     float* d_log_scales, gs_stream_t stream)
 {
-    if (P < 0 || !h_pose7 || (P > 0 && (!unnorm_rotations || !out_opacities || !out_scales || !d_means3D || !d_unnorm_rotations ||
-                                        !d_logit_opacities || !d_log_scales)))
-        return fail(GS_EINVAL, "gs_activate_backward_accumulate: bad argument");
-    hipError_t e = gs::launch_activate_backward(P, isotropic, h_pose7, unnorm_rotations, out_opacities, out_scales, g_means3D, g_rotations,
-                                                g_opacities, g_scales, d_means3D, d_unnorm_rotations, d_logit_opacities, d_log_scales, 1,
-                                                (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_activate_backward_accumulate: %s", hipGetErrorString(e));
-    return GS_OK;
+    return activate_backward_impl("gs_activate_backward_accumulate", 1, P, isotropic, h_pose7, unnorm_rotations, out_opacities, out_scales, g_means3D,
+                                  g_rotations, g_opacities, g_scales, d_means3D, d_unnorm_rotations, d_logit_opacities, d_log_scales, stream);
 }
 
 int gs_activate_backward_pose(int32_t P, int32_t isotropic, const float* h_pose7, const float* means3D, const float* unnorm_rotations,
@@ -961,17 +977,14 @@ int gs_activate_backward_pose(int32_t P, int32_t isotropic, const float* h_pose7
         return fail(GS_EINVAL, "gs_activate_backward_pose: bad argument");
     hipStream_t st = (hipStream_t)stream;
     if (P == 0) {
-        const hipError_t e0 = hipMemsetAsync(dL_dpose7, 0, 7 * sizeof(float), st);
-        if (e0 != hipSuccess) return fail(GS_ELAUNCH, "gs_activate_backward_pose: memset %s", hipGetErrorString(e0));
-        return GS_OK;
+        return launched("gs_activate_backward_pose", "memset", hipMemsetAsync(dL_dpose7, 0, 7 * sizeof(float), st));
     }
     hipError_t e = gs::launch_activate_backward_pose(P, isotropic, h_pose7, means3D, unnorm_rotations, out_opacities, out_scales, g_means3D,
                                                      g_rotations, g_opacities, g_scales, d_means3D, d_unnorm_rotations, d_logit_opacities,
                                                      d_log_scales, accumulate, pose_only ? 2 : 1, (float*)pose_scratch, st);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_activate_backward_pose: %s", hipGetErrorString(e));
+    if (int rc = launched("gs_activate_backward_pose", "", e)) return rc;
     e = gs::launch_pose_grad_finish(gs::pose_rows_count(P), h_pose7, (const float*)pose_scratch, dL_dpose7, st);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_activate_backward_pose: pose reduction %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_activate_backward_pose", "pose reduction", e);
 }
 
 uint64_t gs_mapping_loss_scratch_bytes(int32_t width, int32_t height)
@@ -979,29 +992,32 @@ uint64_t gs_mapping_loss_scratch_bytes(int32_t width, int32_t height)
     return align_up((uint64_t)(2 * gs::kLossAccSlots * 16 + 9 * (uint64_t)(width > 0 ? width : 1) * (uint64_t)(height > 0 ? height : 1)) * 4);   // two sets of accumulator lines + 9 maps
 }
 
+// d_median: the outlier rejection of gs_mapping_loss_outlier (`who` then requires it)
+static int mapping_loss_impl(const char* who, bool outlier, int32_t width, int32_t height, const float* im, const float* gt_im, const float* depth,
+                             const float* depth_sq, const float* gt_depth, float w_im, float w_depth, float* losses, float* dL_dim, float* dL_ddepth,
+                             void* scratch, int64_t persistent_call, const float* d_median, gs_stream_t stream)
+{
+    if (width <= 0 || height <= 0 || !im || !gt_im || !depth || !gt_depth || !losses || !dL_dim || !dL_ddepth || !scratch || persistent_call < 0 ||
+        (outlier && !d_median))
+        return fail(GS_EINVAL, "%s: bad argument", who);
+    return launched(who, "", gs::launch_mapping_loss(width, height, im, gt_im, depth, depth_sq, gt_depth, w_im, w_depth, losses, dL_dim, dL_ddepth,
+                    (float*)scratch, persistent_call, (hipStream_t)stream, d_median));
+}
+
 int gs_mapping_loss(int32_t width, int32_t height, const float* im, const float* gt_im, const float* depth,
                     const float* depth_sq, const float* gt_depth, float w_im, float w_depth, float* losses, float* dL_dim,
                     float* dL_ddepth, void* scratch, int64_t persistent_call, gs_stream_t stream)
 {
-    if (width <= 0 || height <= 0 || !im || !gt_im || !depth || !gt_depth || !losses || !dL_dim || !dL_ddepth || !scratch || persistent_call < 0)
-        return fail(GS_EINVAL, "gs_mapping_loss: bad argument");
-    hipError_t e = gs::launch_mapping_loss(width, height, im, gt_im, depth, depth_sq, gt_depth, w_im, w_depth, losses, dL_dim,
-                                           dL_ddepth, (float*)scratch, persistent_call, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_mapping_loss: %s", hipGetErrorString(e));
-    return GS_OK;
+    return mapping_loss_impl("gs_mapping_loss", false, width, height, im, gt_im, depth, depth_sq, gt_depth, w_im, w_depth, losses, dL_dim, dL_ddepth,
+                             scratch, persistent_call, nullptr, stream);
 }
 
 int gs_mapping_loss_outlier(int32_t width, int32_t height, const float* im, const float* gt_im, const float* depth,
                             const float* depth_sq, const float* gt_depth, float w_im, float w_depth, float* losses, float* dL_dim,
                             float* dL_ddepth, void* scratch, int64_t persistent_call, const float* d_median, gs_stream_t stream)
 {
-    if (width <= 0 || height <= 0 || !im || !gt_im || !depth || !gt_depth || !losses || !dL_dim || !dL_ddepth || !scratch || persistent_call < 0 ||
-        !d_median)
-        return fail(GS_EINVAL, "gs_mapping_loss_outlier: bad argument");
-    hipError_t e = gs::launch_mapping_loss(width, height, im, gt_im, depth, depth_sq, gt_depth, w_im, w_depth, losses, dL_dim,
-                                           dL_ddepth, (float*)scratch, persistent_call, (hipStream_t)stream, d_median);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_mapping_loss_outlier: %s", hipGetErrorString(e));
-    return GS_OK;
+    return mapping_loss_impl("gs_mapping_loss_outlier", true, width, height, im, gt_im, depth, depth_sq, gt_depth, w_im, w_depth, losses, dL_dim,
+                             dL_ddepth, scratch, persistent_call, d_median, stream);
 }
 
 int32_t gs_depth_error_median_workgroups(int32_t width, int32_t height)
@@ -1021,10 +1037,8 @@ int gs_depth_error_median_grid(int32_t width, int32_t height, const float* depth
     if (width <= 0 || height <= 0 || (int64_t)width * height >= ((int64_t)1 << 31)) return fail(GS_EINVAL, "gs_depth_error_median: bad image size");
     if (!depth || !gt_depth || !scratch || !d_median) return fail(GS_EINVAL, "gs_depth_error_median: null pointer");
     if (workgroups < 0 || workgroups > gs::kMedianMaxGrid) return fail(GS_EINVAL, "gs_depth_error_median_grid: 0 (automatic) .. 1024 workgroups");
-    const hipError_t e = gs::launch_depth_error_median((int64_t)width * height, depth, gt_depth, (uint32_t*)scratch, d_median, workgroups,
-                                                       (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_depth_error_median: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_depth_error_median", "", gs::launch_depth_error_median((int64_t)width * height, depth, gt_depth, (uint32_t*)scratch, d_median,
+                    workgroups, (hipStream_t)stream));
 }
 
 int gs_depth_error_median(int32_t width, int32_t height, const float* depth, const float* gt_depth, void* scratch, float* d_median,
@@ -1039,9 +1053,7 @@ int gs_compact_index(int64_t n, const uint8_t* keep, uint32_t* src_index, uint32
 {
     if (n < 0 || !d_count || !scratch || (n > 0 && (!keep || !src_index))) return fail(GS_EINVAL, "gs_compact_index: bad argument");
     if (n >= (int64_t)1 << 32) return fail(GS_ECAPACITY, "gs_compact_index: more than 2^32 rows");
-    hipError_t e = gs::launch_compact_index(n, keep, src_index, d_count, scratch, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_compact_index: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_compact_index", "", gs::launch_compact_index(n, keep, src_index, d_count, scratch, (hipStream_t)stream));
 }
 
 uint64_t gs_compact3_scratch_bytes(int64_t n) { return align_up(gs::compact3_scratch_bytes(n > 0 ? n : 1)); }
@@ -1052,17 +1064,13 @@ int gs_compact_index3(int64_t n, const uint8_t* keep_a, const uint8_t* keep_b, c
     if (n < 0 || repeat_c < 1 || !d_counts || !scratch || (n > 0 && (!keep_a || !keep_b || !keep_c || !src_index)))
         return fail(GS_EINVAL, "gs_compact_index3: bad argument");
     if (n * (2 + (int64_t)repeat_c) >= (int64_t)1 << 32) return fail(GS_ECAPACITY, "gs_compact_index3: more than 2^32 rows");
-    hipError_t e = gs::launch_compact_index3(n, keep_a, keep_b, keep_c, repeat_c, src_index, d_counts, scratch, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_compact_index3: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_compact_index3", "", gs::launch_compact_index3(n, keep_a, keep_b, keep_c, repeat_c, src_index, d_counts, scratch, (hipStream_t)stream));
 }
 
 int gs_gather_rows(int64_t n_out, int32_t row_floats, const uint32_t* src_index, const float* src, float* dst, gs_stream_t stream)
 {
     if (n_out < 0 || row_floats <= 0 || (n_out > 0 && (!src_index || !src || !dst))) return fail(GS_EINVAL, "gs_gather_rows: bad argument");
-    hipError_t e = gs::launch_gather_rows(n_out, row_floats, src_index, src, dst, n_out, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_gather_rows: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_gather_rows", "", gs::launch_gather_rows(n_out, row_floats, src_index, src, dst, n_out, (hipStream_t)stream));
 }
 
 int gs_gather_rows_zero_tail(int64_t n_out, int64_t n_copy, int32_t row_floats, const uint32_t* src_index, const float* src, float* dst,
@@ -1070,9 +1078,7 @@ int gs_gather_rows_zero_tail(int64_t n_out, int64_t n_copy, int32_t row_floats, 
 {
     if (n_out < 0 || n_copy < 0 || n_copy > n_out || row_floats <= 0 || (n_out > 0 && !dst) || (n_copy > 0 && (!src_index || !src)))
         return fail(GS_EINVAL, "gs_gather_rows_zero_tail: bad argument");
-    hipError_t e = gs::launch_gather_rows(n_out, row_floats, src_index, src, dst, n_copy, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_gather_rows_zero_tail: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_gather_rows_zero_tail", "", gs::launch_gather_rows(n_out, row_floats, src_index, src, dst, n_copy, (hipStream_t)stream));
 }
 
 int gs_densify_classify(int32_t N, int32_t scale_dim, const float* log_scales, const float* logit_opacities, const float* grad_accum,
@@ -1083,11 +1089,8 @@ int gs_densify_classify(int32_t N, int32_t scale_dim, const float* log_scales, c
     if (N < 0 || (scale_dim != 1 && scale_dim != 3) || num_to_split_into < 1 || !d_scene_radius ||
         (N > 0 && (!log_scales || !logit_opacities || !keep_orig)) || ((grad_accum == nullptr) != (denom == nullptr)))
         return fail(GS_EINVAL, "gs_densify_classify: bad argument");
-    hipError_t e = gs::launch_densify_classify(N, scale_dim, log_scales, logit_opacities, grad_accum, denom, d_scene_radius, grad_thresh,
-                                               opacity_thresh, remove_big, num_to_split_into, keep_orig, keep_clone, keep_child, split_mask,
-                                               (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_densify_classify: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_densify_classify", "", gs::launch_densify_classify(N, scale_dim, log_scales, logit_opacities, grad_accum, denom, d_scene_radius,
+                    grad_thresh, opacity_thresh, remove_big, num_to_split_into, keep_orig, keep_clone, keep_child, split_mask, (hipStream_t)stream));
 }
 
 int gs_densify_children(int32_t n_child, int32_t scale_dim, int32_t num_to_split_into, const float* unnorm_rotations, const float* samples,
@@ -1096,26 +1099,20 @@ int gs_densify_children(int32_t n_child, int32_t scale_dim, int32_t num_to_split
     if (n_child < 0 || (scale_dim != 1 && scale_dim != 3) || num_to_split_into < 1 ||
         (n_child > 0 && (!unnorm_rotations || !means3D || !log_scales)))
         return fail(GS_EINVAL, "gs_densify_children: bad argument");
-    hipError_t e = gs::launch_densify_children(n_child, scale_dim, num_to_split_into, unnorm_rotations, samples, seed, means3D, log_scales,
-                                               (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_densify_children: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_densify_children", "", gs::launch_densify_children(n_child, scale_dim, num_to_split_into, unnorm_rotations, samples, seed, means3D,
+                    log_scales, (hipStream_t)stream));
 }
 
 int gs_visibility_stats(int32_t P, const int32_t* radii, uint8_t* seen, float* max_2D_radius, gs_stream_t stream)
 {
     if (P < 0 || (P > 0 && !radii)) return fail(GS_EINVAL, "gs_visibility_stats: bad argument");
-    hipError_t e = gs::launch_visibility_stats(P, radii, seen, max_2D_radius, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_visibility_stats: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_visibility_stats", "", gs::launch_visibility_stats(P, radii, seen, max_2D_radius, (hipStream_t)stream));
 }
 
 int gs_accumulate_grad2d(int32_t P, const float* means2D_grad, const uint8_t* seen, float* grad_accum, float* denom, gs_stream_t stream)
 {
     if (P < 0 || (P > 0 && (!means2D_grad || !seen || !grad_accum || !denom))) return fail(GS_EINVAL, "gs_accumulate_grad2d: bad argument");
-    hipError_t e = gs::launch_accumulate_grad2d(P, means2D_grad, seen, grad_accum, denom, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_accumulate_grad2d: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_accumulate_grad2d", "", gs::launch_accumulate_grad2d(P, means2D_grad, seen, grad_accum, denom, (hipStream_t)stream));
 }
 
 static bool dbscan_size_ok(int32_t B, int32_t H, int32_t W, int32_t max_clusters)
@@ -1166,9 +1163,7 @@ int gs_grid_dbscan(int32_t B, int32_t H, int32_t W, const float* values, int64_t
     a.word_prefix = (uint32_t*)(ws + L.word_prefix); a.parent = (uint32_t*)(ws + L.parent); a.root = (int32_t*)(ws + L.root);
     a.row_range = (uint32_t*)(ws + L.row_range);
     a.labels = labels; a.n_clusters = n_clusters; a.table = table; a.sum_value = sum_value; a.total = total;
-    hipError_t e = gs::launch_grid_dbscan(a, B, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_grid_dbscan: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_grid_dbscan", "", gs::launch_grid_dbscan(a, B, (hipStream_t)stream));
 }
 
 int gs_cluster_hulls_layout(int32_t B, int32_t H, int32_t W, int32_t max_clusters, int32_t max_points, GsHullLayout* out)
@@ -1211,9 +1206,7 @@ int gs_cluster_hulls(int32_t B, int32_t H, int32_t W, const int32_t* labels, con
     a.cluster_status = (int32_t*)((char*)workspace + L.cluster_status);
     a.volume = volume; a.n_points = n_points; a.contour_xy = contour_xy;
     a.sum_volume = sum_volume; a.sum_invisibility = sum_invisibility; a.status = status;
-    hipError_t e = gs::launch_cluster_hulls(a, B, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_cluster_hulls: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_cluster_hulls", "", gs::launch_cluster_hulls(a, B, (hipStream_t)stream));
 }
 
 int gs_high_loss_grid(int32_t width, int32_t height, const float* render_depth, const float* opacity, const float* gt_depth,
@@ -1233,9 +1226,7 @@ int gs_high_loss_grid(int32_t width, int32_t height, const float* render_depth, 
     a.W = width; a.H = height; a.gw = grid_width; a.gh = grid_height;
     a.depth_thres = depth_err_thres; a.opacity_thres = opacity_thres;
     a.mask_full = mask_full; a.grid = grid;
-    hipError_t e = gs::launch_high_loss_grid(a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_high_loss_grid: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_high_loss_grid", "", gs::launch_high_loss_grid(a, (hipStream_t)stream));
 }
 
 uint64_t gs_grow_scratch_bytes(int32_t width, int32_t height)
@@ -1252,11 +1243,9 @@ int gs_grow_gaussians(int32_t width, int32_t height, const float* render_depth, 
         !out_means3D || !out_rgb_colors || !out_unnorm_rotations || !out_logit_opacities || !out_log_scales || !d_counts || !scratch)
         return fail(GS_EINVAL, "gs_grow_gaussians: bad argument");
     if ((int64_t)width * height >= ((int64_t)1 << 31)) return fail(GS_EINVAL, "gs_grow_gaussians: bad image size");     // (the median select's 32-bit rank)
-    hipError_t e = gs::launch_grow(width, height, render_depth, silhouette, gt_depth, color, h_intrinsics4, h_c2w12, sil_thres,
-                                   isotropic != 0, out_means3D, out_rgb_colors, out_unnorm_rotations, out_logit_opacities,
-                                   out_log_scales, d_counts, scratch, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_grow_gaussians: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_grow_gaussians", "", gs::launch_grow(width, height, render_depth, silhouette, gt_depth, color, h_intrinsics4, h_c2w12, sil_thres,
+                    isotropic != 0, out_means3D, out_rgb_colors, out_unnorm_rotations, out_logit_opacities, out_log_scales, d_counts, scratch,
+                    (hipStream_t)stream));
 }
 
 int gs_keyframe_overlap(int32_t n_pts, const float* pts_world, int32_t n_keyframes, const float* w2c, const float* h_intrinsics9,
@@ -1265,10 +1254,8 @@ int gs_keyframe_overlap(int32_t n_pts, const float* pts_world, int32_t n_keyfram
     if (n_pts < 0 || n_keyframes < 0 || width <= 0 || height <= 0 || !h_intrinsics9 ||
         (n_keyframes > 0 && (!w2c || !counts)) || (n_pts > 0 && !pts_world))
         return fail(GS_EINVAL, "gs_keyframe_overlap: bad argument");
-    hipError_t e = gs::launch_keyframe_overlap(n_pts, pts_world, n_keyframes, w2c, h_intrinsics9, width, height, edge, counts,
-                                               (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_keyframe_overlap: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_keyframe_overlap", "", gs::launch_keyframe_overlap(n_pts, pts_world, n_keyframes, w2c, h_intrinsics9, width, height, edge, counts,
+                    (hipStream_t)stream));
 }
 
 int gs_frame_ingest(int32_t width, int32_t height, const uint8_t* image, const float* depth, const float* level_value, int32_t n_out,
@@ -1283,9 +1270,7 @@ int gs_frame_ingest(int32_t width, int32_t height, const uint8_t* image, const f
         if (h_sizes[k] < 1 || h_sizes[k] > 16384) return fail(GS_EINVAL, "gs_frame_ingest: output size out of range (1 <= W, H <= 16384)");
     float* const colors[2] = {color0, color1};
     float* const depths[2] = {depth0, depth1};
-    hipError_t e = gs::launch_frame_ingest(width, height, image, depth, level_value, n_out, h_sizes, colors, depths, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_frame_ingest: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_frame_ingest", "", gs::launch_frame_ingest(width, height, image, depth, level_value, n_out, h_sizes, colors, depths, (hipStream_t)stream));
 }
 
 int gs_depth_cloud(int32_t width, int32_t height, const float* depth, const float* h_intrinsics4, const float* h_c2w12, float* points,
@@ -1297,9 +1282,7 @@ int gs_depth_cloud(int32_t width, int32_t height, const float* depth, const floa
     // (written so that a NaN fails it)
     if (!(fabsf(h_intrinsics4[0]) > 0.0f) || !(fabsf(h_intrinsics4[1]) > 0.0f))
         return fail(GS_EINVAL, "gs_depth_cloud: fx and fy must not be zero");
-    hipError_t e = gs::launch_depth_cloud(width, height, depth, h_intrinsics4, h_c2w12, points, valid, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_depth_cloud: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_depth_cloud", "", gs::launch_depth_cloud(width, height, depth, h_intrinsics4, h_c2w12, points, valid, (hipStream_t)stream));
 }
 
 static bool nearest_size_ok(int64_t n) { return n >= 0 && n <= ((int64_t)1 << 30); }
@@ -1319,9 +1302,7 @@ int gs_cloud_nearest(int64_t n_query, const float* query, const uint8_t* query_v
     if (n_query == 0) return GS_OK;
     if (!query || !out || !scratch || (n_points > 0 && !points) || ((uintptr_t)scratch & 3))
         return fail(GS_EINVAL, "gs_cloud_nearest: null pointer (only query_valid and points_valid may be null) or scratch not 4-byte aligned");
-    hipError_t e = gs::launch_cloud_nearest(n_query, query, query_valid, n_points, points, points_valid, flags, out, scratch, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_cloud_nearest: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_cloud_nearest", "", gs::launch_cloud_nearest(n_query, query, query_valid, n_points, points, points_valid, flags, out, scratch, (hipStream_t)stream));
 }
 
 uint64_t gs_completion_row_scratch_bytes(void) { return align_up(gs::completion_row_scratch_bytes()); }
@@ -1333,9 +1314,7 @@ int gs_completion_row(int64_t n_samples, const float* min_dist, int64_t n_acc, c
         return fail(GS_EINVAL, "gs_completion_row: size out of range (1 <= n_samples <= 2^30, 0 <= n_acc <= 2^30)");
     if (!min_dist || !row6 || !scratch || (n_acc > 0 && !acc_dist) || ((uintptr_t)scratch & 7) || ((uintptr_t)row6 & 7))
         return fail(GS_EINVAL, "gs_completion_row: null pointer (only acc_valid may be null), or scratch / row6 not 8-byte aligned");
-    hipError_t e = gs::launch_completion_row(n_samples, min_dist, n_acc, acc_dist, acc_valid, path_length, row6, scratch, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_completion_row: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_completion_row", "", gs::launch_completion_row(n_samples, min_dist, n_acc, acc_dist, acc_valid, path_length, row6, scratch, (hipStream_t)stream));
 }
 
 static int eval_plan_checked(const char* who, int32_t width, int32_t height, int32_t flags, gs::EvalPlan& p)
@@ -1370,9 +1349,7 @@ int gs_eval_frame(int32_t width, int32_t height, const float* im, const float* d
     if (rc != GS_OK) return rc;
     if (!im || !depth || !silhouette || !gt_im || !gt_depth || !row || !scratch || ((uintptr_t)scratch & 7) || ((uintptr_t)row & 7))
         return fail(GS_EINVAL, "gs_eval_frame: null pointer, or scratch / row not 8-byte aligned");
-    hipError_t e = gs::launch_eval_frame(p, im, depth, silhouette, gt_im, gt_depth, sil_thres, flags, row, scratch, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GS_ELAUNCH, "gs_eval_frame: %s", hipGetErrorString(e));
-    return GS_OK;
+    return launched("gs_eval_frame", "", gs::launch_eval_frame(p, im, depth, silhouette, gt_im, gt_depth, sil_thres, flags, row, scratch, (hipStream_t)stream));
 }
 
 }  // extern "C"

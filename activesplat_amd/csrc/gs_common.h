@@ -6,6 +6,7 @@
 #include <math.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "../../include/gsplat_hip.h"
 
@@ -707,26 +708,50 @@ __device__ __forceinline__ void load_sh_jac(const float2* base, size_t i, float 
     clamp_bits = __float_as_uint(e.y);
 }
 
+// Host-side argument blocks of the per-Gaussian stage: api.hip fills in the fields an entry point has, by name, and leaves the rest zero; the
+// launchers hand them to the kernels field by field (no kernel takes one of these).
+struct GaussianInputs {
+    const float* means3D;
+    const float* shs;
+    const float* colors;
+    const float* opac;           // opacities; the logit opacities in raw-parameter mode
+    const float* scales;
+    const float* rots;
+    const float* cov3D;
+};
+struct GaussianGrads { float *dmeans2D, *dmeans3D, *dopac, *dcolors, *dshs, *dscales, *drots, *dcov3D; };
+struct DevPose { const float* q; const float* t; int64_t stride; };      // CamDP's three fields
+// where the raw-parameter mode's frame transform comes from, and which camera-pose gradient the backward forms
+enum PoseSource { POSE_NONE = 0, POSE_HOST, POSE_DEVICE, POSE_BAND };   // none (activated inputs) / pose7 / DevPose (CamDP) / world frame + height band (CamBand)
+enum PoseGrad { POSE_GRAD_NONE = 0, POSE_GRAD_WITH_PARAMS = 1, POSE_GRAD_ONLY = 2 };    // (the kernels' POSE template argument)
+struct PoseRequest {
+    PoseSource source;
+    const float* pose7;          // POSE_HOST: host (qw, qx, qy, qz, tx, ty, tz)
+    DevPose dev;                 // POSE_DEVICE
+    float band_upper, band_lower;   // POSE_BAND
+    PoseGrad grad;
+    float* dL_dpose7;
+    void* pose_scratch;          // one row of kPoseAcc partial sums per 256-Gaussian workgroup
+};
+// the per-Gaussian backward: what it reads, what it writes
+struct GaussianBackward {
+    GaussianInputs in;
+    GaussianGrads out;
+    const int32_t* radii;
+    const uint32_t* clamped;
+    const float2* sh_jac;
+    const float* grad2d;
+    const FusedAdam* adam;
+};
+
 // ---- launchers implemented in the individual translation units -------------------------------------
-hipError_t launch_preprocess_forward(const Cam& cam, int P, const float* means3D, const float* shs,
-                                     const float* colors, const float* opac, const float* scales,
-                                     const float* rots, const float* cov3Dp, int32_t* radii, GeomPtrs gp,
-                                     uint32_t* d_num_rendered, hipStream_t st);
-// device-resident pose (CamDP): raw-parameter forward, and the pose-only raw-parameter backward (pose_rows as launch_preprocess_backward's)
-hipError_t launch_preprocess_forward_dev(const CamDP& cam, int P, const float* means3D, const float* shs, const float* colors,
-                                         const float* opac, const float* scales, const float* rots, int32_t* radii, GeomPtrs gp, hipStream_t st);
-hipError_t launch_preprocess_backward_pose_dev(const CamDP& cam, int P, const float* means3D, const float* shs, const float* scales,
-                                               const float* rots, const int32_t* radii, const uint32_t* clamped, const float2* sh_jac,
-                                               const float* grad2d, float* dmeans2D, const float* logit, float* pose_rows, hipStream_t st);
-hipError_t launch_preprocess_forward_band(const CamBand& cam, int P, const float* means3D, const float* colors, const float* opac, const float* scales,
-                                          const float* rots, int32_t* radii, GeomPtrs gp, hipStream_t st);
+// CamT = Cam, CamDP (device-resident pose: raw-parameter mode only) or CamBand (the planner's top-down maps: raw parameters + colours only)
+template <class CamT>
+hipError_t launch_preprocess_forward(const CamT& cam, int P, const GaussianInputs& in, int32_t* radii, GeomPtrs gp, hipStream_t st);
 hipError_t launch_scan_block_sums(int P, GeomPtrs gp, uint32_t* d_total, hipStream_t st);
-hipError_t launch_preprocess_backward(const Cam& cam, int P, const float* means3D, const float* shs,
-                                      const float* scales, const float* rots, const float* cov3Dp,
-                                      const int32_t* radii, const uint32_t* clamped, const float2* sh_jac, const float* grad2d,
-                                      float* dmeans2D, float* dmeans3D, float* dopac, float* dcolors, float* dshs,
-                                      float* dscales, float* drots, float* dcov3D, const float* logit, const FusedAdam* adam, hipStream_t st,
-                                      int pose_mode = 0, float* pose_rows = nullptr);
+// CamT = Cam, or CamDP (the pose-only backward only)
+template <class CamT>
+hipError_t launch_preprocess_backward(const CamT& cam, int P, const GaussianBackward& g, const PoseRequest& pose, hipStream_t st);
 hipError_t launch_tile_count(const Cam& cam, int P, GeomPtrs gp, uint32_t* tile_total, uint32_t* tile_base,
                              uint2* ranges, uint32_t* d_counts, uint32_t* host_counts, hipStream_t st);
 hipError_t launch_tile_scatter_sort(const Cam& cam, int P, GeomPtrs gp, uint32_t* tile_base, const uint2* ranges,
@@ -805,7 +830,7 @@ hipError_t launch_blend_forward(const Cam& cam, const uint2* ranges, const uint3
                                 float* out_color, float* out_depth, float* out_opacity, float* final_T,
                                 uint32_t* n_contrib, float* out_depth_sq, uint32_t cap, int segments, float* seg_T, float* split_state, uint32_t P, float* zero_fill,
                                 hipStream_t st);
-// the planner's top-down maps (blend_topdown_kernel, blend.hip): geom = records of launch_preprocess_forward_band
+// the planner's top-down maps (blend_topdown_kernel, blend.hip): geom = records of launch_preprocess_forward<CamBand>
 hipError_t launch_blend_topdown(const Cam& cam, const uint2* ranges, const uint32_t* point_list, const float4* geom, float* free_opacity,
                                 uint8_t* free_binary, uint8_t* visible_rgb, uint8_t* visible_binary, uint32_t cap, uint32_t P, hipStream_t st);
 hipError_t launch_blend_backward(const Cam& cam, const uint2* ranges, const uint32_t* point_list, const float4* geom, const float* split_state,

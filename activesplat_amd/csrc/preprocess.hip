@@ -447,25 +447,38 @@ __global__ __launch_bounds__(1024) void scan_block_sums_kernel(uint32_t* __restr
     if (tid == 0) { block_sums[n] = s_carry; *d_total = s_carry; }
 }
 
-hipError_t launch_preprocess_forward(const Cam& cam, int P, const float* means3D, const float* shs,
-                                     const float* colors, const float* opac, const float* scales,
-                                     const float* rots, const float* cov3Dp, int32_t* radii, GeomPtrs gp,
-                                     uint32_t* d_num_rendered, hipStream_t st)
+// Cam: every input mode.  CamDP -- raw-parameter mode with the pose in device memory (tracking): the two ACT kernels.  CamBand -- raw parameters +
+// height band (the planner's top-down maps): preprocess_forward_kernel<0, true>
+template <class CamT>
+hipError_t launch_preprocess_forward(const CamT& cam, int P, const GaussianInputs& in, int32_t* radii, GeomPtrs gp, hipStream_t st)
 {
+    constexpr bool kPlain = std::is_same<CamT, Cam>::value, kDev = std::is_same<CamT, CamDP>::value;
     const int nb = cam.V > 1 ? cam.V * cam.nbv : (P + kBlock - 1) / kBlock;
-    if (cam.act && (cov3Dp || (shs && cam.sh_coeffs != 16))) return hipErrorInvalidValue;      // (api.hip refuses these before)
-    if (nb > 0 && shs && cam.sh_coeffs == 16) {
-        if (cam.act) hipLaunchKernelGGL(preprocess_forward_sh48_kernel<true>, dim3(nb), dim3(kBlock), 0, st, cam, P, means3D, shs, opac, scales, rots, cov3Dp, radii, gp);
-        else hipLaunchKernelGGL(preprocess_forward_sh48_kernel<false>, dim3(nb), dim3(kBlock), 0, st, cam, P, means3D, shs, opac, scales, rots, cov3Dp, radii, gp);
-    } else if (nb > 0 && shs)
-        hipLaunchKernelGGL(preprocess_forward_kernel<1>, dim3(nb), dim3(kBlock), 0, st, cam, P, means3D, shs, colors, opac,
-                           scales, rots, cov3Dp, radii, gp);
-    else if (nb > 0 && cam.act)
-        hipLaunchKernelGGL((preprocess_forward_kernel<0, true>), dim3(nb), dim3(kBlock), 0, st, cam, P, means3D, shs, colors, opac,
-                           scales, rots, cov3Dp, radii, gp);
-    else if (nb > 0)
-        hipLaunchKernelGGL(preprocess_forward_kernel<0>, dim3(nb), dim3(kBlock), 0, st, cam, P, means3D, shs, colors, opac,
-                           scales, rots, cov3Dp, radii, gp);
+    if (cam.act && (in.cov3D || (in.shs && cam.sh_coeffs != 16))) return hipErrorInvalidValue;      // (api.hip refuses these before)
+    if (!kPlain && (!cam.act || cam.V != 1)) return hipErrorInvalidValue;
+    if constexpr (kPlain) {
+        if (nb > 0 && in.shs && cam.sh_coeffs == 16) {
+            if (cam.act) hipLaunchKernelGGL(preprocess_forward_sh48_kernel<true>, dim3(nb), dim3(kBlock), 0, st, cam, P, in.means3D, in.shs, in.opac, in.scales, in.rots, in.cov3D, radii, gp);
+            else hipLaunchKernelGGL(preprocess_forward_sh48_kernel<false>, dim3(nb), dim3(kBlock), 0, st, cam, P, in.means3D, in.shs, in.opac, in.scales, in.rots, in.cov3D, radii, gp);
+        } else if (nb > 0 && in.shs)
+            hipLaunchKernelGGL(preprocess_forward_kernel<1>, dim3(nb), dim3(kBlock), 0, st, cam, P, in.means3D, in.shs, in.colors, in.opac,
+                               in.scales, in.rots, in.cov3D, radii, gp);
+        else if (nb > 0 && cam.act)
+            hipLaunchKernelGGL((preprocess_forward_kernel<0, true>), dim3(nb), dim3(kBlock), 0, st, cam, P, in.means3D, in.shs, in.colors, in.opac,
+                               in.scales, in.rots, in.cov3D, radii, gp);
+        else if (nb > 0)
+            hipLaunchKernelGGL(preprocess_forward_kernel<0>, dim3(nb), dim3(kBlock), 0, st, cam, P, in.means3D, in.shs, in.colors, in.opac,
+                               in.scales, in.rots, in.cov3D, radii, gp);
+    } else if constexpr (kDev) {
+        if (nb > 0 && in.shs)
+            hipLaunchKernelGGL((preprocess_forward_sh48_kernel<true, CamDP>), dim3(nb), dim3(kBlock), 0, st, cam, P, in.means3D, in.shs, in.opac, in.scales, in.rots,
+                               nullptr, radii, gp);
+        else if (nb > 0)
+            hipLaunchKernelGGL((preprocess_forward_kernel<0, true, CamDP>), dim3(nb), dim3(kBlock), 0, st, cam, P, in.means3D, in.shs, in.colors, in.opac,
+                               in.scales, in.rots, nullptr, radii, gp);
+    } else if (nb > 0)
+        hipLaunchKernelGGL((preprocess_forward_kernel<0, true, CamBand>), dim3(nb), dim3(kBlock), 0, st, cam, P, in.means3D, nullptr, in.colors, in.opac,
+                           in.scales, in.rots, nullptr, radii, gp);
     // tile_total must be zero even when the grid above does not cover every tile (tiny P, many tiles)
     if ((size_t)nb * kBlock < (size_t)cam.gx * cam.gy) {
         hipError_t e = hipMemsetAsync(gp.tile_total, 0, (size_t)cam.gx * cam.gy * 4, st);
@@ -473,41 +486,9 @@ hipError_t launch_preprocess_forward(const Cam& cam, int P, const float* means3D
     }
     return hipGetLastError();
 }
-
-// raw-parameter mode with the pose in device memory (tracking): the two ACT kernels above, instantiated with CamDP
-hipError_t launch_preprocess_forward_dev(const CamDP& cam, int P, const float* means3D, const float* shs, const float* colors,
-                                         const float* opac, const float* scales, const float* rots, int32_t* radii, GeomPtrs gp, hipStream_t st)
-{
-    const int nb = (P + kBlock - 1) / kBlock;
-    if (!cam.act || cam.V != 1 || (shs && cam.sh_coeffs != 16)) return hipErrorInvalidValue;
-    if (nb > 0 && shs)
-        hipLaunchKernelGGL((preprocess_forward_sh48_kernel<true, CamDP>), dim3(nb), dim3(kBlock), 0, st, cam, P, means3D, shs, opac, scales, rots,
-                           nullptr, radii, gp);
-    else if (nb > 0)
-        hipLaunchKernelGGL((preprocess_forward_kernel<0, true, CamDP>), dim3(nb), dim3(kBlock), 0, st, cam, P, means3D, shs, colors, opac,
-                           scales, rots, nullptr, radii, gp);
-    if ((size_t)nb * kBlock < (size_t)cam.gx * cam.gy) {
-        hipError_t e = hipMemsetAsync(gp.tile_total, 0, (size_t)cam.gx * cam.gy * 4, st);
-        if (e != hipSuccess) return e;
-    }
-    return hipGetLastError();
-}
-
-// raw parameters + height band (the planner's top-down maps): preprocess_forward_kernel<0, true> instantiated with CamBand
-hipError_t launch_preprocess_forward_band(const CamBand& cam, int P, const float* means3D, const float* colors, const float* opac, const float* scales,
-                                          const float* rots, int32_t* radii, GeomPtrs gp, hipStream_t st)
-{
-    const int nb = (P + kBlock - 1) / kBlock;
-    if (!cam.act || cam.V != 1) return hipErrorInvalidValue;
-    if (nb > 0)
-        hipLaunchKernelGGL((preprocess_forward_kernel<0, true, CamBand>), dim3(nb), dim3(kBlock), 0, st, cam, P, means3D, nullptr, colors, opac,
-                           scales, rots, nullptr, radii, gp);
-    if ((size_t)nb * kBlock < (size_t)cam.gx * cam.gy) {
-        hipError_t e = hipMemsetAsync(gp.tile_total, 0, (size_t)cam.gx * cam.gy * 4, st);
-        if (e != hipSuccess) return e;
-    }
-    return hipGetLastError();
-}
+template hipError_t launch_preprocess_forward<Cam>(const Cam&, int, const GaussianInputs&, int32_t*, GeomPtrs, hipStream_t);
+template hipError_t launch_preprocess_forward<CamDP>(const CamDP&, int, const GaussianInputs&, int32_t*, GeomPtrs, hipStream_t);
+template hipError_t launch_preprocess_forward<CamBand>(const CamBand&, int, const GaussianInputs&, int32_t*, GeomPtrs, hipStream_t);
 
 // per-Gaussian offsets (radix path only): exclusive scan of the per-block tile counts, total -> *d_total
 hipError_t launch_scan_block_sums(int P, GeomPtrs gp, uint32_t* d_total, hipStream_t st)

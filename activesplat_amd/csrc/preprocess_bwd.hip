@@ -441,47 +441,41 @@ pose_reduce:
     if (POSE != 0) pose_grad_block_row(pacc, pose_rows + (size_t)blockIdx.x * kPoseAcc);
 }
 
-hipError_t launch_preprocess_backward(const Cam& cam, int P, const float* means3D, const float* shs,
-                                      const float* scales, const float* rots, const float* cov3Dp,
-                                      const int32_t* radii, const uint32_t* clamped, const float2* sh_jac, const float* grad2d,
-                                      float* dmeans2D, float* dmeans3D, float* dopac, float* dcolors, float* dshs,
-                                      float* dscales, float* drots, float* dcov3D, const float* logit, const FusedAdam* adam, hipStream_t st,
-                                      int pose_mode, float* pose_rows)
+// CamDP (the pose in device memory: tracking) has the pose-only instantiations alone
+template <class CamT>
+hipError_t launch_preprocess_backward(const CamT& cam, int P, const GaussianBackward& g, const PoseRequest& pose, hipStream_t st)
 {
+    constexpr bool kDev = std::is_same<CamT, CamDP>::value;
+    const GaussianInputs& in = g.in;
+    const GaussianGrads& o = g.out;
     const int nb = (P + kBlock - 1) / kBlock;
-    const bool pose_only = pose_mode == 2;
-    if (cam.act && (cov3Dp || !logit || !scales || !rots || (!adam && !pose_only && (!dscales || !drots)) || (shs && cam.sh_coeffs != 16))) return hipErrorInvalidValue;
-    if (adam && (!cam.act || cam.act_accumulate)) return hipErrorInvalidValue;
-    if (pose_mode && (!cam.act || adam || !pose_rows || pose_mode > 2)) return hipErrorInvalidValue;
-    const FusedAdam ad = adam ? *adam : FusedAdam{};
-#define GS_PBWD(...) hipLaunchKernelGGL((preprocess_backward_kernel<__VA_ARGS__>), dim3(nb), dim3(kBlock), 0, st, cam, P, means3D, shs, scales, rots, \
-                                        cov3Dp, radii, clamped, sh_jac, grad2d, dmeans2D, dmeans3D, dopac, dcolors, dshs, dscales, drots, dcov3D, logit, ad, \
-                                        pose_rows)
-    if (nb > 0 && pose_mode) {
-        if (shs) { if (pose_only) GS_PBWD(3, true, false, 2, Cam); else GS_PBWD(3, true, false, 1, Cam); }
-        else { if (pose_only) GS_PBWD(0, true, false, 2, Cam); else GS_PBWD(0, true, false, 1, Cam); }
+    const bool pose_only = pose.grad == POSE_GRAD_ONLY;
+    float* pose_rows = (float*)pose.pose_scratch;
+    if (cam.act && (in.cov3D || !in.opac || !in.scales || !in.rots || (!g.adam && !pose_only && (!o.dscales || !o.drots)) || (in.shs && cam.sh_coeffs != 16)))
+        return hipErrorInvalidValue;
+    if (g.adam && (!cam.act || cam.act_accumulate)) return hipErrorInvalidValue;
+    if (pose.grad && (!cam.act || g.adam || !pose_rows)) return hipErrorInvalidValue;
+    if (kDev && !pose_only) return hipErrorInvalidValue;
+    const FusedAdam ad = g.adam ? *g.adam : FusedAdam{};
+#define GS_PBWD(...) hipLaunchKernelGGL((preprocess_backward_kernel<__VA_ARGS__>), dim3(nb), dim3(kBlock), 0, st, cam, P, in.means3D, in.shs, in.scales, \
+                                        in.rots, in.cov3D, g.radii, g.clamped, g.sh_jac, g.grad2d, o.dmeans2D, o.dmeans3D, o.dopac, o.dcolors, o.dshs, \
+                                        o.dscales, o.drots, o.dcov3D, in.opac, ad, pose_rows)
+    if constexpr (kDev) {
+        if (nb > 0 && in.shs) GS_PBWD(3, true, false, 2, CamDP);
+        else if (nb > 0) GS_PBWD(0, true, false, 2, CamDP);
+    } else {
+        if (nb > 0 && pose.grad) {
+            if (in.shs) { if (pose_only) GS_PBWD(3, true, false, 2, Cam); else GS_PBWD(3, true, false, 1, Cam); }
+            else { if (pose_only) GS_PBWD(0, true, false, 2, Cam); else GS_PBWD(0, true, false, 1, Cam); }
+        }
+        else if (nb > 0 && in.shs && cam.sh_coeffs == 16) { if (g.adam) GS_PBWD(3, true, true); else if (cam.act) GS_PBWD(3, true); else GS_PBWD(3, false); }
+        else if (nb > 0 && in.shs) GS_PBWD(1, false);
+        else if (nb > 0) { if (g.adam) GS_PBWD(0, true, true); else if (cam.act) GS_PBWD(0, true); else GS_PBWD(0, false); }
     }
-    else if (nb > 0 && shs && cam.sh_coeffs == 16) { if (adam) GS_PBWD(3, true, true); else if (cam.act) GS_PBWD(3, true); else GS_PBWD(3, false); }
-    else if (nb > 0 && shs) GS_PBWD(1, false);
-    else if (nb > 0) { if (adam) GS_PBWD(0, true, true); else if (cam.act) GS_PBWD(0, true); else GS_PBWD(0, false); }
 #undef GS_PBWD
     return hipGetLastError();
 }
-
-hipError_t launch_preprocess_backward_pose_dev(const CamDP& cam, int P, const float* means3D, const float* shs, const float* scales,
-                                               const float* rots, const int32_t* radii, const uint32_t* clamped, const float2* sh_jac,
-                                               const float* grad2d, float* dmeans2D, const float* logit, float* pose_rows, hipStream_t st)
-{
-    const int nb = (P + kBlock - 1) / kBlock;
-    if (!cam.act || !logit || !scales || !rots || !pose_rows || (shs && cam.sh_coeffs != 16)) return hipErrorInvalidValue;
-    const FusedAdam ad{};
-#define GS_PBWD_DEV(SH_) hipLaunchKernelGGL((preprocess_backward_kernel<SH_, true, false, 2, CamDP>), dim3(nb), dim3(kBlock), 0, st, cam, P, means3D, \
-                                            shs, scales, rots, nullptr, radii, clamped, sh_jac, grad2d, dmeans2D, nullptr, nullptr, nullptr, \
-                                            nullptr, nullptr, nullptr, nullptr, logit, ad, pose_rows)
-    if (nb > 0 && shs) GS_PBWD_DEV(3);
-    else if (nb > 0) GS_PBWD_DEV(0);
-#undef GS_PBWD_DEV
-    return hipGetLastError();
-}
+template hipError_t launch_preprocess_backward<Cam>(const Cam&, int, const GaussianBackward&, const PoseRequest&, hipStream_t);
+template hipError_t launch_preprocess_backward<CamDP>(const CamDP&, int, const GaussianBackward&, const PoseRequest&, hipStream_t);
 
 }  // namespace gs

@@ -15,9 +15,47 @@ def _declared_symbols():
     return sorted(set(re.findall(r"\b(gs_[a-z_0-9]+)\s*\(", src)))
 
 
+def _prototypes():
+    """symbol -> (return type, [parameter declarations]) of every prototype in include/gsplat_hip.h"""
+    src = open(os.path.join(ROOT, "include", "gsplat_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"(?m)^((?:const\s+)?\w+\s*\**)\s*\b(gs_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", src):
+        params = " ".join(params.split())
+        out[name] = (ret.strip(), [] if params in ("", "void") else [p.strip() for p in params.split(",")])
+    return out
+
+
+def _c_class(decl):
+    """pointer, int32, uint32, int64, uint64, float or double (gs_stream_t is void*; `int` is 32 bits on every platform this builds for)"""
+    if "*" in decl or re.search(r"\bgs_stream_t\b", decl):
+        return "pointer"
+    for c_type, cls in (("uint32_t", "uint32"), ("int32_t", "int32"), ("uint64_t", "uint64"), ("int64_t", "int64"), ("float", "float"),
+                        ("double", "double"), ("int", "int32")):
+        if re.search(r"\b%s\b" % c_type, decl):
+            return cls
+    raise AssertionError(decl)
+
+
+def _ctypes_class(t):
+    import ctypes as C
+    if t in (C.c_void_p, C.c_char_p) or hasattr(t, "contents"):
+        return "pointer"
+    return {C.c_int32: "int32", C.c_uint32: "uint32", C.c_int64: "int64", C.c_uint64: "uint64", C.c_float: "float", C.c_double: "double"}[t]
+
+
 def test_header_and_binding_agree():
+    """Every prototype of the header against the binding's table: the symbols, and per symbol the return type, the number of parameters and
+    every parameter's class -- a miscounted `[vp] * 7` fails here, not on the GPU."""
     from activesplat_amd import _lib
-    assert _declared_symbols() == sorted(_lib.SYMBOLS)
+    protos = _prototypes()
+    assert _declared_symbols() == sorted(protos) == sorted(_lib.SYMBOLS) == sorted(_lib.BINDINGS)
+    for name, (ret, params) in protos.items():
+        restype, argtypes = _lib.BINDINGS[name]
+        assert _ctypes_class(restype) == _c_class(ret), (name, ret)
+        assert len(argtypes) == len(params), (name, len(argtypes), len(params))
+        for i, (t, decl) in enumerate(zip(argtypes, params)):
+            assert _ctypes_class(t) == _c_class(decl), (name, i, decl)
 
 
 def test_hip_library_loads_and_exports_every_symbol():
