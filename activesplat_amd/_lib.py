@@ -62,11 +62,15 @@ class GsHullLayout(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("total_bytes", "cluster_status")]
 
 
+class GsMeshLayout(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("total_bytes", "total", "records", "rects", "tile_count", "tile_offset", "list")]
+
+
 SORT_AUTO, SORT_TILE_LDS, SORT_RADIX = 0, 1, 2
 
 
 #: the GS_ABI_VERSION of include/gsplat_hip.h this binding was written against (checked when a library is bound)
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 vp, i32, u32, i64, u64, f32, f64, cint = C.c_void_p, C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_int
 
@@ -223,6 +227,10 @@ BINDINGS = {
     "gs_keyframe_overlap": (cint, [i32, vp, i32, vp, vp, i32, i32, i32, vp, vp]),
     # (width, height, image, depth, level_value, n_out, h_sizes, color0, depth0, color1, depth1, stream)
     "gs_frame_ingest": (cint, [i32, i32, vp, vp, vp, i32, C.POINTER(i32)] + [vp] * 5),
+    # (num_triangles, width, height, capacity, layout)
+    "gs_mesh_render_layout": (cint, [i32, i32, i32, u32, C.POINTER(GsMeshLayout)]),
+    # (num_vertices, vertices, num_triangles, triangles, vertex_colors, h_intrinsics4, h_w2c12, near_z, width, height, scratch, capacity, depth, tri_id, color, d_counts, stream)
+    "gs_mesh_render": (cint, [i32, vp, i32, vp, vp, C.POINTER(f32), C.POINTER(f32), f32, i32, i32, vp, u32, vp, vp, vp, vp, vp]),
     # (width, height, depth, h_intrinsics4, h_c2w12, points, valid, stream)
     "gs_depth_cloud": (cint, [i32, i32, vp, C.POINTER(f32), C.POINTER(f32), vp, vp, vp]),
     # (n_query, n_points)

@@ -1285,6 +1285,58 @@ int gs_depth_cloud(int32_t width, int32_t height, const float* depth, const floa
     return launched("gs_depth_cloud", "", gs::launch_depth_cloud(width, height, depth, h_intrinsics4, h_c2w12, points, valid, (hipStream_t)stream));
 }
 
+static int mesh_layout_checked(const char* who, int32_t num_triangles, int32_t width, int32_t height, uint32_t capacity, GsMeshLayout& L)
+{
+    if (num_triangles < 0) return fail(GS_EINVAL, "%s: num_triangles must not be negative", who);
+    if (width < 1 || height < 1 || width > 16384 || height > 16384) return fail(GS_EINVAL, "%s: image size out of range (1 <= width, height <= 16384)", who);
+    const uint64_t tiles = tiles_of(width, height);
+    uint64_t at = 0;
+    L.total = at;       at += 256;
+    L.records = at;     at += align_up((uint64_t)num_triangles * 64u);
+    L.rects = at;       at += align_up((uint64_t)num_triangles * 8u);
+    L.tile_count = at;  at += align_up((tiles + 1) * 4u);
+    L.tile_offset = at; at += align_up((tiles + 1) * 4u);
+    L.list = at;        at += align_up((uint64_t)capacity * 4u);
+    L.total_bytes = at;
+    return GS_OK;
+}
+
+int gs_mesh_render_layout(int32_t num_triangles, int32_t width, int32_t height, uint32_t capacity, GsMeshLayout* layout)
+{
+    if (!layout) return fail(GS_EINVAL, "gs_mesh_render_layout: null pointer");
+    return mesh_layout_checked("gs_mesh_render_layout", num_triangles, width, height, capacity, *layout);
+}
+
+int gs_mesh_render(int32_t num_vertices, const float* vertices, int32_t num_triangles, const int32_t* triangles, const uint8_t* vertex_colors,
+                   const float* h_intrinsics4, const float* h_w2c12, float near_z, int32_t width, int32_t height, void* scratch, uint32_t capacity,
+                   float* depth, int32_t* tri_id, uint8_t* color, uint32_t* d_counts, gs_stream_t stream)
+{
+    GsMeshLayout L;
+    const int rc = mesh_layout_checked("gs_mesh_render", num_triangles, width, height, capacity, L);
+    if (rc != GS_OK) return rc;
+    if (num_vertices < 0) return fail(GS_EINVAL, "gs_mesh_render: num_vertices must not be negative");
+    if (!h_intrinsics4 || !h_w2c12 || !scratch || !depth || !tri_id || !color || !d_counts ||
+        (num_triangles > 0 && (!vertices || !triangles || !vertex_colors)) || ((uintptr_t)scratch & 15))
+        return fail(GS_EINVAL, "gs_mesh_render: null pointer (the mesh arrays may be null only with num_triangles == 0) or scratch not 16-byte aligned");
+    // (written so that a NaN fails them)
+    if (!(near_z > 0.0f && near_z <= 3.402823466e38f)) return fail(GS_EINVAL, "gs_mesh_render: near must be positive and finite");
+    for (int i = 0; i < 4; ++i)
+        if (!(fabsf(h_intrinsics4[i]) <= 3.402823466e38f)) return fail(GS_EINVAL, "gs_mesh_render: intrinsics must be finite");
+    if (!(fabsf(h_intrinsics4[0]) > 0.0f) || !(fabsf(h_intrinsics4[1]) > 0.0f)) return fail(GS_EINVAL, "gs_mesh_render: fx and fy must not be zero");
+    gs::MeshArgs a;
+    a.V = num_vertices; a.T = num_triangles;
+    a.vertices = vertices; a.triangles = triangles; a.vertex_colors = vertex_colors;
+    a.fx = h_intrinsics4[0]; a.fy = h_intrinsics4[1]; a.cx = h_intrinsics4[2]; a.cy = h_intrinsics4[3];
+    for (int i = 0; i < 12; ++i) a.w2c[i] = h_w2c12[i];
+    a.near_z = near_z; a.W = width; a.H = height;
+    char* b = (char*)scratch;
+    a.total = (uint64_t*)(b + L.total); a.records = (float4*)(b + L.records); a.rects = (uint2*)(b + L.rects);
+    a.tile_count = (uint32_t*)(b + L.tile_count); a.tile_offset = (uint32_t*)(b + L.tile_offset); a.list = (uint32_t*)(b + L.list);
+    a.capacity = capacity;
+    a.depth = depth; a.tri_id = tri_id; a.color = color; a.d_counts = d_counts;
+    return launched("gs_mesh_render", "", gs::launch_mesh_render(a, (hipStream_t)stream));
+}
+
 static bool nearest_size_ok(int64_t n) { return n >= 0 && n <= ((int64_t)1 << 30); }
 
 uint64_t gs_cloud_nearest_scratch_bytes(int64_t n_query, int64_t n_points)

@@ -459,4 +459,274 @@ hipError_t launch_completion_row(int64_t N, const float* min_d, int64_t P, const
     return hipGetLastError();
 }
 
+// ---- mesh RGB-D sensor (the frame the reference takes from Habitat-sim, src/dataloader/dataloader.py:168-235; the rendering rule:
+// include/gsplat_hip.h, gs_mesh_render) ----------------------------------------------------------------------------------------------
+// A vertex-coloured triangle mesh rendered to planar depth, triangle id and colour by ray casting through per-tile triangle lists:
+//   setup  one thread per triangle: camera-frame vertices, the three edge normals p_i x p_j of the rule (lower vertex index first, separately
+//          rounded operations, negated when the edge runs the other way -- a shared edge gives both triangles the same bits), a 64-byte record,
+//          a conservative rectangle of 16 x 16 tiles (clipped against the near plane where the triangle crosses it) and the tile counts;
+//   scan   one workgroup: exclusive offsets of the tiles, the needed list length D (64 bits) and the longest list;
+//   fill   one thread per triangle: its id into every tile list of its rectangle (nothing when D exceeds the capacity); in setup and fill a
+//          rectangle of more than kMeshSerialTiles tiles is walked by the whole workgroup;
+//   shade  one workgroup per tile, one pixel per thread, a wavefront per 8 x 8 quadrant: the tile's records staged through LDS in chunks of
+//          kMeshChunk, every lane reads each of them once (broadcast reads) and keeps (z, id) of its nearest hit in registers.
+// Integer atomics only (tile counters and list cursors); every cross-workgroup read happens in a later launch.  The order of a tile list depends
+// on scheduling, the image does not: the winner is the smallest z and, among equal z, the lowest triangle index.
+constexpr int kMeshChunk = 256;             // records per pass: 4 x 256 x 16 B = 16 KiB of LDS per workgroup
+
+struct MeshCam { float fx, fy, cx, cy, w2c[12], near_z, clip_z; int W, H, gx, gy; };
+
+// p_i x p_j of the edge (i, j): the lower vertex index first, then negated if that swapped them.  Negation is exact, and so is its passage
+// through the fused multiply-adds of the edge function: the two triangles of an edge get E of the same magnitude from the same operands.
+__device__ __forceinline__ float4 mesh_edge_normal(int i, int j, const float (&pi)[3], const float (&pj)[3], float w)
+{
+#pragma clang fp contract(off)
+    const bool flip = i > j;
+    const float ax = flip ? pj[0] : pi[0], ay = flip ? pj[1] : pi[1], az = flip ? pj[2] : pi[2];
+    const float bx = flip ? pi[0] : pj[0], by = flip ? pi[1] : pj[1], bz = flip ? pi[2] : pj[2];
+    const float x = ay * bz - az * by;
+    const float y = az * bx - ax * bz;
+    const float z = ax * by - ay * bx;
+    return make_float4(flip ? -x : x, flip ? -y : y, flip ? -z : z, w);
+}
+
+__device__ __forceinline__ void mesh_project(const MeshCam& c, float X, float Y, float Z, float (&lo)[2], float (&hi)[2], bool& wild)
+{
+    const float u = c.fx * (X / Z) + c.cx, v = c.fy * (Y / Z) + c.cy;
+    wild = wild || u != u || v != v;
+    lo[0] = fminf(lo[0], u); hi[0] = fmaxf(hi[0], u);
+    lo[1] = fminf(lo[1], v); hi[1] = fmaxf(hi[1], v);
+}
+
+// The tile rectangle that holds every pixel the triangle can hit, or (1, 0) for none.  A hit has z >= near and lies, seen from the pixel centre,
+// inside the projection of the part of the triangle with z >= near; the clip plane is put a little in front of near (clip_z = near (1 - 2^-10)),
+// so that a z the kernel rounds up to near is still inside.  The box is grown by a pixel; where the triangle crosses the plane the cut points are
+// rounded and projected with a small divisor, and the box is grown by a further 1/1024 of the image.  A projection that is not a number lists the
+// triangle in every tile.  Known limit (stated in the header): the pad does not scale with the rounding of the edge vectors, so the tip of a
+// needle whose edges meet well below 1e-3 rad can reach beyond the box.
+__device__ __forceinline__ uint2 mesh_tile_rect(const MeshCam& c, const float (&p)[3][3])
+{
+    const uint2 none = make_uint2(1u, 0u);
+    const bool in[3] = {p[0][2] >= c.clip_z, p[1][2] >= c.clip_z, p[2][2] >= c.clip_z};
+    if (!in[0] && !in[1] && !in[2]) return none;
+    const float inf = __uint_as_float(0x7f800000u);
+    float lo[2] = {inf, inf}, hi[2] = {-inf, -inf};
+    bool wild = false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int l = k == 2 ? 0 : k + 1;
+        if (in[k]) mesh_project(c, p[k][0], p[k][1], p[k][2], lo, hi, wild);
+        if (in[k] != in[l]) {
+            const float s = (c.clip_z - p[k][2]) / (p[l][2] - p[k][2]);
+            mesh_project(c, p[k][0] + s * (p[l][0] - p[k][0]), p[k][1] + s * (p[l][1] - p[k][1]), c.clip_z, lo, hi, wild);
+        }
+    }
+    int x0 = 0, x1 = c.W - 1, y0 = 0, y1 = c.H - 1;
+    if (!wild) {
+        const bool crossing = !(in[0] && in[1] && in[2]);
+        const float pad = crossing ? 1.0f + (float)(c.W > c.H ? c.W : c.H) * (1.0f / 1024.0f) : 1.0f;
+        lo[0] -= pad; lo[1] -= pad; hi[0] += pad; hi[1] += pad;
+        if (hi[0] < 0.0f || hi[1] < 0.0f || lo[0] > (float)(c.W - 1) || lo[1] > (float)(c.H - 1)) return none;
+        x0 = (int)floorf(fmaxf(lo[0], 0.0f)); x1 = (int)ceilf(fminf(hi[0], (float)(c.W - 1)));
+        y0 = (int)floorf(fmaxf(lo[1], 0.0f)); y1 = (int)ceilf(fminf(hi[1], (float)(c.H - 1)));
+    }
+    return make_uint2((uint32_t)(x0 / kTile) | ((uint32_t)(x1 / kTile) << 16), (uint32_t)(y0 / kTile) | ((uint32_t)(y1 / kTile) << 16));
+}
+
+// Every tile of the rectangles of a workgroup's triangles goes to visit(tile, triangle): a rectangle of at most kMeshSerialTiles tiles is walked
+// by its own thread, a larger one (a wall seen from inside the room covers the image) by all threads of the workgroup together -- one thread
+// walking 1 024 tiles, an atomic each, took 0.25 ms at 512 x 512.  Called by every thread of the workgroup (live = false: no triangle).
+constexpr int kMeshSerialTiles = 8;
+
+template <class F>
+__device__ __forceinline__ void mesh_for_tiles(uint2 rect, bool live, int gx, uint2* s_rect, int* s_big, int* s_nbig, F visit)
+{
+    if (threadIdx.x == 0) *s_nbig = 0;
+    s_rect[threadIdx.x] = rect;
+    __syncthreads();
+    const int x0 = rect.x & 0xffff, x1 = rect.x >> 16, y0 = rect.y & 0xffff, y1 = rect.y >> 16;
+    const int w = x1 - x0 + 1, n = live && w > 0 ? w * (y1 - y0 + 1) : 0;
+    if (n > kMeshSerialTiles) s_big[atomicAdd(s_nbig, 1)] = (int)threadIdx.x;
+    else
+        for (int i = 0; i < n; ++i) visit((y0 + i / w) * gx + x0 + i % w, (int)threadIdx.x);
+    __syncthreads();
+    const int nbig = *s_nbig;
+    for (int b = 0; b < nbig; ++b) {
+        const int who = s_big[b];
+        const uint2 r = s_rect[who];
+        const int bx0 = r.x & 0xffff, by0 = r.y & 0xffff, bw = (int)(r.x >> 16) - bx0 + 1, bn = bw * ((int)(r.y >> 16) - by0 + 1);
+        for (int i = threadIdx.x; i < bn; i += kBlock) visit((by0 + i / bw) * gx + bx0 + i % bw, who);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void mesh_setup_kernel(MeshCam c, int T, int V, const float* __restrict__ verts, const int32_t* __restrict__ tris,
+                                                             const uint8_t* __restrict__ cols, float4* __restrict__ records, uint2* __restrict__ rects,
+                                                             uint32_t* __restrict__ tile_count)
+{
+    __shared__ uint2 s_rect[kBlock];
+    __shared__ int s_big[kBlock], s_nbig;
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool live = t < T;
+    const int idx[3] = {live ? tris[3 * t] : -1, live ? tris[3 * t + 1] : -1, live ? tris[3 * t + 2] : -1};
+    uint2 rect = make_uint2(1u, 0u);
+    // (a triangle with an index outside the vertex array is dropped, not read)
+    if ((unsigned)idx[0] < (unsigned)V && (unsigned)idx[1] < (unsigned)V && (unsigned)idx[2] < (unsigned)V) {
+        float p[3][3];
+        uint32_t col[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float* v = verts + 3 * (int64_t)idx[k];
+            const uint8_t* q = cols + 3 * (int64_t)idx[k];
+            const float X = v[0], Y = v[1], Z = v[2];
+            p[k][0] = c.w2c[0] * X + c.w2c[1] * Y + c.w2c[2] * Z + c.w2c[3];
+            p[k][1] = c.w2c[4] * X + c.w2c[5] * Y + c.w2c[6] * Z + c.w2c[7];
+            p[k][2] = c.w2c[8] * X + c.w2c[9] * Y + c.w2c[10] * Z + c.w2c[11];
+            col[k] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
+        }
+        // U = E(b, c) weighs vertex a, V = E(c, a) vertex b, W = E(a, b) vertex c; .w carries that vertex's z
+        records[4 * t + 0] = mesh_edge_normal(idx[1], idx[2], p[1], p[2], p[0][2]);
+        records[4 * t + 1] = mesh_edge_normal(idx[2], idx[0], p[2], p[0], p[1][2]);
+        records[4 * t + 2] = mesh_edge_normal(idx[0], idx[1], p[0], p[1], p[2][2]);
+        records[4 * t + 3] = make_float4(__uint_as_float(col[0]), __uint_as_float(col[1]), __uint_as_float(col[2]), __uint_as_float((uint32_t)t));
+        rect = mesh_tile_rect(c, p);
+    }
+    if (live) rects[t] = rect;
+    mesh_for_tiles(rect, live, c.gx, s_rect, s_big, &s_nbig, [&](int tile, int) { atomicAdd(tile_count + tile, 1u); });
+}
+
+// One workgroup: exclusive offsets of the tile lists (a 64-bit running sum, chunk after chunk), the counters set back to zero for the fill's
+// cursors, the total and the longest list.  Serial in the number of tiles (4 chunks at 512 x 512, 4 096 at 16384 x 16384: a known limit, in the header).
+__global__ __launch_bounds__(kBlock) void mesh_scan_kernel(int tiles, uint32_t* __restrict__ tile_count, uint32_t* __restrict__ tile_offset,
+                                                            uint64_t* __restrict__ total, uint32_t* __restrict__ d_counts)
+{
+    __shared__ uint64_t s_sum[kBlock];
+    __shared__ uint32_t s_max[kBlock];
+    uint64_t carry = 0;
+    uint32_t longest = 0;
+    for (int base = 0; base < tiles; base += kBlock) {
+        const int i = base + threadIdx.x;
+        const uint32_t v = i < tiles ? tile_count[i] : 0u;
+        if (i < tiles) tile_count[i] = 0u;
+        longest = v > longest ? v : longest;
+        s_sum[threadIdx.x] = v;
+        __syncthreads();
+        for (int d = 1; d < kBlock; d <<= 1) {
+            const uint64_t add = (int)threadIdx.x >= d ? s_sum[threadIdx.x - d] : 0;
+            __syncthreads();
+            s_sum[threadIdx.x] += add;
+            __syncthreads();
+        }
+        if (i < tiles) tile_offset[i] = (uint32_t)(carry + s_sum[threadIdx.x] - v);   // (wraps only when D exceeds 2^32: then nothing reads it)
+        carry += s_sum[kBlock - 1];
+        __syncthreads();
+    }
+    s_max[threadIdx.x] = longest;
+    __syncthreads();
+    for (int d = kBlock / 2; d > 0; d >>= 1) {
+        if ((int)threadIdx.x < d) s_max[threadIdx.x] = s_max[threadIdx.x] > s_max[threadIdx.x + d] ? s_max[threadIdx.x] : s_max[threadIdx.x + d];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        tile_offset[tiles] = (uint32_t)carry;
+        *total = carry;
+        d_counts[0] = carry > 0xffffffffull ? 0xffffffffu : (uint32_t)carry;
+        d_counts[1] = s_max[0];
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void mesh_fill_kernel(int T, int gx, const uint2* __restrict__ rects, const uint32_t* __restrict__ tile_offset,
+                                                            uint32_t* __restrict__ cursor, const uint64_t* __restrict__ total, uint32_t capacity,
+                                                            uint32_t* __restrict__ list)
+{
+    __shared__ uint2 s_rect[kBlock];
+    __shared__ int s_big[kBlock], s_nbig;
+    if (*total > (uint64_t)capacity) return;                    // too short a list: nothing is written, the shade clears the image
+    const int64_t first = (int64_t)blockIdx.x * kBlock, t = first + threadIdx.x;
+    const bool live = t < T;
+    mesh_for_tiles(live ? rects[t] : make_uint2(1u, 0u), live, gx, s_rect, s_big, &s_nbig, [&](int tile, int who) {
+        list[tile_offset[tile] + atomicAdd(cursor + tile, 1u)] = (uint32_t)(first + who);  // < tile_offset[tile + 1] <= D <= capacity
+    });
+}
+
+__global__ __launch_bounds__(kBlock) void mesh_shade_kernel(MeshCam c, const float4* __restrict__ records, const uint32_t* __restrict__ tile_offset,
+                                                             const uint32_t* __restrict__ list, const uint64_t* __restrict__ total, uint32_t capacity,
+                                                             float* __restrict__ depth, int32_t* __restrict__ tri_id, uint8_t* __restrict__ color)
+{
+    __shared__ float4 s_rec[4][kMeshChunk];
+    const int tile = blockIdx.y * c.gx + blockIdx.x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int x = blockIdx.x * kTile + (wave & 1) * kQuad + (lane & 7);
+    const int y = blockIdx.y * kTile + (wave >> 1) * kQuad + (lane >> 3);
+    const bool listed = *total <= (uint64_t)capacity;
+    const uint32_t begin = listed ? tile_offset[tile] : 0u, end = listed ? tile_offset[tile + 1] : 0u;
+    const float dx = ((float)x - c.cx) / c.fx, dy = ((float)y - c.cy) / c.fy;
+    float best_z = __uint_as_float(0x7f800000u), best_u = 0.0f, best_v = 0.0f, best_w = 0.0f;
+    uint32_t best_id = 0xffffffffu;
+    for (uint32_t base = begin; base < end; base += kMeshChunk) {
+        const int n = end - base < (uint32_t)kMeshChunk ? (int)(end - base) : kMeshChunk;
+        __syncthreads();                                        // the chunk before this one has been read by every wavefront
+        if ((int)threadIdx.x < n) {
+            const float4* r = records + 4 * (int64_t)list[base + threadIdx.x];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s_rec[j][threadIdx.x] = r[j];
+        }
+        __syncthreads();
+        for (int k = 0; k < n; ++k) {
+            const float4 a = s_rec[0][k], b = s_rec[1][k], w = s_rec[2][k];
+            // E = d . n with d = (dx, dy, 1): explicit fused multiply-adds, so that every edge is evaluated by the same two operations
+            const float U = __fmaf_rn(dx, a.x, __fmaf_rn(dy, a.y, a.z));
+            const float V = __fmaf_rn(dx, b.x, __fmaf_rn(dy, b.y, b.z));
+            const float W = __fmaf_rn(dx, w.x, __fmaf_rn(dy, w.y, w.z));
+            if (!((U >= 0.0f && V >= 0.0f && W >= 0.0f) || (U <= 0.0f && V <= 0.0f && W <= 0.0f))) continue;
+            const float S = U + V + W;
+            if (S == 0.0f) continue;
+            const float z = (U * a.w + V * b.w + W * w.w) / S;
+            const uint32_t id = __float_as_uint(s_rec[3][k].w);
+            if (fabsf(z) <= 3.402823466e38f && z >= c.near_z && (z < best_z || (z == best_z && id < best_id))) {
+                best_z = z; best_id = id; best_u = U; best_v = V; best_w = W;
+            }
+        }
+    }
+    if (x >= c.W || y >= c.H) return;
+    const int64_t pix = (int64_t)y * c.W + x;
+    const bool hit = best_id != 0xffffffffu;
+    uint32_t rgb[3] = {0u, 0u, 0u};
+    if (hit) {
+        const float4 q = records[4 * (int64_t)best_id + 3];
+        const uint32_t ca = __float_as_uint(q.x), cb = __float_as_uint(q.y), cc = __float_as_uint(q.z);
+        const float S = best_u + best_v + best_w;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float va = (float)((ca >> (8 * ch)) & 255u), vb = (float)((cb >> (8 * ch)) & 255u), vc = (float)((cc >> (8 * ch)) & 255u);
+            const float l = floorf((best_u * va + best_v * vb + best_w * vc) / S + 0.5f);
+            rgb[ch] = l < 0.0f ? 0u : (l > 255.0f ? 255u : (uint32_t)l);
+        }
+    }
+    depth[pix] = hit ? best_z : 0.0f;
+    tri_id[pix] = hit ? (int32_t)best_id : -1;
+    color[3 * pix + 0] = (uint8_t)rgb[0]; color[3 * pix + 1] = (uint8_t)rgb[1]; color[3 * pix + 2] = (uint8_t)rgb[2];
+}
+
+hipError_t launch_mesh_render(const MeshArgs& a, hipStream_t st)
+{
+    MeshCam c;
+    c.fx = a.fx; c.fy = a.fy; c.cx = a.cx; c.cy = a.cy; c.near_z = a.near_z; c.clip_z = a.near_z * (1.0f - 1.0f / 1024.0f);
+    for (int i = 0; i < 12; ++i) c.w2c[i] = a.w2c[i];
+    c.W = a.W; c.H = a.H; c.gx = (a.W + kTile - 1) / kTile; c.gy = (a.H + kTile - 1) / kTile;
+    const int tiles = c.gx * c.gy;
+    hipError_t e = hipMemsetAsync(a.tile_count, 0, (size_t)(tiles + 1) * 4, st);
+    if (e != hipSuccess) return e;
+    const unsigned tb = (unsigned)(((int64_t)a.T + kBlock - 1) / kBlock);
+    if (a.T > 0)
+        hipLaunchKernelGGL(mesh_setup_kernel, dim3(tb), dim3(kBlock), 0, st, c, a.T, a.V, a.vertices, a.triangles, a.vertex_colors, a.records, a.rects,
+                           a.tile_count);
+    hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(kBlock), 0, st, tiles, a.tile_count, a.tile_offset, a.total, a.d_counts);
+    if (a.T > 0)
+        hipLaunchKernelGGL(mesh_fill_kernel, dim3(tb), dim3(kBlock), 0, st, a.T, c.gx, (const uint2*)a.rects, (const uint32_t*)a.tile_offset, a.tile_count,
+                           (const uint64_t*)a.total, a.capacity, a.list);
+    hipLaunchKernelGGL(mesh_shade_kernel, dim3(c.gx, c.gy), dim3(kBlock), 0, st, c, (const float4*)a.records, (const uint32_t*)a.tile_offset,
+                       (const uint32_t*)a.list, (const uint64_t*)a.total, a.capacity, a.depth, a.tri_id, a.color);
+    return hipGetLastError();
+}
+
 }  // namespace gs

@@ -945,6 +945,23 @@ hipError_t launch_cloud_nearest(int64_t Q, const float* query, const uint8_t* qv
 uint64_t completion_row_scratch_bytes();
 hipError_t launch_completion_row(int64_t N, const float* min_d, int64_t P, const float* acc_d, const uint8_t* acc_valid, double path_length,
                                  double* row, void* scratch, hipStream_t st);
+// the mesh RGB-D sensor (grow.hip; the rendering rule: include/gsplat_hip.h, gs_mesh_render).  Scratch pointers as carved by the layout call.
+struct MeshArgs {
+    int V, T;                                                          // vertices, triangles
+    const float* vertices;                                             // [V, 3] world frame
+    const int32_t* triangles;                                          // [T, 3]
+    const uint8_t* vertex_colors;                                      // [V, 3]
+    float fx, fy, cx, cy, w2c[12], near_z;
+    int W, H;
+    uint64_t* total;                                                   // scratch: the needed list length, 64 bits
+    float4* records;                                                   // scratch: [T] x 4
+    uint2* rects;                                                      // scratch: [T] tile rectangles (x0 | x1 << 16, y0 | y1 << 16; x0 > x1: none)
+    uint32_t *tile_count, *tile_offset, *list;                         // scratch: [tiles + 1], [tiles + 1], [capacity]
+    uint32_t capacity;
+    float* depth; int32_t* tri_id; uint8_t* color;                     // [H, W], [H, W], [H, W, 3]
+    uint32_t* d_counts;                                                // [2]: needed list length (saturating), longest tile list
+};
+hipError_t launch_mesh_render(const MeshArgs& a, hipStream_t st);
 // map-quality evaluation of one frame (loss.hip; the rules: include/gsplat_hip.h, gs_eval_frame).  One plan for the layout call, the launches and
 // the finish kernel: level sizes, workgroup records per pass, offsets of the records (in doubles) and of the pooled images (in bytes)
 struct EvalPlan {

@@ -14,7 +14,8 @@ all cores to finish.  Here the same answer is three library calls per frame (inc
 
 The back-projection rule restates what Open3D's create_from_rgbd_image documents; it was NOT run against Open3D (not installed, not a
 dependency).  Frames: points, samples and poses must share one frame.  `SplatMapper.judge` feeds poses relative to frame 0's camera, so its
-samples must be given in that frame; transforming a mesh into it is the caller's work.
+samples must be given in that frame; transforming a mesh into it is the caller's work (sensor.MeshScene.transformed and sensor.sample_surface do
+it for a mesh that is on the device).
 
 There is no CPU fallback.
 """

@@ -403,6 +403,15 @@ class SplatMapper:
                                                                                    self.device)
         return self.run(frame)
 
+    def run_sensor(self, sensor, X_WV, frame_id, quat, position):
+        """run_raw with the frame produced on the device: `sensor` (sensor.MeshSensor) renders the mesh at the pose X_WV -- the pose run_raw
+        takes --, gs_frame_ingest resizes its device tensors to the mapping and the densification resolution, then run().  No pixel goes to
+        the host; the sensor's two tile-list counters do (sensor.render_mesh).  The frame is on the device already, so this ALWAYS takes the
+        device ingest (ingest.FrameIngest, the pose through its pinned slot), whatever cfg["device_ingest"] says: that key chooses run_raw's path only."""
+        image, depth = sensor.frame(X_WV)
+        gt_w2c, self.first_abs_pose = FR.gt_w2c_from_pose(X_WV, self.first_abs_pose)
+        return self.run(self._ingest_raw(image, depth, gt_w2c, frame_id, quat, position))
+
     def _ingest_raw(self, image, depth, gt_w2c, frame_id, quat, position):
         """run_raw's frame dict with device_ingest: one upload and one launch for both resolutions (ingest.FrameIngest)."""
         from . import ingest as IN

@@ -181,7 +181,7 @@ const char* gs_version(void);
 /* Integer version of THIS binary interface: bumped whenever an entry point's argument list or a published record layout changes (e.g.
  * the seed argument of gs_densify_children, the 40-byte SH Jacobian record).  A host binding compares it with the GS_ABI_VERSION it was
  * written against before the first call, so that a stale prebuilt library fails at load time instead of misreading its arguments. */
-#define GS_ABI_VERSION 20
+#define GS_ABI_VERSION 21
 int32_t gs_abi_version(void);
 
 /* Optional per-stage timing (hipEvents recorded on the caller's stream around each stage's launches).
@@ -718,6 +718,58 @@ int gs_keyframe_overlap(int32_t n_pts, const float* pts_world, int32_t n_keyfram
  * Supported: 1 <= width, height, W_k, H_k <= 16384, n_out in {1, 2}; anything else, or a null pointer, is GS_EINVAL before any launch. */
 int gs_frame_ingest(int32_t width, int32_t height, const uint8_t* image, const float* depth, const float* level_value, int32_t n_out,
                     const int32_t* h_sizes, float* color0, float* depth0, float* color1, float* depth1, gs_stream_t stream);
+
+/* ---- Mesh RGB-D sensor (the frame the reference takes from Habitat-sim: colour, planar depth, src/dataloader/dataloader.py:168-235) ----
+ * A vertex-coloured triangle mesh rendered to the frame gs_frame_ingest takes, by ray casting on the compute path (no graphics pipeline).
+ * vertices fp32 [num_vertices, 3] world frame, triangles int32 [num_triangles, 3], vertex_colors uint8 [num_vertices, 3]: DEVICE.
+ * h_intrinsics4 = HOST {fx, fy, cx, cy}; h_w2c12 = HOST row-major 3x4 [R|t] world-to-camera, the inverse of the c2w gs_depth_cloud takes
+ * (camera: x right, y down, z forward).  THE RULE, all fp32:
+ *   camera-frame vertex   p = R v + t
+ *   ray of pixel (x, y)   d = ((x - cx) / fx, (y - cy) / fy, 1): d.z = 1, so a hit's ray parameter IS its planar depth (what Habitat's depth
+ *                         sensor returns)
+ *   edge function         for vertex indices i < j: E(i, j) = d . (p_i x p_j); for i > j: E(i, j) = -E(j, i), evaluated with the lower index
+ *                         first and negated.  A shared edge then gives both of its triangles the same magnitude from the same operands, which
+ *                         keeps a closed mesh watertight in fp32.  (The kernels form p_i x p_j once per triangle with separately rounded
+ *                         operations and negate the vector; negation is exact and passes unchanged through the two fused multiply-adds
+ *                         fma(dx, n.x, fma(dy, n.y, n.z)) that evaluate every edge.)
+ *   hit test              triangle (a, b, c): U = E(b, c), V = E(c, a), W = E(a, b), S = (U + V) + W.  Hit iff (U, V, W all >= 0 or all <= 0)
+ *                         and S != 0 and z = (U z_a + V z_b + W z_c) / S is finite and z >= near.  TWO-SIDED: no back-face culling (whether
+ *                         Habitat's renderer culls back faces was not established).  A degenerate triangle has S = 0 and never hits; so does one
+ *                         with an index outside 0 .. num_vertices - 1, which is dropped without being read.
+ *   winner                the smallest z; among equal z the lowest triangle index: the image does not depend on the order of any list
+ *   outputs               depth fp32 [height * width], 0 where nothing is hit; tri_id int32 [height * width], -1 where nothing is hit; color uint8
+ *                         [height * width * 3] interleaved, clamp(floor((U C_a + V C_b + W C_c) / S + 0.5), 0, 255), 0 where nothing is hit.
+ * Not modelled: textures, sensor noise, a far plane.
+ * Four launches on `stream`: per-triangle setup (edge vectors, a conservative rectangle of 16 x 16 tiles -- clipped against z = near where the
+ * triangle crosses it -- and the tile counts), a scan over the tiles, the fill of the tile lists, and one workgroup per tile that casts its 256
+ * rays.  Integer atomics only; nothing a workgroup reads was written by another workgroup of the same launch; two calls on the same inputs give
+ * the same bits.  The total length D of the tile lists depends on the data: the caller provides room for `capacity` entries;
+ * d_counts[0] (DEVICE) receives D (0xffffffff when it does not fit 32 bits) and d_counts[1] the longest tile list.  When D > capacity nothing is
+ * written to the lists and the three outputs are CLEARED (0, -1, 0): read d_counts[0] and call again with capacity >= D.
+ * KNOWN LIMITS.  (1) Needle triangles.  A triangle is tested only by the tiles of its rectangle: the projection of its (clipped) vertices grown by
+ * one pixel (by a further 1/1024 of the image where it crosses the near plane).  The hit test uses the fp32-rounded edge vectors; where two
+ * edges meet at an angle well below about 1e-3 rad the two rounded edge lines can cross more than a pixel beyond the true vertex, and a pixel
+ * there that a brute-force evaluation of the rule over all triangles would hit is not tested: the tip of such a needle can lose pixels.
+ * Triangles with angles above that are covered with room to spare.  (2) Large images.  The scan over the tiles is ONE workgroup that walks them
+ * 256 at a time (4 chunks at 512 x 512); at the largest permitted image, 16384 x 16384, that is 4096 serial chunks of about 18 barriers each,
+ * i.e. milliseconds: correct, but not tuned for images of that size.
+ * scratch: DEVICE, gs_mesh_render_layout(num_triangles, width, height, capacity).total_bytes bytes, 16-byte aligned; the offsets are published
+ * for tests.  Refused with GS_EINVAL before any launch: a null pointer (the three mesh arrays may be null when num_triangles is 0), width or
+ * height outside 1 .. 16384, num_triangles < 0, num_vertices < 0, near not positive and finite, an intrinsic that is not finite, fx or fy zero.
+ * num_triangles == 0 is valid and clears the outputs. */
+typedef struct GsMeshLayout {
+    uint64_t total_bytes;
+    uint64_t total;         /* uint64: D */
+    uint64_t records;       /* num_triangles x 64 bytes: three (edge vector, z of the opposite vertex), then three packed colours and the index */
+    uint64_t rects;         /* num_triangles x 2 uint32: tile rectangle x0 | x1 << 16, y0 | y1 << 16 (x0 > x1: no tile) */
+    uint64_t tile_count;    /* (tiles + 1) uint32 */
+    uint64_t tile_offset;   /* (tiles + 1) uint32: exclusive offsets, [tiles] = D */
+    uint64_t list;          /* capacity uint32: triangle indices, tile after tile */
+} GsMeshLayout;
+int gs_mesh_render_layout(int32_t num_triangles, int32_t width, int32_t height, uint32_t capacity, GsMeshLayout* layout);
+int gs_mesh_render(int32_t num_vertices, const float* vertices, int32_t num_triangles, const int32_t* triangles, const uint8_t* vertex_colors,
+                   const float* h_intrinsics4, const float* h_w2c12, float near_z, int32_t width, int32_t height, void* scratch, uint32_t capacity,
+                   float* depth, int32_t* tri_id, uint8_t* color, uint32_t* d_counts, gs_stream_t stream);
 
 /* ---- Completion / accuracy judge (ActiveSplat's own figure: scripts/judges/eval_actions.py:33-40,139-152) ----
  * Per frame the reference back-projects the sensor depth (rgbd_to_pointcloud, src/utils/gui_utils.py:96-125, called with depth scale 1000 and
