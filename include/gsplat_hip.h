@@ -86,7 +86,8 @@ typedef struct GsGeomLayout {
     uint64_t block_sums;    /* uint32 [ceil(P/256)+1] exclusive scan of per-block tile counts */
     uint64_t clamped;       /* uint8  [P][4]: SH colour clamp flags (r,g,b,pad) */
     uint64_t tile_total;    /* uint32 [tiles]: instances per tile */
-    uint64_t tile_base;     /* uint32 [ceil(P/4096)][tiles]: slice reserved by each binning workgroup */
+    uint64_t tile_base;     /* uint32 [ceil(P/2048)][tiles]: slice reserved by each binning workgroup (one row per 2048 Gaussians is written; the
+                             * region holds ceil(P/1024) rows; images of more than 8192 tiles: one word) */
     uint64_t sh_jac;        /* float [P][10]: 3x3 d(rgb)/d(view direction) of SH inputs + the colour clamp flags in the tenth word, written when
                              * want_backward (the `clamped` array is then not written) */
     uint64_t depth_bits;    /* uint32 [P]: float bits of the view-space depth (binning key) */
@@ -97,8 +98,9 @@ typedef struct GsImageLayout {
     uint64_t ranges;        /* uint32 [tiles][2] : [start,end) into point_list */
     uint64_t final_T;       /* float  [H*W] */
     uint64_t n_contrib;     /* uint32 [H*W] : 1-based position in the tile list of the last contributor */
-    uint64_t split_state;   /* images of at most 256 tiles: float [12][5][H*W] + [4][H*W] + 1 word, per-pixel running state at the list
-                             * positions 128 * 2^k, where the backward may cut a quadrant's walk in two */
+    uint64_t split_state;   /* images of at most 256 tiles: float [21][5][H*W] + [4][H*W] + 1 word, per-pixel running state at the recorded list
+                             * positions (every 256th up to 4096, then the powers of two up to 131072), where the backward may cut a
+                             * quadrant's walk; larger images: the hand-over state of the chained backward walks, the whole region */
 } GsImageLayout;
 
 #define GS_SORT_AUTO 0

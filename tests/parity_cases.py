@@ -1378,12 +1378,11 @@ def close_frac(a, b, rtol, atol):
     return util.close_frac(a, b, rtol, atol)
 
 
-def check_optimistic_launch(device):
+def check_optimistic_launch(device, N=20000):
     """The binning workspace of frame k is sized from frame k-1 and the render enqueued before the counters are read:
     a hit (same view again) and a miss (a view with 10x the instances, re-launched with exact sizes after the
     capacity-clamped first attempt) must both reproduce the exactly-sized launch bit for bit."""
     from activesplat_amd import GaussianRasterizer, rasterizer as R
-    N = 20000
     rs_far, rv = util.scene(N, 96, 80, seed=11, device=device, w2c=util.pose(0.0, (0.0, 0.0, -3.3)))     # most of the scene behind the camera
     rs_near, _ = util.scene(N, 96, 80, seed=11, device=device)
     m2d = torch.zeros(N, 3, device=device)
