@@ -70,7 +70,7 @@ SORT_AUTO, SORT_TILE_LDS, SORT_RADIX = 0, 1, 2
 
 
 #: the GS_ABI_VERSION of include/gsplat_hip.h this binding was written against (checked when a library is bound)
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 vp, i32, u32, i64, u64, f32, f64, cint = C.c_void_p, C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_int
 
@@ -97,6 +97,8 @@ BINDINGS = {
     "gs_set_backward_chain_tickets": (cint, [i32]),
     # (polls)
     "gs_set_backward_chain_polls": (cint, [i32]),
+    # (mode, param)
+    "gs_set_forward_priority": (cint, [i32, f32]),
     # (host_word)
     "gs_async_status_word": (cint, [C.POINTER(C.POINTER(u32))]),
     # ()

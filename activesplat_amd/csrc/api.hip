@@ -202,6 +202,16 @@ int gs_set_backward_chain_polls(int32_t polls)
     return GS_OK;
 }
 
+int gs_set_forward_priority(int32_t mode, float param)
+{
+    if (mode > gs::kFwdPrioChunk) return fail(GS_EINVAL, "gs_set_forward_priority: mode out of range");
+    if (mode == gs::kFwdPrioT && param >= 1.0f) return fail(GS_EINVAL, "gs_set_forward_priority: a transmittance threshold lies below 1");
+    if (mode < 0) { mode = gs::kFwdPrioDefault; param = gs::kFwdPrioDefaultParam; }      // negative: what the library ships with
+    gs::g_fwd_prio_param = param > 0.0f ? param : 0.0f;         // (0: the predictor's default, chosen at the launch)
+    gs::g_fwd_prio = mode;
+    return GS_OK;
+}
+
 int gs_async_status_word(uint32_t** host_word)
 {
     // one host-mapped word per process (portable: every device can raise it); plain host reads see it once the raising kernel has ended

@@ -132,7 +132,17 @@ __device__ __forceinline__ unsigned scan_blocks(const float4& q0, const float4& 
     return (__builtin_amdgcn_inverse_ballot_w64(b0) ? 1u : 0u) | (__builtin_amdgcn_inverse_ballot_w64(b1) ? 2u : 0u) |
            (__builtin_amdgcn_inverse_ballot_w64(b2) ? 4u : 0u) | (__builtin_amdgcn_inverse_ballot_w64(b3) ? 8u : 0u);
 }
-constexpr int kRoundSlack = 4;         // a round is closed after a chunk of n hit records if cnt + n + this many would not fit in the 64 staging slots
+// Issue priority of the calling wavefront (0 ... 3; the SIMD's arbiter picks by priority, then age).  s_setprio takes an immediate and ignores
+// EXEC, so `level` is made a scalar first and the ladder is scalar compares and branches around four constants: call it outside divergent code only.
+__device__ __forceinline__ void set_wave_priority(int level)
+{
+    level = __builtin_amdgcn_readfirstlane(level);
+    if (level >= 3) __builtin_amdgcn_s_setprio(3);
+    else if (level == 2) __builtin_amdgcn_s_setprio(2);
+    else if (level == 1) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(0);
+}
+constexpr int kRoundSlack = 4;        // a round is closed after a chunk of n hit records if cnt + n + this many would not fit in the 64 staging slots
 
 // ---------------------------------------------------------------------------------------------------
 // Forward: the quadrant's 64 lanes form NS streams of 64/NS lanes (NS = 4: 4x4 pixel blocks,
@@ -254,6 +264,37 @@ __global__ __launch_bounds__(NW * kWave) void blend_forward_streams_kernel(
                 for (int f = 0; f < kFillPerStep; f++)
                     if (zf < zf_end) { zero_fill[zf] = make_float4(0.f, 0.f, 0.f, 0.f); zf += NW * kWave; }
             }
+            // issue priority by the walk's estimated REMAINING length (cam.fwd_prio, gs_set_forward_priority; SEG = 0): the walkers of a SIMD are
+            // all resident from the start and end by saturation at very different depths; one left alone cannot fill its SIMD, so the one that
+            // will run longest should take the issue slots while the others are still there to use the leftovers.  The estimate is wave-uniform
+            // (ballots of per-lane compares against scalar thresholds); it steers the arbiter only: no arithmetic statement depends on it.
+            if (SEG == 0 && cam.fwd_prio != kFwdPrioOff) {
+                const float chunks = (float)((base - first) >> 6);                  // chunks walked so far
+                const float p = cam.fwd_prio_param;
+                int level;
+                if (cam.fwd_prio == kFwdPrioChunk) {                                // control: the position in the list alone
+                    level = (chunks >= p ? 1 : 0) + (chunks >= 2.0f * p ? 1 : 0) + (chunks >= 3.0f * p ? 1 : 0);
+                } else {
+                    // the largest transmittance among the pixels still blending, against three thresholds:
+                    //   kFwdPrioT     : p, p^2, p^3 -- a quadrant whose stubborn pixel is still transparent has far to go
+                    //   kFwdPrioDecay : that pixel went from 1 to T in `chunks` chunks; at the same rate it needs log(T / kTmin) / (-log(T) / chunks)
+                    //                   more: more than R chunks  <=>  T > kTmin ^ (chunks / (chunks + R)), for R = p, 2 p, 4 p
+                    float t1 = p, t2 = p * p, t3 = p * p * p;
+                    if (cam.fwd_prio == kFwdPrioDecay) {
+                        constexpr float kLog2Tmin = -13.287712f;                    // log2(kTmin)
+                        t1 = __builtin_amdgcn_exp2f(kLog2Tmin * chunks * __builtin_amdgcn_rcpf(chunks + p));
+                        t2 = __builtin_amdgcn_exp2f(kLog2Tmin * chunks * __builtin_amdgcn_rcpf(chunks + 2.0f * p));
+                        t3 = __builtin_amdgcn_exp2f(kLog2Tmin * chunks * __builtin_amdgcn_rcpf(chunks + 4.0f * p));
+                    }
+                    level = (__ballot(!done && T > t1) != 0ull ? 1 : 0) + (__ballot(!done && T > t2) != 0ull ? 1 : 0) +
+                            (__ballot(!done && T > t3) != 0ull ? 1 : 0);
+                    // ... and no walk outlasts its list: the same three levels from the chunks the list still holds (this is what decides on
+                    // scenes whose lists end before most pixels saturate)
+                    const uint32_t left = (n - base) >> 6;
+                    level = min(level, (left > kFwdPrioListChunks ? 1 : 0) + (left > 2u * kFwdPrioListChunks ? 1 : 0) + (left > 3u * kFwdPrioListChunks ? 1 : 0));
+                }
+                set_wave_priority(level);
+            }
             const float4 q0 = r0, q1 = r1, q2 = r2;
             const uint32_t id_cur = id_next;
             id_next = id_next2;
@@ -324,6 +365,7 @@ __global__ __launch_bounds__(NW * kWave) void blend_forward_streams_kernel(
             if (SEG != 1 && __all(done)) break;
             if (SEG == 1 && __all(!inside || T < kTmin)) break;      // every pixel is below the stop threshold: the rest cannot matter
         }
+        if (SEG == 0 && cam.fwd_prio != kFwdPrioOff) __builtin_amdgcn_s_setprio(0);      // (the walk is over: the stores that follow wait for nobody)
     }
     GS_FILL_REST();
     if (SEG == 1) {
@@ -1220,6 +1262,9 @@ std::atomic<int> g_chain_min_tiles{kChainMinTiles};
 // chain order is the workgroup index, which the dispatcher hands out in order.  Either way a wait is bounded and a timeout is reported.
 std::atomic<int> g_chain_tickets{0};
 std::atomic<int> g_chain_polls{kChainPollsDefault};      // bound of a piece's wait for the piece in front (gs_set_backward_chain_polls: tests)
+// issue priority of the streams forward's walkers by their estimated remaining walk (gs_set_forward_priority; profiles/forward_priority.txt)
+std::atomic<int> g_fwd_prio{kFwdPrioDefault};
+std::atomic<float> g_fwd_prio_param{kFwdPrioDefaultParam};
 uint32_t* g_async_status_dev = nullptr;      // device view of the host-mapped status word (api.hip: gs_async_status_word)
 uint32_t* g_chain_fail_dev = nullptr;        // its sticky device-memory twin (Cam::chain_fail)
 int g_chain_fail_device = -1;
@@ -1243,6 +1288,9 @@ hipError_t launch_blend_forward(const Cam& cam_in, const uint2* ranges, const ui
     // workspace holds them -- more than kFewTiles tiles -- whatever gs_set_backward_chain says at this moment: the backward takes its own
     // decision from the knob when IT is launched, and must find zeroed flags even if the knob changed in between)
     cam.chain = (cam.V == 1 && split_state && cam.gx * cam.gy > kFewTiles) ? kChainPieces : 0;
+    cam.fwd_prio = g_fwd_prio.load(std::memory_order_relaxed);
+    cam.fwd_prio_param = g_fwd_prio_param.load(std::memory_order_relaxed);
+    if (!(cam.fwd_prio_param > 0.0f)) cam.fwd_prio_param = fwd_prio_default_param(cam.fwd_prio);
     const int nb = ((cam.gx * cam.gy + 7) >> 3) << 3;
 #define GS_FWD(DSQ, SEG, GRID)                                                                                                     \
     hipLaunchKernelGGL((blend_forward_streams_kernel<DSQ, kFwdStreams, SEG, 4>), GRID, dim3(kBlock), 0, st, cam, ranges, point_list, geom, \

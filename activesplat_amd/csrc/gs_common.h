@@ -40,6 +40,10 @@ struct Cam {
     const float* campos;
     // forward blend, images of few tiles: the producer / consumer kernel (set by the blend launchers)
     int half;
+    // forward blend, streams kernel: issue priority of a walker by its estimated remaining walk (kFwdPrio*, gs_set_forward_priority; set by
+    // the forward launcher; changes the order in which the wavefronts of a SIMD issue, never a result)
+    int fwd_prio;
+    float fwd_prio_param;
     // backward blend, images of few tiles: every tile list is walked in `split` (2 or 3) segments by as many wavefronts per quadrant; the front
     // one starts from the per-pixel state the forward left at the boundary (set by the blend launchers)
     int split;
@@ -762,6 +766,18 @@ extern std::atomic<int> g_chain_pieces;
 extern std::atomic<int> g_chain_min_tiles;
 extern std::atomic<int> g_chain_tickets;
 extern std::atomic<int> g_chain_polls;
+// forward blend issue priority (Cam::fwd_prio): the predictor of a walk's remaining length, and its parameter (<= 0: the predictor's default)
+enum { kFwdPrioOff = 0, kFwdPrioT = 1, kFwdPrioDecay = 2, kFwdPrioChunk = 3 };
+constexpr int kFwdPrioDefault = kFwdPrioT;                // what the library starts with (and a negative mode restores)
+constexpr float kFwdPrioDefaultParam = 0.0f;
+constexpr uint32_t kFwdPrioListChunks = 3;                // kFwdPrioT / kFwdPrioDecay: one level less below 9, 6, 3 chunks of list left
+extern std::atomic<int> g_fwd_prio;
+extern std::atomic<float> g_fwd_prio_param;
+inline float fwd_prio_default_param(int mode)
+{
+    // kFwdPrioT: transmittance thresholds p, p^2, p^3; kFwdPrioDecay: more than p, 2 p, 4 p chunks to go; kFwdPrioChunk: chunk index p, 2 p, 3 p
+    return mode == kFwdPrioT ? 0.1f : mode == kFwdPrioDecay ? 3.0f : 6.0f;
+}
 extern uint32_t* g_async_status_dev;
 extern uint32_t* g_chain_fail_dev;      // device-memory twin of the status word (Cam::chain_fail); null until gs_async_status_word has been called
 extern int g_chain_fail_device;         // the device it lives on

@@ -21,7 +21,7 @@
  *   - return value 0 = success, otherwise a GS_E* code; gs_last_error() gives the message;
  *   - no torch types.  Process-wide state: the last-error string (thread-local), the host-mapped status word (gs_async_status_word) and the
  *     development knobs gs_set_sort_path, gs_set_forward_segments, gs_set_half_quadrants, gs_set_backward_chain[_tickets|_polls],
- *     gs_set_backward_segments (defaults: automatic path choice, segments on, few-tile kernels up to 256 tiles, three chained pieces above 768 tiles).
+ *     gs_set_backward_segments, gs_set_forward_priority (defaults: automatic path choice, segments on, few-tile kernels up to 256 tiles, three chained pieces above 768 tiles).
  *     The knobs are atomics that every launch reads ONCE: set from another thread (the reference runs a visualiser thread next to the mapper) a
  *     new value takes effect at a launch boundary of the other threads, never inside one launch's decisions; a forward and the backward that
  *     consumes its state tolerate a change in between (the forward clears the hand-over flags and records its "recorded" word whatever the
@@ -165,6 +165,21 @@ int gs_set_backward_chain(int32_t pieces, int32_t min_tiles);
  * synchronises the device and clears that word: steps run again.  Step counters the host advanced for skipped steps stay advanced. */
 int gs_set_backward_chain_tickets(int32_t on);
 int gs_set_backward_chain_polls(int32_t polls);
+/* Issue priority of the forward blend's quadrant walkers (images of more than 256 tiles, unsegmented lists).  All walkers of a frame are resident
+ * from the start and end by saturation at very different list depths; once per 64-entry chunk a walker estimates how far it still has to go and
+ * sets its wavefront's priority (0 ... 3) from that, so that the longest walk of a SIMD runs at its own pace while the others fill the issue slots
+ * it leaves.  The library starts in mode 1 with its default parameter (measurements: profiles/forward_priority.txt).
+ *      mode 0: off (every wavefront at priority 0);
+ *      1: by the largest transmittance T among the quadrant's pixels that still blend: one level for each of T > param, param^2, param^3
+ *         (param in (0, 1); default 0.1);
+ *      2: by the chunks still to go if that pixel keeps the decay rate it has shown so far: one level for each of more than param, 2 param,
+ *         4 param chunks (default 3);
+ *      3: by the chunk index alone (a control without information about the walk): one level for each of param, 2 param, 3 param chunks walked
+ *         (default 6).
+ * Modes 1 and 2 never rate a walk longer than its list: one level less below 9, 6 and 3 chunks of list left.  param <= 0 selects the mode's
+ * default; a negative mode restores the mode and parameter the library starts with.  Only the order in which wavefronts issue changes: every
+ * output is bit-identical in all modes. */
+int gs_set_forward_priority(int32_t mode, float param);
 int gs_async_status_word(uint32_t** host_word);
 int gs_async_status_clear(void);
 /* Introspection of the few-tile backward's cuts: the recorded list position nearest to `target` (0: none below it) and its level (-1: none) --
@@ -183,7 +198,7 @@ const char* gs_version(void);
 /* Integer version of THIS binary interface: bumped whenever an entry point's argument list or a published record layout changes (e.g.
  * the seed argument of gs_densify_children, the 40-byte SH Jacobian record).  A host binding compares it with the GS_ABI_VERSION it was
  * written against before the first call, so that a stale prebuilt library fails at load time instead of misreading its arguments. */
-#define GS_ABI_VERSION 21
+#define GS_ABI_VERSION 22
 int32_t gs_abi_version(void);
 
 /* Optional per-stage timing (hipEvents recorded on the caller's stream around each stage's launches).

@@ -51,5 +51,5 @@ PY
 cd $R/activesplat_amd/csrc
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -munsafe-fp-atomics -fno-slp-vectorize -c blend_tracef_tmp.hip -o $T/blend_tracef.o
 rm -f blend_tracef_tmp.hip
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libgsplat_hip_tracef.so api.o preprocess.o preprocess_bwd.o binning.o tilebin.o $T/blend_tracef.o adam.o compact.o loss.o activate.o grow.o stats.o densify.o rows.o sort_rocprim.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libgsplat_hip_tracef.so api.o preprocess.o preprocess_bwd.o binning.o tilebin.o $T/blend_tracef.o adam.o compact.o loss.o activate.o grow.o stats.o densify.o rows.o sort_radix.o
 echo built activesplat_amd/libgsplat_hip_tracef.so

@@ -29,6 +29,9 @@ def run(N=500_000, W=640, H=480, steps=int(os.environ.get("STEPS", 30)), warmup=
         lib.gs_set_backward_chain_tickets(int(os.environ["TICKETS"]))
     if os.environ.get("SEGS"):                              # gs_set_backward_segments: list segments per quadrant in the few-tile backward
         lib.gs_set_backward_segments(int(os.environ["SEGS"]))
+    if os.environ.get("FWD_PRIO"):                          # gs_set_forward_priority: "mode" or "mode:param" (0 = off; A/B of the forward blend's issue priority)
+        mode, _, param = os.environ["FWD_PRIO"].partition(":")
+        lib.gs_set_forward_priority(int(mode), float(param or 0))
     if os.environ.get("HALF"):                              # gs_set_half_quadrants: images of at most this many tiles use half-quadrant wavefronts
         lib.gs_set_half_quadrants(int(os.environ["HALF"]))
 
