@@ -66,44 +66,71 @@ __device__ __forceinline__ bool tile_ctx_nw(const Cam& cam, int wave, int lane, 
     return tile_ctx_at<NW>(cam, blockIdx.x, wave, lane, c, segments);
 }
 
-// does the record's alpha-visible box overlap the 8x8 quadrant at pixel origin (qx0,qy0)?
-__device__ __forceinline__ bool quadrant_hit(const float4& q0, const float4& q2, float qx0, float qy0)
+// ---- the walker steps the four kernels below share: one copy each; every kernel keeps its own loop structure and pipelining ----
+// (All of them take values and return values.  A running state handed to a step by reference stays in memory until the step is inlined, and is
+// then scalarised differently than a local -- a bool as a byte phi, a float4 as a vector: other registers, other occupancy.)
+
+// lane -> (stream, pixel): the 16 lanes of stream sid (one DPP row) own the 4x4 block (sid & 1, sid >> 1) of the quadrant at pixel origin
+// (qx0, qy0), lane l of the stream its pixel (l & 3, l >> 2)
+struct StreamPixel { int sid, l, px, py; float pxf, pyf; bool inside; };
+__device__ __forceinline__ StreamPixel stream_pixel(const Cam& cam, float qx0, float qy0, int lane)
 {
-    const float ex = q2.z, ey = q2.w;
-    return ex >= 0.0f && (q0.x + ex >= qx0) && (q0.x - ex <= qx0 + 7.0f) && (q0.y + ey >= qy0) && (q0.y - ey <= qy0 + 7.0f);
+    StreamPixel s;
+    s.sid = lane >> 4; s.l = lane & 15;
+    s.px = (int)qx0 + (s.sid & 1) * 4 + (s.l & 3); s.py = (int)qy0 + (s.sid >> 1) * 4 + (s.l >> 2);
+    s.inside = s.px < cam.W && s.py < cam.H;
+    s.pxf = (float)s.px; s.pyf = (float)s.py;
+    return s;
 }
 
-// LDS staging form: the conic pre-scaled so that the inner loop is  p = (A dx + B dy) dx + C dy dy ; G = 2^p
+// LDS staging form of a record's first plane and conic: (x, y, A', B') and C', pre-scaled so that the inner loop is
+// p = (A' dx + B' dy) dx + C' dy dy ; G = 2^p  (splat_alpha).  What else a kernel stages with it is its own business.
+struct StagedConic { float4 s0; float c; };
+__device__ __forceinline__ StagedConic staged_conic(const float4& q0, const float4& q1)
+{
+    return {make_float4(q0.x, q0.y, -0.5f * kLog2e * q0.z, -kLog2e * q0.w), -0.5f * kLog2e * q1.x};
+}
+// the plain forward's staging: (C', opacity, r, g) and (b, depth, id, -) behind the conic
 __device__ __forceinline__ void stage_record(float4* s0, float4* s1, float4* s2, int lane, const float4& q0,
                                              const float4& q1, const float4& q2, uint32_t id)
 {
-    s0[lane] = make_float4(q0.x, q0.y, -0.5f * kLog2e * q0.z, -kLog2e * q0.w);
-    s1[lane] = make_float4(-0.5f * kLog2e * q1.x, q1.y, q1.z, q1.w);
+    const StagedConic k = staged_conic(q0, q1);
+    s0[lane] = k.s0;
+    s1[lane] = make_float4(k.c, q1.y, q1.z, q1.w);
     s2[lane] = make_float4(q2.x, q2.y, __uint_as_float(id), 0.0f);
 }
 
-// does the record's alpha-visible box overlap the 4x4 sub-block at pixel origin (x0,y0)?
-__device__ __forceinline__ bool subblock_hit(const float4& q0, const float4& q2, float x0, float y0)
+// power, falloff and alpha of a staged record (a0 = (x, y, A', B'), c = C', op = opacity) at the pixel (pxf, pyf); `hit`: the pixel sees it.
+// The sentinel slot (opacity 0) gives alpha 0 and never hits, so a stream that has run dry needs no validity flag in the inner loop.
+struct SplatAlpha { float alpha, p, G; bool hit; };
+__device__ __forceinline__ SplatAlpha splat_alpha(const float4& a0, float c, float op, float pxf, float pyf)
 {
-    const float ex = q2.z, ey = q2.w;
-    return ex >= 0.0f && (q0.x + ex >= x0) && (q0.x - ex <= x0 + 3.0f) && (q0.y + ey >= y0) && (q0.y - ey <= y0 + 3.0f);
+    SplatAlpha a;
+    const float dx = a0.x - pxf, dy = a0.y - pyf;
+    float bdy, cyy;
+    {   // the two products of p that stay rounded products (the other three become FMAs).  Pinned: which product of a sum the compiler fuses
+        // depends on the operand order it finds after inlining, and every kernel must round p the same way
+#pragma clang fp contract(off)
+        bdy = a0.w * dy; cyy = (c * dy) * dy;
+    }
+    a.p = (a0.z * dx + bdy) * dx + cyy;
+    a.G = __builtin_amdgcn_exp2f(a.p);
+    a.alpha = fminf(0.99f, op * a.G);
+    a.hit = a.p <= 0.0f && a.alpha >= kAlphaMin;
+    return a;
 }
 
-// pop the lowest / highest set bit of a wave-uniform mask; returns its index -- or kWave, the SENTINEL slot of the
-// staging arrays, when the mask is empty: that slot holds a record with opacity 0, whose alpha fails the 1/255 test
-// for every pixel, so a stream that has run dry needs no validity flag in the inner loop
-__device__ __forceinline__ int pop_low(unsigned long long& m)
+// one front-to-back compositing step of a pixel's running state (T, done) with a record of this alpha that the pixel sees iff `hit`:
+// `ok` iff it contributes (the pixel had not stopped and does not stop here: T (1 - alpha) >= 1e-4), `w` = its blend weight alpha T (else 0)
+struct Composite { float T, w; bool done, ok; };             // (T, done: the state after the step)
+__device__ __forceinline__ Composite composite_step(float T, bool done, float alpha, bool hit)
 {
-    const int j = m ? __ffsll(m) - 1 : kWave;
-    m &= m - 1;
-    return j;
+    const float test_T = T * (1.0f - alpha);
+    const bool vis = !done && hit;
+    const bool ok = vis && test_T >= kTmin;
+    return {ok ? test_T : T, ok ? alpha * T : 0.0f, done || (vis != ok), ok};      // (ok implies vis: one mask operation, no second compare)
 }
-__device__ __forceinline__ int pop_high(unsigned long long& m)
-{
-    const int j = m ? 63 - __clzll(m) : kWave;
-    m &= ~(1ull << (j & 63));
-    return j;
-}
+
 __device__ __forceinline__ void write_sentinel(float4* s0, float4* s1, float4* s2, int lane)
 {
     if (lane == 0) {
@@ -131,6 +158,81 @@ __device__ __forceinline__ unsigned scan_blocks(const float4& q0, const float4& 
     if (masks) { masks[0] = b0; masks[1] = b1; masks[2] = b2; masks[3] = b3; }
     return (__builtin_amdgcn_inverse_ballot_w64(b0) ? 1u : 0u) | (__builtin_amdgcn_inverse_ballot_w64(b1) ? 2u : 0u) |
            (__builtin_amdgcn_inverse_ballot_w64(b2) ? 4u : 0u) | (__builtin_amdgcn_inverse_ballot_w64(b3) ? 8u : 0u);
+}
+// the forward's scan: a block is switched off once none of its 16 lanes is in `going` (the mask of lanes = pixels that still blend)
+__device__ __forceinline__ void scan_going_blocks(const float4& q0, const float4& q2, bool valid, float qx0, float qy0, unsigned long long going,
+                                                  unsigned long long& m_any, unsigned long long* masks)
+{
+    scan_blocks(q0, q2, valid, qx0, qy0, (going & 0xffffull) != 0ull, (going & 0xffff0000ull) != 0ull, (going & 0xffff00000000ull) != 0ull,
+                (going >> 48) != 0ull, m_any, masks);
+}
+
+// The per-stream lists of up to 64 staged records (lane = staged slot; mb[s] = the lanes whose record meets block s): `lists` is four rows of 64
+// bytes.  Sentinel fill (one store per lane covers the 4 x 64 bytes: slot kWave), then every hit lane drops its slot index at its rank in the
+// mask -- one mbcnt, no scalar pop sequences.  Returns the longest list's length; `ranks` (the backward's gather) receives the lane's position in
+// every row's list, 0xff where it is not in it.  The caller places the wave barrier (or workgroup barrier) in front of the first reader.
+__device__ __forceinline__ int build_stream_lists(uint8_t* lists, const unsigned long long* mb, int lane, int* ranks = nullptr)
+{
+    reinterpret_cast<uint32_t*>(lists)[lane] = 0x40404040u;
+    __builtin_amdgcn_wave_barrier();
+    int ntrips = 0;
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const unsigned long long m = mb[s];
+        const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        const bool in = __builtin_amdgcn_inverse_ballot_w64(m);
+        if (in) lists[s * kWave + rank] = (uint8_t)lane;
+        if (ranks) ranks[s] = in ? rank : 0xff;
+        ntrips = max(ntrips, (int)__popcll(m));
+    }
+    return ntrips;
+}
+
+// Side job of the forward kernels that run in front of a backward: the workgroup's slice of the backward's gradient records is zero-filled here
+// instead of by a fill launch -- plain fire-and-forget 16-byte stores, kPerStep of them per trip of the kernel's chunk loop.  (Issued all at once
+// at the top of the kernel -- the first version -- they are a 128 MB memset at 2 M Gaussians that every CU's store queue has to drain BEFORE its
+// wavefronts get to blend: ~25 us of the forward; interleaved they ride along.)  What is left when a wavefront's walk ends is stored by
+// grad_fill_rest.  (`threads` = the workgroup's size; a null zero_fill gives an empty slice.)
+struct GradFill {
+    size_t at, end;                               // this thread's next float4 of the workgroup's slice, and the slice's end
+};
+__device__ __forceinline__ GradFill grad_fill_start(const float4* zero_fill, uint32_t P, int tid)
+{
+    GradFill f = {0, 0};
+    if (zero_fill) {
+        const size_t total = (size_t)P * (kGradStride / 4), per = (total + gridDim.x - 1) / gridDim.x;
+        f.at = (size_t)blockIdx.x * per + tid; f.end = min(total, (size_t)blockIdx.x * per + per);
+    }
+    return f;
+}
+__device__ __forceinline__ GradFill grad_fill_step(float4* zero_fill, GradFill f, int threads)
+{
+    constexpr int kPerStep = 2;
+#pragma unroll
+    for (int k = 0; k < kPerStep; k++)
+        if (f.at < f.end) { zero_fill[f.at] = make_float4(0.f, 0.f, 0.f, 0.f); f.at += threads; }
+    return f;
+}
+__device__ __forceinline__ void grad_fill_rest(float4* zero_fill, GradFill f, int threads)
+{
+    for (; f.at < f.end; f.at += threads) zero_fill[f.at] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// a pixel's outputs of the unsegmented forward: T and the last contributor's position for the backward, the composited sums over the background
+template <bool DEPTH_SQ>
+__device__ __forceinline__ void store_pixel_outputs(const Cam& cam, int px, int py, float T, uint32_t last, float C0, float C1, float C2, float Dp, float Dq,
+                                                    float* out_color, float* out_depth, float* out_opacity, float* final_T, uint32_t* n_contrib,
+                                                    float* out_depth_sq)
+{
+    const size_t pix = (size_t)py * cam.W + px, HW = (size_t)cam.H * cam.W;
+    final_T[pix] = T;
+    n_contrib[pix] = last;
+    out_color[pix] = C0 + T * cam.bg[0];
+    out_color[HW + pix] = C1 + T * cam.bg[1];
+    out_color[2 * HW + pix] = C2 + T * cam.bg[2];
+    out_depth[pix] = Dp;
+    out_opacity[pix] = 1.0f - T;
+    if (DEPTH_SQ) out_depth_sq[pix] = Dq;
 }
 // Issue priority of the calling wavefront (0 ... 3; the SIMD's arbiter picks by priority, then age).  s_setprio takes an immediate and ignores
 // EXEC, so `level` is made a scalar first and the ladder is scalar compares and branches around four constants: call it outside divergent code only.
@@ -172,41 +274,27 @@ __global__ __launch_bounds__(NW * kWave) void blend_forward_streams_kernel(
     float* __restrict__ out_depth_sq, uint32_t cap, float* __restrict__ seg_T, float* __restrict__ split_state, uint32_t P,
     float4* __restrict__ zero_fill)
 {
-    constexpr int LS = kWave / NS;          // lanes per stream
-    constexpr int BH = LS / 4;              // block = 4 x BH pixels
-    __shared__ float4 s_rec[NW][3][kWave + 1];           // + the sentinel slot
-    // NS rows of 64 entries per wave (+16 bytes so that the look-ahead read behind the last row stays inside the wave's slab)
-    __shared__ __attribute__((aligned(16))) uint8_t s_list[NW][NS * kWave + 16];
     static_assert(NS == 4 && kWave / NS == 16, "the scan tests the four 4x4 blocks of a quadrant");
+    __shared__ float4 s_rec[NW][3][kWave + 1];           // + the sentinel slot
+    // four rows of 64 entries per wave (+16 bytes so that the look-ahead read behind the last row stays inside the wave's slab)
+    __shared__ __attribute__((aligned(16))) uint8_t s_list[NW][4 * kWave + 16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // side job (SEG = 0 only): this workgroup's slice of the backward's gradient records is zero-filled here instead of by a fill launch
-    // in front of the backward -- plain fire-and-forget 16-byte stores, kFillPerStep of them per trip of the chunk loop below.  (Issued
-    // all at once at the top of the kernel -- the first version -- they are a 128 MB memset at 2 M Gaussians that every CU's store
-    // queue has to drain BEFORE its wavefronts get to blend: ~25 us of the forward; interleaved they ride along.)  What is left when a
-    // wavefront's walk ends is stored then.
-    constexpr int kFillPerStep = 2;
-    size_t zf = 0, zf_end = 0;
-    if (SEG == 0 && zero_fill) {
-        const size_t total = (size_t)P * (kGradStride / 4), per = (total + gridDim.x - 1) / gridDim.x;
-        zf = (size_t)blockIdx.x * per + tid; zf_end = min(total, (size_t)blockIdx.x * per + per);
-    }
-#define GS_FILL_REST() if (SEG == 0) { for (; zf < zf_end; zf += NW * kWave) zero_fill[zf] = make_float4(0.f, 0.f, 0.f, 0.f); }
+    GradFill fill = grad_fill_start(SEG == 0 ? zero_fill : nullptr, P, tid);        // side job (SEG = 0 only): see GradFill
     TileCtx c;
     // chained backward walks: the ticket counters (behind the hand-over flags) start from zero with every forward
     if (SEG == 0 && cam.chain > 1 && split_state && blockIdx.x == 0 && tid < 8)
         reinterpret_cast<uint32_t*>(split_state)[(size_t)cam.gx * cam.gy * 4 * (kChainStateFloats + kChainPieces - 1) + (size_t)tid * kChainTicketStride] = 0u;
-    if (!tile_ctx_nw<NW>(cam, wave, lane, c)) { GS_FILL_REST(); return; }
+    if (!tile_ctx_nw<NW>(cam, wave, lane, c)) { if (SEG == 0) grad_fill_rest(zero_fill, fill, NW * kWave); return; }
     // chained backward walks: the quadrant's hand-over flags start from zero with every forward (the backward's epoch is never zero)
     if (SEG == 0 && cam.chain > 1 && split_state && lane < kChainPieces - 1)
         reinterpret_cast<uint32_t*>(split_state)[(size_t)cam.gx * cam.gy * 4 * kChainStateFloats + (size_t)(c.tile * 4 + c.quad) * (kChainPieces - 1) + lane] = 0u;
-    // lane -> pixel: stream sid owns block (sid & 1, sid >> 1) of the quadrant
-    const int sid = lane / LS, l = lane % LS;
-    const int px = (int)c.qx0 + (sid & 1) * 4 + (l & 3), py = (int)c.qy0 + (sid >> 1) * BH + (l >> 2);
-    const bool inside = px < cam.W && py < cam.H;
-    const float pxf = (float)px, pyf = (float)py;
+    const StreamPixel sp = stream_pixel(cam, c.qx0, c.qy0, lane);
+    const int px = sp.px, py = sp.py;
+    const bool inside = sp.inside;
+    const float pxf = sp.pxf, pyf = sp.pyf;
     float4* s0 = s_rec[wave][0]; float4* s1 = s_rec[wave][1]; float4* s2 = s_rec[wave][2];
     write_sentinel(s0, s1, s2, lane);
-    uint8_t* my_list = s_list[wave] + sid * kWave;
+    uint8_t* my_list = s_list[wave] + sp.sid * kWave;
     uint2 range = ranges[c.tile];
     range.x = min(range.x, cap); range.y = min(range.y, cap);
     const uint32_t n_all = range.y - range.x;
@@ -259,11 +347,7 @@ __global__ __launch_bounds__(NW * kWave) void blend_forward_streams_kernel(
             r0 = gr[0]; r1 = gr[1]; r2 = gr[2];
         }
         for (uint32_t base = first; base < n; base += kWave) {
-            if (SEG == 0) {
-#pragma unroll
-                for (int f = 0; f < kFillPerStep; f++)
-                    if (zf < zf_end) { zero_fill[zf] = make_float4(0.f, 0.f, 0.f, 0.f); zf += NW * kWave; }
-            }
+            if (SEG == 0) fill = grad_fill_step(zero_fill, fill, NW * kWave);
             // issue priority by the walk's estimated REMAINING length (cam.fwd_prio, gs_set_forward_priority; SEG = 0): the walkers of a SIMD are
             // all resident from the start and end by saturation at very different depths; one left alone cannot fill its SIMD, so the one that
             // will run longest should take the issue slots while the others are still there to use the leftovers.  The estimate is wave-uniform
@@ -311,25 +395,10 @@ __global__ __launch_bounds__(NW * kWave) void blend_forward_streams_kernel(
             // branches, the lane's rank in a list is one mbcnt of the block's mask
             const unsigned long long going = SEG == 1 ? ~0ull : ~__ballot(done);
             unsigned long long m_any, mb[4];
-            scan_blocks(q0, q2, id_cur != kNoId, c.qx0, c.qy0, (going & 0xffffull) != 0ull, (going & 0xffff0000ull) != 0ull,
-                        (going & 0xffff00000000ull) != 0ull, (going >> 48) != 0ull, m_any, mb);
+            scan_going_blocks(q0, q2, id_cur != kNoId, c.qx0, c.qy0, going, m_any, mb);
             if (m_any == 0ull) continue;
             stage_record(s0, s1, s2, lane, q0, q1, q2, id_cur);
-            // per-stream lists: sentinel fill (one store per lane covers NS x 64 bytes), then every hit lane drops its index
-            {
-                uint32_t* fill = reinterpret_cast<uint32_t*>(s_list[wave]);
-                constexpr int kWords = NS * kWave / 4;
-                for (int w = lane; w < kWords; w += kWave) fill[w] = 0x40404040u;
-            }
-            __builtin_amdgcn_wave_barrier();
-            int ntrips = 0;
-#pragma unroll
-            for (int s = 0; s < NS; s++) {
-                const unsigned long long m = mb[s];
-                const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                if (__builtin_amdgcn_inverse_ballot_w64(m)) s_list[wave][s * kWave + rank] = (uint8_t)lane;
-                ntrips = max(ntrips, (int)__popcll(m));
-            }
+            const int ntrips = build_stream_lists(s_list[wave], mb, lane);
             __builtin_amdgcn_wave_barrier();
             uint32_t jj2_next = *reinterpret_cast<const uint16_t*>(my_list);                // two list entries per read
             int lj = -1;                             // staged slot of this chunk's last contributor (slots ascend along a stream's list)
@@ -342,22 +411,16 @@ __global__ __launch_bounds__(NW * kWave) void blend_forward_streams_kernel(
                 for (int u = 0; u < 2; u++) { a0[u] = s0[jj[u]]; a1[u] = s1[jj[u]]; a2[u] = s2[jj[u]]; }
 #pragma unroll
                 for (int u = 0; u < 2; u++) {
-                    const float dx = a0[u].x - pxf, dy = a0[u].y - pyf;
-                    const float p = (a0[u].z * dx + a0[u].w * dy) * dx + (a1[u].x * dy) * dy;
-                    const float alpha = fminf(0.99f, a1[u].y * __builtin_amdgcn_exp2f(p));
+                    const SplatAlpha a = splat_alpha(a0[u], a1[u].x, a1[u].y, pxf, pyf);
                     if (SEG == 1) {                                                  // transmittance of the segment only
-                        T = (p <= 0.0f && alpha >= kAlphaMin) ? T * (1.0f - alpha) : T;
+                        T = a.hit ? T * (1.0f - a.alpha) : T;
                         continue;
                     }
-                    const float test_T = T * (1.0f - alpha);
-                    const bool vis = !done && p <= 0.0f && alpha >= kAlphaMin;     // sentinel: alpha = 0
-                    const bool ok = vis && test_T >= kTmin;
-                    done = done || (vis != ok);                                    // (ok implies vis: one mask operation, no second compare)
-                    const float w = ok ? alpha * T : 0.0f;
-                    C0 += a1[u].z * w; C1 += a1[u].w * w; C2 += a2[u].x * w; Dp += a2[u].y * w;
-                    if (DEPTH_SQ) Dq += a2[u].y * a2[u].y * w;
-                    T = ok ? test_T : T;
-                    lj = ok ? jj[u] : lj;
+                    const Composite k = composite_step(T, done, a.alpha, a.hit);
+                    T = k.T; done = k.done;
+                    C0 += a1[u].z * k.w; C1 += a1[u].w * k.w; C2 += a2[u].x * k.w; Dp += a2[u].y * k.w;
+                    if (DEPTH_SQ) Dq += a2[u].y * a2[u].y * k.w;
+                    lj = k.ok ? jj[u] : lj;
                 }
             }
             last = lj >= 0 ? base + (uint32_t)lj + 1u : last;
@@ -367,7 +430,7 @@ __global__ __launch_bounds__(NW * kWave) void blend_forward_streams_kernel(
         }
         if (SEG == 0 && cam.fwd_prio != kFwdPrioOff) __builtin_amdgcn_s_setprio(0);      // (the walk is over: the stores that follow wait for nobody)
     }
-    GS_FILL_REST();
+    if (SEG == 0) grad_fill_rest(zero_fill, fill, NW * kWave);
     if (SEG == 1) {
         my_seg_T[0] = T;
         if (__all(!inside || T < kTmin) && lane == 0) atomicOr(seg_flag, 1u << blockIdx.y);
@@ -387,24 +450,13 @@ __global__ __launch_bounds__(NW * kWave) void blend_forward_streams_kernel(
         }
         return;
     }
-    if (inside) {
-        const size_t pix = (size_t)py * cam.W + px, HW = (size_t)cam.H * cam.W;
-        final_T[pix] = T;
-        n_contrib[pix] = last;
-        out_color[pix] = C0 + T * cam.bg[0];
-        out_color[HW + pix] = C1 + T * cam.bg[1];
-        out_color[2 * HW + pix] = C2 + T * cam.bg[2];
-        out_depth[pix] = Dp;
-        out_opacity[pix] = 1.0f - T;
-        if (DEPTH_SQ) out_depth_sq[pix] = Dq;
-    }
+    if (inside) store_pixel_outputs<DEPTH_SQ>(cam, px, py, T, last, C0, C1, C2, Dp, Dq, out_color, out_depth, out_opacity, final_T, n_contrib, out_depth_sq);
 }
-
-#undef GS_FILL_REST
 
 // ---------------------------------------------------------------------------------------------------
 // The planner's top-down maps (gs_render_forward_topdown; visualizer.py:923-965 renders them as two raster passes over one camera): the plain
-// streams forward above (SEG = 0, NW = 4: same gather, scan, per-stream lists and pipelining) with TWO running states per pixel --
+// streams forward above (SEG = 0, NW = 4; shared steps: stream_pixel, scan_going_blocks, staged_conic, build_stream_lists, splat_alpha; the
+// prefetch and the compositing step are copies: shared, the records came as 128-bit instead of dword loads and the walk ran 1.3 % slower) with TWO states per pixel --
 //   all  : (C, T) over every list entry            -> visible_rgb = bytes of C + T bg, visible_binary = grey(bytes) == 255
 //   band : T_band over the entries whose record carries the height-band bit (the sign of its opacity, preprocess.hip: CamBand)
 //                                                  -> free_opacity = 1 - T_band, free_binary = free_opacity <= 0.4
@@ -432,20 +484,20 @@ __global__ __launch_bounds__(kBlock) void blend_topdown_kernel(
     float* __restrict__ free_opacity, uint8_t* __restrict__ free_binary, uint8_t* __restrict__ visible_rgb, uint8_t* __restrict__ visible_binary,
     uint32_t cap, uint32_t P)
 {
-    constexpr int NW = 4, NS = kFwdStreams, LS = kWave / NS;
+    constexpr int NW = 4;
+    static_assert(kFwdStreams == 4, "the scan tests the four 4x4 blocks of a quadrant");
     __shared__ float4 s_rec[NW][3][kWave + 1];           // + the sentinel slot
-    __shared__ __attribute__((aligned(16))) uint8_t s_list[NW][NS * kWave + 16];
-    static_assert(NS == 4 && kWave / NS == 16, "the scan tests the four 4x4 blocks of a quadrant");
+    __shared__ __attribute__((aligned(16))) uint8_t s_list[NW][4 * kWave + 16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     TileCtx c;
     if (!tile_ctx_nw<NW>(cam, wave, lane, c)) return;
-    const int sid = lane / LS, l = lane % LS;
-    const int px = (int)c.qx0 + (sid & 1) * 4 + (l & 3), py = (int)c.qy0 + (sid >> 1) * 4 + (l >> 2);
-    const bool inside = px < cam.W && py < cam.H;
-    const float pxf = (float)px, pyf = (float)py;
+    const StreamPixel sp = stream_pixel(cam, c.qx0, c.qy0, lane);
+    const int px = sp.px, py = sp.py, l = sp.l;
+    const bool inside = sp.inside;
+    const float pxf = sp.pxf, pyf = sp.pyf;
     float4* s0 = s_rec[wave][0]; float4* s1 = s_rec[wave][1]; float4* s2 = s_rec[wave][2];
     write_sentinel(s0, s1, s2, lane);
-    uint8_t* my_list = s_list[wave] + sid * kWave;
+    uint8_t* my_list = s_list[wave] + sp.sid * kWave;
     uint2 range = ranges[c.tile];
     range.x = min(range.x, cap); range.y = min(range.y, cap);
     const uint32_t n = range.y - range.x;
@@ -477,27 +529,14 @@ __global__ __launch_bounds__(kBlock) void blend_topdown_kernel(
             // a stream is switched off when all its pixels have stopped in both states
             const unsigned long long going = ~__ballot(done && done_b);
             unsigned long long m_any, mb[4];
-            scan_blocks(q0, q2, id_cur != kNoId, c.qx0, c.qy0, (going & 0xffffull) != 0ull, (going & 0xffff0000ull) != 0ull,
-                        (going & 0xffff00000000ull) != 0ull, (going >> 48) != 0ull, m_any, mb);
+            scan_going_blocks(q0, q2, id_cur != kNoId, c.qx0, c.qy0, going, m_any, mb);
             if (m_any == 0ull) continue;
             // staging form of the forward above; the opacity without its sign, the band bit and the blue channel in the third plane's first half
-            s0[lane] = make_float4(q0.x, q0.y, -0.5f * kLog2e * q0.z, -kLog2e * q0.w);
-            s1[lane] = make_float4(-0.5f * kLog2e * q1.x, fabsf(q1.y), q1.z, q1.w);
+            const StagedConic k = staged_conic(q0, q1);
+            s0[lane] = k.s0;
+            s1[lane] = make_float4(k.c, fabsf(q1.y), q1.z, q1.w);
             s2[lane] = make_float4(q2.x, __uint_as_float(__float_as_uint(q1.y) >> 31), 0.0f, 0.0f);
-            {
-                uint32_t* fill = reinterpret_cast<uint32_t*>(s_list[wave]);
-                constexpr int kWords = NS * kWave / 4;
-                for (int w = lane; w < kWords; w += kWave) fill[w] = 0x40404040u;
-            }
-            __builtin_amdgcn_wave_barrier();
-            int ntrips = 0;
-#pragma unroll
-            for (int s = 0; s < NS; s++) {
-                const unsigned long long m = mb[s];
-                const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                if (__builtin_amdgcn_inverse_ballot_w64(m)) s_list[wave][s * kWave + rank] = (uint8_t)lane;
-                ntrips = max(ntrips, (int)__popcll(m));
-            }
+            const int ntrips = build_stream_lists(s_list[wave], mb, lane);
             __builtin_amdgcn_wave_barrier();
             uint32_t jj2_next = *reinterpret_cast<const uint16_t*>(my_list);
             for (int t = 0; t < ntrips; t += 2) {
@@ -510,24 +549,15 @@ __global__ __launch_bounds__(kBlock) void blend_topdown_kernel(
                 for (int u = 0; u < 2; u++) { a0[u] = s0[jj[u]]; a1[u] = s1[jj[u]]; a2[u] = *reinterpret_cast<const float2*>(&s2[jj[u]]); }
 #pragma unroll
                 for (int u = 0; u < 2; u++) {
-                    const float dx = a0[u].x - pxf, dy = a0[u].y - pyf;
-                    const float p = (a0[u].z * dx + a0[u].w * dy) * dx + (a1[u].x * dy) * dy;
-                    const float alpha = fminf(0.99f, a1[u].y * __builtin_amdgcn_exp2f(p));
-                    const bool hit = p <= 0.0f && alpha >= kAlphaMin;                // sentinel: alpha = 0
-                    // state `all`
-                    const float test_T = T * (1.0f - alpha);
-                    const bool vis = !done && hit;
-                    const bool ok = vis && test_T >= kTmin;
-                    done = done || (vis != ok);
-                    const float w = ok ? alpha * T : 0.0f;
+                    const SplatAlpha a = splat_alpha(a0[u], a1[u].x, a1[u].y, pxf, pyf);
+                    // state `all`, then state `band`: composite_step twice, written out (through the helper this kernel measured 1 % slower)
+                    const float test_T = T * (1.0f - a.alpha), test_b = Tb * (1.0f - a.alpha);
+                    const bool vis = !done && a.hit, vis_b = !done_b && a.hit && __float_as_uint(a2[u].y) != 0u;
+                    const bool ok = vis && test_T >= kTmin, ok_b = vis_b && test_b >= kTmin;
+                    done = done || (vis != ok); done_b = done_b || (vis_b != ok_b);
+                    const float w = ok ? a.alpha * T : 0.0f;
                     C0 += a1[u].z * w; C1 += a1[u].w * w; C2 += a2[u].x * w;
-                    T = ok ? test_T : T;
-                    // state `band`
-                    const float test_b = Tb * (1.0f - alpha);
-                    const bool vis_b = !done_b && hit && __float_as_uint(a2[u].y) != 0u;
-                    const bool ok_b = vis_b && test_b >= kTmin;
-                    done_b = done_b || (vis_b != ok_b);
-                    Tb = ok_b ? test_b : Tb;
+                    T = ok ? test_T : T; Tb = ok_b ? test_b : Tb;
                 }
             }
             __builtin_amdgcn_wave_barrier();
@@ -598,12 +628,7 @@ __global__ __launch_bounds__(kPcWaves * kWave) void blend_forward_pc_kernel(
     const int pair = wave & 3, role = wave >> 2;                                      // role 0: lister, 1: producer, 2: consumer
     const int ntiles = cam.gx * cam.gy, per = (ntiles + 7) >> 3;
     const int tile = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
-    // the backward's gradient records: this workgroup's slice, a few 16-byte stores per step of the loop below
-    size_t zf = 0, zf_end = 0;
-    if (zero_fill) {
-        const size_t total = (size_t)P * (kGradStride / 4), pw = (total + gridDim.x - 1) / gridDim.x;
-        zf = (size_t)blockIdx.x * pw + tid; zf_end = min(total, (size_t)blockIdx.x * pw + pw);
-    }
+    GradFill fill = grad_fill_start(zero_fill, P, tid);     // the backward's gradient records: this workgroup's slice, a few stores per step of the loop below
     const size_t HWs = (size_t)cam.W * cam.H;
     // (the recorded planes and their "recorded" word exist only in the workspace of an image of at most kFewTiles tiles; gs_set_half_quadrants
     // may send a larger image here, whose workspace holds the chained backward's hand-over state at that offset instead)
@@ -611,15 +636,15 @@ __global__ __launch_bounds__(kPcWaves * kWave) void blend_forward_pc_kernel(
     const bool record = few && cam.split != 0 && zero_fill != nullptr && split_state != nullptr;
     if (few && split_state && blockIdx.x == 0 && tid == 0) reinterpret_cast<uint32_t*>(split_state + (kCutLevels * 5 + 4) * HWs)[0] = record ? 1u : 0u;
     if ((int)(blockIdx.x >> 3) >= per || tile >= ntiles) {                             // (uniform for the workgroup)
-        for (; zf < zf_end; zf += kPcWaves * kWave) zero_fill[zf] = make_float4(0.f, 0.f, 0.f, 0.f);
+        grad_fill_rest(zero_fill, fill, kPcWaves * kWave);
         return;
     }
     const int tx = tile % cam.gx, ty = tile / cam.gx;
     const float qx0 = (float)(tx * kTile + (pair & 1) * kQuad), qy0 = (float)(ty * kTile + (pair >> 1) * kQuad);
-    const int sid = lane >> 4, l = lane & 15;
-    const int px = (int)qx0 + (sid & 1) * 4 + (l & 3), py = (int)qy0 + (sid >> 1) * 4 + (l >> 2);
-    const bool inside = px < cam.W && py < cam.H;
-    const float pxf = (float)px, pyf = (float)py;
+    const StreamPixel sp = stream_pixel(cam, qx0, qy0, lane);
+    const int sid = sp.sid, px = sp.px, py = sp.py;
+    const bool inside = sp.inside;
+    const float pxf = sp.pxf, pyf = sp.pyf;
     uint2 range = ranges[tile];
     range.x = min(range.x, cap); range.y = min(range.y, cap);
     const uint32_t n = range.y - range.x;
@@ -646,8 +671,9 @@ __global__ __launch_bounds__(kPcWaves * kWave) void blend_forward_pc_kernel(
     auto stage = [&](int chunk, const float4 (&g)[3]) {
         if (lane < 16 && chunk < nchunks) {
             const int b = chunk & 3, slot = pair * 16 + lane;
-            s_rec[b][0][slot] = make_float4(g[0].x, g[0].y, -0.5f * kLog2e * g[0].z, -kLog2e * g[0].w);
-            s_rec[b][1][slot] = make_float4(-0.5f * kLog2e * g[1].x, g[1].y, g[2].z, g[2].w);
+            const StagedConic k = staged_conic(g[0], g[1]);
+            s_rec[b][0][slot] = k.s0;
+            s_rec[b][1][slot] = make_float4(k.c, g[1].y, g[2].z, g[2].w);
             s_rec[b][2][slot] = make_float4(g[1].z, g[1].w, g[2].x, g[2].y);
         }
     };
@@ -661,19 +687,8 @@ __global__ __launch_bounds__(kPcWaves * kWave) void blend_forward_pc_kernel(
         // (the four block tests as wave masks in scalar registers: scan_blocks; a record slot behind the list's end was staged with extent -1)
         const unsigned long long going = s_going[pair];
         unsigned long long m_any, mb[4];
-        scan_blocks(make_float4(q0.x, q0.y, 0.f, 0.f), make_float4(0.f, 0.f, q2.x, q2.y), true, qx0, qy0, (going & 0xffffull) != 0ull,
-                    (going & 0xffff0000ull) != 0ull, (going & 0xffff00000000ull) != 0ull, (going >> 48) != 0ull, m_any, mb);
-        if (m_any != 0ull) {
-            reinterpret_cast<uint32_t*>(s_list[pair][lb])[lane] = 0x40404040u;        // sentinel fill: 4 x 64 bytes
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int st = 0; st < 4; st++) {
-                const unsigned long long m = mb[st];
-                const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                if (__builtin_amdgcn_inverse_ballot_w64(m)) s_list[pair][lb][st * kWave + rank] = (uint8_t)lane;
-                ntrips = max(ntrips, (int)__popcll(m));
-            }
-        }
+        scan_going_blocks(make_float4(q0.x, q0.y, 0.f, 0.f), make_float4(0.f, 0.f, q2.x, q2.y), true, qx0, qy0, going, m_any, mb);
+        if (m_any != 0ull) ntrips = build_stream_lists(s_list[pair][lb], mb, lane);
         if (lane == 0) s_ntrips[pair][lb] = ntrips;
     };
     float4 held[3], flying[3];                       // lister: records of chunk it + 2 (arrived, staged during step it) / of chunk it + 3 (in flight)
@@ -693,8 +708,7 @@ __global__ __launch_bounds__(kPcWaves * kWave) void blend_forward_pc_kernel(
     uint32_t last = 0;
     bool done = !inside;
     for (int it = 0; it <= nchunks; it++) {
-        for (int f = 0; f < 2; f++)
-            if (zf < zf_end) { zero_fill[zf] = make_float4(0.f, 0.f, 0.f, 0.f); zf += kPcWaves * kWave; }
+        fill = grad_fill_step(zero_fill, fill, kPcWaves * kWave);
         const bool quad_done = s_done[(it + 1) & 1][pair] != 0;                         // as of the end of step it - 1
         if (role == 0) {
             // ---- lister: records of chunk it + 3 requested, lists of chunk it + 1, chunk it + 2 staged ----
@@ -726,10 +740,8 @@ __global__ __launch_bounds__(kPcWaves * kWave) void blend_forward_pc_kernel(
                     for (int u = 0; u < 4; u++) { const int j = (int)((jj4 >> (8 * u)) & 0xffu); a0[u] = s0[j]; a1[u] = *reinterpret_cast<const float2*>(&s1[j]); }
 #pragma unroll
                     for (int u = 0; u < 4; u++) {
-                        const float dx = a0[u].x - pxf, dy = a0[u].y - pyf;
-                        const float p = (a0[u].z * dx + a0[u].w * dy) * dx + (a1[u].x * dy) * dy;
-                        const float alpha = fminf(0.99f, a1[u].y * __builtin_amdgcn_exp2f(p));
-                        al[u] = (p <= 0.0f && alpha >= kAlphaMin) ? alpha : 0.0f;                        // 0 = this pixel does not see the record
+                        const SplatAlpha a = splat_alpha(a0[u], a1[u].x, a1[u].y, pxf, pyf);
+                        al[u] = a.hit ? a.alpha : 0.0f;                                                  // 0 = this pixel does not see the record
                     }
                     plane[(t >> 2) * kWave] = make_float4(al[0], al[1], al[2], al[3]);
                 }
@@ -763,15 +775,11 @@ __global__ __launch_bounds__(kPcWaves * kWave) void blend_forward_pc_kernel(
                     for (int u = 0; u < 4; u++) {
                         const float alpha = al[u];
                         const float4 cc = b2[u];                                 // (r, g, b, depth)
-                        const float test_T = T * (1.0f - alpha);
-                        const bool vis = !done && alpha > 0.0f;
-                        const bool ok = vis && test_T >= kTmin;
-                        done = done || (vis != ok);                              // (ok implies vis)
-                        const float w = ok ? alpha * T : 0.0f;
-                        C0 += cc.x * w; C1 += cc.y * w; C2 += cc.z * w; Dp += cc.w * w;
-                        if (DEPTH_SQ) Dq += cc.w * cc.w * w;
-                        T = ok ? test_T : T;
-                        lj = ok ? jj[u] : lj;
+                        const Composite k = composite_step(T, done, alpha, alpha > 0.0f);
+                        T = k.T; done = k.done;
+                        C0 += cc.x * k.w; C1 += cc.y * k.w; C2 += cc.z * k.w; Dp += cc.w * k.w;
+                        if (DEPTH_SQ) Dq += cc.w * cc.w * k.w;
+                        lj = k.ok ? jj[u] : lj;
                     }
                 }
                 last = lj >= 0 ? base + (uint32_t)lj + 1u : last;
@@ -784,18 +792,11 @@ __global__ __launch_bounds__(kPcWaves * kWave) void blend_forward_pc_kernel(
         __syncthreads();
         if (s_done[it & 1][0] && s_done[it & 1][1] && s_done[it & 1][2] && s_done[it & 1][3]) break;      // (uniform: written before the barrier)
     }
-    for (; zf < zf_end; zf += kPcWaves * kWave) zero_fill[zf] = make_float4(0.f, 0.f, 0.f, 0.f);
+    grad_fill_rest(zero_fill, fill, kPcWaves * kWave);
     if (role == 2 && inside) {
-        const size_t pix = (size_t)py * cam.W + px, HW = (size_t)cam.H * cam.W;
-        final_T[pix] = T;
-        n_contrib[pix] = last;
-        out_color[pix] = C0 + T * cam.bg[0];
-        out_color[HW + pix] = C1 + T * cam.bg[1];
-        out_color[2 * HW + pix] = C2 + T * cam.bg[2];
-        out_depth[pix] = Dp;
-        out_opacity[pix] = 1.0f - T;
-        if (DEPTH_SQ) out_depth_sq[pix] = Dq;
+        store_pixel_outputs<DEPTH_SQ>(cam, px, py, T, last, C0, C1, C2, Dp, Dq, out_color, out_depth, out_opacity, final_T, n_contrib, out_depth_sq);
         if (record) {
+            const size_t pix = (size_t)py * cam.W + px, HW = (size_t)cam.H * cam.W;
             float* tot = split_state + (size_t)kCutLevels * 5 * HW + pix;
             tot[0] = C0; tot[HW] = C1; tot[2 * HW] = C2; tot[3 * HW] = Dp;
         }
@@ -883,10 +884,10 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(3, 3
     const int piece = pieces > 1 ? (int)(vb / group) : 0;
     if (!tile_ctx_at<NW>(cam, pieces > 1 ? vb - (unsigned)piece * group : vb, wave, lane, c, nseg)) return;
     // phase A role: row (lane>>4) = 4x4 sub-block, (lane&15) = pixel inside it
-    const int row = lane >> 4, l16 = lane & 15;
-    const int px = (int)c.qx0 + (row & 1) * 4 + (l16 & 3), py = (int)c.qy0 + (row >> 1) * 4 + (l16 >> 2);
-    const bool inside = px < cam.W && py < cam.H;
-    const float pxf = (float)px, pyf = (float)py;
+    const StreamPixel sp = stream_pixel(cam, c.qx0, c.qy0, lane);
+    const int row = sp.sid, px = sp.px, py = sp.py;
+    const bool inside = sp.inside;
+    const float pxf = sp.pxf, pyf = sp.pyf;
     float4* s0 = s_rec[wave][0]; float4* s1 = s_rec[wave][1]; float4* s2 = s_rec[wave][2];
     write_sentinel(s0, s1, s2, lane);
     const uint8_t* my_list = s_list[wave] + row * kWave;
@@ -1058,8 +1059,9 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(3, 3
             const bool stage = hf != 0u && rel < n_stage;
             if (stage) {
                 const int slot = cnt + rel;
-                s0[slot] = make_float4(q0.x, q0.y, -0.5f * kLog2e * q0.z, -kLog2e * q0.w);
-                s1[slot] = make_float4(-0.5f * kLog2e * q1.x, q1.y, q1.z, q1.w);
+                const StagedConic k = staged_conic(q0, q1);
+                s0[slot] = k.s0;
+                s1[slot] = make_float4(k.c, q1.y, q1.z, q1.w);
                 s2[slot] = make_float4(q2.x, __uint_as_float(cpos + (uint32_t)lane), q2.y, __uint_as_float(id_cur));
                 s_flag[wave][slot] = (uint8_t)hf;
             }
@@ -1079,22 +1081,12 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(3, 3
         // ---- a round: lane = staging slot ----
         __builtin_amdgcn_wave_barrier();
         const unsigned fl = lane < cnt ? (unsigned)s_flag[wave][lane] : 0u;
-        const bool h0 = (fl & 1u) != 0u, h1 = (fl & 2u) != 0u, h2 = (fl & 4u) != 0u, h3 = (fl & 8u) != 0u;
-        const unsigned long long m0 = __ballot(h0), m1 = __ballot(h1), m2 = __ballot(h2), m3 = __ballot(h3);
-        reinterpret_cast<uint32_t*>(s_list[wave])[lane] = 0x40404040u;          // sentinel fill: one store per lane = 4 x 64 bytes
-        __builtin_amdgcn_wave_barrier();
-        const int n0 = (int)__popcll(m0), n1 = (int)__popcll(m1), n2 = (int)__popcll(m2), n3 = (int)__popcll(m3);
-#define GS_RANK(m) ((int)__builtin_amdgcn_mbcnt_hi((uint32_t)((m) >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)(m), 0u)))
+        const unsigned long long mb[4] = {__ballot((fl & 1u) != 0u), __ballot((fl & 2u) != 0u), __ballot((fl & 4u) != 0u), __ballot((fl & 8u) != 0u)};
         // slots are in walk order (deepest first); the lane (= record) remembers where it sits in every row's list (0xff: not in that row's list)
-        const int p0 = h0 ? GS_RANK(m0) : 0xff, p1 = h1 ? GS_RANK(m1) : 0xff;
-        const int p2 = h2 ? GS_RANK(m2) : 0xff, p3 = h3 ? GS_RANK(m3) : 0xff;
-        if (h0) s_list[wave][0 * kWave + p0] = (uint8_t)lane;
-        if (h1) s_list[wave][1 * kWave + p1] = (uint8_t)lane;
-        if (h2) s_list[wave][2 * kWave + p2] = (uint8_t)lane;
-        if (h3) s_list[wave][3 * kWave + p3] = (uint8_t)lane;
-#undef GS_RANK
+        int rank[4];
+        const int ntrips = build_stream_lists(s_list[wave], mb, lane, rank);
+        const int p0 = rank[0], p1 = rank[1], p2 = rank[2], p3 = rank[3];
         float racc[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};    // this record's moments, summed over rows and batches
-        const int ntrips = max(max(n0, n1), max(n2, n3));
         __builtin_amdgcn_wave_barrier();
         for (int t0 = 0; t0 < ntrips; t0 += kBT) {
             // ---- phase A: up to kBT list positions, two per iteration ----
@@ -1105,17 +1097,15 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(3, 3
                 jj2_next = *reinterpret_cast<const uint16_t*>(my_list + t0 + t + 2);
                 const int jj[2] = {(int)(jj2 & 0xffu), (int)(jj2 >> 8)};
                 float4 a0[2], a1[2], a2[2];
-                float dx[2], dy[2], G[2], alpha[2];
+                float G[2], alpha[2];
                 bool ok[2];
 #pragma unroll
                 for (int u = 0; u < 2; u++) { a0[u] = s0[jj[u]]; a1[u] = s1[jj[u]]; a2[u] = s2[jj[u]]; }
 #pragma unroll
                 for (int u = 0; u < 2; u++) {
-                    dx[u] = a0[u].x - pxf; dy[u] = a0[u].y - pyf;
-                    const float p = (a0[u].z * dx[u] + a0[u].w * dy[u]) * dx[u] + (a1[u].x * dy[u]) * dy[u];
-                    G[u] = __builtin_amdgcn_exp2f(p);
-                    alpha[u] = fminf(0.99f, a1[u].y * G[u]);
-                    ok[u] = __float_as_uint(a2[u].y) < last && p <= 0.0f && alpha[u] >= kAlphaMin;     // (list position below this pixel's last contributor)
+                    const SplatAlpha a = splat_alpha(a0[u], a1[u].x, a1[u].y, pxf, pyf);
+                    G[u] = a.G; alpha[u] = a.alpha;
+                    ok[u] = __float_as_uint(a2[u].y) < last && a.hit;                                   // (list position below this pixel's last contributor)
                 }
                 float* w1 = m1p + (t * kMT + lane); float* w2 = m2p + (t * kMT + lane);
 #pragma unroll
@@ -1271,6 +1261,17 @@ int g_chain_fail_device = -1;
 // list segments (walkers) per quadrant in the few-tile backward: 3 x 256 tiles x 4 quadrants = the chip's 3072 walker slots (gs_set_backward_segments)
 std::atomic<int> g_few_segments{kFewSegmentsMax};
 
+// for the forward paths whose kernel does not do it itself: the chained backward's hand-over flags (and ticket counters) start from zero
+static hipError_t clear_handover_flags(const Cam& cam, float* split_state, hipStream_t st)
+{
+    return hipMemsetAsync(split_state + (size_t)cam.gx * cam.gy * 4 * kChainStateFloats, 0, chain_flag_words((size_t)cam.gx * cam.gy) * sizeof(uint32_t), st);
+}
+// the "recorded" word of a few-tile image's workspace: this forward records no states for a segmented backward
+static hipError_t mark_nothing_recorded(const Cam& cam, float* split_state, hipStream_t st)
+{
+    return hipMemsetAsync(split_state + (kCutLevels * 5 + 4) * ((size_t)cam.W * cam.H), 0, sizeof(uint32_t), st);
+}
+
 hipError_t launch_blend_forward(const Cam& cam_in, const uint2* ranges, const uint32_t* point_list, const float4* geom,
                                 float* out_color, float* out_depth, float* out_opacity, float* final_T,
                                 uint32_t* n_contrib, float* out_depth_sq, uint32_t cap, int segments, float* seg_T, float* split_state, uint32_t P,
@@ -1305,10 +1306,8 @@ hipError_t launch_blend_forward(const Cam& cam_in, const uint2* ranges, const ui
         if (e == hipSuccess) e = hipMemsetAsync(out_depth, 0, HW * sizeof(float), st);
         if (e == hipSuccess && out_depth_sq) e = hipMemsetAsync(out_depth_sq, 0, HW * sizeof(float), st);
         if (e == hipSuccess) e = hipMemsetAsync(n_contrib, 0, HW * sizeof(uint32_t), st);
-        if (e == hipSuccess && split_state && cam.gx * cam.gy <= kFewTiles)
-            e = hipMemsetAsync(split_state + (kCutLevels * 5 + 4) * HW, 0, sizeof(uint32_t), st);    // nothing recorded
-        if (e == hipSuccess && cam.chain > 1)      // (the segmented kernels do not clear the chained backward's hand-over flags)
-            e = hipMemsetAsync(split_state + (size_t)cam.gx * cam.gy * 4 * kChainStateFloats, 0, chain_flag_words((size_t)cam.gx * cam.gy) * sizeof(uint32_t), st);
+        if (e == hipSuccess && split_state && cam.gx * cam.gy <= kFewTiles) e = mark_nothing_recorded(cam, split_state, st);
+        if (e == hipSuccess && cam.chain > 1) e = clear_handover_flags(cam, split_state, st);      // (the segmented kernels do not clear them)
         if (e != hipSuccess) return e;
         const dim3 grid(nb, segments);
         if (out_depth_sq) { GS_FWD(true, 1, grid); GS_FWD(true, 2, grid); }
@@ -1316,7 +1315,7 @@ hipError_t launch_blend_forward(const Cam& cam_in, const uint2* ranges, const ui
     } else if (cam.half || cam.split) {
         // images of few tiles: one producer / consumer workgroup per tile
         if (cam.chain > 1) {      // (an image of more than kFewTiles tiles sent here by gs_set_half_quadrants: this kernel does not clear the hand-over flags)
-            hipError_t e = hipMemsetAsync(split_state + (size_t)cam.gx * cam.gy * 4 * kChainStateFloats, 0, chain_flag_words((size_t)cam.gx * cam.gy) * sizeof(uint32_t), st);
+            hipError_t e = clear_handover_flags(cam, split_state, st);
             if (e != hipSuccess) return e;
         }
         const dim3 grid(((cam.gx * cam.gy + 7) >> 3) << 3), block(kPcWaves * kWave);
@@ -1328,7 +1327,7 @@ hipError_t launch_blend_forward(const Cam& cam_in, const uint2* ranges, const ui
                                final_T, n_contrib, out_depth_sq, cap, split_state, P, (float4*)zero_fill);
     } else {
         if (split_state && cam.gx * cam.gy <= kFewTiles) {          // a small image with the few-tile paths switched off: "nothing recorded"
-            hipError_t e = hipMemsetAsync(split_state + (kCutLevels * 5 + 4) * HW, 0, sizeof(uint32_t), st);
+            hipError_t e = mark_nothing_recorded(cam, split_state, st);
             if (e != hipSuccess) return e;
         }
         if (out_depth_sq) GS_FWD(true, 0, dim3(nb)); else GS_FWD(false, 0, dim3(nb));
