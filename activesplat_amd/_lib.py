@@ -66,11 +66,16 @@ class GsMeshLayout(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("total_bytes", "total", "records", "rects", "tile_count", "tile_offset", "list")]
 
 
+class GsImageGrads(C.Structure):
+    """dL/d of the four image outputs (include/gsplat_hip.h); all but dL_dcolor nullable"""
+    _fields_ = [(n, C.c_void_p) for n in ("dL_dcolor", "dL_ddepth", "dL_dopacity", "dL_ddepth_sq")]
+
+
 SORT_AUTO, SORT_TILE_LDS, SORT_RADIX = 0, 1, 2
 
 
 #: the GS_ABI_VERSION of include/gsplat_hip.h this binding was written against (checked when a library is bound)
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 vp, i32, u32, i64, u64, f32, f64, cint = C.c_void_p, C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_int
 
@@ -137,6 +142,12 @@ BINDINGS = {
     "gs_pose_grad_scratch_bytes": (u64, [i32]),
     # (cam, P, D, means3D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, h_pose7, isotropic, accumulate, radii, geom_state, point_list, image_state, dL_dcolor, dL_ddepth, dL_dmeans2D, dL_dmeans3D, dL_dlogit_opacities, dL_dcolors_precomp, dL_dshs, dL_dlog_scales, dL_dunnorm_rotations, scratch, scratch_zeroed, have_sh_jacobian, pose_only, dL_dpose7, pose_scratch, stream)
     "gs_render_backward_raw_pose": (cint, [C.POINTER(GsCamera), i32, i64] + [vp] * 7 + [i32, i32] + [vp] * 14 + [i32, i32, i32, vp, vp, vp]),
+    # (cam, P, D, means3D, shs, colors_precomp, scales, rotations, cov3D_precomp, radii, geom_state, point_list, image_state, grads, dL_dmeans2D, dL_dmeans3D, dL_dopacities, dL_dcolors_precomp, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, scratch, scratch_zeroed, have_sh_jacobian, stream)
+    "gs_render_backward_grads": (cint, [C.POINTER(GsCamera), i32, i64] + [vp] * 10 + [C.POINTER(GsImageGrads)] + [vp] * 9 + [i32, i32, vp]),
+    # (cam, P, D, means3D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, h_pose7, isotropic, accumulate, radii, geom_state, point_list, image_state, grads, dL_dmeans2D, dL_dmeans3D, dL_dlogit_opacities, dL_dcolors_precomp, dL_dshs, dL_dlog_scales, dL_dunnorm_rotations, scratch, scratch_zeroed, have_sh_jacobian, stream)
+    "gs_render_backward_raw_grads": (cint, [C.POINTER(GsCamera), i32, i64] + [vp] * 7 + [i32, i32] + [vp] * 4 + [C.POINTER(GsImageGrads)] + [vp] * 8 + [i32, i32, vp]),
+    # (cam, P, D, means3D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, h_pose7, isotropic, accumulate, radii, geom_state, point_list, image_state, grads, dL_dmeans2D, dL_dmeans3D, dL_dlogit_opacities, dL_dcolors_precomp, dL_dshs, dL_dlog_scales, dL_dunnorm_rotations, scratch, scratch_zeroed, have_sh_jacobian, pose_only, dL_dpose7, pose_scratch, stream)
+    "gs_render_backward_raw_pose_grads": (cint, [C.POINTER(GsCamera), i32, i64] + [vp] * 7 + [i32, i32] + [vp] * 4 + [C.POINTER(GsImageGrads)] + [vp] * 8 + [i32, i32, i32, vp, vp, vp]),
     # (n, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, stream)
     "gs_adam_step": (cint, [i64] + [vp] * 4 + [f64] * 4 + [i32, vp]),
     # (count, tensors, stream)

@@ -620,6 +620,7 @@ struct BackwardCall {
     int32_t isotropic, accumulate;
     const void* geom_state; const uint32_t* point_list; const void* image_state;
     const float* dL_dcolor; const float* dL_ddepth;
+    const float* dL_dopacity; const float* dL_ddepth_sq;      // the opt-in image gradients (GsImageGrads; the *_grads entry points only)
     void* scratch; int32_t scratch_zeroed, have_sh_jacobian;
     const GsAdamTensor* adam5;
 };
@@ -644,6 +645,8 @@ static int render_backward_impl(const GsCamera* cam, const BackwardCall& c, gs_s
     if (pose.grad && (!k.act || c.adam5 || (!pose.dL_dpose7 && pose.source != gs::POSE_DEVICE) || !pose.pose_scratch))
         return fail(GS_EINVAL, "gs_render_backward_raw_pose: raw-parameter mode with a pose-gradient output and its scratch only");
     if (pose.source == gs::POSE_DEVICE && !pose_only) return fail(GS_EINVAL, "gs_render_backward_raw_pose_dev: the pose-only backward only");
+    if ((c.dL_dopacity || c.dL_ddepth_sq) && (c.adam5 || pose.source == gs::POSE_DEVICE))
+        return fail(GS_EINVAL, "gs_render_backward: opacity / depth_sq gradients have no optimiser-step or device-pose form");
     if (P == 0) {
         if (pose.grad && pose.dL_dpose7)
             return launched("gs_render_backward_raw_pose", "memset", hipMemsetAsync(pose.dL_dpose7, 0, 7 * sizeof(float), (hipStream_t)stream));
@@ -694,7 +697,7 @@ static int render_backward_impl(const GsCamera* cam, const BackwardCall& c, gs_s
         e = gs::launch_blend_backward(k, (const uint2*)(ib + IL.ranges), c.point_list, gp.geom,
                                       (const float*)(ib + IL.split_state),
                                       (const float*)(ib + IL.final_T),
-                                      (const uint32_t*)(ib + IL.n_contrib), c.dL_dcolor, c.dL_ddepth, grad2d, st);
+                                      (const uint32_t*)(ib + IL.n_contrib), c.dL_dcolor, c.dL_ddepth, grad2d, st, c.dL_dopacity, c.dL_ddepth_sq);
         if (int rc = launched("gs_render_backward", "blend", e)) return rc;
     }
     g.clamped = gp.clamped; g.sh_jac = (in.shs && c.have_sh_jacobian) ? gp.sh_jac : nullptr; g.grad2d = grad2d;
@@ -715,6 +718,24 @@ static int render_backward_impl(const GsCamera* cam, const BackwardCall& c, gs_s
     return GS_OK;
 }
 
+int gs_render_backward_grads(const GsCamera* cam, int32_t P, int64_t D, const float* means3D, const float* shs,
+                       const float* colors_precomp, const float* scales, const float* rotations,
+                       const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
+                       const uint32_t* point_list, const void* image_state, const GsImageGrads* grads, float* dL_dmeans2D, float* dL_dmeans3D, float* dL_dopacities, float* dL_dcolors_precomp,
+                       float* dL_dshs, float* dL_dscales, float* dL_drotations, float* dL_dcov3D, void* scratch,
+                       int32_t scratch_zeroed, int32_t have_sh_jacobian, gs_stream_t stream)
+{
+    if (!grads) return fail(GS_EINVAL, "gs_render_backward_grads: null image-gradient block");
+    BackwardCall c{};
+    c.P = P; c.D = D;
+    c.g.in.means3D = means3D; c.g.in.shs = shs; c.g.in.colors = colors_precomp; c.g.in.scales = scales; c.g.in.rots = rotations; c.g.in.cov3D = cov3D_precomp;
+    c.g.radii = radii; c.geom_state = geom_state; c.point_list = point_list; c.image_state = image_state; c.dL_dcolor = grads->dL_dcolor; c.dL_ddepth = grads->dL_ddepth; c.dL_dopacity = grads->dL_dopacity; c.dL_ddepth_sq = grads->dL_ddepth_sq;
+    c.g.out.dmeans2D = dL_dmeans2D; c.g.out.dmeans3D = dL_dmeans3D; c.g.out.dopac = dL_dopacities; c.g.out.dcolors = dL_dcolors_precomp;
+    c.g.out.dshs = dL_dshs; c.g.out.dscales = dL_dscales; c.g.out.drots = dL_drotations; c.g.out.dcov3D = dL_dcov3D;
+    c.scratch = scratch; c.scratch_zeroed = scratch_zeroed; c.have_sh_jacobian = have_sh_jacobian;
+    return render_backward_impl(cam, c, stream);
+}
+
 int gs_render_backward(const GsCamera* cam, int32_t P, int64_t D, const float* means3D, const float* shs,
                        const float* colors_precomp, const float* scales, const float* rotations,
                        const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
@@ -723,12 +744,26 @@ int gs_render_backward(const GsCamera* cam, int32_t P, int64_t D, const float* m
                        float* dL_dshs, float* dL_dscales, float* dL_drotations, float* dL_dcov3D, void* scratch,
                        int32_t scratch_zeroed, int32_t have_sh_jacobian, gs_stream_t stream)
 {
+    // (the two new images NULL: the kernels of every call before GsImageGrads)
+    const GsImageGrads grads{dL_dcolor, dL_ddepth, nullptr, nullptr};
+    return gs_render_backward_grads(cam, P, D, means3D, shs, colors_precomp, scales, rotations, cov3D_precomp, radii, geom_state, point_list, image_state, &grads, dL_dmeans2D, dL_dmeans3D, dL_dopacities, dL_dcolors_precomp, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, scratch, scratch_zeroed, have_sh_jacobian, stream);
+}
+
+int gs_render_backward_raw_grads(const GsCamera* cam, int32_t P, int64_t D, const float* means3D, const float* shs, const float* colors_precomp,
+                           const float* logit_opacities, const float* log_scales, const float* unnorm_rotations, const float* h_pose7,
+                           int32_t isotropic, int32_t accumulate, const int32_t* radii, const void* geom_state, const uint32_t* point_list,
+                           const void* image_state, const GsImageGrads* grads, float* dL_dmeans2D, float* dL_dmeans3D,
+                           float* dL_dlogit_opacities, float* dL_dcolors_precomp, float* dL_dshs, float* dL_dlog_scales,
+                           float* dL_dunnorm_rotations, void* scratch, int32_t scratch_zeroed, int32_t have_sh_jacobian, gs_stream_t stream)
+{
+    if (!grads) return fail(GS_EINVAL, "gs_render_backward_raw_grads: null image-gradient block");
+    if (!h_pose7 || (P > 0 && !logit_opacities)) return fail(GS_EINVAL, "gs_render_backward_raw: null pose / opacity parameters");
     BackwardCall c{};
-    c.P = P; c.D = D;
-    c.g.in.means3D = means3D; c.g.in.shs = shs; c.g.in.colors = colors_precomp; c.g.in.scales = scales; c.g.in.rots = rotations; c.g.in.cov3D = cov3D_precomp;
-    c.g.radii = radii; c.geom_state = geom_state; c.point_list = point_list; c.image_state = image_state; c.dL_dcolor = dL_dcolor; c.dL_ddepth = dL_ddepth;
-    c.g.out.dmeans2D = dL_dmeans2D; c.g.out.dmeans3D = dL_dmeans3D; c.g.out.dopac = dL_dopacities; c.g.out.dcolors = dL_dcolors_precomp;
-    c.g.out.dshs = dL_dshs; c.g.out.dscales = dL_dscales; c.g.out.drots = dL_drotations; c.g.out.dcov3D = dL_dcov3D;
+    c.g.in.means3D = means3D; c.g.in.shs = shs; c.g.in.colors = colors_precomp; c.g.in.opac = logit_opacities; c.g.in.scales = log_scales; c.g.in.rots = unnorm_rotations;
+    c.P = P; c.D = D; c.pose.source = gs::POSE_HOST; c.pose.pose7 = h_pose7; c.isotropic = isotropic; c.accumulate = accumulate;
+    c.g.radii = radii; c.geom_state = geom_state; c.point_list = point_list; c.image_state = image_state; c.dL_dcolor = grads->dL_dcolor; c.dL_ddepth = grads->dL_ddepth; c.dL_dopacity = grads->dL_dopacity; c.dL_ddepth_sq = grads->dL_ddepth_sq;
+    c.g.out.dmeans2D = dL_dmeans2D; c.g.out.dmeans3D = dL_dmeans3D; c.g.out.dopac = dL_dlogit_opacities; c.g.out.dcolors = dL_dcolors_precomp;
+    c.g.out.dshs = dL_dshs; c.g.out.dscales = dL_dlog_scales; c.g.out.drots = dL_dunnorm_rotations;
     c.scratch = scratch; c.scratch_zeroed = scratch_zeroed; c.have_sh_jacobian = have_sh_jacobian;
     return render_backward_impl(cam, c, stream);
 }
@@ -740,18 +775,34 @@ int gs_render_backward_raw(const GsCamera* cam, int32_t P, int64_t D, const floa
                            float* dL_dlogit_opacities, float* dL_dcolors_precomp, float* dL_dshs, float* dL_dlog_scales,
                            float* dL_dunnorm_rotations, void* scratch, int32_t scratch_zeroed, int32_t have_sh_jacobian, gs_stream_t stream)
 {
-    if (!h_pose7 || (P > 0 && !logit_opacities)) return fail(GS_EINVAL, "gs_render_backward_raw: null pose / opacity parameters");
+    // (the two new images NULL: the kernels of every call before GsImageGrads)
+    const GsImageGrads grads{dL_dcolor, dL_ddepth, nullptr, nullptr};
+    return gs_render_backward_raw_grads(cam, P, D, means3D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, h_pose7, isotropic, accumulate, radii, geom_state, point_list, image_state, &grads, dL_dmeans2D, dL_dmeans3D, dL_dlogit_opacities, dL_dcolors_precomp, dL_dshs, dL_dlog_scales, dL_dunnorm_rotations, scratch, scratch_zeroed, have_sh_jacobian, stream);
+}
+
+uint64_t gs_pose_grad_scratch_bytes(int32_t P) { return align_up((uint64_t)gs::pose_rows_count(P > 0 ? P : 1) * gs::kPoseAcc * 4); }
+
+int gs_render_backward_raw_pose_grads(const GsCamera* cam, int32_t P, int64_t D, const float* means3D, const float* shs, const float* colors_precomp,
+                                const float* logit_opacities, const float* log_scales, const float* unnorm_rotations, const float* h_pose7,
+                                int32_t isotropic, int32_t accumulate, const int32_t* radii, const void* geom_state, const uint32_t* point_list,
+                                const void* image_state, const GsImageGrads* grads, float* dL_dmeans2D, float* dL_dmeans3D,
+                                float* dL_dlogit_opacities, float* dL_dcolors_precomp, float* dL_dshs, float* dL_dlog_scales,
+                                float* dL_dunnorm_rotations, void* scratch, int32_t scratch_zeroed, int32_t have_sh_jacobian, int32_t pose_only,
+                                float* dL_dpose7, void* pose_scratch, gs_stream_t stream)
+{
+    if (!grads) return fail(GS_EINVAL, "gs_render_backward_raw_pose_grads: null image-gradient block");
+    if (!h_pose7 || (P > 0 && !logit_opacities)) return fail(GS_EINVAL, "gs_render_backward_raw_pose: null pose / opacity parameters");
+    if (!dL_dpose7 || !pose_scratch) return fail(GS_EINVAL, "gs_render_backward_raw_pose: null pose-gradient output or scratch");
     BackwardCall c{};
     c.g.in.means3D = means3D; c.g.in.shs = shs; c.g.in.colors = colors_precomp; c.g.in.opac = logit_opacities; c.g.in.scales = log_scales; c.g.in.rots = unnorm_rotations;
     c.P = P; c.D = D; c.pose.source = gs::POSE_HOST; c.pose.pose7 = h_pose7; c.isotropic = isotropic; c.accumulate = accumulate;
-    c.g.radii = radii; c.geom_state = geom_state; c.point_list = point_list; c.image_state = image_state; c.dL_dcolor = dL_dcolor; c.dL_ddepth = dL_ddepth;
+    c.pose.grad = pose_only ? gs::POSE_GRAD_ONLY : gs::POSE_GRAD_WITH_PARAMS; c.pose.dL_dpose7 = dL_dpose7; c.pose.pose_scratch = pose_scratch;
+    c.g.radii = radii; c.geom_state = geom_state; c.point_list = point_list; c.image_state = image_state; c.dL_dcolor = grads->dL_dcolor; c.dL_ddepth = grads->dL_ddepth; c.dL_dopacity = grads->dL_dopacity; c.dL_ddepth_sq = grads->dL_ddepth_sq;
     c.g.out.dmeans2D = dL_dmeans2D; c.g.out.dmeans3D = dL_dmeans3D; c.g.out.dopac = dL_dlogit_opacities; c.g.out.dcolors = dL_dcolors_precomp;
     c.g.out.dshs = dL_dshs; c.g.out.dscales = dL_dlog_scales; c.g.out.drots = dL_dunnorm_rotations;
     c.scratch = scratch; c.scratch_zeroed = scratch_zeroed; c.have_sh_jacobian = have_sh_jacobian;
     return render_backward_impl(cam, c, stream);
 }
-
-uint64_t gs_pose_grad_scratch_bytes(int32_t P) { return align_up((uint64_t)gs::pose_rows_count(P > 0 ? P : 1) * gs::kPoseAcc * 4); }
 
 int gs_render_backward_raw_pose(const GsCamera* cam, int32_t P, int64_t D, const float* means3D, const float* shs, const float* colors_precomp,
                                 const float* logit_opacities, const float* log_scales, const float* unnorm_rotations, const float* h_pose7,
@@ -761,17 +812,9 @@ int gs_render_backward_raw_pose(const GsCamera* cam, int32_t P, int64_t D, const
                                 float* dL_dunnorm_rotations, void* scratch, int32_t scratch_zeroed, int32_t have_sh_jacobian, int32_t pose_only,
                                 float* dL_dpose7, void* pose_scratch, gs_stream_t stream)
 {
-    if (!h_pose7 || (P > 0 && !logit_opacities)) return fail(GS_EINVAL, "gs_render_backward_raw_pose: null pose / opacity parameters");
-    if (!dL_dpose7 || !pose_scratch) return fail(GS_EINVAL, "gs_render_backward_raw_pose: null pose-gradient output or scratch");
-    BackwardCall c{};
-    c.g.in.means3D = means3D; c.g.in.shs = shs; c.g.in.colors = colors_precomp; c.g.in.opac = logit_opacities; c.g.in.scales = log_scales; c.g.in.rots = unnorm_rotations;
-    c.P = P; c.D = D; c.pose.source = gs::POSE_HOST; c.pose.pose7 = h_pose7; c.isotropic = isotropic; c.accumulate = accumulate;
-    c.pose.grad = pose_only ? gs::POSE_GRAD_ONLY : gs::POSE_GRAD_WITH_PARAMS; c.pose.dL_dpose7 = dL_dpose7; c.pose.pose_scratch = pose_scratch;
-    c.g.radii = radii; c.geom_state = geom_state; c.point_list = point_list; c.image_state = image_state; c.dL_dcolor = dL_dcolor; c.dL_ddepth = dL_ddepth;
-    c.g.out.dmeans2D = dL_dmeans2D; c.g.out.dmeans3D = dL_dmeans3D; c.g.out.dopac = dL_dlogit_opacities; c.g.out.dcolors = dL_dcolors_precomp;
-    c.g.out.dshs = dL_dshs; c.g.out.dscales = dL_dlog_scales; c.g.out.drots = dL_dunnorm_rotations;
-    c.scratch = scratch; c.scratch_zeroed = scratch_zeroed; c.have_sh_jacobian = have_sh_jacobian;
-    return render_backward_impl(cam, c, stream);
+    // (the two new images NULL: the kernels of every call before GsImageGrads)
+    const GsImageGrads grads{dL_dcolor, dL_ddepth, nullptr, nullptr};
+    return gs_render_backward_raw_pose_grads(cam, P, D, means3D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, h_pose7, isotropic, accumulate, radii, geom_state, point_list, image_state, &grads, dL_dmeans2D, dL_dmeans3D, dL_dlogit_opacities, dL_dcolors_precomp, dL_dshs, dL_dlog_scales, dL_dunnorm_rotations, scratch, scratch_zeroed, have_sh_jacobian, pose_only, dL_dpose7, pose_scratch, stream);
 }
 
 int gs_render_backward_raw_pose_dev(const GsCamera* cam, int32_t P, int64_t D, const float* means3D, const float* shs, const float* colors_precomp,

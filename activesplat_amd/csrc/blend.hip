@@ -811,7 +811,8 @@ __global__ __launch_bounds__(kPcWaves * kWave) void blend_forward_pc_kernel(
 // preprocess_bwd.hip):  with Z = G dL/dG, d = mean - pixel
 //   0: sum Z dx   1: sum Z dy   2: sum Z dx dx   3: sum Z dx dy   4: sum Z dy dy   5: sum G dL/dalpha   6..8: sum w dL/dC
 //   9: sum w dL/d(depth)   (DEPTH_GRAD: the depth output is one more blended channel whose per-Gaussian value is the
-//      view-space z; this is the fused replacement of the reference's second, [z,1,z^2] raster pass)
+//      view-space z; this is the fused replacement of the reference's second, [z,1,z^2] raster pass).  With the opt-in depth_sq gradient
+//      (OUT = 2) it is the whole dL/dz of the record: sum w (dL/d(depth) + 2 z dL/d(depth_sq))
 //
 // The expensive part of a one-phase walk (round 1: 213 us on BASELINE configs[1]) was summing those ten moments over the 16 pixels
 // of a row for every (row, record) pair: a transposed DPP butterfly (35 DPP adds + selects per two-record iteration, each a 4.2-cycle
@@ -844,18 +845,39 @@ constexpr int kMT = kWave + 4;         // floats per position in an exchange pla
 constexpr int kPairStride = 12;        // floats per pair / record slot in the sum exchanges: components 0-4 at [0,5), 5-9 at [6,11)
 constexpr int kMPlane = (kBT - 1) * kMT + kWave;   // floats of one exchange plane
 
-template <bool DEPTH_GRAD, int NW, bool FEW = false>        // FEW: two or three list segments per quadrant (images of few tiles)
+// the k-th of a kernel's trailing image-gradient arguments (OUT instantiations of blend_backward_kernel; folds to the argument itself)
+template <class... E>
+__device__ __forceinline__ const float* extra_image(int k, E... e)
+{
+    const float* const all[] = {e..., nullptr};
+    return all[k];
+}
+
+// OUT (opt-in gradients of the other image outputs; the instantiations with OUT = 0 and no trailing arguments are those of every call that
+// does not ask for them, unchanged): the kernel takes two more images, dL/dopacity and dL/ddepth_sq, each nullable -- as is dL_ddepth there.
+//   opacity  O = 1 - T_final, dO/dalpha_i = T_final / (1 - alpha_i): the background term of dL/dalpha with the opposite sign -- one per-pixel
+//            scalar in the prologue, nothing per record; list segments and chained pieces are untouched;
+//   depth_sq Q = sum z^2 alpha T (OUT = 2): one more blended channel of per-Gaussian value z^2 in phase A's dot, its dL/dQ in a second
+//            256-byte LDS plane next to dL/ddepth's.  dL/dz_i = sum_pix w (dL/dD + 2 z_i dL/dQ), and z_i is a constant of the record phase B
+//            already holds: the pair sum of w dL/dQ is folded into moment 9 there (sm[9] += 2 z_i sum w dL/dQ) -- no eleventh moment, the
+//            gradient record, the flush and the per-Gaussian kernels stay as they are.  The forward records no sum z^2 state for resumed list
+//            segments, so OUT = 2 is never FEW: launch_blend_backward walks such a call with one walker per quadrant.
+template <bool DEPTH_GRAD, int NW, bool FEW = false, int OUT = 0, class... Extra>        // FEW: two or three list segments per quadrant (images of few tiles)
 __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(3, 3))) void blend_backward_kernel(
     Cam cam, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
     const float4* __restrict__ geom, const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
     const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth, float* __restrict__ grad2d,
-    const float* __restrict__ split_state)
+    const float* __restrict__ split_state, Extra... extra)
 {
+    static_assert(OUT == 0 ? sizeof...(Extra) == 0 : (sizeof...(Extra) == 2 && DEPTH_GRAD), "OUT: dL_dopacity and dL_ddepth_sq trail the arguments");
+    static_assert(OUT != 2 || !FEW, "no recorded sum z^2 state: depth_sq gradients walk with one walker per quadrant");
+    constexpr bool DSQ = OUT == 2;
     __shared__ float4 s_rec[NW][3][kWave + 1];           // + the sentinel slot
     __shared__ __attribute__((aligned(16))) uint8_t s_list[NW][4 * kWave + 16];
     __shared__ __attribute__((aligned(16))) float s_m[NW][2][kMPlane];
     __shared__ uint8_t s_flag[NW][kWave];                // per staging slot: which of the four blocks the record's box meets
     __shared__ __attribute__((aligned(16))) float s_ez[DEPTH_GRAD ? NW : 1][DEPTH_GRAD ? kWave : 4];      // dL/ddepth of the quadrant, (block, pixel) order
+    __shared__ __attribute__((aligned(16))) float s_eq[DSQ ? NW : 1][DSQ ? kWave : 4];                    // (OUT = 2) dL/ddepth_sq, the same order
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     TileCtx c;
     const int nseg = FEW ? cam.split : 0;                    // 0: one walker per quadrant; 2 / 3: list segments (walkers) per quadrant
@@ -929,8 +951,19 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(3, 3
     if (k_hi >= 0) { last = min(last, seg_hi); wmax = min(wmax, seg_hi); }
     const float d0 = inside ? dL_dcolor[pix] : 0.f, d1 = inside ? dL_dcolor[HW + pix] : 0.f,
                 d2 = inside ? dL_dcolor[2 * HW + pix] : 0.f;
-    const float dz_ = (DEPTH_GRAD && inside) ? dL_ddepth[pix] : 0.f;
-    const float tfbg = Tf * (cam.bg[0] * d0 + cam.bg[1] * d1 + cam.bg[2] * d2);    // background term of dL/dalpha
+    float dz_ = 0.f, do_ = 0.f, dq_ = 0.f;                   // this pixel's dL/ddepth, dL/dopacity, dL/ddepth_sq
+    if constexpr (OUT != 0) {
+        const float* const dL_dopacity = extra_image(0, extra...);
+        const float* const dL_ddepth_sq = extra_image(1, extra...);
+        if (inside && dL_ddepth) dz_ = dL_ddepth[pix];
+        if (inside && dL_dopacity) do_ = dL_dopacity[pix];
+        if (DSQ && inside && dL_ddepth_sq) dq_ = dL_ddepth_sq[pix];
+    } else {
+        dz_ = (DEPTH_GRAD && inside) ? dL_ddepth[pix] : 0.f;
+    }
+    // background term of dL/dalpha: C = ... + T_final bg and O = 1 - T_final both hang on alpha_i through T_final / (1 - alpha_i)
+    const float tfbg = OUT != 0 ? Tf * ((cam.bg[0] * d0 + cam.bg[1] * d1 + cam.bg[2] * d2) - do_)
+                                : Tf * (cam.bg[0] * d0 + cam.bg[1] * d1 + cam.bg[2] * d2);
     // The colour blended BEHIND the current record enters the replay only through its product with this pixel's dL/dcolour (and
     // dL/ddepth): one scalar S = behind . dL instead of a three- (four-) component accumulator -- dot = c . dL - S, S += alpha dot
     // (four vector operations per record less than the component-wise form)
@@ -975,6 +1008,7 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(3, 3
         float* xs = s_m[wave][0];
         xs[lane] = d0; xs[kWave + lane] = d1; xs[2 * kWave + lane] = d2;
         if (DEPTH_GRAD) s_ez[wave][lane] = dz_;
+        if (DSQ) s_eq[wave][lane] = dq_;
         __builtin_amdgcn_wave_barrier();
         const float4* x4 = reinterpret_cast<const float4*>(xs + rb * 16);
 #pragma unroll
@@ -1117,7 +1151,8 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(3, 3
                     T = T * rcp;                                      // transmittance in front of this record
                     float cd = a1[u].z * d0 + a1[u].w * d1 + a2[u].x * d2;
                     if (DEPTH_GRAD) cd += a2[u].z * dz_;
-                    const float dot = cd - S;                         // (colour of this record - colour behind it) . dL
+                    if (DSQ) cd += (a2[u].z * a2[u].z) * dq_;
+                    const float dot = cd - S;                        // (colour of this record - colour behind it) . dL
                     const float dL_dalpha = dot * T - tfbg * rcp;
                     S += a_eff * dot;
                     const float GdA = G_eff * dL_dalpha;
@@ -1169,6 +1204,17 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(3, 3
                         const float4 z = z4[v];
                         sm[9] = fmaf(ww[4 * v + 3], z.w, fmaf(ww[4 * v + 2], z.z, fmaf(ww[4 * v + 1], z.y, fmaf(ww[4 * v], z.x, sm[9]))));
                     }
+                }
+                if (DSQ) {
+                    // dL/dz of this record through the depth_sq channel: 2 z sum w dL/dQ, added to the depth channel's moment
+                    const float4* q4 = reinterpret_cast<const float4*>(s_eq[wave] + rb * 16);
+                    float sq = 0.0f;
+#pragma unroll
+                    for (int v = 0; v < 4; v++) {
+                        const float4 z = q4[v];
+                        sq = fmaf(ww[4 * v + 3], z.w, fmaf(ww[4 * v + 2], z.z, fmaf(ww[4 * v + 1], z.y, fmaf(ww[4 * v], z.x, sq))));
+                    }
+                    sm[9] = fmaf(2.0f * s2[jjb].z, sq, sm[9]);
                 }
                 // pair sums -> LDS (over the scalars just consumed: every lane has issued its reads; LDS serves a wave in order),
                 // then every RECORD lane picks up the pairs of its record
@@ -1350,7 +1396,7 @@ hipError_t launch_blend_topdown(const Cam& cam_in, const uint2* ranges, const ui
 
 hipError_t launch_blend_backward(const Cam& cam_in, const uint2* ranges, const uint32_t* point_list, const float4* geom, const float* split_state,
                                  const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor,
-                                 const float* dL_ddepth, float* grad2d, hipStream_t st)
+                                 const float* dL_ddepth, float* grad2d, hipStream_t st, const float* dL_dopacity, const float* dL_ddepth_sq)
 {
     // one-wavefront workgroups (see blend_backward_kernel): per XCD band ceil(tiles/8) tiles x 4 quadrants; images of few tiles: x 2 list
     // segments (the forward of such an image has recorded the state at the cut; if it has not, the back walkers exit at once)
@@ -1359,6 +1405,9 @@ hipError_t launch_blend_backward(const Cam& cam_in, const uint2* ranges, const u
     const int k_half = g_half_quadrant_tiles.load(std::memory_order_relaxed), k_fseg = g_few_segments.load(std::memory_order_relaxed);
     const int k_pieces = g_chain_pieces.load(std::memory_order_relaxed), k_min = g_chain_min_tiles.load(std::memory_order_relaxed);
     cam.split = (split_state != nullptr && cam.gx * cam.gy <= min(k_half, kFewTiles) && k_fseg > 1) ? k_fseg : 0;
+    // a call that carries dL/ddepth_sq walks with one walker per quadrant, whatever gs_set_backward_segments says: the states the forward
+    // records for resumed segments hold no sum z^2 (split_state: T, C0-C2, Dp per level).  Chained pieces hand over (T, S) only and need nothing.
+    if (dL_ddepth_sq) cam.split = 0;
     cam.chain = (cam.V == 1 && split_state && cam.gx * cam.gy > max(k_min, kFewTiles) && k_pieces > 1) ? k_pieces : 0;
     static std::atomic<unsigned> epoch{0};
     do { cam.chain_epoch = ++epoch; } while (cam.chain_epoch == 0u);          // (the forward leaves zero in the hand-over flags)
@@ -1369,8 +1418,15 @@ hipError_t launch_blend_backward(const Cam& cam_in, const uint2* ranges, const u
 #define GS_BWD(DG, FEW)                                                                                                          \
     hipLaunchKernelGGL((blend_backward_kernel<DG, 1, FEW>), dim3(per * 8 * 4), dim3(kWave), 0, st, cam, ranges, point_list, geom, final_T, \
                        n_contrib, dL_dcolor, dL_ddepth, grad2d, split_state)
-    if (cam.split) { if (dL_ddepth) GS_BWD(true, true); else GS_BWD(false, true); }
+    // the opt-in image gradients: their own instantiations (every pointer of theirs nullable), two trailing arguments
+#define GS_BWD_OUT(FEW, OUT)                                                                                                     \
+    hipLaunchKernelGGL((blend_backward_kernel<true, 1, FEW, OUT, const float*, const float*>), dim3(per * 8 * 4), dim3(kWave), 0, st, cam, ranges, \
+                       point_list, geom, final_T, n_contrib, dL_dcolor, dL_ddepth, grad2d, split_state, dL_dopacity, dL_ddepth_sq)
+    if (dL_ddepth_sq) GS_BWD_OUT(false, 2);
+    else if (dL_dopacity) { if (cam.split) GS_BWD_OUT(true, 1); else GS_BWD_OUT(false, 1); }
+    else if (cam.split) { if (dL_ddepth) GS_BWD(true, true); else GS_BWD(false, true); }
     else { if (dL_ddepth) GS_BWD(true, false); else GS_BWD(false, false); }
+#undef GS_BWD_OUT
 #undef GS_BWD
     return hipGetLastError();
 }

@@ -851,7 +851,8 @@ hipError_t launch_blend_topdown(const Cam& cam, const uint2* ranges, const uint3
                                 uint8_t* free_binary, uint8_t* visible_rgb, uint8_t* visible_binary, uint32_t cap, uint32_t P, hipStream_t st);
 hipError_t launch_blend_backward(const Cam& cam, const uint2* ranges, const uint32_t* point_list, const float4* geom, const float* split_state,
                                  const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor,
-                                 const float* dL_ddepth, float* grad2d, hipStream_t st);
+                                 const float* dL_ddepth, float* grad2d, hipStream_t st, const float* dL_dopacity = nullptr,
+                                 const float* dL_ddepth_sq = nullptr);      // (the two opt-in image gradients: GsImageGrads, gsplat_hip.h)
 hipError_t launch_adam_multi(int count, const GsAdamTensor* tensors, hipStream_t st);
 hipError_t launch_rows(int mode, int count, const GsRowTensor* t, int64_t row0, int64_t n_valid, int64_t n_rows, const float* in, float* out,
                        hipStream_t st);

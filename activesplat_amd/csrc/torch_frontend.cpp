@@ -139,8 +139,10 @@ struct Rasterize : public torch::autograd::Function<Rasterize> {
     static variable_list forward(AutogradContext* ctx, Tensor means3D, std::optional<Tensor> means2D_, std::optional<Tensor> shs_, std::optional<Tensor> colors_,
                                  Tensor opacities, std::optional<Tensor> scales_, std::optional<Tensor> rotations_, std::optional<Tensor> cov3D_, Tensor bg,
                                  Tensor view, Tensor proj, Tensor campos, int64_t W, int64_t H, double tanfovx, double tanfovy, double scale_modifier,
-                                 int64_t sh_degree, bool fused, int64_t guess_d, int64_t guess_tile, bool want_bwd)
+                                 int64_t sh_degree, bool fused, int64_t guess_d, int64_t guess_tile, bool want_bwd, int64_t outputs)
     {
+        // outputs (differentiable_outputs= of the Python calls): -1 = the call's default (fused: depth; else none), else bit 0 depth, bit 1
+        // opacity, bit 2 depth_sq -- the image outputs besides the colour that carry a gradient; the others are marked non-differentiable
         const at::Device dev = means3D.device();
         const int P = (int)means3D.size(0);
         auto un = [](const std::optional<Tensor>& t) { return t.has_value() ? *t : Tensor(); };
@@ -217,9 +219,18 @@ struct Rasterize : public torch::autograd::Function<Rasterize> {
         ctx->save_for_backward({means3D, shs, colors, scales, rotations, cov3D, radii, ws, plist2, bg, view, proj, campos});
         auto& sd = ctx->saved_data;
         sd["W"] = W; sd["H"] = H; sd["tanfovx"] = tanfovx; sd["tanfovy"] = tanfovy; sd["mod"] = scale_modifier; sd["sh_degree"] = sh_degree;
-        sd["fused"] = fused; sd["D"] = D; sd["want_bwd"] = want_bwd; sd["clean"] = need_scratch;
+        sd["fused"] = fused; sd["outputs"] = outputs; sd["D"] = D; sd["want_bwd"] = want_bwd; sd["clean"] = need_scratch;
         sd["o_image"] = (int64_t)o_image; sd["o_scratch"] = (int64_t)(need_scratch ? o_scratch : 0); sd["o_plist"] = (int64_t)o_plist;
         ctx->set_materialize_grads(false);
+        if (outputs >= 0) {
+            variable_list fixed{radii};
+            if (!(outputs & 1)) fixed.push_back(depth);
+            if (!(outputs & 2)) fixed.push_back(opacity);
+            if (fused && !(outputs & 4)) fixed.push_back(depth_sq);
+            ctx->mark_non_differentiable(fixed);
+            if (fused) return {color, radii, depth, opacity, depth_sq};
+            return {color, radii, depth, opacity};
+        }
         if (fused) {
             ctx->mark_non_differentiable({radii, opacity, depth_sq});
             return {color, radii, depth, opacity, depth_sq};
@@ -242,7 +253,12 @@ struct Rasterize : public torch::autograd::Function<Rasterize> {
                      (float)sd["mod"].toDouble(), 0, fp(bg), fp(view), fp(proj), fp(campos)};
         auto f_opts = at::TensorOptions().dtype(at::kFloat).device(dev);
         Tensor g_color = grads[0].defined() ? f32(grads[0], dev) : at::zeros({3, H, W}, f_opts);
-        Tensor g_depth = (fused && grads.size() > 2 && grads[2].defined()) ? f32(grads[2], dev) : Tensor();
+        const int64_t outputs = sd["outputs"].toInt();
+        const bool depth_on = outputs >= 0 ? (outputs & 1) != 0 : fused;
+        Tensor g_depth = (depth_on && grads.size() > 2 && grads[2].defined()) ? f32(grads[2], dev) : Tensor();
+        // the opt-in image gradients: a backward that carries one goes through gs_render_backward_grads, every other one makes the call it always made
+        Tensor g_opacity = (outputs >= 0 && (outputs & 2) && grads.size() > 3 && grads[3].defined()) ? f32(grads[3], dev) : Tensor();
+        Tensor g_depth_sq = (outputs >= 0 && (outputs & 4) && grads.size() > 4 && grads[4].defined()) ? f32(grads[4], dev) : Tensor();
         uint8_t* base = ws.data_ptr<uint8_t>();
         const int64_t o_scratch = sd["o_scratch"].toInt();
         Tensor fresh;
@@ -260,11 +276,18 @@ struct Rasterize : public torch::autograd::Function<Rasterize> {
         Tensor d_cov = cov3D.defined() ? at::empty({P, 6}, f_opts) : Tensor();
         const hipStream_t st = c10::hip::getCurrentHIPStream(dev.index()).stream();
         auto mp = [](Tensor& t) -> float* { return t.defined() ? t.data_ptr<float>() : nullptr; };
-        check(gs_render_backward(&cam, P, D, fp(means3D), fp(shs), fp(colors), fp(scales), fp(rotations), fp(cov3D), radii.data_ptr<int32_t>(), base,
-                                 plist, base + sd["o_image"].toInt(), fp(g_color), fp(g_depth), mp(d_m2d), mp(d_m3d), mp(d_op), mp(d_col), mp(d_shs), mp(d_sc),
-                                 mp(d_rot), mp(d_cov), scratch, clean ? 1 : 0, sd["want_bwd"].toBool() ? 1 : 0, st));
+        if (g_opacity.defined() || g_depth_sq.defined()) {
+            const GsImageGrads ig{fp(g_color), fp(g_depth), fp(g_opacity), fp(g_depth_sq)};
+            check(gs_render_backward_grads(&cam, P, D, fp(means3D), fp(shs), fp(colors), fp(scales), fp(rotations), fp(cov3D), radii.data_ptr<int32_t>(),
+                                           base, plist, base + sd["o_image"].toInt(), &ig, mp(d_m2d), mp(d_m3d), mp(d_op), mp(d_col), mp(d_shs), mp(d_sc),
+                                           mp(d_rot), mp(d_cov), scratch, clean ? 1 : 0, sd["want_bwd"].toBool() ? 1 : 0, st));
+        } else {
+            check(gs_render_backward(&cam, P, D, fp(means3D), fp(shs), fp(colors), fp(scales), fp(rotations), fp(cov3D), radii.data_ptr<int32_t>(), base,
+                                     plist, base + sd["o_image"].toInt(), fp(g_color), fp(g_depth), mp(d_m2d), mp(d_m3d), mp(d_op), mp(d_col), mp(d_shs),
+                                     mp(d_sc), mp(d_rot), mp(d_cov), scratch, clean ? 1 : 0, sd["want_bwd"].toBool() ? 1 : 0, st));
+        }
         Tensor none;
-        return {d_m3d, d_m2d, d_shs, d_col, d_op, d_sc, d_rot, d_cov, none, none, none, none, none, none, none, none, none, none, none, none, none, none};
+        return {d_m3d, d_m2d, d_shs, d_col, d_op, d_sc, d_rot, d_cov, none, none, none, none, none, none, none, none, none, none, none, none, none, none, none};
     }
 };
 
@@ -273,8 +296,9 @@ std::tuple<std::vector<Tensor>, int64_t, int64_t, bool, std::vector<Tensor>, std
     const Tensor& means3D, const std::optional<Tensor>& means2D, const std::optional<Tensor>& shs, const std::optional<Tensor>& colors,
     const Tensor& opacities, const std::optional<Tensor>& scales, const std::optional<Tensor>& rotations, const std::optional<Tensor>& cov3D,
     const Tensor& bg, const Tensor& view, const Tensor& proj, const Tensor& campos, int64_t W, int64_t H, double tanfovx, double tanfovy, double scale_modifier,
-    int64_t sh_degree, bool fused, int64_t guess_d, int64_t guess_tile, bool want_state)
+    int64_t sh_degree, bool fused, int64_t guess_d, int64_t guess_tile, bool want_state, int64_t outputs)
 {
+    if (outputs > 7 || (!fused && outputs > 3)) throw std::runtime_error("rasterize: unknown differentiable output");
     if (!means3D.is_cuda()) throw std::runtime_error("activesplat_amd rasteriser needs ROCm device tensors (no CPU fallback)");
     poll_async_status();
     auto opt = [](const std::optional<Tensor>& t) { return (t.has_value() && t->defined()) ? t : std::optional<Tensor>(); };
@@ -289,11 +313,22 @@ std::tuple<std::vector<Tensor>, int64_t, int64_t, bool, std::vector<Tensor>, std
     tl_want_state = want_state;
     tl_state.clear(); tl_offsets.clear();
     auto out = Rasterize::apply(means3D, m2d, s, c, opacities, sc, r, cv, bg, view, proj, campos, W, H, tanfovx, tanfovy, scale_modifier, sh_degree, fused,
-                                guess_d, guess_tile, want_bwd);
+                                guess_d, guess_tile, want_bwd, outputs < 0 ? (int64_t)-1 : outputs);
     tl_want_state = false;
     std::vector<Tensor> state;
     state.swap(tl_state);
     return {out, tl_D, tl_max_tile, tl_hit != 0, state, tl_offsets};
+}
+
+// the call without an output request (every image output as the reference has it)
+std::tuple<std::vector<Tensor>, int64_t, int64_t, bool, std::vector<Tensor>, std::vector<int64_t>> rasterize_default(
+    const Tensor& means3D, const std::optional<Tensor>& means2D, const std::optional<Tensor>& shs, const std::optional<Tensor>& colors,
+    const Tensor& opacities, const std::optional<Tensor>& scales, const std::optional<Tensor>& rotations, const std::optional<Tensor>& cov3D,
+    const Tensor& bg, const Tensor& view, const Tensor& proj, const Tensor& campos, int64_t W, int64_t H, double tanfovx, double tanfovy, double scale_modifier,
+    int64_t sh_degree, bool fused, int64_t guess_d, int64_t guess_tile, bool want_state)
+{
+    return rasterize(means3D, means2D, shs, colors, opacities, scales, rotations, cov3D, bg, view, proj, campos, W, H, tanfovx, tanfovy, scale_modifier, sh_degree,
+                     fused, guess_d, guess_tile, want_state, -1);
 }
 
 }  // namespace
@@ -302,5 +337,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
 {
     m.doc() = "C++ autograd front-end of the drop-in GaussianRasterizer call (plumbing above libgsplat_hip.so's C ABI)";
     m.def("rasterize", &rasterize, pybind11::call_guard<pybind11::gil_scoped_release>());
+    m.def("rasterize", &rasterize_default, pybind11::call_guard<pybind11::gil_scoped_release>());
     m.def("abi_version", []() { return (int)gs_abi_version(); });
 }

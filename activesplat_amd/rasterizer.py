@@ -14,8 +14,9 @@ utils/slam_helpers.py:131-138.  Contract:
 `color` [3,H,W] is differentiable w.r.t. means3D, colors_precomp/shs, opacities, scales, rotations,
 cov3D_precomp and the dummy `means2D` [P,3] (NDC-scaled screen-space gradient, read by the reference's
 densifier at utils/slam_external.py:100-108).  `radii` [P] int32 (>0 <=> visible), `depth` [1,H,W]
-(sum z*alpha*T) and `opacity` [1,H,W] (1 - T_final) are non-differentiable, which is all the reference
-needs (they are only read under torch.no_grad(), splatam.py:414,430).
+(sum z*alpha*T) and `opacity` [1,H,W] (1 - T_final) are non-differentiable by default, which is all the reference
+needs (they are only read under torch.no_grad(), splatam.py:414,430); GaussianRasterizer(raster_settings,
+differentiable_outputs=("depth", "opacity")) opts in to their gradients.
 
 All compute is in libgsplat_hip.so through the C ABI of include/gsplat_hip.h; there is no fallback.
 """
@@ -257,14 +258,33 @@ class RawInputs(NamedTuple):
 _RawCtx = collections.namedtuple("_RawCtx", "pose iso accumulate logit")
 
 
+#: the image outputs besides `color` that can carry a gradient, under their internal names; "silhouette" is render_rgbd's name for opacity
+_OUTPUT_NAMES = {"depth": "depth", "opacity": "opacity", "silhouette": "opacity", "depth_sq": "depth_sq"}
+
+
+def _output_request(differentiable_outputs, allowed, default, who):
+    """The `differentiable_outputs` keyword -> None (the call's default: the very path and kernels of a call without the keyword) or a frozenset of
+    internal names.  allowed: the names this entry point takes."""
+    if isinstance(differentiable_outputs, str):
+        differentiable_outputs = (differentiable_outputs,)
+    names = tuple(differentiable_outputs)
+    for n in names:
+        if n not in allowed:
+            raise ValueError(f"{who}: differentiable_outputs takes {sorted(allowed)}, not {n!r}")
+    req = frozenset(_OUTPUT_NAMES[n] for n in names)
+    return None if req == default else req
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """fused=False: the reference contract (color differentiable; radii, depth, opacity not).
     fused=True : one pass also yields the reference's SECOND raster pass -- depth (differentiable), silhouette
-                 (= opacity) and depth^2 -- see render_rgbd()."""
+                 (= opacity) and depth^2 -- see render_rgbd().
+    outputs    : None, or the frozenset of {"depth", "opacity", "depth_sq"} that carry a gradient INSTEAD of that default
+                 (differentiable_outputs= of the public calls); the others stay marked non-differentiable."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, rs, fused=False, raw=None,
-                cam_rot=None, cam_trans=None):
+                cam_rot=None, cam_trans=None, outputs=None):
         """raw = RawInputs: means3D / opacities / scales / rotations are the mapper's PARAMETERS (world-frame means, logit
         opacities, log scales, unnormalised quaternions); frame transform + activations run inside the per-Gaussian kernels (render_rgbd_raw).
         cam_rot [4] / cam_trans [3] (raw only): device tensors whose VALUES are pose7; the backward returns dL/d of them (gaussians_grad False:
@@ -291,6 +311,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             pose_req = (not raw.gaussians_grad, cam_rot.shape, cam_trans.shape)
         ctx.pose_req = pose_req
         ctx.cam_inputs = cam_rot is not None         # the backward then owes autograd two more entries (None when the camera is frozen)
+        ctx.outputs = outputs                        # (given: the call had all fourteen inputs, the backward owes one entry each)
         want_bwd = 1 if any(ctx.needs_input_grad[:8]) or pose_req is not None else 0
         pose = None
         ctx.devpose = raw.device_pose if raw is not None else None
@@ -355,6 +376,10 @@ class _RasterizeGaussians(torch.autograd.Function):
                               scales if scales is not None else e, rotations if rotations is not None else e,
                               cov3D_precomp if cov3D_precomp is not None else e, radii, geom, point_list, image)
         ctx.set_materialize_grads(False)          # no zero-filled grad tensors for the non-differentiable outputs
+        if outputs is not None:
+            images = dict(depth=depth, opacity=opacity, depth_sq=depth_sq)
+            ctx.mark_non_differentiable(radii, *[t for k, t in images.items() if t is not None and k not in outputs])
+            return (color, radii, depth, opacity, depth_sq) if fused else (color, radii, depth, opacity)
         if fused:
             ctx.mark_non_differentiable(radii, opacity, depth_sq)
             return color, radii, depth, opacity, depth_sq
@@ -362,14 +387,16 @@ class _RasterizeGaussians(torch.autograd.Function):
         return color, radii, depth, opacity
 
     @staticmethod
-    def backward(ctx, grad_color, _gr=None, grad_depth=None, _go=None, _gq=None):
-        out = _RasterizeGaussians._backward(ctx, grad_color, grad_depth)
+    def backward(ctx, grad_color, _gr=None, grad_depth=None, grad_opacity=None, grad_depth_sq=None):
+        out = _RasterizeGaussians._backward(ctx, grad_color, grad_depth, grad_opacity, grad_depth_sq)
         if getattr(ctx, "cam_inputs", False) and len(out) == 11:
             out = out + (None, None)                     # camera tensors given but not differentiable (frozen pose)
+        if getattr(ctx, "outputs", None) is not None:
+            out = out + (None,) * (14 - len(out))
         return out
 
     @staticmethod
-    def _backward(ctx, grad_color, grad_depth):
+    def _backward(ctx, grad_color, grad_depth, grad_opacity=None, grad_depth_sq=None):
         lib = _lib.get()
         means3D, shs, colors, scales, rots, cov3Dp, radii, geom, point_list, image = ctx.saved_tensors
         has_sh, has_col, has_sc, has_rot, has_cov = ctx.has
@@ -380,7 +407,16 @@ class _RasterizeGaussians(torch.autograd.Function):
         if grad_color is None:
             grad_color = torch.zeros(3, int(ctx.rs.image_height), int(ctx.rs.image_width), device=device)
         grad_color = _f32(grad_color, device)
-        grad_depth = _f32(grad_depth, device) if (ctx.fused and grad_depth is not None) else None
+        outs = getattr(ctx, "outputs", None)
+        depth_on = ctx.fused if outs is None else "depth" in outs
+        grad_depth = _f32(grad_depth, device) if (depth_on and grad_depth is not None) else None
+        # the opt-in image gradients (differentiable_outputs=): a backward that carries one goes through the *_grads entry points; every other
+        # one -- a call with the keyword whose loss left those outputs alone included -- makes the same library call as before the keyword
+        grad_opacity = _f32(grad_opacity, device) if (outs is not None and "opacity" in outs and grad_opacity is not None) else None
+        grad_depth_sq = _f32(grad_depth_sq, device) if (outs is not None and "depth_sq" in outs and grad_depth_sq is not None) else None
+        grads = None
+        if grad_opacity is not None or grad_depth_sq is not None:
+            grads = _lib.GsImageGrads(grad_color.data_ptr(), *[None if g is None else g.data_ptr() for g in (grad_depth, grad_opacity, grad_depth_sq)])
         scratch, clean = _take_scratch(ctx, lib, P, device)
         z = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)  # noqa: E731  (kernel writes every row)
         pose_req = getattr(ctx, "pose_req", None)
@@ -395,6 +431,10 @@ class _RasterizeGaussians(torch.autograd.Function):
             head = (C.byref(cam), P, ctx.D, _ptr(means3D), _ptr(shs if has_sh else None), _ptr(colors if has_col else None), _ptr(rc.logit),
                     _ptr(scales), _ptr(rots), rc.pose, rc.iso)
             mid = (_ptr(radii), _ptr(geom), _ptr(point_list), _ptr(image), _ptr(grad_color), _ptr(grad_depth), _ptr(d_m2d))
+            if grads is not None:
+                mid = mid[:4] + (C.byref(grads), mid[6])
+            raw_backward = lib.gs_render_backward_raw if grads is None else lib.gs_render_backward_raw_grads
+            pose_backward = lib.gs_render_backward_raw_pose if grads is None else lib.gs_render_backward_raw_pose_grads
             scr = (_ptr(scratch), 1 if clean else 0, int(ctx.sh_jac))
             if ctx.adam is not None:
                 # single-keyframe step: Adam on the five per-Gaussian tensors rides in the per-Gaussian backward kernel (no gradient tensors)
@@ -418,8 +458,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 pose_tail = (d_pose[:4].view(pose_req[1]), d_pose[4:].view(pose_req[2]))
                 if pose_req[0]:
                     # tracking: the pose gradient only -- no parameter gradient is formed (gs_render_backward_raw_pose, pose_only = 1)
-                    _lib.check(lib.gs_render_backward_raw_pose(*head, 0, *mid, None, None, None, None, None, None, *scr, 1, _ptr(d_pose), _ptr(pscr),
-                                                               _stream(device)))
+                    _lib.check(pose_backward(*head, 0, *mid, None, None, None, None, None, None, *scr, 1, _ptr(d_pose), _ptr(pscr), _stream(device)))
                     return (None, d_m2d) + (None,) * 9 + pose_tail
         d_m3d, d_op = z(P, 3), z(P, 1)
         d_col = z(P, 3) if has_col else None
@@ -446,10 +485,10 @@ class _RasterizeGaussians(torch.autograd.Function):
             tail = ()
             if pose_req is not None:
                 # bundle adjustment: the same launch also reduces the camera-pose gradient (parameter gradients bit-identical to the plain call)
-                _lib.check(lib.gs_render_backward_raw_pose(*args, 0, _ptr(d_pose), _ptr(pscr), _stream(device)))
+                _lib.check(pose_backward(*args, 0, _ptr(d_pose), _ptr(pscr), _stream(device)))
                 tail = pose_tail
             else:
-                _lib.check(lib.gs_render_backward_raw(*args, _stream(device)))
+                _lib.check(raw_backward(*args, _stream(device)))
             if into is not None:
                 if not acc:
                     for x, t in zip(leaves, into):
@@ -459,10 +498,11 @@ class _RasterizeGaussians(torch.autograd.Function):
             return (d_m3d, d_m2d, d_shs, d_col, d_op, d_sc, d_rot, None, None, None, None) + tail
         d_sc = z(P, 3) if has_sc else None
         d_cov = z(P, 6) if has_cov else None
-        _lib.check(lib.gs_render_backward(
+        image_grads = (_ptr(grad_color), _ptr(grad_depth)) if grads is None else (C.byref(grads),)
+        _lib.check((lib.gs_render_backward if grads is None else lib.gs_render_backward_grads)(
             C.byref(cam), P, ctx.D, _ptr(means3D), _ptr(shs if has_sh else None), _ptr(colors if has_col else None),
             _ptr(scales if has_sc else None), _ptr(rots if has_rot else None), _ptr(cov3Dp if has_cov else None),
-            _ptr(radii), _ptr(geom), _ptr(point_list), _ptr(image), _ptr(grad_color), _ptr(grad_depth),
+            _ptr(radii), _ptr(geom), _ptr(point_list), _ptr(image), *image_grads,
             _ptr(d_m2d), _ptr(d_m3d), _ptr(d_op), _ptr(d_col), _ptr(d_shs), _ptr(d_sc), _ptr(d_rot), _ptr(d_cov),
             _ptr(scratch), 1 if clean else 0, int(ctx.sh_jac), _stream(device)))
         return d_m3d, d_m2d, d_shs, d_col, d_op, d_sc, d_rot, d_cov, None, None, None
@@ -535,7 +575,11 @@ def backward_pose_dev(ctx, grad_color, grad_depth, pose_scratch, d_pose=None):
 use_frontend = True
 
 
-def _frontend_apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, rs, fused):
+#: the C++ front-end's encoding of an output request: -1 = the call's default, else a bit set
+_OUTPUT_BITS = {"depth": 1, "opacity": 2, "depth_sq": 4}
+
+
+def _frontend_apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, rs, fused, outputs=None):
     """The drop-in forward through the C++ front-end; None when this call is not one for it (then the Python twin takes it)."""
     if not use_frontend or _lib.emulated() or means3D.device.type != "cuda":
         return None
@@ -552,7 +596,8 @@ def _frontend_apply(means3D, means2D, shs, colors_precomp, opacities, scales, ro
     out, D, max_tile, hit, state, off = ext.rasterize(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, rs.bg,
                                                       rs.viewmatrix, rs.projmatrix, rs.campos, W, H, float(rs.tanfovx), float(rs.tanfovy),
                                                       float(rs.scale_modifier), int(rs.sh_degree), bool(fused), guess[0] if guess else 0,
-                                                      guess[1] if guess else 0, cap is not None)
+                                                      guess[1] if guess else 0, cap is not None,
+                                                      -1 if outputs is None else sum(_OUTPUT_BITS[k] for k in outputs))
     if cap is not None:
         # capture(): views of the one workspace (and of the exact re-render's buffers after a miss), under the names the Python twin publishes
         lib = _lib.get()
@@ -567,16 +612,25 @@ def _frontend_apply(means3D, means2D, shs, colors_precomp, opacities, scales, ro
 
 
 def rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                        raster_settings):
-    out = _frontend_apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, raster_settings, False)
+                        raster_settings, differentiable_outputs=()):
+    outputs = _output_request(differentiable_outputs, ("depth", "opacity"), frozenset(), "GaussianRasterizer") if differentiable_outputs else None
+    out = _frontend_apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, raster_settings, False, outputs)
     if out is not None:
         return out
+    if outputs is not None:
+        return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, raster_settings,
+                                         False, None, None, None, outputs)
     return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                      cov3D_precomp, raster_settings)
 
 
+#: what render_rgbd / render_rgbd_raw take in differentiable_outputs, and their default
+_FUSED_OUTPUTS = ("depth", "silhouette", "opacity", "depth_sq")
+_FUSED_DEFAULT = frozenset(("depth",))
+
+
 def render_rgbd(raster_settings, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, differentiable_outputs=("depth",)):
     """Single-pass RGB + depth + silhouette render -- an ADDITIONAL entry point, the
     drop-in GaussianRasterizer is unchanged.
 
@@ -588,21 +642,29 @@ def render_rgbd(raster_settings, means3D, means2D, opacities, shs=None, colors_p
         color [3,H,W], radii [P], depth [1,H,W], silhouette [1,H,W], depth_sq [1,H,W]
     with `color` AND `depth` differentiable (the mapping loss back-propagates through both; silhouette and
     depth_sq are only used as masks / detached, splatam.py:213-231).  The depth gradient reaches means3D through
-    the per-Gaussian view depth exactly as in the two-pass formulation."""
+    the per-Gaussian view depth exactly as in the two-pass formulation.
+    differentiable_outputs: which of "depth", "silhouette" and "depth_sq" carry a gradient (default: depth alone, as the reference's losses
+    need).  With all three the pass is a complete differentiable replacement of the reference's second raster pass: a silhouette or
+    free-space opacity loss, a depth-variance regulariser (depth_sq - depth^2).  The others stay marked non-differentiable.  A backward that
+    carries dL/ddepth_sq walks images of few tiles with one walker per quadrant (the forward records no sum z^2 state for list segments)."""
     if (shs is None) == (colors_precomp is None):
         raise Exception("Please provide excatly one of either SHs or precomputed colors!")
     if ((scales is None or rotations is None) and cov3D_precomp is None) or \
             ((scales is not None or rotations is not None) and cov3D_precomp is not None):
         raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
-    out = _frontend_apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, raster_settings, True)
+    outputs = _output_request(differentiable_outputs, _FUSED_OUTPUTS, _FUSED_DEFAULT, "render_rgbd")
+    out = _frontend_apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, raster_settings, True, outputs)
     if out is not None:
         return out
+    if outputs is not None:
+        return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                                         raster_settings, True, None, None, None, outputs)
     return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                      raster_settings, True)
 
 
 def render_rgbd_raw(raster_settings, means3D, means2D, logit_opacities, log_scales, unnorm_rotations, pose7, shs=None, colors_precomp=None,
-                    accumulate_grads=False, visibility=None, adam=None, camera=None, gaussians_grad=True):
+                    accumulate_grads=False, visibility=None, adam=None, camera=None, gaussians_grad=True, differentiable_outputs=("depth",)):
     """render_rgbd straight from the mapper's PARAMETERS: the frame transform + activations of transform_to_frame /
     transformed_params2rendervar (slam_helpers.py:252-304,124-139; `mapping.fused_rendervar` does them in two launches of their own) happen
     inside the per-Gaussian kernels of the rasteriser, forward and backward.  pose7 = host (qw,qx,qy,qz,tx,ty,tz) of the frame's relative
@@ -624,9 +686,16 @@ def render_rgbd_raw(raster_settings, means3D, means2D, logit_opacities, log_scal
     is taken as build_rotation(cam_rot) (which renormalises) and the Gaussians' rotations as quat_mult(cam_rot, .), so the gradient is right
     for a unit-quaternion leaf passed as is as well as after F.normalize.  Camera tensors that do not require grad are a frozen pose (no pose
     reduction runs).  pose7 = None reads the values from the two tensors (one small device-to-host copy).  gaussians_grad=False (tracking): the pose gradient only -- the backward forms no parameter gradient and the
-    Gaussian tensors (colours / SH rows included) receive none; means2D.grad and the visibility statistics are delivered as usual.  Not with adam=."""
+    Gaussian tensors (colours / SH rows included) receive none; means2D.grad and the visibility statistics are delivered as usual.  Not with adam=.
+    differentiable_outputs: as for render_rgbd; works with accumulate_grads, camera= and gaussians_grad=False (the pose gradient rides on the same
+    moments).  Not with adam=: the backward with the optimiser step inside has no form that takes dL/dsilhouette or dL/ddepth_sq."""
     if (shs is None) == (colors_precomp is None):
         raise Exception("Please provide excatly one of either SHs or precomputed colors!")
+    outputs = _output_request(differentiable_outputs, _FUSED_OUTPUTS, _FUSED_DEFAULT, "render_rgbd_raw")
+    if adam is not None and outputs is not None and (outputs - _FUSED_DEFAULT):
+        raise Exception("render_rgbd_raw: adam= takes differentiable_outputs=('depth',) only (the backward with the optimiser step inside "
+                        "has no form for the silhouette / depth_sq gradients)")
+    tail = () if outputs is None else (outputs,)
     if shs is not None and int(shs.shape[1]) != 16:
         raise Exception("render_rgbd_raw: SH rows of 16 coefficients only")
     iso = int(log_scales.shape[1]) == 1
@@ -640,7 +709,8 @@ def render_rgbd_raw(raster_settings, means3D, means2D, logit_opacities, log_scal
         if not gaussians_grad:
             raise Exception("render_rgbd_raw: gaussians_grad=False is the pose-only backward: it needs camera=(cam_rot, cam_trans)")
         return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, None,
-                                         raster_settings, True, RawInputs(pose7, iso, accumulate=accumulate_grads, visibility=visibility, adam=adam))
+                                         raster_settings, True, RawInputs(pose7, iso, accumulate=accumulate_grads, visibility=visibility, adam=adam),
+                                         *((None, None) + tail if tail else ()))
     cam_rot, cam_trans = camera
     if cam_rot.numel() != 4 or cam_trans.numel() != 3:
         raise Exception("render_rgbd_raw: camera = (cam_rot with 4 values, cam_trans with 3)")
@@ -656,13 +726,17 @@ def render_rgbd_raw(raster_settings, means3D, means2D, logit_opacities, log_scal
         accumulate_grads = False
     return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, logit_opacities, log_scales, unnorm_rotations, None,
                                      raster_settings, True, RawInputs(pose7, iso, accumulate=accumulate_grads, visibility=visibility, gaussians_grad=gaussians_grad),
-                                     cam_rot, cam_trans)
+                                     cam_rot, cam_trans, *tail)
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings: GaussianRasterizationSettings):
+    def __init__(self, raster_settings: GaussianRasterizationSettings, differentiable_outputs=()):
+        """differentiable_outputs: any of "depth", "opacity" -- those image outputs carry a gradient as well (an addition to the reference's
+        contract, off by default: without it both stay marked non-differentiable)."""
         super().__init__()
         self.raster_settings = raster_settings
+        _output_request(differentiable_outputs, ("depth", "opacity"), frozenset(), "GaussianRasterizer")      # (an unknown name fails here)
+        self.differentiable_outputs = tuple(differentiable_outputs) if not isinstance(differentiable_outputs, str) else (differentiable_outputs,)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None):
@@ -672,7 +746,8 @@ class GaussianRasterizer(nn.Module):
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
-        return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, rs)
+        return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, rs,
+                                   self.differentiable_outputs)
 
 
 @torch.no_grad()

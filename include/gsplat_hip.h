@@ -198,7 +198,7 @@ const char* gs_version(void);
 /* Integer version of THIS binary interface: bumped whenever an entry point's argument list or a published record layout changes (e.g.
  * the seed argument of gs_densify_children, the 40-byte SH Jacobian record).  A host binding compares it with the GS_ABI_VERSION it was
  * written against before the first call, so that a stale prebuilt library fails at load time instead of misreading its arguments. */
-#define GS_ABI_VERSION 22
+#define GS_ABI_VERSION 23
 int32_t gs_abi_version(void);
 
 /* Optional per-stage timing (hipEvents recorded on the caller's stream around each stage's launches).
@@ -248,7 +248,8 @@ int gs_render_forward(const GsCamera* cam, int32_t P, int64_t D, uint32_t max_ti
                       float* out_color, float* out_depth, float* out_opacity, float* out_depth_sq,
                       void* backward_scratch, gs_stream_t stream);
 
-/* Backward of `out_color` (and, when dL_ddepth [1,H,W] is non-NULL, of `out_depth`) w.r.t. every input.  Any dL_d* output pointer may be NULL if that input
+/* Backward of `out_color` (and, when dL_ddepth [1,H,W] is non-NULL, of `out_depth`; of out_opacity and out_depth_sq as well through
+ * gs_render_backward_grads below) w.r.t. every input.  Any dL_d* output pointer may be NULL if that input
  * was not given (shs vs colors_precomp, scales/rotations vs cov3D_precomp).
  * dL_dmeans2D [P,3] receives the NDC-scaled screen-space gradient (x*0.5W, y*0.5H, 0).
  * scratch: gs_backward_scratch_bytes(P) bytes; scratch_zeroed != 0 promises that it is all zero (see gs_render_forward's
@@ -302,6 +303,46 @@ int gs_render_backward_raw_pose(const GsCamera* cam, int32_t P, int64_t D, const
                                 float* dL_dlogit_opacities, float* dL_dcolors_precomp, float* dL_dshs, float* dL_dlog_scales,
                                 float* dL_dunnorm_rotations, void* scratch, int32_t scratch_zeroed, int32_t have_sh_jacobian, int32_t pose_only,
                                 float* dL_dpose7, void* pose_scratch, gs_stream_t stream);
+
+/* Gradients of EVERY image output (opt-in: the three calls above differentiate colour and depth only).  The four images a loss may hang on:
+ * dL_dcolor [3,H,W] (required), dL_ddepth [1,H,W], dL_dopacity [1,H,W] (out_opacity = the silhouette, 1 - T_final) and dL_ddepth_sq [1,H,W]
+ * (out_depth_sq, sum z^2*alpha*T); the last three nullable.  With them the one pass is a complete differentiable replacement of the
+ * reference's second, [z, 1, z^2] raster pass (slam_helpers.py:196-249), not only for the losses the reference happens to use.
+ * The three *_grads entry points are gs_render_backward, gs_render_backward_raw and gs_render_backward_raw_pose with the (dL_dcolor, dL_ddepth)
+ * pair replaced by this block; those three are wrappers that pass NULL for the two new images and launch the same kernels as before.
+ * dL_dopacity costs one per-pixel scalar.  dL_ddepth_sq adds a blended channel to the replay; the forward records no sum z^2 state for the
+ * list segments of few-tile images, so a call that carries it walks such an image with one walker per quadrant whatever
+ * gs_set_backward_segments says (chained walks are unaffected).
+ * NOT covered: gs_render_backward_raw_adam, gs_render_backward_raw_pose_dev and the fused loss kernels in front of them (gs_mapping_loss*,
+ * gs_tracking_loss*) produce and take colour and depth gradients only. */
+typedef struct GsImageGrads {
+    const float* dL_dcolor;
+    const float* dL_ddepth;
+    const float* dL_dopacity;
+    const float* dL_ddepth_sq;
+} GsImageGrads;
+int gs_render_backward_grads(const GsCamera* cam, int32_t P, int64_t D,
+                             const float* means3D, const float* shs, const float* colors_precomp,
+                             const float* scales, const float* rotations, const float* cov3D_precomp,
+                             const int32_t* radii, const void* geom_state, const uint32_t* point_list,
+                             const void* image_state, const GsImageGrads* grads,
+                             float* dL_dmeans2D, float* dL_dmeans3D, float* dL_dopacities,
+                             float* dL_dcolors_precomp, float* dL_dshs, float* dL_dscales,
+                             float* dL_drotations, float* dL_dcov3D, void* scratch, int32_t scratch_zeroed,
+                             int32_t have_sh_jacobian, gs_stream_t stream);
+int gs_render_backward_raw_grads(const GsCamera* cam, int32_t P, int64_t D, const float* means3D, const float* shs, const float* colors_precomp,
+                                 const float* logit_opacities, const float* log_scales, const float* unnorm_rotations, const float* h_pose7,
+                                 int32_t isotropic, int32_t accumulate, const int32_t* radii, const void* geom_state, const uint32_t* point_list,
+                                 const void* image_state, const GsImageGrads* grads, float* dL_dmeans2D, float* dL_dmeans3D,
+                                 float* dL_dlogit_opacities, float* dL_dcolors_precomp, float* dL_dshs, float* dL_dlog_scales,
+                                 float* dL_dunnorm_rotations, void* scratch, int32_t scratch_zeroed, int32_t have_sh_jacobian, gs_stream_t stream);
+int gs_render_backward_raw_pose_grads(const GsCamera* cam, int32_t P, int64_t D, const float* means3D, const float* shs, const float* colors_precomp,
+                                      const float* logit_opacities, const float* log_scales, const float* unnorm_rotations, const float* h_pose7,
+                                      int32_t isotropic, int32_t accumulate, const int32_t* radii, const void* geom_state,
+                                      const uint32_t* point_list, const void* image_state, const GsImageGrads* grads, float* dL_dmeans2D,
+                                      float* dL_dmeans3D, float* dL_dlogit_opacities, float* dL_dcolors_precomp, float* dL_dshs,
+                                      float* dL_dlog_scales, float* dL_dunnorm_rotations, void* scratch, int32_t scratch_zeroed,
+                                      int32_t have_sh_jacobian, int32_t pose_only, float* dL_dpose7, void* pose_scratch, gs_stream_t stream);
 
 /* Fused dense Adam step over one flat parameter tensor with torch.optim.Adam semantics
  * (non-amsgrad, no weight decay): splatam.py:118-124 uses betas (0.9,0.999), eps 1e-15.
