@@ -13,7 +13,10 @@
 //                  (Direct global atomics per instance measured 61-140 us for 1.2M instances on 1200 counters.)
 //   tile_scan    : exclusive scan of the per-tile totals -> ranges[tile], D, max instances per tile.
 //   tile_scatter : same expansion; LDS returning atomics hand out slots inside the reserved slices;
-//                  one 8-byte (depth_bits<<32 | id) store per instance.
+//                  one 8-byte (depth_bits<<32 | id) store per instance.  Every load of a workgroup -- tile counts, rects and depth bits of
+//                  its 2048 Gaussians, the cursor words -- is requested up front, one memory round trip instead of four to five
+//                  (40.7 -> 32.7 us at 2 M; the same form LOST in the count pass, and counting inside the per-Gaussian forward lost
+//                  more than the count launch costs: profiles/fused_tile_count.txt).
 //   per-tile sort, chosen PER TILE on the device (keys are unique, so the result does not depend on the atomics' arrival order):
 //     tile_bucket_sort        : lists of at most 5632 keys (every list of a 640 x 480 frame up to ~2.3 M Gaussians): ONE 512-thread workgroup per
 //                               tile, keys in registers; a tile's depths lie in a narrow interval, so a LINEAR map onto up to 2048 bins is a
@@ -78,15 +81,52 @@ __global__ __launch_bounds__(THREADS) void tile_bin_kernel(Cam cam, int P, GeomP
     const int cid = SCATTER ? (b & 7) * cper + (b >> 3) : b;
     if (cid >= nchunks) continue;
     uint32_t* my_base = tile_base + (size_t)cid * tiles;
-    __syncthreads();
-    for (int t = tid; t < tiles; t += THREADS) s_hist[t] = SCATTER ? ranges[t].x + my_base[t] : 0u;
-    __syncthreads();
     const int cbase = cid * chunk;
+    // Scatter pass: ONE memory round trip per workgroup.  The tile counts, rects and depth bits of every iteration of the chunk and the cursor
+    // words of the first kBinCursorRounds x THREADS tiles are requested before anything waits; the dependent form -- the cursor loads and
+    // their barrier, then per iteration tiles[i] and, behind `if (n)`, rect[i] and depth_bits[i] -- was four to five serial trips per workgroup
+    // (2 M Gaussians: 40.7 -> 32.7 us).  Rows past P read row P - 1 and are ignored; a culled Gaussian's rect and depth bits were never written
+    // (preprocess.hip), so those reads return stale bytes of the [P] arrays, ignored as well (n = 0).  The count pass keeps the dependent form:
+    // with every request up front it measured 10.5 -> 11.7 us (profiles/fused_tile_count.txt).
+    constexpr int kBinRounds = SCATTER ? kBinChunk / THREADS : 1, kBinCursorRounds = SCATTER ? 2 : 1;
+    uint32_t rn[kBinRounds], rd[kBinRounds], cur[kBinCursorRounds];
+    uint2 rr[kBinRounds];
+    if (SCATTER) {
+#pragma unroll
+        for (int q = 0; q < kBinRounds; q++) {
+            const int ic = min(cbase + q * THREADS + tid, P - 1);
+            rn[q] = gp.tiles[ic];
+            rr[q] = gp.rect[ic];
+            rd[q] = gp.depth_bits[ic];
+        }
+#pragma unroll
+        for (int k = 0; k < kBinCursorRounds; k++) {
+            const int tc = min(tid + k * THREADS, tiles - 1);
+            cur[k] = ranges[tc].x + my_base[tc];
+        }
+    }
+    __syncthreads();
+    if (SCATTER) {
+#pragma unroll
+        for (int k = 0; k < kBinCursorRounds; k++) if (tid + k * THREADS < tiles) s_hist[tid + k * THREADS] = cur[k];
+        for (int t = tid + kBinCursorRounds * THREADS; t < tiles; t += THREADS) s_hist[t] = ranges[t].x + my_base[t];
+    } else {
+        for (int t = tid; t < tiles; t += THREADS) s_hist[t] = 0u;
+    }
+    __syncthreads();
     for (int r = 0; r < chunk / THREADS; r++) {
         const int i = cbase + r * THREADS + tid;
         if (cbase + r * THREADS >= P) break;                      // uniform
         uint32_t n = 0, x0 = 0, w = 1, y0 = 0, dbits = 0;
-        if (i < P) {
+        if (SCATTER) {
+            // (`chunk` is kBinChunk -- bin_config -- so r < kBinRounds; the registers of iteration r, picked by selects on the uniform r)
+            uint32_t pn = rn[0], pd = rd[0];
+            uint2 prc = rr[0];
+#pragma unroll
+            for (int q = 1; q < kBinRounds; q++) if (r == q) { pn = rn[q]; pd = rd[q]; prc = rr[q]; }
+            n = i < P ? pn : 0u;
+            if (n) { x0 = prc.x & 0xffffu; w = (prc.x >> 16) - x0; y0 = prc.y & 0xffffu; dbits = pd; }
+        } else if (i < P) {
             n = gp.tiles[i];
             if (n) {
                 const uint2 rc = gp.rect[i];
