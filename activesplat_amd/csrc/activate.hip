@@ -187,14 +187,14 @@ __global__ __launch_bounds__(kBlock) void tracking_step_kernel(int64_t pose_nrow
     float norm;
     normalize_pose_column(rots_col, stride, pu.q, norm);
     const float* u = pu.q;
-    float g[7];
+    double g[7];                                                         // (unrounded: the whole chain is double, the gradient is rounded once)
     pose_grad_finish_block(pose_nrows, pu, pose_rows, g);                 // (all threads; thread 0 comes back with g)
     if (threadIdx.x != 0) return;
     // F.normalize backward: x / max(|x|, eps) -> dL/dx = (g - u (u . g)) / |x|  (|x| below eps: the clamp passes g / eps)
     const double n = norm, ug = (double)u[0] * g[0] + (double)u[1] * g[1] + (double)u[2] * g[2] + (double)u[3] * g[3];
     float grad[7];
-    for (int k = 0; k < 4; k++) grad[k] = n >= 1e-12 ? (float)((g[k] - (double)u[k] * ug) / n) : (float)((double)g[k] / 1e-12);
-    for (int k = 4; k < 7; k++) grad[k] = g[k];
+    for (int k = 0; k < 4; k++) grad[k] = n >= 1e-12 ? (float)((g[k] - (double)u[k] * ug) / n) : (float)(g[k] / 1e-12);
+    for (int k = 4; k < 7; k++) grad[k] = (float)g[k];
     float p[7];
     for (int k = 0; k < 4; k++) p[k] = rots_col[k * stride];
     for (int k = 0; k < 3; k++) p[4 + k] = trans_col[k * stride];

@@ -285,8 +285,10 @@ __device__ __forceinline__ void pose_grad_block_row(float (&acc)[kPoseAcc], floa
 // a fixed order (thread t adds column t % 16 of rows t / 16, t / 16 + 16, ...; then the 16 slices in order), dL/dR turned into dL/dq_cam through
 // build_rotation's normalisation and quat_to_rot's formula and added to the rotation term; thread 0 writes out[7] = dL/d(qw,qx,qy,qz,tx,ty,tz)
 // of the pose the rows were formed at (pose.q = its quaternion (w,x,y,z)).  Every thread of the workgroup must call it; only thread 0 comes back with `out` written.
-template <class PoseT>
-__device__ __forceinline__ void pose_grad_finish_block(int64_t nrows, const PoseT& pose, const float* __restrict__ rows, float* __restrict__ out)
+// OutT = float: the result rounded once (dL_dpose7); double: unrounded, for the tracking step, which takes it on through F.normalize's Jacobian
+// and rounds at the end -- a float in between costs a component that cancels there an ulp of the LARGEST term instead of its own.
+template <class PoseT, class OutT>
+__device__ __forceinline__ void pose_grad_finish_block(int64_t nrows, const PoseT& pose, const float* __restrict__ rows, OutT* __restrict__ out)
 {
     constexpr int kSlices = kBlock / kPoseAcc;
     __shared__ double s[kSlices][kPoseAcc];
@@ -314,9 +316,9 @@ __device__ __forceinline__ void pose_grad_finish_block(int64_t nrows, const Pose
     const double d2 = 2.0 * (-2.0 * y * dR[0] + x * dR[1] + r * dR[2] + x * dR[3] + z * dR[5] - r * dR[6] + z * dR[7] - 2.0 * y * dR[8]);
     const double d3 = 2.0 * (-2.0 * z * dR[0] - r * dR[1] + x * dR[2] + r * dR[3] - 2.0 * z * dR[4] + y * dR[5] + x * dR[6] + y * dR[7]);
     const double dot = r * d0 + x * d1 + y * d2 + z * d3;
-    out[0] = (float)((d0 - r * dot) / nq + t[12]); out[1] = (float)((d1 - x * dot) / nq + t[13]);
-    out[2] = (float)((d2 - y * dot) / nq + t[14]); out[3] = (float)((d3 - z * dot) / nq + t[15]);
-    out[4] = (float)t[0]; out[5] = (float)t[1]; out[6] = (float)t[2];
+    out[0] = (OutT)((d0 - r * dot) / nq + t[12]); out[1] = (OutT)((d1 - x * dot) / nq + t[13]);
+    out[2] = (OutT)((d2 - y * dot) / nq + t[14]); out[3] = (OutT)((d3 - z * dot) / nq + t[15]);
+    out[4] = (OutT)t[0]; out[5] = (OutT)t[1]; out[6] = (OutT)t[2];
 }
 
 // ---- fixed-order fp64 sums: the same bits on every run ----

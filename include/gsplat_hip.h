@@ -560,7 +560,8 @@ int gs_tracking_begin(const float* cam_unnorm_rots, const float* cam_trans, int6
 
 /* The tail of tracking iteration `step` (1-based), one workgroup: (1) the loss rows of gs_tracking_loss (same width, height, weights) reduced as
  * that call reduces them; (2) the pose rows of gs_render_backward_raw_pose_dev (same P) reduced as gs_render_backward_raw_pose reduces them, then
- * taken through F.normalize's Jacobian at the unnormalised column: dL/dcam_unnorm_rots[..., t] and dL/dcam_trans[..., t]; (3) torch.optim.Adam's
+ * taken through F.normalize's Jacobian at the unnormalised column, all in double and rounded to fp32 once: dL/dcam_unnorm_rots[..., t] and
+ * dL/dcam_trans[..., t]; (3) torch.optim.Adam's
  * update of those 7 values in place (betas 0.9 / 0.999, eps 1e-8, lr_rot for the quaternion and lr_trans for the translation, the bias
  * corrections of `step`, torch's fp32 operation order); skipped while a chained backward in front has failed (gs_async_status_word);
  * (4) the best candidate: loss < the smallest loss so far (strict) -> that loss and the column AFTER this update become the candidate;
