@@ -68,8 +68,9 @@ _capacity_lock = threading.Lock()
 def capture():
     """`with capture() as state:` -- the state buffers of the forwards run inside the block by THIS thread (the last one wins) are put
     into `state` (geom / image / binning workspaces, point_list, their layouts, D, P, W, H; layouts in include/gsplat_hip.h) so that
-    tests and bench.py can decode the integer artefacts.  Nothing is retained outside a capture block: the reference's `debug=True`
-    settings flag alone does not pin any buffer."""
+    tests and bench.py can decode the integer artefacts.  render_views publishes its atlas the same way: P = the virtual row count, W = the
+    atlas width, plus `radii` [P], `view_stride` and `rows_per_view`.  Nothing is retained outside a capture block: the reference's
+    `debug=True` settings flag alone does not pin any buffer."""
     stack = getattr(_tls, "captures", None)
     if stack is None:
         stack = _tls.captures = []
@@ -812,9 +813,15 @@ def render_views(settings_list, means3D, opacities, shs=None, colors_precomp=Non
                                          _ptr(color), _ptr(depth), _ptr(opacity), None, None, st))
 
     # key = None: always at exact size and outside the capacity table (D and the longest tile list size the binning workspace)
-    _bin_and_render(lib, fr, None, P, AW, H, launch)
+    D, _, bl, binning, point_list = _bin_and_render(lib, fr, None, P, AW, H, launch)
+    rows = Pv // V
+    cap = _capture_target()
+    if cap is not None:
+        # the atlas as one frame of Pv virtual rows and AW columns (util.artefacts decodes it like any other), plus where a view sits in it:
+        # view v owns rows [v rows, v rows + P) and columns [v stride, v stride + W)
+        cap.update(geom=geom, image=image, binning=binning, point_list=point_list, gl=fr.gl, il=fr.il, bl=bl, D=D, P=max(Pv, 1), W=AW, H=H,
+                   radii=radii, view_stride=S, rows_per_view=rows)
     if return_atlas:
         return color, depth, opacity, S
-    rows = Pv // V
     return [(color[:, :, v * S:v * S + W], radii[v * rows:v * rows + P], depth[:, :, v * S:v * S + W], opacity[:, :, v * S:v * S + W])
             for v in range(V)]

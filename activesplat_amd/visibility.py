@@ -39,10 +39,12 @@ from .camera import setup_camera
 MAX_NODES_PER_PASS = 21
 #: nodes per raster pass by default.  A node's three views then sit in atlas slots 0-2, exactly where `look_around` renders them, and the
 #: panoramas are bit-identical to per-node `look_around`.  In a later slot the view's pixel offset (128 per slot) is added to the projected
-#: means in fp32, whose rounding grows with the slot; the smooth part of the difference stays inside the project's atlas bound scaled to 63
-#: slots (opacity 1e-4 at slot 50), but in every pass of more than one node a few pixels flip a Gaussian's alpha >= 1/255 test and move by up
-#: to 1/255 (measured on the MI355X at 21 nodes per pass: opacity 3.9e-3, depth 1.1e-2; profiles/visibility_clusters.txt), which is over
-#: that bound.  `nodes_per_pass=21` renders all 63 views in one pass for callers that accept such flips.
+#: means in fp32 and rounded once (include/gsplat_hip.h, "THE SLOT RULE"); that rounding grows with the slot and is ALL that differs from a
+#: single-view render.  Its smooth part stays inside the project's atlas bound scaled to 63 slots (opacity 1e-4 at slot 50); a few pixels per
+#: pass flip a Gaussian's alpha >= 1/255 test and move by up to 1/255 (measured on the MI355X at 21 nodes per pass: opacity 3.9e-3, depth
+#: 1.1e-2; profiles/visibility_clusters.txt), which is over that bound.  These pixels are predicted one by one by the slot-shifted fp64
+#: reference of tests/atlas_cases.py (case `pano63`: all 63 slots, n_contrib equal at every pixel; profiles/README.md, "Atlas, view by view").
+#: `nodes_per_pass=21` renders all 63 views in one pass for callers that accept a panorama that differs from per-node `look_around` there.
 NODES_PER_PASS = 1
 GLOBAL_THRESHOLD, GLOBAL_EPS, GLOBAL_MIN_SAMPLES = 0.8, 5, 25           # src/mapper/__init__.py:12, :18
 GLOBAL_FOOTPRINT = (15, 15)                                             # src/mapper/__init__.py:38

@@ -127,7 +127,14 @@ typedef struct GsBinLayout {
  * padded to whole 256-row blocks) and binning, sorting and blending see ONE image of V view slots side by side, every slot
  * padded to whole tiles.  Sizes for the caller: virtual_P = rows of radii[] and the P to pass to gs_geom_layout; atlas_width =
  * the width to pass to the layout functions and the row length of the output images; view v occupies columns
- * [v * view_stride, v * view_stride + view_width).  gs_preprocess_forward / gs_render_forward still take the INPUT count P. */
+ * [v * view_stride, v * view_stride + view_width).  gs_preprocess_forward / gs_render_forward still take the INPUT count P.
+ * THE SLOT RULE.  With rows = virtual_P / V and gxv = view_stride / 16, input Gaussian i of view v is virtual row v * rows + i; the rows
+ * [v * rows + P, (v + 1) * rows) are padding (radius 0, tile count 0).  A live row's record is the single view's record with ONE change: its
+ * pixel x is fl32(x_in_view + 16 * gxv * v), the view-local fp32 pixel mean plus the slot offset, rounded once to fp32.  Pixel y, conic,
+ * opacity, colour and depth are bit for bit what a single-view forward of view v's settings computes.  The tile rect is clamped to the view's
+ * own gxv columns and both x bounds are then moved by v * gxv; atlas tile (ty, v * gxv + tx) holds the list of view v's tile (tx, ty) with
+ * v * rows added to every index.  (The blend forms pixel - mean in fp32 from the rounded x: a view in a later slot differs from its
+ * single-view render by that rounding -- up to 2^-12 px in slots past column 4096 -- and by nothing else.) */
 int gs_atlas_layout(int32_t P, int32_t view_width, int32_t num_views, int32_t* virtual_P, int32_t* atlas_width, int32_t* view_stride);
 int gs_geom_layout(int32_t P, int32_t width, int32_t height, GsGeomLayout* out);
 int gs_image_layout(int32_t width, int32_t height, GsImageLayout* out);

@@ -395,7 +395,8 @@ def check_look_around_nodes(device, K, params=None, nodes_per_pass=None):
     nodes_per_pass=None, the default of the call: the issue's cap, the atlas bound of tests/test_lookaround.py scaled by 63 / 3, for EVERY value.
       Measured on the MI355X with all 63 slots in one pass (K = 21): max |opacity difference| 3.9e-3 (cap 2.1e-4), max |depth difference| 1.1e-2
       (cap 4.2e-4 + 2.1e-4 |depth|): single pixels where a Gaussian's alpha >= 1/255 test flips; the smooth part (fp32 rounding of the slot offset)
-      is 2e-5 per node, 1e-4 at node 17, inside the cap.  On the emulated kernels a pass of only TWO nodes already has such a pixel (2.3e-3), so
+      is 2e-5 per node, 1e-4 at node 17, inside the cap.  Both parts are now PREDICTED, not only measured: tests/atlas_cases.py (case `pano63`, the
+      same 63 slots) holds every pixel of every view to an fp64 replay whose pixel means carry the slot's fp32 rounding, n_contrib equal everywhere.  On the emulated kernels a pass of only TWO nodes already has such a pixel (2.3e-3), so
       the call renders ONE node per pass by default, as the issue prescribes for a measured maximum over the cap: a node's views then sit in
       slots 0-2, where look_around renders them, and the measured maximum is 0 (every figure printed below).
     nodes_per_pass=21 (the option that renders 63 views in one pass): the same cap under the project's rule for alpha = 1/255 decision flips
