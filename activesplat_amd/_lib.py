@@ -66,6 +66,15 @@ class GsMeshLayout(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("total_bytes", "total", "records", "rects", "tile_count", "tile_offset", "list")]
 
 
+TEXTURE_MAX_LEVELS = 15
+WRAP_REPEAT, WRAP_CLAMP, WRAP_MIRROR = 0, 1, 2
+
+
+class GsTextureDesc(C.Structure):
+    """one texture of the mesh sensor's pool (include/gsplat_hip.h); levels and level_offset are gs_texture_layout's"""
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "wrap_s", "wrap_t", "levels", "reserved")] + [("level_offset", C.c_uint64 * TEXTURE_MAX_LEVELS)]
+
+
 class GsImageGrads(C.Structure):
     """dL/d of the four image outputs (include/gsplat_hip.h); all but dL_dcolor nullable"""
     _fields_ = [(n, C.c_void_p) for n in ("dL_dcolor", "dL_ddepth", "dL_dopacity", "dL_ddepth_sq")]
@@ -75,7 +84,7 @@ SORT_AUTO, SORT_TILE_LDS, SORT_RADIX = 0, 1, 2
 
 
 #: the GS_ABI_VERSION of include/gsplat_hip.h this binding was written against (checked when a library is bound)
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 vp, i32, u32, i64, u64, f32, f64, cint = C.c_void_p, C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_int
 
@@ -244,6 +253,13 @@ BINDINGS = {
     "gs_mesh_render_layout": (cint, [i32, i32, i32, u32, C.POINTER(GsMeshLayout)]),
     # (num_vertices, vertices, num_triangles, triangles, vertex_colors, h_intrinsics4, h_w2c12, near_z, width, height, scratch, capacity, depth, tri_id, color, d_counts, stream)
     "gs_mesh_render": (cint, [i32, vp, i32, vp, vp, C.POINTER(f32), C.POINTER(f32), f32, i32, i32, vp, u32, vp, vp, vp, vp, vp]),
+    # (num_textures, h_textures, pool_texels)
+    "gs_texture_layout": (cint, [i32, C.POINTER(GsTextureDesc), C.POINTER(u64)]),
+    # (num_textures, h_textures, textures, pool, pool_texels, stream)
+    "gs_texture_build_mips": (cint, [i32, C.POINTER(GsTextureDesc), vp, vp, u64, vp]),
+    # (num_vertices, vertices, num_triangles, triangles, vertex_colors, h_intrinsics4, h_w2c12, near_z, width, height, scratch, capacity, depth, tri_id, color, d_counts, uvs, tri_texture, num_textures, h_textures, textures, pool, pool_texels, stream)
+    "gs_mesh_render_textured": (cint, [i32, vp, i32, vp, vp, C.POINTER(f32), C.POINTER(f32), f32, i32, i32, vp, u32, vp, vp, vp, vp, vp, vp, i32,
+                                       C.POINTER(GsTextureDesc), vp, vp, u64, vp]),
     # (width, height, depth, h_intrinsics4, h_c2w12, points, valid, stream)
     "gs_depth_cloud": (cint, [i32, i32, vp, C.POINTER(f32), C.POINTER(f32), vp, vp, vp]),
     # (n_query, n_points)

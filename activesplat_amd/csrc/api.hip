@@ -1360,23 +1360,23 @@ int gs_mesh_render_layout(int32_t num_triangles, int32_t width, int32_t height, 
     return mesh_layout_checked("gs_mesh_render_layout", num_triangles, width, height, capacity, *layout);
 }
 
-int gs_mesh_render(int32_t num_vertices, const float* vertices, int32_t num_triangles, const int32_t* triangles, const uint8_t* vertex_colors,
-                   const float* h_intrinsics4, const float* h_w2c12, float near_z, int32_t width, int32_t height, void* scratch, uint32_t capacity,
-                   float* depth, int32_t* tri_id, uint8_t* color, uint32_t* d_counts, gs_stream_t stream)
+// the argument checks of gs_mesh_render and the carving of its scratch, shared with gs_mesh_render_textured
+static int mesh_args_checked(const char* who, int32_t num_vertices, const float* vertices, int32_t num_triangles, const int32_t* triangles,
+                             const uint8_t* vertex_colors, const float* h_intrinsics4, const float* h_w2c12, float near_z, int32_t width, int32_t height,
+                             void* scratch, uint32_t capacity, float* depth, int32_t* tri_id, uint8_t* color, uint32_t* d_counts, gs::MeshArgs& a)
 {
     GsMeshLayout L;
-    const int rc = mesh_layout_checked("gs_mesh_render", num_triangles, width, height, capacity, L);
+    const int rc = mesh_layout_checked(who, num_triangles, width, height, capacity, L);
     if (rc != GS_OK) return rc;
-    if (num_vertices < 0) return fail(GS_EINVAL, "gs_mesh_render: num_vertices must not be negative");
+    if (num_vertices < 0) return fail(GS_EINVAL, "%s: num_vertices must not be negative", who);
     if (!h_intrinsics4 || !h_w2c12 || !scratch || !depth || !tri_id || !color || !d_counts ||
         (num_triangles > 0 && (!vertices || !triangles || !vertex_colors)) || ((uintptr_t)scratch & 15))
-        return fail(GS_EINVAL, "gs_mesh_render: null pointer (the mesh arrays may be null only with num_triangles == 0) or scratch not 16-byte aligned");
+        return fail(GS_EINVAL, "%s: null pointer (the mesh arrays may be null only with num_triangles == 0) or scratch not 16-byte aligned", who);
     // (written so that a NaN fails them)
-    if (!(near_z > 0.0f && near_z <= 3.402823466e38f)) return fail(GS_EINVAL, "gs_mesh_render: near must be positive and finite");
+    if (!(near_z > 0.0f && near_z <= 3.402823466e38f)) return fail(GS_EINVAL, "%s: near must be positive and finite", who);
     for (int i = 0; i < 4; ++i)
-        if (!(fabsf(h_intrinsics4[i]) <= 3.402823466e38f)) return fail(GS_EINVAL, "gs_mesh_render: intrinsics must be finite");
-    if (!(fabsf(h_intrinsics4[0]) > 0.0f) || !(fabsf(h_intrinsics4[1]) > 0.0f)) return fail(GS_EINVAL, "gs_mesh_render: fx and fy must not be zero");
-    gs::MeshArgs a;
+        if (!(fabsf(h_intrinsics4[i]) <= 3.402823466e38f)) return fail(GS_EINVAL, "%s: intrinsics must be finite", who);
+    if (!(fabsf(h_intrinsics4[0]) > 0.0f) || !(fabsf(h_intrinsics4[1]) > 0.0f)) return fail(GS_EINVAL, "%s: fx and fy must not be zero", who);
     a.V = num_vertices; a.T = num_triangles;
     a.vertices = vertices; a.triangles = triangles; a.vertex_colors = vertex_colors;
     a.fx = h_intrinsics4[0]; a.fy = h_intrinsics4[1]; a.cx = h_intrinsics4[2]; a.cy = h_intrinsics4[3];
@@ -1387,7 +1387,102 @@ int gs_mesh_render(int32_t num_vertices, const float* vertices, int32_t num_tria
     a.tile_count = (uint32_t*)(b + L.tile_count); a.tile_offset = (uint32_t*)(b + L.tile_offset); a.list = (uint32_t*)(b + L.list);
     a.capacity = capacity;
     a.depth = depth; a.tri_id = tri_id; a.color = color; a.d_counts = d_counts;
+    return GS_OK;
+}
+
+int gs_mesh_render(int32_t num_vertices, const float* vertices, int32_t num_triangles, const int32_t* triangles, const uint8_t* vertex_colors,
+                   const float* h_intrinsics4, const float* h_w2c12, float near_z, int32_t width, int32_t height, void* scratch, uint32_t capacity,
+                   float* depth, int32_t* tri_id, uint8_t* color, uint32_t* d_counts, gs_stream_t stream)
+{
+    gs::MeshArgs a;
+    const int rc = mesh_args_checked("gs_mesh_render", num_vertices, vertices, num_triangles, triangles, vertex_colors, h_intrinsics4, h_w2c12, near_z, width,
+                                     height, scratch, capacity, depth, tri_id, color, d_counts, a);
+    if (rc != GS_OK) return rc;
     return launched("gs_mesh_render", "", gs::launch_mesh_render(a, (hipStream_t)stream));
+}
+
+// levels and offsets of one texture after `at` texels; false: a size out of range
+static bool texture_plan(int32_t width, int32_t height, uint64_t& at, int32_t& levels, uint64_t (&offset)[GS_TEXTURE_MAX_LEVELS])
+{
+    if (width < 1 || height < 1 || width > 16384 || height > 16384) return false;
+    levels = 1;
+    for (int m = width > height ? width : height; m > 1; m >>= 1) ++levels;
+    for (int l = 0; l < GS_TEXTURE_MAX_LEVELS; ++l) {
+        offset[l] = l < levels ? at : 0;
+        if (l < levels) at += (uint64_t)((width >> l) > 1 ? (width >> l) : 1) * (uint64_t)((height >> l) > 1 ? (height >> l) : 1);
+    }
+    return true;
+}
+
+// a HOST table as gs_texture_layout left it, for a pool of pool_texels
+static int texture_table_checked(const char* who, int32_t num_textures, const GsTextureDesc* h, uint64_t pool_texels)
+{
+    uint64_t at = 0;
+    for (int k = 0; k < num_textures; ++k) {
+        int32_t levels;
+        uint64_t offset[GS_TEXTURE_MAX_LEVELS];
+        if (!texture_plan(h[k].width, h[k].height, at, levels, offset)) return fail(GS_EINVAL, "%s: texture size out of range (1 <= width, height <= 16384)", who);
+        if ((uint32_t)h[k].wrap_s > 2u || (uint32_t)h[k].wrap_t > 2u) return fail(GS_EINVAL, "%s: wrap mode out of range (0 repeat, 1 clamp, 2 mirror)", who);
+        bool same = h[k].levels == levels;
+        for (int l = 0; l < GS_TEXTURE_MAX_LEVELS; ++l) same = same && h[k].level_offset[l] == offset[l];
+        if (!same) return fail(GS_EINVAL, "%s: levels / level offsets of the texture table are not gs_texture_layout's", who);
+    }
+    if (at != pool_texels) return fail(GS_EINVAL, "%s: pool_texels is not the total gs_texture_layout returned", who);
+    return GS_OK;
+}
+
+int gs_texture_layout(int32_t num_textures, GsTextureDesc* h_textures, uint64_t* pool_texels)
+{
+    if (num_textures < 0) return fail(GS_EINVAL, "gs_texture_layout: num_textures must not be negative");
+    if (!pool_texels || (num_textures > 0 && !h_textures)) return fail(GS_EINVAL, "gs_texture_layout: null pointer");
+    for (int k = 0; k < num_textures; ++k) {                   // (everything is checked before anything is written)
+        if (h_textures[k].width < 1 || h_textures[k].height < 1 || h_textures[k].width > 16384 || h_textures[k].height > 16384)
+            return fail(GS_EINVAL, "gs_texture_layout: texture size out of range (1 <= width, height <= 16384)");
+        if ((uint32_t)h_textures[k].wrap_s > 2u || (uint32_t)h_textures[k].wrap_t > 2u)
+            return fail(GS_EINVAL, "gs_texture_layout: wrap mode out of range (0 repeat, 1 clamp, 2 mirror)");
+    }
+    uint64_t at = 0;
+    for (int k = 0; k < num_textures; ++k) {
+        texture_plan(h_textures[k].width, h_textures[k].height, at, h_textures[k].levels, h_textures[k].level_offset);
+        h_textures[k].reserved = 0;
+    }
+    *pool_texels = at;
+    return GS_OK;
+}
+
+int gs_texture_build_mips(int32_t num_textures, const GsTextureDesc* h_textures, const GsTextureDesc* textures, uint32_t* pool, uint64_t pool_texels,
+                          gs_stream_t stream)
+{
+    if (num_textures < 0) return fail(GS_EINVAL, "gs_texture_build_mips: num_textures must not be negative");
+    if (num_textures == 0) return GS_OK;
+    if (!h_textures || !textures || !pool || ((uintptr_t)textures & 7) || ((uintptr_t)pool & 3))
+        return fail(GS_EINVAL, "gs_texture_build_mips: null pointer, table not 8-byte aligned or pool not 4-byte aligned");
+    const int rc = texture_table_checked("gs_texture_build_mips", num_textures, h_textures, pool_texels);
+    if (rc != GS_OK) return rc;
+    if (num_textures > 65535) return fail(GS_EINVAL, "gs_texture_build_mips: at most 65535 textures");
+    return launched("gs_texture_build_mips", "", gs::launch_texture_mips(num_textures, h_textures, textures, pool, (hipStream_t)stream));
+}
+
+int gs_mesh_render_textured(int32_t num_vertices, const float* vertices, int32_t num_triangles, const int32_t* triangles, const uint8_t* vertex_colors,
+                            const float* h_intrinsics4, const float* h_w2c12, float near_z, int32_t width, int32_t height, void* scratch,
+                            uint32_t capacity, float* depth, int32_t* tri_id, uint8_t* color, uint32_t* d_counts, const float* uvs,
+                            const int32_t* tri_texture, int32_t num_textures, const GsTextureDesc* h_textures, const GsTextureDesc* textures,
+                            const uint32_t* pool, uint64_t pool_texels, gs_stream_t stream)
+{
+    gs::MeshArgs a;
+    int rc = mesh_args_checked("gs_mesh_render_textured", num_vertices, vertices, num_triangles, triangles, vertex_colors, h_intrinsics4, h_w2c12, near_z,
+                               width, height, scratch, capacity, depth, tri_id, color, d_counts, a);
+    if (rc != GS_OK) return rc;
+    if (num_textures < 0) return fail(GS_EINVAL, "gs_mesh_render_textured: num_textures must not be negative");
+    if (num_textures > 0) {
+        if (!h_textures || !textures || !pool || (num_triangles > 0 && (!uvs || !tri_texture)) || ((uintptr_t)uvs & 7) || ((uintptr_t)textures & 7) ||
+            ((uintptr_t)pool & 3))
+            return fail(GS_EINVAL, "gs_mesh_render_textured: null pointer (uvs, tri_texture, the two tables and the pool may be null only with num_textures == 0), "
+                                   "uvs or table not 8-byte aligned, or pool not 4-byte aligned");
+        rc = texture_table_checked("gs_mesh_render_textured", num_textures, h_textures, pool_texels);
+        if (rc != GS_OK) return rc;
+    }
+    return launched("gs_mesh_render_textured", "", gs::launch_mesh_render_textured(a, uvs, tri_texture, num_textures, textures, pool, (hipStream_t)stream));
 }
 
 static bool nearest_size_ok(int64_t n) { return n >= 0 && n <= ((int64_t)1 << 30); }

@@ -729,4 +729,164 @@ hipError_t launch_mesh_render(const MeshArgs& a, hipStream_t st)
     return hipGetLastError();
 }
 
+// ---- textures of the mesh sensor (the rule: include/gsplat_hip.h, gs_mesh_render_textured) -----------------------------------------------
+// The pool holds every level of every texture, one packed RGBX word per texel (R in the low byte, X = 0); the table says where.
+//   mips     one launch per level index over all textures (blockIdx.y = texture), one destination texel per thread, integers only; level l
+//            reads level l - 1, which the launch before it wrote;
+//   texture  after the four launches of the render: one workgroup per 16 x 16 tile with mesh_shade_kernel's pixel-to-lane map (an 8 x 8 quadrant
+//            per wavefront, so that the texels of a wavefront lie together).  A thread reads tri_id of its pixel, the winner's three edge records
+//            from the scratch the render wrote, its three vertex indices and uvs, eight texels, and stores three bytes.  It reads nothing this
+//            launch writes and uses no atomics.
+__global__ __launch_bounds__(kBlock) void texture_mip_kernel(const GsTextureDesc* __restrict__ table, int level, uint32_t* __restrict__ pool)
+{
+    const GsTextureDesc* d = table + blockIdx.y;                // (read field by field: a copy indexed by `level` would live in scratch)
+    if (level >= d->levels) return;
+    const int w0 = d->width, h0 = d->height;
+    const int ws = w0 >> (level - 1) > 1 ? w0 >> (level - 1) : 1, hs = h0 >> (level - 1) > 1 ? h0 >> (level - 1) : 1;
+    const int wd = w0 >> level > 1 ? w0 >> level : 1, hd = h0 >> level > 1 ? h0 >> level : 1;
+    const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (idx >= (int64_t)wd * hd) return;
+    const int i = (int)(idx % wd), j = (int)(idx / wd);
+    const int i0 = 2 * i, i1 = 2 * i + 1 < ws ? 2 * i + 1 : ws - 1, j0 = 2 * j, j1 = 2 * j + 1 < hs ? 2 * j + 1 : hs - 1;
+    const uint32_t* src = pool + d->level_offset[level - 1];
+    const uint32_t a = src[(int64_t)j0 * ws + i0], b = src[(int64_t)j0 * ws + i1], c = src[(int64_t)j1 * ws + i0], e = src[(int64_t)j1 * ws + i1];
+    uint32_t out = 0u;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const uint32_t sum = ((a >> (8 * ch)) & 255u) + ((b >> (8 * ch)) & 255u) + ((c >> (8 * ch)) & 255u) + ((e >> (8 * ch)) & 255u) + 2u;
+        out |= (sum >> 2) << (8 * ch);
+    }
+    pool[d->level_offset[level] + idx] = out;
+}
+
+hipError_t launch_texture_mips(int num_textures, const GsTextureDesc* h_table, const GsTextureDesc* table, uint32_t* pool, hipStream_t st)
+{
+    for (int level = 1; level < GS_TEXTURE_MAX_LEVELS; ++level) {
+        int64_t most = 0;                                       // the largest level `level` of any texture that has one
+        for (int k = 0; k < num_textures; ++k) {
+            if (level >= h_table[k].levels) continue;
+            const int64_t wd = h_table[k].width >> level > 1 ? h_table[k].width >> level : 1, hd = h_table[k].height >> level > 1 ? h_table[k].height >> level : 1;
+            most = wd * hd > most ? wd * hd : most;
+        }
+        if (most == 0) break;
+        hipLaunchKernelGGL(texture_mip_kernel, dim3((unsigned)((most + kBlock - 1) / kBlock), (unsigned)num_textures), dim3(kBlock), 0, st, table, level, pool);
+    }
+    return hipGetLastError();
+}
+
+// wrap(i) and wrap(i + 1) over n texels.  i is an integer of magnitude below 2^35 (|u| <= 2^20 times at most 2^14 texels): the remainder is taken
+// in 32 bits where i fits them, which is every case but a wild uv
+__device__ __forceinline__ void texture_wrap2(long long i, int n, int mode, int& m0, int& m1)
+{
+    if (mode == GS_WRAP_CLAMP) {
+        m0 = i < 0 ? 0 : (i > n - 1 ? n - 1 : (int)i);
+        m1 = i + 1 < 0 ? 0 : (i + 1 > n - 1 ? n - 1 : (int)(i + 1));
+        return;
+    }
+    const int p = mode == GS_WRAP_MIRROR ? 2 * n : n;
+    int m = i >= -2147483647ll && i <= 2147483647ll ? (int)i % p : (int)(i % p);
+    if (m < 0) m += p;
+    const int mn = m + 1 == p ? 0 : m + 1;
+    m0 = m >= n ? 2 * n - 1 - m : m;                            // (only MIRROR has m >= n)
+    m1 = mn >= n ? 2 * n - 1 - mn : mn;
+}
+
+// the bilinear sample of one level at (u, v), both finite and of magnitude at most 2^20: columns first, then rows
+__device__ __forceinline__ void texture_level_sample(const GsTextureDesc* d, int w0, int h0, int wrap_s, int wrap_t, const uint32_t* __restrict__ pool,
+                                                     int level, float u, float v, float (&out)[3])
+{
+#pragma clang fp contract(off)
+    const int wl = w0 >> level > 1 ? w0 >> level : 1, hl = h0 >> level > 1 ? h0 >> level : 1;
+    const float s = u * (float)wl - 0.5f, t = v * (float)hl - 0.5f;
+    const float fi = floorf(s), fj = floorf(t);
+    const float al = s - fi, be = t - fj;
+    int i0, i1, j0, j1;
+    texture_wrap2((long long)fi, wl, wrap_s, i0, i1);
+    texture_wrap2((long long)fj, hl, wrap_t, j0, j1);
+    const uint32_t* base = pool + d->level_offset[level];
+    const uint32_t t00 = base[(int64_t)j0 * wl + i0], t01 = base[(int64_t)j0 * wl + i1];
+    const uint32_t t10 = base[(int64_t)j1 * wl + i0], t11 = base[(int64_t)j1 * wl + i1];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const float a = (float)((t00 >> (8 * ch)) & 255u), b = (float)((t01 >> (8 * ch)) & 255u);
+        const float c = (float)((t10 >> (8 * ch)) & 255u), e = (float)((t11 >> (8 * ch)) & 255u);
+        const float top = (1.0f - al) * a + al * b, bot = (1.0f - al) * c + al * e;
+        out[ch] = (1.0f - be) * top + be * bot;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void mesh_texture_kernel(MeshCam c, const float4* __restrict__ records, const int32_t* __restrict__ tris, int V,
+                                                               const float2* __restrict__ uvs, const int32_t* __restrict__ tri_texture, int num_textures,
+                                                               const GsTextureDesc* __restrict__ table, const uint32_t* __restrict__ pool,
+                                                               const int32_t* __restrict__ tri_id, uint8_t* __restrict__ color)
+{
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int x = blockIdx.x * kTile + (wave & 1) * kQuad + (lane & 7);
+    const int y = blockIdx.y * kTile + (wave >> 1) * kQuad + (lane >> 3);
+    if (x >= c.W || y >= c.H) return;
+    const int64_t pix = (int64_t)y * c.W + x;
+    const int32_t t = tri_id[pix];
+    if (t < 0) return;
+    const int32_t tex = tri_texture[t];
+    if ((unsigned)tex >= (unsigned)num_textures) return;       // vertex colour, as gs_mesh_render left it
+    const int32_t ia = tris[3 * (int64_t)t], ib = tris[3 * (int64_t)t + 1], ic = tris[3 * (int64_t)t + 2];
+    if ((unsigned)ia >= (unsigned)V || (unsigned)ib >= (unsigned)V || (unsigned)ic >= (unsigned)V) return;   // (never a winner: dropped by the setup)
+    const float4 ea = records[4 * (int64_t)t], eb = records[4 * (int64_t)t + 1], ec = records[4 * (int64_t)t + 2];
+    const float2 ua = uvs[ia], ub = uvs[ib], uc = uvs[ic];
+    const GsTextureDesc* d = table + tex;                       // (read field by field: a copy indexed by the level would live in scratch)
+    const int w0 = d->width, h0 = d->height, wrap_s = d->wrap_s, wrap_t = d->wrap_t;
+    // q at the pixel, at its right neighbour and at the one below, on the winner's plane: the edge functions as mesh_shade_kernel evaluates them
+    float qu[3], qv[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float dx = ((float)(x + (k == 1)) - c.cx) / c.fx, dy = ((float)(y + (k == 2)) - c.cy) / c.fy;
+        const float U = __fmaf_rn(dx, ea.x, __fmaf_rn(dy, ea.y, ea.z));
+        const float Vv = __fmaf_rn(dx, eb.x, __fmaf_rn(dy, eb.y, eb.z));
+        const float Ww = __fmaf_rn(dx, ec.x, __fmaf_rn(dy, ec.y, ec.z));
+        const float S = U + Vv + Ww;
+        qu[k] = (U * ua.x + Vv * ub.x + Ww * uc.x) / S;
+        qv[k] = (U * ua.y + Vv * ub.y + Ww * uc.y) / S;
+    }
+    const int top = d->levels - 1;
+    float col[3];
+    if (!(fabsf(qu[0]) <= 1048576.0f) || !(fabsf(qv[0]) <= 1048576.0f)) {                  // (a NaN fails both)
+        const uint32_t w = pool[d->level_offset[top]];
+        col[0] = (float)(w & 255u); col[1] = (float)((w >> 8) & 255u); col[2] = (float)((w >> 16) & 255u);
+    } else {
+        const float exu = (qu[1] - qu[0]) * (float)w0, exv = (qv[1] - qv[0]) * (float)h0;
+        const float eyu = (qu[2] - qu[0]) * (float)w0, eyv = (qv[2] - qv[0]) * (float)h0;
+        const float rx = sqrtf(exu * exu + exv * exv), ry = sqrtf(eyu * eyu + eyv * eyv);
+        const float rho = rx != rx || ry != ry ? rx + ry : fmaxf(rx, ry);                   // (fmaxf would drop a NaN)
+        float lambda = (float)top;
+        if (rho <= 1.0f) lambda = 0.0f;
+        else if (rho <= 3.402823466e38f) lambda = fminf(log2f(rho), (float)top);
+        const float l0 = floorf(lambda), f = lambda - l0;
+        const int level0 = (int)l0, level1 = level0 + 1 < top ? level0 + 1 : top;
+        float s0[3], s1[3];
+        texture_level_sample(d, w0, h0, wrap_s, wrap_t, pool, level0, qu[0], qv[0], s0);
+        texture_level_sample(d, w0, h0, wrap_s, wrap_t, pool, level1, qu[0], qv[0], s1);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) col[ch] = (1.0f - f) * s0[ch] + f * s1[ch];
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const float l = floorf(col[ch] + 0.5f);
+        color[3 * pix + ch] = (uint8_t)(l < 0.0f ? 0u : (l > 255.0f ? 255u : (uint32_t)l));
+    }
+}
+
+hipError_t launch_mesh_render_textured(const MeshArgs& a, const float* uvs, const int32_t* tri_texture, int num_textures, const GsTextureDesc* table,
+                                       const uint32_t* pool, hipStream_t st)
+{
+    const hipError_t e = launch_mesh_render(a, st);
+    if (e != hipSuccess || num_textures == 0 || a.T == 0) return e;
+    MeshCam c;
+    c.fx = a.fx; c.fy = a.fy; c.cx = a.cx; c.cy = a.cy; c.near_z = a.near_z; c.clip_z = 0.0f;
+    for (int i = 0; i < 12; ++i) c.w2c[i] = a.w2c[i];
+    c.W = a.W; c.H = a.H; c.gx = (a.W + kTile - 1) / kTile; c.gy = (a.H + kTile - 1) / kTile;
+    hipLaunchKernelGGL(mesh_texture_kernel, dim3(c.gx, c.gy), dim3(kBlock), 0, st, c, (const float4*)a.records, a.triangles, a.V, (const float2*)uvs,
+                       tri_texture, num_textures, table, pool, (const int32_t*)a.tri_id, a.color);
+    return hipGetLastError();
+}
+
 }  // namespace gs

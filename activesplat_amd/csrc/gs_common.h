@@ -981,6 +981,11 @@ struct MeshArgs {
     uint32_t* d_counts;                                                // [2]: needed list length (saturating), longest tile list
 };
 hipError_t launch_mesh_render(const MeshArgs& a, hipStream_t st);
+// textures of the mesh sensor (grow.hip; the rule: include/gsplat_hip.h, gs_mesh_render_textured).  h_table: the HOST copy the entry point checked
+// (it sizes the launches), table: the DEVICE copy the kernels read.  The textured render is launch_mesh_render plus one launch.
+hipError_t launch_texture_mips(int num_textures, const GsTextureDesc* h_table, const GsTextureDesc* table, uint32_t* pool, hipStream_t st);
+hipError_t launch_mesh_render_textured(const MeshArgs& a, const float* uvs, const int32_t* tri_texture, int num_textures, const GsTextureDesc* table,
+                                       const uint32_t* pool, hipStream_t st);
 // map-quality evaluation of one frame (loss.hip; the rules: include/gsplat_hip.h, gs_eval_frame).  One plan for the layout call, the launches and
 // the finish kernel: level sizes, workgroup records per pass, offsets of the records (in doubles) and of the pooled images (in bytes)
 struct EvalPlan {

@@ -1,18 +1,24 @@
 """Mesh RGB-D sensor on the device: the frame the reference takes from Habitat-sim (colour, planar depth, a pose; src/dataloader/dataloader.py:168-235),
-produced from a vertex-coloured triangle mesh by ray casting on the compute path, and the mesh samples its judge needs
+produced from a vertex-coloured or textured triangle mesh by ray casting on the compute path, and the mesh samples its judge needs
 (scripts/judges/eval_actions.py:59-66).
 
 Habitat-sim rasterises the scene mesh through OpenGL/EGL.  Here the same two images come from `gs_mesh_render` (include/gsplat_hip.h states the
 rendering rule: fp32 edge functions evaluated with the lower vertex index first, two-sided, nearest hit, ties to the lower triangle index):
 
-* `MeshScene`      -- the mesh on the device: vertices, triangles, vertex colours; uploaded and validated once;
+* `MeshScene`      -- the mesh on the device: vertices, triangles, vertex colours, and optionally uvs, a pool of mip-mapped textures and a texture
+                      index per triangle; uploaded and validated once, the mip chains built once (gs_texture_build_mips);
+* `load_glb`       -- a MeshScene from a binary glTF file (what Gibson and Matterport scenes are shipped as), read on the host;
 * `render_mesh`    -- the public primitive: (colour uint8 [H,W,3], planar depth float32 [H,W], triangle id int32 [H,W]) at a world-to-camera pose;
 * `MeshSensor`     -- fixed intrinsics and size; `.frame(X_WV)` takes the pose `SplatMapper.run_raw` takes and returns what `ingest.ingest_frame`
                       takes, so that `SplatMapper.run_sensor` goes sense -> ingest -> map without a pixel leaving the device;
 * `sample_surface` -- area-weighted surface samples for `judge.CompletionJudge`.
 
-Only the depth / colour sensor of the simulator is here: no textures (vertex colours, interpolated), no sensor noise, no far plane, no semantic
-ids, no actions, physics or navmesh.  The rule is two-sided; whether Habitat's renderer culls back faces was not established (no Habitat here),
+A triangle with a texture takes its colour from `gs_mesh_render_textured` (the rule is in the header too): uvs interpolated with the barycentrics
+that decided the hit, a level of detail from the footprint of one pixel step, trilinear filtering between two levels of a mip chain built with
+exact integers, REPEAT / CLAMP / MIRROR wrapping.  Texels are used as stored.  Not modelled: sRGB decoding (filtering happens in stored space),
+base-colour factors, vertex-colour modulation, alpha, anisotropic filtering.
+
+Only the depth / colour sensor of the simulator is here: no sensor noise, no far plane, no semantic ids, no actions, physics or navmesh.  The rule is two-sided; whether Habitat's renderer culls back faces was not established (no Habitat here),
 so a mesh seen from behind differs if it does.  Nothing was run against Habitat-sim.
 
 There is no CPU fallback.
@@ -31,6 +37,7 @@ from .judge import _host_floats
 
 MAX_SIZE = 16384                      # gs_mesh_render: 1 <= width, height <= 16384
 MID_GREY = 128
+WRAP_REPEAT, WRAP_CLAMP, WRAP_MIRROR = _lib.WRAP_REPEAT, _lib.WRAP_CLAMP, _lib.WRAP_MIRROR
 
 
 def _as_tensor(a):
@@ -45,9 +52,14 @@ class MeshScene:
     range 0 .. V-1 are checked at construction (the range check reads two integers back when the triangles are already on the device).
     `device`: where to keep it; default: the device of `vertices` if that is a tensor, the current ROCm device for an array.
 
+    Textures (all three or none): `uvs` [V,2] floating point (kept as float32; glTF convention: origin top-left, v down), `textures` a list of
+    uint8 [h,w,3] images (arrays or tensors, 1 <= h, w <= 16384) or (image, wrap_s, wrap_t) tuples with the wraps WRAP_REPEAT (the default),
+    WRAP_CLAMP or WRAP_MIRROR, and `tri_texture` [T] of an integer type (kept as int32): the texture of each triangle, -1 for its vertex
+    colours; None: texture 0 for every triangle.  The pool is uploaded and its mip chains are built here, once.
+
     `capacities` remembers, per (width, height), how many tile-list entries the last `render_mesh` of this scene needed (see there)."""
 
-    def __init__(self, vertices, triangles, vertex_colors=None, device=None):
+    def __init__(self, vertices, triangles, vertex_colors=None, device=None, uvs=None, textures=None, tri_texture=None):
         v, t = _as_tensor(vertices), _as_tensor(triangles)
         if device is None:
             device = v.device if torch.is_tensor(vertices) else torch.device("cuda")
@@ -79,6 +91,73 @@ class MeshScene:
         self.vertex_colors = c.to(self.device).contiguous()
         self.capacities = {}
         self.last_counts = None           # (D, longest tile list) of the last render_mesh
+        self._upload_textures(uvs, textures, tri_texture)
+
+    def _upload_textures(self, uvs, textures, tri_texture):
+        V, T = self.num_vertices, self.num_triangles
+        self.uvs = self.tri_texture = self.texture_table = self.texture_pool = self._h_table = None
+        self.pool_texels = 0
+        textures = list(textures) if textures is not None else []
+        self.num_textures = len(textures)
+        if not textures:
+            if uvs is not None or tri_texture is not None:
+                raise ValueError("uvs and tri_texture need textures")
+            return
+        if uvs is None:
+            raise ValueError("textures need uvs")
+        uv = _as_tensor(uvs)
+        if not uv.dtype.is_floating_point:
+            raise TypeError(f"uvs must be floating point, got {uv.dtype}")
+        if tuple(uv.shape) != (V, 2):
+            raise ValueError(f"uvs must have shape [{V}, 2], got {list(uv.shape)}")
+        if tri_texture is None:
+            tt = torch.zeros(T, dtype=torch.int32)
+        else:
+            tt = _as_tensor(tri_texture)
+            if tt.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8):
+                raise TypeError(f"tri_texture must be of a signed integer type, got {tt.dtype}")
+            if tuple(tt.shape) != (T,):
+                raise ValueError(f"tri_texture must have shape [{T}], got {list(tt.shape)}")
+            if T and (int(tt.min()) < -1 or int(tt.max()) >= len(textures)):
+                raise ValueError(f"tri_texture outside -1 .. {len(textures) - 1}")
+        table = (_lib.GsTextureDesc * len(textures))()
+        images = []
+        for k, item in enumerate(textures):
+            image, wrap_s, wrap_t = item if isinstance(item, tuple) else (item, WRAP_REPEAT, WRAP_REPEAT)
+            im = _as_tensor(image)
+            if im.dtype != torch.uint8:
+                raise TypeError(f"texture {k} must be uint8, got {im.dtype}")
+            if im.dim() != 3 or im.shape[2] != 3 or not (1 <= im.shape[0] <= MAX_SIZE and 1 <= im.shape[1] <= MAX_SIZE):
+                raise ValueError(f"texture {k} must have shape [h, w, 3] with 1 <= h, w <= {MAX_SIZE}, got {list(im.shape)}")
+            if wrap_s not in (WRAP_REPEAT, WRAP_CLAMP, WRAP_MIRROR) or wrap_t not in (WRAP_REPEAT, WRAP_CLAMP, WRAP_MIRROR):
+                raise ValueError(f"texture {k}: wrap modes must be WRAP_REPEAT, WRAP_CLAMP or WRAP_MIRROR, got {wrap_s!r}, {wrap_t!r}")
+            table[k].width, table[k].height, table[k].wrap_s, table[k].wrap_t = int(im.shape[1]), int(im.shape[0]), int(wrap_s), int(wrap_t)
+            images.append(im)
+        lib = _lib.get()
+        texels = C.c_uint64(0)
+        _lib.check(lib.gs_texture_layout(len(textures), table, C.byref(texels)))
+        self._h_table, self.pool_texels = table, int(texels.value)
+        # one RGBX word per texel (R in the low byte); the levels above 0 are written by the device
+        pool = torch.zeros(self.pool_texels, dtype=torch.int32, device=self.device)
+        for k, im in enumerate(images):
+            rgb = im.to(self.device).to(torch.int32)
+            at = int(table[k].level_offset[0])
+            pool[at:at + rgb.shape[0] * rgb.shape[1]] = (rgb[..., 0] | (rgb[..., 1] << 8) | (rgb[..., 2] << 16)).reshape(-1)
+        raw = np.frombuffer(bytes(table), dtype=np.uint8).copy()
+        self.texture_table = torch.from_numpy(raw).to(self.device)
+        self.texture_pool = pool
+        self.uvs = uv.to(device=self.device, dtype=torch.float32).contiguous()
+        self.tri_texture = tt.to(device=self.device, dtype=torch.int32).contiguous()
+        _lib.check(lib.gs_texture_build_mips(self.num_textures, table, R._ptr(self.texture_table), R._ptr(pool), self.pool_texels, _lib.stream_ptr(self.device)))
+
+    def texture_level(self, k, level):
+        """level `level` of texture `k` as the device holds it -> uint8 [h_l, w_l, 3] (a copy; for inspection and tests)"""
+        d = self._h_table[k]
+        if not 0 <= level < d.levels:
+            raise ValueError(f"texture {k} has levels 0 .. {d.levels - 1}")
+        w, h, at = max(1, d.width >> level), max(1, d.height >> level), int(d.level_offset[level])
+        words = self.texture_pool[at:at + w * h].reshape(h, w)
+        return torch.stack([words & 255, (words >> 8) & 255, (words >> 16) & 255], 2).to(torch.uint8)
 
     @property
     def num_vertices(self):
@@ -91,7 +170,7 @@ class MeshScene:
     @torch.no_grad()
     def transformed(self, transform):
         """The same mesh in another frame: every vertex through the 4x4 (or 3x4) HOST matrix `transform`, computed in float64 on the device and
-        rounded to float32 once; triangles and colours are shared, not copied.  With the world-to-camera matrix of frame 0 this puts the mesh,
+        rounded to float32 once; triangles, colours, uvs and the texture pool are shared, not copied.  With the world-to-camera matrix of frame 0 this puts the mesh,
         and `sample_surface` of it, into the frame `SplatMapper.judge` works in."""
         m = _host_floats(transform, "transform", ((4, 4), (3, 4)))
         rot = torch.from_numpy(np.ascontiguousarray(m[:3, :3])).to(self.device)
@@ -100,6 +179,8 @@ class MeshScene:
         out.device = self.device
         out.vertices = (self.vertices.double() @ rot.T + off).float().contiguous()
         out.triangles, out.vertex_colors = self.triangles, self.vertex_colors
+        for name in ("uvs", "tri_texture", "texture_table", "texture_pool", "_h_table", "pool_texels", "num_textures"):
+            setattr(out, name, getattr(self, name))
         out.capacities, out.last_counts = {}, None
         return out
 
@@ -116,8 +197,10 @@ def render_mesh(scene, intrinsics, w2c, width, height, near=0.01):
     """`scene` seen from the world-to-camera pose `w2c` (4x4 or 3x4; camera x right, y down, z forward: the inverse of the c2w
     `judge.depth_cloud` takes) through `intrinsics` (3x3, or fx, fy, cx, cy); both HOST values ->
       (color uint8 [height, width, 3], depth float32 [height, width], tri_id int32 [height, width])  on the scene's device:
-    planar depth in metres (0 where no triangle is hit), the index of the triangle hit (-1), its interpolated vertex colour (0).  The rule is
-    in include/gsplat_hip.h (gs_mesh_render); triangles nearer than `near` along z are not seen.
+    planar depth in metres (0 where no triangle is hit), the index of the triangle hit (-1), its interpolated vertex colour or, where the
+    triangle has a texture, its mip-mapped texture sample (0).  The rules are in include/gsplat_hip.h (gs_mesh_render, and
+    gs_mesh_render_textured, which a scene with textures goes through: the same launches plus one that overwrites the colour of textured
+    hits; a scene without textures takes gs_mesh_render as before); triangles nearer than `near` along z are not seen.
 
     The length D of the per-tile triangle lists depends on the mesh and the pose.  The call is made with the capacity remembered for this
     (scene, size) in `scene.capacities` (at first a guess from the triangle count) and the two counters it writes -- D and the longest list,
@@ -140,9 +223,15 @@ def render_mesh(scene, intrinsics, w2c, width, height, near=0.01):
         layout = _lib.GsMeshLayout()
         _lib.check(lib.gs_mesh_render_layout(T, W, H, capacity, C.byref(layout)))
         scratch = torch.empty(int(layout.total_bytes), dtype=torch.uint8, device=dev)
-        _lib.check(lib.gs_mesh_render(scene.num_vertices, R._ptr(scene.vertices) if T else None, T, R._ptr(scene.triangles) if T else None,
-                                      R._ptr(scene.vertex_colors) if T else None, k4.ctypes.data_as(fp), m12.ctypes.data_as(fp), float(near), W, H,
-                                      R._ptr(scratch), capacity, R._ptr(depth), R._ptr(tri_id), R._ptr(color), R._ptr(counts), _lib.stream_ptr(dev)))
+        args = (scene.num_vertices, R._ptr(scene.vertices) if T else None, T, R._ptr(scene.triangles) if T else None,
+                R._ptr(scene.vertex_colors) if T else None, k4.ctypes.data_as(fp), m12.ctypes.data_as(fp), float(near), W, H,
+                R._ptr(scratch), capacity, R._ptr(depth), R._ptr(tri_id), R._ptr(color), R._ptr(counts))
+        if scene.num_textures:
+            _lib.check(lib.gs_mesh_render_textured(*args, R._ptr(scene.uvs) if T else None, R._ptr(scene.tri_texture) if T else None, scene.num_textures,
+                                                   scene._h_table, R._ptr(scene.texture_table), R._ptr(scene.texture_pool), scene.pool_texels,
+                                                   _lib.stream_ptr(dev)))
+        else:
+            _lib.check(lib.gs_mesh_render(*args, _lib.stream_ptr(dev)))
         need, longest = (int(v) & 0xffffffff for v in counts.tolist())         # the one copy that waits for the device
         if need <= capacity:
             break
@@ -206,3 +295,207 @@ def sample_surface(scene, n, uniforms=None, generator=None, return_faces=False):
     fa, fb, fc = a[face], b[face], c[face]
     points = (fa + r1[:, None] * (fb - fa) + r2[:, None] * (fc - fa)).float().contiguous()
     return (points, face) if return_faces else points
+
+
+# ---- binary glTF (GLB) -----------------------------------------------------------------------------------------------------------------------
+# What the reference's scenes are shipped as (Gibson / Matterport: config/datasets/gibson.json).  Read on the host with json + struct + numpy; PIL
+# only where an embedded image has to be decoded.  The subset: one binary chunk, triangle lists, POSITION / TEXCOORD_0 / COLOR_0 / indices of any
+# accessor component type and stride, node hierarchy (matrix or TRS), the base-colour texture of a material and its sampler's wrap modes.
+# Everything else that would change the picture raises, naming what it met, instead of being skipped.
+
+_GLTF_COMPONENT = {5120: np.int8, 5121: np.uint8, 5122: np.int16, 5123: np.uint16, 5125: np.uint32, 5126: np.float32}
+_GLTF_WIDTH = {"SCALAR": 1, "VEC2": 2, "VEC3": 3, "VEC4": 4}
+_GLTF_WRAP = {10497: WRAP_REPEAT, 33071: WRAP_CLAMP, 33648: WRAP_MIRROR}
+
+
+def _glb_chunks(path):
+    import json
+    import struct
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 20 or data[:4] != b"glTF":
+        raise ValueError(f"{path}: not a GLB file (no glTF magic)")
+    version, length = struct.unpack_from("<II", data, 4)
+    if version != 2:
+        raise ValueError(f"{path}: GLB container version {version}, only 2 is read")
+    if length > len(data):
+        raise ValueError(f"{path}: header says {length} bytes, the file has {len(data)}")
+    doc, binary, at = None, None, 12
+    while at + 8 <= length:
+        n, kind = struct.unpack_from("<II", data, at)
+        body = data[at + 8:at + 8 + n]
+        if len(body) != n:
+            raise ValueError(f"{path}: chunk at byte {at} runs past the end of the file")
+        if kind == 0x4E4F534A and doc is None:
+            doc = json.loads(body.decode("utf-8"))
+        elif kind == 0x004E4942:
+            if binary is not None:
+                raise ValueError(f"{path}: more than one binary chunk")
+            binary = body
+        at += 8 + n + (-n) % 4
+    if doc is None:
+        raise ValueError(f"{path}: no JSON chunk")
+    return doc, binary
+
+
+def _glb_accessor(doc, binary, index, what):
+    """accessor `index` -> array [count, width] of its component type"""
+    acc = doc["accessors"][index]
+    if "sparse" in acc:
+        raise NotImplementedError(f"{what}: sparse accessor {index}")
+    if acc["componentType"] not in _GLTF_COMPONENT or acc["type"] not in _GLTF_WIDTH:
+        raise NotImplementedError(f"{what}: accessor {index} of component type {acc['componentType']}, type {acc['type']}")
+    dtype, width, count = np.dtype(_GLTF_COMPONENT[acc["componentType"]]), _GLTF_WIDTH[acc["type"]], int(acc["count"])
+    if "bufferView" not in acc:
+        return np.zeros((count, width), dtype)
+    view = doc["bufferViews"][acc["bufferView"]]
+    buffer = doc["buffers"][view["buffer"]]
+    if "uri" in buffer:
+        raise NotImplementedError(f"{what}: external buffer {buffer['uri'][:40]!r} (only the GLB's own binary chunk is read)")
+    if view["buffer"] != 0 or binary is None:
+        raise ValueError(f"{what}: buffer {view['buffer']} has no binary chunk")
+    start = int(view.get("byteOffset", 0)) + int(acc.get("byteOffset", 0))
+    row = width * dtype.itemsize
+    stride = int(view.get("byteStride", 0)) or row
+    if count and (stride < row or start + (count - 1) * stride + row > len(binary)):
+        raise ValueError(f"{what}: accessor {index} runs outside the binary chunk")
+    raw = np.frombuffer(binary, np.uint8)
+    rows = np.lib.stride_tricks.as_strided(raw[start:], (count, row), (stride, 1)) if count else np.zeros((0, row), np.uint8)
+    return np.ascontiguousarray(rows).view(dtype.newbyteorder("<")).astype(dtype).reshape(count, width)
+
+
+def _glb_unit(a, normalized, what):
+    """an attribute in [0, 1]: floats as they are, normalized unsigned integers over their range, in float64"""
+    if a.dtype == np.float32:
+        return a.astype(np.float64)
+    if normalized and a.dtype in (np.uint8, np.uint16):
+        return a.astype(np.float64) / float(np.iinfo(a.dtype).max)
+    raise NotImplementedError(f"{what}: component type {a.dtype}{'' if normalized else ' not normalized'}")
+
+
+def _glb_node_matrix(node):
+    if "matrix" in node:
+        return np.asarray(node["matrix"], np.float64).reshape(4, 4).T          # (glTF stores columns)
+    m = np.eye(4)
+    x, y, z, w = np.asarray(node.get("rotation", (0, 0, 0, 1)), np.float64)
+    rot = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                    [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                    [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+    m[:3, :3] = rot * np.asarray(node.get("scale", (1, 1, 1)), np.float64)[None, :]
+    m[:3, 3] = np.asarray(node.get("translation", (0, 0, 0)), np.float64)
+    return m
+
+
+def read_glb(path):
+    """The arrays `MeshScene` takes, from a GLB file, on the host -> dict(vertices float32 [V,3] (node transforms applied in float64), triangles
+    int32 [T,3], vertex_colors uint8 [V,3] (COLOR_0, mid-grey where a primitive has none), uvs float32 [V,2] (TEXCOORD_0, 0 where none),
+    textures [(uint8 [h,w,3], wrap_s, wrap_t)], tri_texture int32 [T]); uvs, textures and tri_texture are None when no material has a base-colour
+    texture.  One pool entry per glTF texture (image + sampler) in use; alpha is dropped.  Raises for what it does not read: external buffers and
+    images, Draco and other required extensions, sparse accessors, primitives that are not triangle lists, texture coordinate sets other than 0."""
+    doc, binary = _glb_chunks(path)
+    for ext in doc.get("extensionsRequired", ()):
+        raise NotImplementedError(f"{path}: required extension {ext}")
+    scenes = doc.get("scenes") or [{"nodes": list(range(len(doc.get("nodes", ()))))}]
+    roots = scenes[int(doc.get("scene", 0))].get("nodes", [])
+    nodes, meshes = doc.get("nodes", []), doc.get("meshes", [])
+    pool_index, pool = {}, []
+
+    def texture_of(material, what):
+        if material is None:
+            return -1
+        info = doc["materials"][material].get("pbrMetallicRoughness", {}).get("baseColorTexture")
+        if info is None:
+            return -1
+        if info.get("texCoord", 0) != 0:
+            raise NotImplementedError(f"{what}: base-colour texture on TEXCOORD_{info['texCoord']}")
+        if info["index"] not in pool_index:
+            tex = doc["textures"][info["index"]]
+            if "source" not in tex:
+                raise NotImplementedError(f"{what}: texture {info['index']} without a source image ({sorted(tex.get('extensions', {}))})")
+            image = doc["images"][tex["source"]]
+            if "bufferView" not in image:
+                raise NotImplementedError(f"{what}: external image {str(image.get('uri'))[:40]!r} (only embedded images are read)")
+            view = doc["bufferViews"][image["bufferView"]]
+            if "uri" in doc["buffers"][view["buffer"]] or binary is None:
+                raise NotImplementedError(f"{what}: image {tex['source']} in an external buffer")
+            import io
+            from PIL import Image
+            start = int(view.get("byteOffset", 0))
+            with Image.open(io.BytesIO(binary[start:start + int(view["byteLength"])])) as im:
+                pixels = np.array(im.convert("RGB"), np.uint8)                    # (a copy: PIL hands out read-only memory)
+            sampler = doc["samplers"][tex["sampler"]] if "sampler" in tex else {}
+            wraps = []
+            for key in ("wrapS", "wrapT"):
+                if sampler.get(key, 10497) not in _GLTF_WRAP:
+                    raise NotImplementedError(f"{what}: sampler {key} {sampler[key]}")
+                wraps.append(_GLTF_WRAP[sampler.get(key, 10497)])
+            pool_index[info["index"]] = len(pool)
+            pool.append((pixels, wraps[0], wraps[1]))
+        return pool_index[info["index"]]
+
+    parts, n_vertices = [], 0
+    stack = [(int(r), np.eye(4)) for r in reversed(roots)]
+    visited = 0
+    while stack:
+        index, parent = stack.pop()
+        visited += 1
+        if visited > 16 * max(1, len(nodes)) + 1024:
+            raise ValueError(f"{path}: the node hierarchy does not end (a cycle?)")
+        node = nodes[index]
+        world = parent @ _glb_node_matrix(node)
+        stack.extend((int(c), world) for c in reversed(node.get("children", ())))
+        if "mesh" not in node:
+            continue
+        for p, prim in enumerate(meshes[node["mesh"]]["primitives"]):
+            what = f"{path}: mesh {node['mesh']} primitive {p}"
+            if prim.get("mode", 4) != 4:
+                raise NotImplementedError(f"{what}: mode {prim['mode']} (only triangle lists, mode 4)")
+            for ext in prim.get("extensions", {}):
+                raise NotImplementedError(f"{what}: extension {ext}")
+            attrs = prim["attributes"]
+            if "POSITION" not in attrs:
+                raise ValueError(f"{what}: no POSITION")
+            pos = _glb_accessor(doc, binary, attrs["POSITION"], what)
+            if pos.dtype != np.float32 or pos.shape[1] != 3:
+                raise NotImplementedError(f"{what}: POSITION of {pos.dtype} x {pos.shape[1]}")
+            n = len(pos)
+            if "indices" in prim:
+                idx = _glb_accessor(doc, binary, prim["indices"], what).reshape(-1).astype(np.int64)
+            else:
+                idx = np.arange(n, dtype=np.int64)
+            if len(idx) % 3 or (len(idx) and (idx.min() < 0 or idx.max() >= n)):
+                raise ValueError(f"{what}: {len(idx)} indices into {n} vertices")
+            tex = texture_of(prim.get("material"), what)
+            if "TEXCOORD_0" in attrs:
+                acc = doc["accessors"][attrs["TEXCOORD_0"]]
+                uv = _glb_unit(_glb_accessor(doc, binary, attrs["TEXCOORD_0"], what), acc.get("normalized", False), what + " TEXCOORD_0")
+                if uv.shape != (n, 2):
+                    raise ValueError(f"{what}: TEXCOORD_0 of shape {list(uv.shape)}")
+            elif tex >= 0:
+                raise ValueError(f"{what}: a base-colour texture without TEXCOORD_0")
+            else:
+                uv = np.zeros((n, 2))
+            if "COLOR_0" in attrs:
+                acc = doc["accessors"][attrs["COLOR_0"]]
+                col = _glb_unit(_glb_accessor(doc, binary, attrs["COLOR_0"], what), acc.get("normalized", False), what + " COLOR_0")
+                if col.shape[0] != n or col.shape[1] not in (3, 4):
+                    raise ValueError(f"{what}: COLOR_0 of shape {list(col.shape)}")
+                col = np.clip(np.floor(col[:, :3] * 255.0 + 0.5), 0, 255).astype(np.uint8)
+            else:
+                col = np.full((n, 3), MID_GREY, np.uint8)
+            p64 = pos.astype(np.float64) @ world[:3, :3].T + world[:3, 3]
+            parts.append((p64.astype(np.float32), (idx.reshape(-1, 3) + n_vertices), col, uv.astype(np.float32), np.full(len(idx) // 3, tex, np.int32)))
+            n_vertices += n
+    if n_vertices >= 2 ** 31:
+        raise ValueError(f"{path}: {n_vertices} vertices")
+    cat = lambda k, shape, dtype: np.concatenate([p[k] for p in parts]).astype(dtype) if parts else np.zeros(shape, dtype)  # noqa: E731
+    out = dict(vertices=cat(0, (0, 3), np.float32), triangles=cat(1, (0, 3), np.int32), vertex_colors=cat(2, (0, 3), np.uint8),
+               uvs=cat(3, (0, 2), np.float32), textures=pool, tri_texture=cat(4, (0,), np.int32))
+    if not pool:
+        out["uvs"] = out["textures"] = out["tri_texture"] = None
+    return out
+
+
+def load_glb(path, device=None):
+    """`read_glb(path)` as a MeshScene on `device` (default: the current ROCm device)."""
+    return MeshScene(device=device, **read_glb(path))

@@ -205,7 +205,7 @@ const char* gs_version(void);
 /* Integer version of THIS binary interface: bumped whenever an entry point's argument list or a published record layout changes (e.g.
  * the seed argument of gs_densify_children, the 40-byte SH Jacobian record).  A host binding compares it with the GS_ABI_VERSION it was
  * written against before the first call, so that a stale prebuilt library fails at load time instead of misreading its arguments. */
-#define GS_ABI_VERSION 23
+#define GS_ABI_VERSION 24
 int32_t gs_abi_version(void);
 
 /* Optional per-stage timing (hipEvents recorded on the caller's stream around each stage's launches).
@@ -805,7 +805,7 @@ int gs_frame_ingest(int32_t width, int32_t height, const uint8_t* image, const f
  *   winner                the smallest z; among equal z the lowest triangle index: the image does not depend on the order of any list
  *   outputs               depth fp32 [height * width], 0 where nothing is hit; tri_id int32 [height * width], -1 where nothing is hit; color uint8
  *                         [height * width * 3] interleaved, clamp(floor((U C_a + V C_b + W C_c) / S + 0.5), 0, 255), 0 where nothing is hit.
- * Not modelled: textures, sensor noise, a far plane.
+ * Not modelled: sensor noise, a far plane; textures are gs_mesh_render_textured's (below), with what THEY leave unmodelled stated there.
  * Four launches on `stream`: per-triangle setup (edge vectors, a conservative rectangle of 16 x 16 tiles -- clipped against z = near where the
  * triangle crosses it -- and the tile counts), a scan over the tiles, the fill of the tile lists, and one workgroup per tile that casts its 256
  * rays.  Integer atomics only; nothing a workgroup reads was written by another workgroup of the same launch; two calls on the same inputs give
@@ -836,6 +836,68 @@ int gs_mesh_render_layout(int32_t num_triangles, int32_t width, int32_t height, 
 int gs_mesh_render(int32_t num_vertices, const float* vertices, int32_t num_triangles, const int32_t* triangles, const uint8_t* vertex_colors,
                    const float* h_intrinsics4, const float* h_w2c12, float near_z, int32_t width, int32_t height, void* scratch, uint32_t capacity,
                    float* depth, int32_t* tri_id, uint8_t* color, uint32_t* d_counts, gs_stream_t stream);
+
+/* ---- Textures of the mesh sensor (the reference's scenes are Gibson / Matterport GLBs, config/datasets/gibson.json, whose colour lives in
+ * texture images) ----
+ * gs_mesh_render_textured is gs_mesh_render followed by ONE more launch that overwrites the colour of the hits whose triangle has a texture:
+ * depth, tri_id and the colour of every other pixel are gs_mesh_render's bits.  gs_mesh_render itself is unchanged.
+ * SCENE ADDITIONS.  uvs fp32 [num_vertices, 2] DEVICE, 8-byte aligned, glTF convention: origin top-left, v down, row = v * h, no flip.
+ * tri_texture int32 [num_triangles] DEVICE: the texture of each triangle; -1, or any value outside 0 .. num_textures - 1, means "vertex
+ * colour, as gs_mesh_render gives it" -- such a value is never used to index the table.  A texture pool: texture k has a level 0 of
+ * width x height texels (1 .. 16384 each), wrap_s / wrap_t in {GS_WRAP_REPEAT 0, GS_WRAP_CLAMP 1, GS_WRAP_MIRROR 2} and
+ * L = 1 + floor(log2(max(width, height))) levels; level l has max(1, width >> l) x max(1, height >> l) texels, so level L - 1 is ONE texel.
+ * The pool is one DEVICE array of packed 32-bit RGBX words, one per texel (R in bits 0-7, G 8-15, B 16-23, X = 0), row-major, level after level,
+ * texture after texture: a fetch is one dword load.  gs_texture_layout fills `levels` and `level_offset` (in texels) of every entry of a HOST
+ * table and returns the pool's size; the caller writes level 0 of every texture into the pool and copies the table to the device.
+ * MIP CHAIN (exact integers; gs_texture_build_mips, on the device, once per scene).  Level l + 1 texel (i, j), per channel:
+ *   (t[2j][2i] + t[2j][i1] + t[j1][2i] + t[j1][i1] + 2) >> 2   with i1 = min(2i + 1, w_l - 1), j1 = min(2j + 1, h_l - 1), t = level l.
+ * One launch per level index over all textures (not one per texture), one destination texel per thread, integer arithmetic only.
+ * THE RULE per pixel (x, y) whose winner t = (a, b, c) has a texture, all fp32:
+ *   q(x', y')   = (U uv_a + V uv_b + W uv_c) / ((U + V) + W), with U, V, W the winner's three edge functions at the ray of pixel (x', y'): the edge
+ *                 vectors gs_mesh_render stored and the same two fused multiply-adds per edge, so that at (x, y) they are exactly the
+ *                 barycentrics that decided the hit.  q is evaluated at (x, y), (x + 1, y) and (x, y + 1), ON THE WINNER'S PLANE: the two
+ *                 neighbours are taken whether or not they hit the triangle (or anything), and also beyond the image edge.
+ *   footprint     ex = (q(x + 1, y) - q(x, y)) o (width, height), ey likewise from (x, y + 1); rho = max(|ex|_2, |ey|_2)
+ *   level         lambda = clamp(log2 rho, 0, L - 1); lambda = 0 when rho <= 1; lambda = L - 1 when rho is NaN or infinite
+ *   level sample  at (u, v) = q(x, y), level l of w_l x h_l texels: s = u w_l - 0.5, i = floor(s), alpha = s - i; t = v h_l - 0.5, j = floor(t),
+ *                 beta = t - j; the texels T[wrap(j), wrap(j + 1)][wrap(i), wrap(i + 1)]; columns first, then rows:
+ *                   top = (1 - alpha) T[j][i] + alpha T[j][i+1];  bot = (1 - alpha) T[j+1][i] + alpha T[j+1][i+1];  (1 - beta) top + beta bot
+ *   wrap over n   REPEAT: i mod n, non-negative.  CLAMP: clip to 0 .. n - 1.  MIRROR: m = i mod 2n (non-negative); m >= n -> 2n - 1 - m.
+ *   safety        if a component of q(x, y) is not finite or exceeds 2^20 in magnitude the pixel takes the single texel of level L - 1: the
+ *                 float -> integer conversion of floor(s) is then always defined (|s| < 2^35, converted to 64 bits)
+ *   mix           l0 = floor(lambda), f = lambda - l0;  c = (1 - f) sample(l0) + f sample(min(l0 + 1, L - 1));  out = clamp(floor(c + 0.5), 0, 255)
+ * TEXELS ARE USED AS STORED.  Not modelled: sRGB decoding (filtering happens in stored space), base-colour factors, vertex-colour modulation,
+ * alpha, anisotropic filtering.  Nothing was run against Habitat-sim.
+ * THE TEXTURE PASS: one workgroup per 16 x 16 pixels with the pixel-to-lane map of the render's last launch (an 8 x 8 quadrant per wavefront, so
+ * that the texel fetches of a wavefront stay local).  A thread reads tri_id of its pixel, the winner's three edge records from the scratch the
+ * render just wrote, its three vertex indices and uvs, eight texels, and stores three bytes.  No atomics; nothing is read that the same launch
+ * writes; two calls on the same inputs give the same bits.  When D > capacity the outputs are cleared as by gs_mesh_render.
+ * THE TABLE TWICE.  gs_texture_build_mips and gs_mesh_render_textured take the table as h_textures (HOST: checked before any launch, and it sizes
+ * the mip launches) and as textures (DEVICE: what the kernels read).  The caller passes two copies of the same bytes; only the host copy
+ * can be checked without waiting for the device.
+ * Refused with GS_EINVAL before any launch, besides everything gs_mesh_render refuses: num_textures < 0; with num_textures > 0 a null uvs (or one
+ * not 8-byte aligned), tri_texture, h_textures, textures or pool; a wrap mode outside 0 .. 2; a texture size outside 1 .. 16384; levels or
+ * level offsets that are not gs_texture_layout's, or a pool_texels that is not its total.  With num_textures == 0 everything texture-related
+ * may be null and the call equals gs_mesh_render.  uvs and tri_texture may also be null when num_triangles is 0. */
+#define GS_WRAP_REPEAT 0
+#define GS_WRAP_CLAMP 1
+#define GS_WRAP_MIRROR 2
+#define GS_TEXTURE_MAX_LEVELS 15     /* 1 + log2(16384) */
+typedef struct GsTextureDesc {
+    int32_t width, height;           /* level 0: 1 .. 16384 */
+    int32_t wrap_s, wrap_t;          /* GS_WRAP_* along u (columns) and v (rows) */
+    int32_t levels;                  /* written by gs_texture_layout: 1 + floor(log2(max(width, height))) */
+    int32_t reserved;                /* 0 */
+    uint64_t level_offset[GS_TEXTURE_MAX_LEVELS];   /* written by gs_texture_layout: first texel of level l in the pool; 0 beyond the last level */
+} GsTextureDesc;
+int gs_texture_layout(int32_t num_textures, GsTextureDesc* h_textures, uint64_t* pool_texels);
+int gs_texture_build_mips(int32_t num_textures, const GsTextureDesc* h_textures, const GsTextureDesc* textures, uint32_t* pool, uint64_t pool_texels,
+                          gs_stream_t stream);
+int gs_mesh_render_textured(int32_t num_vertices, const float* vertices, int32_t num_triangles, const int32_t* triangles, const uint8_t* vertex_colors,
+                            const float* h_intrinsics4, const float* h_w2c12, float near_z, int32_t width, int32_t height, void* scratch,
+                            uint32_t capacity, float* depth, int32_t* tri_id, uint8_t* color, uint32_t* d_counts, const float* uvs,
+                            const int32_t* tri_texture, int32_t num_textures, const GsTextureDesc* h_textures, const GsTextureDesc* textures,
+                            const uint32_t* pool, uint64_t pool_texels, gs_stream_t stream);
 
 /* ---- Completion / accuracy judge (ActiveSplat's own figure: scripts/judges/eval_actions.py:33-40,139-152) ----
  * Per frame the reference back-projects the sensor depth (rgbd_to_pointcloud, src/utils/gui_utils.py:96-125, called with depth scale 1000 and
