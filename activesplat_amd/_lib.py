@@ -84,7 +84,7 @@ SORT_AUTO, SORT_TILE_LDS, SORT_RADIX = 0, 1, 2
 
 
 #: the GS_ABI_VERSION of include/gsplat_hip.h this binding was written against (checked when a library is bound)
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 vp, i32, u32, i64, u64, f32, f64, cint = C.c_void_p, C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_int
 
@@ -274,6 +274,14 @@ BINDINGS = {
     "gs_eval_frame_layout": (cint, [i32, i32, i32, C.POINTER(GsEvalLayout)]),
     # (width, height, im, depth, silhouette, gt_im, gt_depth, sil_thres, flags, row, scratch, stream)
     "gs_eval_frame": (cint, [i32, i32] + [vp] * 5 + [f32, i32, vp, vp, vp]),
+    # (nx, ny, nz, h_origin3, voxel_size, trunc, max_weight, tsdf, weight, color, n_frames, width, height, depth, frame_color, silhouette, h_intrinsics4, h_w2c12, sil_thres, depth_max, stream)
+    "gs_tsdf_integrate": (cint, [i32, i32, i32, C.POINTER(f32), f32, f32, f32, vp, vp, vp, i32, i32, i32, vp, vp, vp, C.POINTER(f32), C.POINTER(f32), f32, f32, vp]),
+    # (nx, ny, nz)
+    "gs_tsdf_extract_scratch_bytes": (u64, [i32, i32, i32]),
+    # (nx, ny, nz, tsdf, weight, min_weight, scratch, d_counts, stream)
+    "gs_tsdf_count": (cint, [i32, i32, i32, vp, vp, f32, vp, vp, vp]),
+    # (nx, ny, nz, h_origin3, voxel_size, tsdf, color, scratch, max_vertices, max_triangles, vertices, vertex_colors, triangles, stream)
+    "gs_tsdf_emit": (cint, [i32, i32, i32, C.POINTER(f32), f32, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
 }
 
 SYMBOLS = tuple(BINDINGS)

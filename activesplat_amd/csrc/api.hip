@@ -1338,6 +1338,108 @@ int gs_depth_cloud(int32_t width, int32_t height, const float* depth, const floa
     return launched("gs_depth_cloud", "", gs::launch_depth_cloud(width, height, depth, h_intrinsics4, h_c2w12, points, valid, (hipStream_t)stream));
 }
 
+// ---- TSDF fusion and surface extraction (grow.hip) ----
+static bool finite_f(float v) { return fabsf(v) <= 3.402823466e38f; }                  // (a NaN fails it)
+static bool positive_finite(float v) { return v > 0.0f && v <= 3.402823466e38f; }
+
+// the checks on a volume's shape shared by the three calls; fills g
+static int tsdf_grid_checked(const char* who, int32_t nx, int32_t ny, int32_t nz, const float* h_origin3, float voxel_size, gs::TsdfGrid& g)
+{
+    if (nx < 1 || ny < 1 || nz < 1) return fail(GS_EINVAL, "%s: volume dimensions must be at least 1", who);
+    if ((int64_t)nx * ny >= ((int64_t)1 << 31) || (int64_t)nx * ny * nz >= ((int64_t)1 << 31))
+        return fail(GS_EINVAL, "%s: nx * ny * nz must be below 2^31", who);
+    g.nx = nx; g.ny = ny; g.nz = nz; g.n = (int64_t)nx * ny * nz;
+    g.ox = g.oy = g.oz = 0.0f; g.vs = 1.0f;
+    if (h_origin3) {
+        if (!finite_f(h_origin3[0]) || !finite_f(h_origin3[1]) || !finite_f(h_origin3[2])) return fail(GS_EINVAL, "%s: origin must be finite", who);
+        if (!positive_finite(voxel_size)) return fail(GS_EINVAL, "%s: voxel_size must be positive and finite", who);
+        g.ox = h_origin3[0]; g.oy = h_origin3[1]; g.oz = h_origin3[2]; g.vs = voxel_size;
+    }
+    return GS_OK;
+}
+
+int gs_tsdf_integrate(int32_t nx, int32_t ny, int32_t nz, const float* h_origin3, float voxel_size, float trunc, float max_weight, float* tsdf,
+                      float* weight, float* color, int32_t n_frames, int32_t width, int32_t height, const float* depth, const float* frame_color,
+                      const float* silhouette, const float* h_intrinsics4, const float* h_w2c12, float sil_thres, float depth_max, gs_stream_t stream)
+{
+    gs::TsdfArgs a;
+    if (!h_origin3 || !h_intrinsics4 || !h_w2c12 || !tsdf || !weight || !depth || (frame_color && !color))
+        return fail(GS_EINVAL, "gs_tsdf_integrate: null pointer (color may be null only without frame_color; frame_color and silhouette may be null)");
+    if ((((uintptr_t)tsdf | (uintptr_t)weight | (uintptr_t)color) & 15) || (((uintptr_t)depth | (uintptr_t)frame_color | (uintptr_t)silhouette) & 3))
+        return fail(GS_EINVAL, "gs_tsdf_integrate: tsdf / weight / color must be 16-byte aligned (the kernel makes 128-bit accesses), the images 4-byte aligned");
+    const int rc = tsdf_grid_checked("gs_tsdf_integrate", nx, ny, nz, h_origin3, voxel_size, a.g);
+    if (rc != GS_OK) return rc;
+    if (!positive_finite(trunc)) return fail(GS_EINVAL, "gs_tsdf_integrate: trunc must be positive and finite");
+    if (!(max_weight >= 1.0f && max_weight <= 3.402823466e38f)) return fail(GS_EINVAL, "gs_tsdf_integrate: max_weight must be at least 1 and finite");
+    if (n_frames < 0 || n_frames > gs::kTsdfMaxFrames) return fail(GS_EINVAL, "gs_tsdf_integrate: 0 <= n_frames <= 16 (the poses travel in the kernel arguments)");
+    if (width < 1 || height < 1 || width > 16384 || height > 16384)
+        return fail(GS_EINVAL, "gs_tsdf_integrate: image size out of range (1 <= width, height <= 16384)");
+    if (!positive_finite(h_intrinsics4[0]) || !positive_finite(h_intrinsics4[1])) return fail(GS_EINVAL, "gs_tsdf_integrate: fx and fy must be positive and finite");
+    if (!finite_f(h_intrinsics4[2]) || !finite_f(h_intrinsics4[3])) return fail(GS_EINVAL, "gs_tsdf_integrate: cx and cy must be finite");
+    for (int i = 0; i < 12 * n_frames; ++i)
+        if (!finite_f(h_w2c12[i])) return fail(GS_EINVAL, "gs_tsdf_integrate: poses must be finite");
+    if (!(depth_max > 0.0f)) return fail(GS_EINVAL, "gs_tsdf_integrate: depth_max must be positive (infinity: no limit)");
+    if (sil_thres != sil_thres) return fail(GS_EINVAL, "gs_tsdf_integrate: sil_thres must not be NaN");
+    a.trunc = trunc; a.max_weight = max_weight;
+    a.tsdf = tsdf; a.weight = weight; a.color = color;
+    a.frames = n_frames; a.W = width; a.H = height;
+    a.depth = depth; a.frame_color = frame_color; a.silhouette = silhouette;
+    a.fx = h_intrinsics4[0]; a.fy = h_intrinsics4[1]; a.cx = h_intrinsics4[2]; a.cy = h_intrinsics4[3];
+    a.sil_thres = sil_thres; a.depth_max = depth_max;
+    memset(a.f, 0, sizeof(a.f));
+    for (int f = 0; f < n_frames; ++f) {
+        const float* m = h_w2c12 + 12 * f;
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) a.f[f].r[3 * r + c] = m[4 * r + c];
+            a.f[f].t[r] = m[4 * r + 3];
+        }
+    }
+    return launched("gs_tsdf_integrate", "", gs::launch_tsdf_integrate(a, (hipStream_t)stream));
+}
+
+// a vertex index is an int32 and a grid point owns up to seven vertices
+static const int64_t kTsdfExtractMaxPoints = (((int64_t)1 << 31) - 1) / 7;
+
+uint64_t gs_tsdf_extract_scratch_bytes(int32_t nx, int32_t ny, int32_t nz)
+{
+    gs::TsdfGrid g;
+    if (tsdf_grid_checked("gs_tsdf_extract_scratch_bytes", nx, ny, nz, nullptr, 1.0f, g) != GS_OK || g.n > kTsdfExtractMaxPoints) return 0;
+    return gs::tsdf_extract_scratch_bytes(g.n);
+}
+
+int gs_tsdf_count(int32_t nx, int32_t ny, int32_t nz, const float* tsdf, const float* weight, float min_weight, void* scratch, uint32_t* d_counts,
+                  gs_stream_t stream)
+{
+    gs::TsdfExtractArgs a;
+    if (!tsdf || !weight || !scratch || !d_counts || ((uintptr_t)scratch & 15) || (((uintptr_t)tsdf | (uintptr_t)weight | (uintptr_t)d_counts) & 3))
+        return fail(GS_EINVAL, "gs_tsdf_count: null pointer, scratch not 16-byte aligned or an array not 4-byte aligned");
+    const int rc = tsdf_grid_checked("gs_tsdf_count", nx, ny, nz, nullptr, 1.0f, a.g);
+    if (rc != GS_OK) return rc;
+    if (a.g.n > kTsdfExtractMaxPoints) return fail(GS_EINVAL, "gs_tsdf_count: 7 * nx * ny * nz must be below 2^31 (vertex indices are int32)");
+    if (min_weight != min_weight) return fail(GS_EINVAL, "gs_tsdf_count: min_weight must not be NaN");
+    a.min_weight = min_weight; a.tsdf = tsdf; a.weight = weight; a.color = nullptr;
+    gs::tsdf_extract_carve(a.g.n, scratch, a);
+    return launched("gs_tsdf_count", "", gs::launch_tsdf_count(a, d_counts, (hipStream_t)stream));
+}
+
+int gs_tsdf_emit(int32_t nx, int32_t ny, int32_t nz, const float* h_origin3, float voxel_size, const float* tsdf, const float* color, void* scratch,
+                 int32_t max_vertices, int32_t max_triangles, float* vertices, float* vertex_colors, int32_t* triangles, gs_stream_t stream)
+{
+    gs::TsdfExtractArgs a;
+    if (max_vertices < 0 || max_triangles < 0) return fail(GS_EINVAL, "gs_tsdf_emit: max_vertices and max_triangles must not be negative");
+    if (!h_origin3 || !tsdf || !scratch || (max_vertices > 0 && (!vertices || (color && !vertex_colors))) || (max_triangles > 0 && !triangles) ||
+        ((uintptr_t)scratch & 15) || (((uintptr_t)tsdf | (uintptr_t)color | (uintptr_t)vertices | (uintptr_t)vertex_colors | (uintptr_t)triangles) & 3))
+        return fail(GS_EINVAL, "gs_tsdf_emit: null pointer (color may be null: no vertex colours; an output may be null when its maximum is 0), scratch not "
+                               "16-byte aligned or an array not 4-byte aligned");
+    const int rc = tsdf_grid_checked("gs_tsdf_emit", nx, ny, nz, h_origin3, voxel_size, a.g);
+    if (rc != GS_OK) return rc;
+    if (a.g.n > kTsdfExtractMaxPoints) return fail(GS_EINVAL, "gs_tsdf_emit: 7 * nx * ny * nz must be below 2^31 (vertex indices are int32)");
+    a.min_weight = 0.0f; a.tsdf = tsdf; a.weight = nullptr; a.color = color;
+    gs::tsdf_extract_carve(a.g.n, scratch, a);
+    return launched("gs_tsdf_emit", "", gs::launch_tsdf_emit(a, (uint32_t)max_vertices, (uint32_t)max_triangles, vertices, vertex_colors, triangles,
+                    (hipStream_t)stream));
+}
+
 static int mesh_layout_checked(const char* who, int32_t num_triangles, int32_t width, int32_t height, uint32_t capacity, GsMeshLayout& L)
 {
     if (num_triangles < 0) return fail(GS_EINVAL, "%s: num_triangles must not be negative", who);

@@ -149,6 +149,12 @@ hipError_t launch_compact_index(int64_t n, const uint8_t* keep, uint32_t* src_in
     return hipGetLastError();
 }
 
+hipError_t launch_block_counts_scan(uint32_t* block_counts, int nb, int lists, uint32_t* d_counts, hipStream_t st)
+{
+    hipLaunchKernelGGL(compact_scan_kernel, dim3(lists), dim3(1024), 0, st, block_counts, nb, d_counts);
+    return hipGetLastError();
+}
+
 uint64_t compact3_scratch_bytes(int64_t n) { return 3 * compact_scratch_bytes(n); }
 
 hipError_t launch_compact_index3(int64_t n, const uint8_t* ka, const uint8_t* kb, const uint8_t* kc, int n_rep, uint32_t* src_index,

@@ -889,4 +889,439 @@ hipError_t launch_mesh_render_textured(const MeshArgs& a, const float* uvs, cons
     return hipGetLastError();
 }
 
+// ---- TSDF fusion and surface extraction (a NEW capability: the reference has no counterpart; the rules: include/gsplat_hip.h,
+// gs_tsdf_integrate / gs_tsdf_count / gs_tsdf_emit) --------------------------------------------------------------------------------------
+// Integration: a thread owns a run of four voxels along the flat index (x fastest) for the whole call and keeps their tsdf, weight and colour
+// in registers across the frames of the batch: the volume is read and written once per call (16-byte accesses: the flat index of a run is a
+// multiple of four, so a run is aligned whatever nx is), and a batch gives the bits of the same frames integrated call by call -- a store and a
+// load of an fp32 value change nothing.  A run no frame touched is not written back.  Poses and intrinsics are kernel arguments; the frame
+// loop is uniform over the grid, so they are scalar loads.  No atomics, no LDS, no scratch.  Every fp32 operation is rounded on its own.
+__device__ __forceinline__ float tsdf_centre(float o, int i, float vs)
+{
+#pragma clang fp contract(off)
+    return o + ((float)i + 0.5f) * vs;
+}
+
+__global__ __launch_bounds__(kBlock) void tsdf_integrate_kernel(TsdfArgs a)
+{
+#pragma clang fp contract(off)
+    const int64_t runs = (a.g.n + 3) >> 2;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    const int64_t npix = (int64_t)a.W * a.H;
+    const int64_t nxy = (int64_t)a.g.nx * a.g.ny;
+    const bool colour = a.frame_color != nullptr;
+    for (int64_t run = (int64_t)blockIdx.x * kBlock + threadIdx.x; run < runs; run += stride) {
+        const int64_t first = run << 2;
+        const int live = a.g.n - first < 4 ? (int)(a.g.n - first) : 4;
+        float tv[4], wv[4], cv[12];
+        if (live == 4) {
+            const float4 t4 = *reinterpret_cast<const float4*>(a.tsdf + first), w4 = *reinterpret_cast<const float4*>(a.weight + first);
+            tv[0] = t4.x; tv[1] = t4.y; tv[2] = t4.z; tv[3] = t4.w;
+            wv[0] = w4.x; wv[1] = w4.y; wv[2] = w4.z; wv[3] = w4.w;
+            if (colour) {
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    const float4 c4 = *reinterpret_cast<const float4*>(a.color + 3 * first + 4 * q);
+                    cv[4 * q] = c4.x; cv[4 * q + 1] = c4.y; cv[4 * q + 2] = c4.z; cv[4 * q + 3] = c4.w;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const bool in = v < live;
+                tv[v] = in ? a.tsdf[first + v] : 0.0f;
+                wv[v] = in ? a.weight[first + v] : 0.0f;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) cv[3 * v + ch] = in && colour ? a.color[3 * (first + v) + ch] : 0.0f;
+            }
+        }
+        // the voxel centres of the run (a run may wrap into the next row)
+        float px[4], py[4], pz[4];
+        {
+            int k = (int)(first / nxy);
+            const int64_t rest = first - (int64_t)k * nxy;
+            int j = (int)(rest / a.g.nx), i = (int)(rest - (int64_t)j * a.g.nx);
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                px[v] = tsdf_centre(a.g.ox, i, a.g.vs); py[v] = tsdf_centre(a.g.oy, j, a.g.vs); pz[v] = tsdf_centre(a.g.oz, k, a.g.vs);
+                if (++i == a.g.nx) { i = 0; if (++j == a.g.ny) { j = 0; ++k; } }
+            }
+        }
+        bool dirty = false;
+        for (int f = 0; f < a.frames; ++f) {
+            const TsdfFrame& m = a.f[f];
+            const float* __restrict__ depth = a.depth + (int64_t)f * npix;
+            const float* __restrict__ sil = a.silhouette ? a.silhouette + (int64_t)f * npix : nullptr;
+            const float* __restrict__ fcol = colour ? a.frame_color + 3 * (int64_t)f * npix : nullptr;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                if (v >= live) continue;
+                const float z = m.r[6] * px[v] + m.r[7] * py[v] + m.r[8] * pz[v] + m.t[2];
+                if (!(z > 0.0f)) continue;
+                const float x = m.r[0] * px[v] + m.r[1] * py[v] + m.r[2] * pz[v] + m.t[0];
+                const float y = m.r[3] * px[v] + m.r[4] * py[v] + m.r[5] * pz[v] + m.t[1];
+                const float fu = floorf(a.fx * x / z + a.cx + 0.5f), fv = floorf(a.fy * y / z + a.cy + 0.5f);
+                if (!(fu >= 0.0f && fu < (float)a.W && fv >= 0.0f && fv < (float)a.H)) continue;     // (a NaN fails it)
+                const int64_t pix = (int64_t)fv * a.W + (int64_t)fu;
+                float d = depth[pix];
+                if (sil != nullptr) {
+                    const float s = sil[pix];
+                    if (!(s > a.sil_thres)) continue;
+                    d = d / s;
+                }
+                if (!(d > 0.0f && d <= a.depth_max)) continue;                                         // (a NaN fails it)
+                const float sdf = d - z;
+                if (sdf < -a.trunc) continue;
+                const float s = fminf(1.0f, sdf / a.trunc), w = wv[v], w1 = w + 1.0f;
+                tv[v] = (tv[v] * w + s) / w1;
+                if (colour) {
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch) cv[3 * v + ch] = (cv[3 * v + ch] * w + fcol[ch * npix + pix]) / w1;
+                }
+                wv[v] = fminf(w1, a.max_weight);
+                dirty = true;
+            }
+        }
+        if (!dirty) continue;
+        if (live == 4) {
+            *reinterpret_cast<float4*>(a.tsdf + first) = make_float4(tv[0], tv[1], tv[2], tv[3]);
+            *reinterpret_cast<float4*>(a.weight + first) = make_float4(wv[0], wv[1], wv[2], wv[3]);
+            if (colour) {
+#pragma unroll
+                for (int q = 0; q < 3; ++q)
+                    *reinterpret_cast<float4*>(a.color + 3 * first + 4 * q) = make_float4(cv[4 * q], cv[4 * q + 1], cv[4 * q + 2], cv[4 * q + 3]);
+            }
+        } else {
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                if (v >= live) continue;
+                a.tsdf[first + v] = tv[v];
+                a.weight[first + v] = wv[v];
+                if (colour) {
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch) a.color[3 * (first + v) + ch] = cv[3 * v + ch];
+                }
+            }
+        }
+    }
+}
+
+hipError_t launch_tsdf_integrate(const TsdfArgs& a, hipStream_t st)
+{
+    if (a.frames <= 0 || a.g.n <= 0) return hipSuccess;
+    int64_t nb = ((a.g.n + 3) / 4 + kBlock - 1) / kBlock;
+    if (nb > 256 * 16) nb = 256 * 16;                            // the rest of the runs by the grid's stride
+    hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)nb), dim3(kBlock), 0, st, a);
+    return hipGetLastError();
+}
+
+// Extraction: marching tetrahedra on Kuhn's split of every cell.  For each permutation (a, b, c) of the axes one tetrahedron with the corners
+// 0 -> e_a -> e_a + e_b -> (1, 1, 1); the split is the same in every cell, so neighbours agree on the diagonals of their shared faces and the
+// surface closes without a matching pass.  The 16-case table of a tetrahedron is DERIVED (make_tet_table, on the host, once per launch): the
+// triangles of a case from which corners are inside, their winding from the geometry of a reference tetrahedron -- the right-hand normal points
+// from the inside corners (tsdf < 0) to the outside ones.  A tetrahedron of an odd permutation is the mirror image: its winding is flipped.
+//   count   tsdf_cell_kernel    one thread per cell (= its lowest grid point): valid iff all eight corners have weight >= min_weight; 0..12 triangles
+//           tsdf_point_kernel   one thread per grid point: the 7-bit mask of its live owned edges (towards +x, +y, +z, +xy, +xz, +yz, +xyz: ends of
+//                               different sign, inside a valid cell) and the sums of both counts per 1 024 grid points
+//   scan    compact.hip's block-count scan, two lists; the totals go to d_counts for the host to size the outputs
+//   emit    tsdf_vertex_kernel  the workgroup's exclusive scan of the mask counts -> the first vertex of every grid point, its vertices
+//           tsdf_triangle_kernel the same over the cells; a triangle's corner is the vertex of an edge: first vertex of the owner + the rank of
+//                               the edge's slot in the owner's mask
+// Vertices come out in (grid point, slot) order, triangles in (cell, tetrahedron, triangle) order: no atomics, the same bytes every run.
+struct TetTable {
+    uint32_t cases[16];      // bits 0-1: triangles; corner c of triangle t at bits 2 + 4 (3 t + c): the tetrahedron's edge (qa, qb), qa | qb << 2, qa < qb
+    uint32_t tets[6];        // the cell corners (bit 0 +x, bit 1 +y, bit 2 +z) of the four tetrahedron corners, 3 bits each; bit 12: odd permutation
+};
+
+static TetTable make_tet_table()
+{
+    TetTable T;
+    const double P[4][3] = {{0, 0, 0}, {1, 0, 0}, {0, 1, 0}, {0, 0, 1}};    // a reference tetrahedron of positive orientation
+    for (int m = 0; m < 16; ++m) {
+        int in[4], out[4], nin = 0, nout = 0;
+        for (int q = 0; q < 4; ++q) { if ((m >> q) & 1) in[nin++] = q; else out[nout++] = q; }
+        int tri[2][3][2], ntri = 0;                              // triangle corners as (inside corner, outside corner) edges
+        if (nin == 1 || nin == 3) {                              // the lone corner is cut off
+            const int lone = nin == 1 ? in[0] : out[0];
+            const int* rest = nin == 1 ? out : in;
+            for (int c = 0; c < 3; ++c) { tri[0][c][0] = nin == 1 ? lone : rest[c]; tri[0][c][1] = nin == 1 ? rest[c] : lone; }
+            ntri = 1;
+        } else if (nin == 2) {                                   // a quad: consecutive corners share a face of the tetrahedron
+            const int quad[4][2] = {{in[0], out[0]}, {in[0], out[1]}, {in[1], out[1]}, {in[1], out[0]}};
+            const int pick[2][3] = {{0, 1, 2}, {0, 2, 3}};
+            for (int t = 0; t < 2; ++t)
+                for (int c = 0; c < 3; ++c) { tri[t][c][0] = quad[pick[t][c]][0]; tri[t][c][1] = quad[pick[t][c]][1]; }
+            ntri = 2;
+        }
+        if (ntri) {
+            // the winding: normal of the first triangle (corners at the edge midpoints) against centroid(outside) - centroid(inside)
+            double v[3][3], g[3] = {0, 0, 0};
+            for (int c = 0; c < 3; ++c)
+                for (int x = 0; x < 3; ++x) v[c][x] = 0.5 * (P[tri[0][c][0]][x] + P[tri[0][c][1]][x]);
+            for (int x = 0; x < 3; ++x) {
+                for (int q = 0; q < nout; ++q) g[x] += P[out[q]][x] / nout;
+                for (int q = 0; q < nin; ++q) g[x] -= P[in[q]][x] / nin;
+            }
+            const double e1[3] = {v[1][0] - v[0][0], v[1][1] - v[0][1], v[1][2] - v[0][2]}, e2[3] = {v[2][0] - v[0][0], v[2][1] - v[0][1], v[2][2] - v[0][2]};
+            const double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+            if (n[0] * g[0] + n[1] * g[1] + n[2] * g[2] < 0.0)
+                for (int t = 0; t < ntri; ++t)
+                    for (int x = 0; x < 2; ++x) { const int s = tri[t][1][x]; tri[t][1][x] = tri[t][2][x]; tri[t][2][x] = s; }
+        }
+        uint32_t word = (uint32_t)ntri;
+        for (int t = 0; t < ntri; ++t)
+            for (int c = 0; c < 3; ++c) {
+                const int lo = tri[t][c][0] < tri[t][c][1] ? tri[t][c][0] : tri[t][c][1], hi = tri[t][c][0] + tri[t][c][1] - lo;
+                word |= (uint32_t)(lo | (hi << 2)) << (2 + 4 * (3 * t + c));
+            }
+        T.cases[m] = word;
+    }
+    int k = 0;
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+            if (b == a) continue;
+            const int c = 3 - a - b;
+            const bool odd = ((a > b) + (a > c) + (b > c)) & 1;
+            T.tets[k++] = 0u | ((1u << a) << 3) | (((1u << a) | (1u << b)) << 6) | (7u << 9) | ((odd ? 1u : 0u) << 12);
+        }
+    return T;
+}
+
+constexpr int kTsdfBlock = 1024;            // grid points per workgroup of the scanned passes (= the records of block_sums)
+
+__host__ __device__ constexpr int tsdf_slot_dir(int slot) { return slot == 0 ? 1 : slot == 1 ? 2 : slot == 2 ? 4 : slot == 3 ? 3 : slot == 4 ? 5 : slot == 5 ? 6 : 7; }
+__host__ __device__ constexpr int tsdf_dir_slot(int d) { return d == 1 ? 0 : d == 2 ? 1 : d == 4 ? 2 : d == 3 ? 3 : d == 5 ? 4 : d == 6 ? 5 : 6; }
+
+// every thread of the workgroup calls it (static indices: the table is a kernel argument and stays in scalar registers)
+__device__ __forceinline__ void tet_table_stage(const TetTable& t, uint32_t* s_cases, uint32_t* s_tets)
+{
+#pragma unroll
+    for (int q = 0; q < 16; ++q)
+        if ((int)threadIdx.x == q) s_cases[q] = t.cases[q];
+#pragma unroll
+    for (int q = 0; q < 6; ++q)
+        if ((int)threadIdx.x == 16 + q) s_tets[q] = t.tets[q];
+    __syncthreads();
+}
+
+// the 4-bit case of a tetrahedron from the cell's 8-bit inside pattern
+__device__ __forceinline__ uint32_t tet_case(uint32_t pattern, uint32_t tet)
+{
+    uint32_t m = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) m |= ((pattern >> ((tet >> (3 * q)) & 7u)) & 1u) << q;
+    return m;
+}
+
+__device__ __forceinline__ void tsdf_ijk(const TsdfGrid& g, int64_t p, int& i, int& j, int& k)
+{
+    const int64_t nxy = (int64_t)g.nx * g.ny;
+    k = (int)(p / nxy);
+    const int64_t rest = p - (int64_t)k * nxy;
+    j = (int)(rest / g.nx);
+    i = (int)(rest - (int64_t)j * g.nx);
+}
+
+__device__ __forceinline__ uint32_t tsdf_cell_pattern(const TsdfGrid& g, const float* __restrict__ tsdf, int64_t p)
+{
+    const int64_t nxy = (int64_t)g.nx * g.ny;
+    uint32_t pattern = 0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) pattern |= (tsdf[p + (c & 1) + ((c >> 1) & 1) * (int64_t)g.nx + (c >> 2) * nxy] < 0.0f ? 1u : 0u) << c;
+    return pattern;
+}
+
+__global__ __launch_bounds__(kBlock) void tsdf_cell_kernel(TsdfExtractArgs a, TetTable table)
+{
+    __shared__ uint32_t s_cases[16], s_tets[6];
+    tet_table_stage(table, s_cases, s_tets);
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= a.g.n) return;
+    int i, j, k;
+    tsdf_ijk(a.g, p, i, j, k);
+    uint32_t info = 0;
+    if (i + 1 < a.g.nx && j + 1 < a.g.ny && k + 1 < a.g.nz) {
+        const int64_t nxy = (int64_t)a.g.nx * a.g.ny;
+        bool valid = true;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) valid = valid && a.weight[p + (c & 1) + ((c >> 1) & 1) * (int64_t)a.g.nx + (c >> 2) * nxy] >= a.min_weight;   // (a NaN fails it)
+        if (valid) {
+            const uint32_t pattern = tsdf_cell_pattern(a.g, a.tsdf, p);
+            uint32_t count = 0;
+            for (int t = 0; t < 6; ++t) count += s_cases[tet_case(pattern, s_tets[t])] & 3u;
+            info = 0x80u | count;
+        }
+    }
+    a.cell_info[p] = (uint8_t)info;
+}
+
+// the sum of v over the workgroup's kTsdfBlock threads, returned to thread 0 (every thread calls it)
+__device__ __forceinline__ uint32_t tsdf_block_sum(uint32_t v, uint32_t* s_w)
+{
+    const uint32_t w = wave_sum_u32(v);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = w;
+    __syncthreads();
+    uint32_t s = 0;
+    if (threadIdx.x == 0)
+        for (int q = 0; q < kTsdfBlock / kWave; ++q) s += s_w[q];
+    __syncthreads();
+    return s;
+}
+
+__global__ __launch_bounds__(kTsdfBlock) void tsdf_point_kernel(TsdfExtractArgs a)
+{
+    __shared__ uint32_t s_w[kTsdfBlock / kWave];
+    const int64_t p = (int64_t)blockIdx.x * kTsdfBlock + threadIdx.x;
+    const int64_t nxy = (int64_t)a.g.nx * a.g.ny;
+    uint32_t mask = 0, triangles = 0;
+    if (p < a.g.n) {
+        int i, j, k;
+        tsdf_ijk(a.g, p, i, j, k);
+        triangles = a.cell_info[p] & 0x7fu;
+        const bool inside = a.tsdf[p] < 0.0f;
+#pragma unroll
+        for (int d = 1; d < 8; ++d) {
+            const int dx = d & 1, dy = (d >> 1) & 1, dz = d >> 2;
+            if (i + dx >= a.g.nx || j + dy >= a.g.ny || k + dz >= a.g.nz) continue;
+            if ((a.tsdf[p + dx + dy * (int64_t)a.g.nx + dz * nxy] < 0.0f) == inside) continue;
+            // a valid cell that holds both ends: its lowest point is this one moved back along the axes the edge does not run along
+            bool live = false;
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                if (s & d) continue;
+                const int sx = s & 1, sy = (s >> 1) & 1, sz = s >> 2;
+                if (i - sx < 0 || j - sy < 0 || k - sz < 0) continue;
+                live = live || (a.cell_info[p - sx - sy * (int64_t)a.g.nx - sz * nxy] & 0x80u) != 0;
+            }
+            if (live) mask |= 1u << tsdf_dir_slot(d);
+        }
+        a.edge_mask[p] = (uint8_t)mask;
+    }
+    const uint32_t nv = tsdf_block_sum((uint32_t)__popc(mask), s_w), nt = tsdf_block_sum(triangles, s_w);
+    if (threadIdx.x == 0) { a.block_sums[blockIdx.x] = nv; a.block_sums[a.blocks + blockIdx.x] = nt; }
+}
+
+// the exclusive prefix of v over the workgroup's kTsdfBlock threads (every thread calls it)
+__device__ __forceinline__ uint32_t tsdf_block_exclusive(uint32_t v, uint32_t* s_w)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t inc = wave_inclusive_scan(v, lane);
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    uint32_t before = 0;
+    for (int q = 0; q < wave; ++q) before += s_w[q];
+    return before + inc - v;
+}
+
+// vertex on the edge from grid point a (the owner: the lower linear index) to b: t = va / (va - vb), a + t (b - a), operation by operation
+__global__ __launch_bounds__(kTsdfBlock) void tsdf_vertex_kernel(TsdfExtractArgs a, uint32_t max_vertices, float* __restrict__ vertices,
+                                                                 float* __restrict__ vertex_colors)
+{
+#pragma clang fp contract(off)
+    __shared__ uint32_t s_w[kTsdfBlock / kWave];
+    // (a workgroup whose grid points own no vertex: the scanned sums say so to every thread alike; the last workgroup always runs)
+    if ((int)blockIdx.x + 1 < a.blocks && a.block_sums[blockIdx.x + 1] == a.block_sums[blockIdx.x]) return;
+    const int64_t p = (int64_t)blockIdx.x * kTsdfBlock + threadIdx.x;
+    const int64_t nxy = (int64_t)a.g.nx * a.g.ny;
+    const uint32_t mask = p < a.g.n ? a.edge_mask[p] : 0u;
+    uint32_t at = a.block_sums[blockIdx.x] + tsdf_block_exclusive((uint32_t)__popc(mask), s_w);
+    if (mask == 0) return;
+    a.vertex_offset[p] = at;
+    int i, j, k;
+    tsdf_ijk(a.g, p, i, j, k);
+    const float va = a.tsdf[p];
+    const float ax = tsdf_centre(a.g.ox, i, a.g.vs), ay = tsdf_centre(a.g.oy, j, a.g.vs), az = tsdf_centre(a.g.oz, k, a.g.vs);
+    float ca[3] = {0.0f, 0.0f, 0.0f};
+    if (a.color != nullptr) { ca[0] = a.color[3 * p]; ca[1] = a.color[3 * p + 1]; ca[2] = a.color[3 * p + 2]; }
+#pragma unroll
+    for (int slot = 0; slot < 7; ++slot) {
+        if (!((mask >> slot) & 1u)) continue;
+        const int d = tsdf_slot_dir(slot), dx = d & 1, dy = (d >> 1) & 1, dz = d >> 2;
+        const int64_t q = p + dx + dy * (int64_t)a.g.nx + dz * nxy;
+        const float vb = a.tsdf[q];
+        const float t = va / (va - vb);
+        if (at < max_vertices) {
+            const float bx = tsdf_centre(a.g.ox, i + dx, a.g.vs), by = tsdf_centre(a.g.oy, j + dy, a.g.vs), bz = tsdf_centre(a.g.oz, k + dz, a.g.vs);
+            vertices[3 * (int64_t)at + 0] = ax + t * (bx - ax);
+            vertices[3 * (int64_t)at + 1] = ay + t * (by - ay);
+            vertices[3 * (int64_t)at + 2] = az + t * (bz - az);
+            if (a.color != nullptr) {
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) vertex_colors[3 * (int64_t)at + ch] = ca[ch] + t * (a.color[3 * q + ch] - ca[ch]);
+            }
+        }
+        ++at;
+    }
+}
+
+__global__ __launch_bounds__(kTsdfBlock) void tsdf_triangle_kernel(TsdfExtractArgs a, TetTable table, uint32_t max_triangles, int32_t* __restrict__ triangles)
+{
+    __shared__ uint32_t s_cases[16], s_tets[6], s_w[kTsdfBlock / kWave];
+    if ((int)blockIdx.x + 1 < a.blocks && a.block_sums[a.blocks + blockIdx.x + 1] == a.block_sums[a.blocks + blockIdx.x]) return;   // (no triangle in this workgroup's cells)
+    tet_table_stage(table, s_cases, s_tets);
+    const int64_t p = (int64_t)blockIdx.x * kTsdfBlock + threadIdx.x;
+    const int64_t nxy = (int64_t)a.g.nx * a.g.ny;
+    const uint32_t count = p < a.g.n ? a.cell_info[p] & 0x7fu : 0u;
+    uint32_t at = a.block_sums[a.blocks + blockIdx.x] + tsdf_block_exclusive(count, s_w);
+    if (count == 0) return;
+    const uint32_t pattern = tsdf_cell_pattern(a.g, a.tsdf, p);
+    for (int t = 0; t < 6; ++t) {
+        const uint32_t tet = s_tets[t], word = s_cases[tet_case(pattern, tet)];
+        const bool mirrored = (tet >> 12) & 1u;
+        for (uint32_t n = 0; n < (word & 3u); ++n, ++at) {
+            if (at >= max_triangles) continue;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int from = mirrored && c ? 3 - c : c;         // (a mirror image: corners 1 and 2 change places)
+                const uint32_t edge = (word >> (2 + 4 * (3 * n + from))) & 15u;
+                const uint32_t lo = (tet >> (3 * (edge & 3u))) & 7u, hi = (tet >> (3 * (edge >> 2))) & 7u;   // cell corners; lo is a subset of hi
+                const int64_t owner = p + (lo & 1u) + ((lo >> 1) & 1u) * (int64_t)a.g.nx + (lo >> 2) * nxy;
+                const uint32_t d = lo ^ hi;
+                const uint32_t slot = (0x65423100u >> (4 * d)) & 15u;                                        // tsdf_dir_slot as nibbles, d = 1..7
+                triangles[3 * (int64_t)at + c] = (int32_t)(a.vertex_offset[owner] + (uint32_t)__popc(a.edge_mask[owner] & ((1u << slot) - 1u)));
+            }
+        }
+    }
+}
+
+static_assert(((0x65423100u >> 4) & 15u) == (uint32_t)tsdf_dir_slot(1) && ((0x65423100u >> 8) & 15u) == (uint32_t)tsdf_dir_slot(2) &&
+              ((0x65423100u >> 12) & 15u) == (uint32_t)tsdf_dir_slot(3) && ((0x65423100u >> 16) & 15u) == (uint32_t)tsdf_dir_slot(4) &&
+              ((0x65423100u >> 20) & 15u) == (uint32_t)tsdf_dir_slot(5) && ((0x65423100u >> 24) & 15u) == (uint32_t)tsdf_dir_slot(6) &&
+              (0x65423100u >> 28) == (uint32_t)tsdf_dir_slot(7), "the nibble table of tsdf_triangle_kernel");
+
+static uint64_t tsdf_align(uint64_t v) { return (v + 255) / 256 * 256; }
+
+uint64_t tsdf_extract_scratch_bytes(int64_t n)
+{
+    const uint64_t blocks = (uint64_t)((n + kTsdfBlock - 1) / kTsdfBlock);
+    return 2 * tsdf_align((uint64_t)n) + tsdf_align((uint64_t)n * 4) + tsdf_align(2 * blocks * 4);
+}
+
+void tsdf_extract_carve(int64_t n, void* scratch, TsdfExtractArgs& a)
+{
+    char* b = (char*)scratch;
+    a.edge_mask = (uint8_t*)b;                   b += tsdf_align((uint64_t)n);
+    a.cell_info = (uint8_t*)b;                   b += tsdf_align((uint64_t)n);
+    a.vertex_offset = (uint32_t*)b;              b += tsdf_align((uint64_t)n * 4);
+    a.block_sums = (uint32_t*)b;
+    a.blocks = (int)((n + kTsdfBlock - 1) / kTsdfBlock);
+}
+
+hipError_t launch_tsdf_count(const TsdfExtractArgs& a, uint32_t* d_counts, hipStream_t st)
+{
+    const TetTable table = make_tet_table();
+    hipLaunchKernelGGL(tsdf_cell_kernel, dim3((unsigned)((a.g.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a, table);
+    hipLaunchKernelGGL(tsdf_point_kernel, dim3((unsigned)a.blocks), dim3(kTsdfBlock), 0, st, a);
+    return launch_block_counts_scan(a.block_sums, a.blocks, 2, d_counts, st);
+}
+
+hipError_t launch_tsdf_emit(const TsdfExtractArgs& a, uint32_t max_vertices, uint32_t max_triangles, float* vertices, float* vertex_colors,
+                            int32_t* triangles, hipStream_t st)
+{
+    const TetTable table = make_tet_table();
+    if (max_vertices > 0) hipLaunchKernelGGL(tsdf_vertex_kernel, dim3((unsigned)a.blocks), dim3(kTsdfBlock), 0, st, a, max_vertices, vertices, vertex_colors);
+    if (max_triangles > 0) hipLaunchKernelGGL(tsdf_triangle_kernel, dim3((unsigned)a.blocks), dim3(kTsdfBlock), 0, st, a, table, max_triangles, triangles);
+    return hipGetLastError();
+}
+
 }  // namespace gs

@@ -986,6 +986,38 @@ hipError_t launch_mesh_render(const MeshArgs& a, hipStream_t st);
 hipError_t launch_texture_mips(int num_textures, const GsTextureDesc* h_table, const GsTextureDesc* table, uint32_t* pool, hipStream_t st);
 hipError_t launch_mesh_render_textured(const MeshArgs& a, const float* uvs, const int32_t* tri_texture, int num_textures, const GsTextureDesc* table,
                                        const uint32_t* pool, hipStream_t st);
+// TSDF fusion and surface extraction (grow.hip; the rules: include/gsplat_hip.h, gs_tsdf_integrate / gs_tsdf_count / gs_tsdf_emit).  A new
+// capability: the reference has no counterpart.  One argument block for the integration kernel (poses and intrinsics travel in it), one for the
+// extraction's kernels, with the scratch carved as tsdf_extract_scratch_bytes lays it out.
+constexpr int kTsdfMaxFrames = 16;          // frames per gs_tsdf_integrate launch (16 x 48 B of poses in the kernel arguments)
+struct TsdfFrame { float r[9], t[3]; };     // row-major rotation and translation of one world-to-camera pose
+struct TsdfGrid { int nx, ny, nz; int64_t n; float ox, oy, oz, vs; };
+struct TsdfArgs {
+    TsdfGrid g;
+    float trunc, max_weight;
+    float *tsdf, *weight, *color;                                      // [n], [n], [n, 3] (color null without frame colours)
+    int frames, W, H;
+    const float *depth, *frame_color, *silhouette;                     // [frames, H, W], [frames, 3, H, W] or null, [frames, H, W] or null
+    float fx, fy, cx, cy, sil_thres, depth_max;
+    TsdfFrame f[kTsdfMaxFrames];
+};
+hipError_t launch_tsdf_integrate(const TsdfArgs& a, hipStream_t st);
+struct TsdfExtractArgs {
+    TsdfGrid g;
+    float min_weight;
+    const float *tsdf, *weight, *color;                                // color nullable: no vertex colours
+    uint8_t *edge_mask, *cell_info;                                    // scratch [n] each: live owned edges | 0x80 valid + triangle count
+    uint32_t* vertex_offset;                                           // scratch [n]: first vertex of a grid point (written where its mask is not 0)
+    uint32_t* block_sums;                                              // scratch [2][blocks]: vertices, triangles per 1 024 grid points, scanned in place
+    int blocks;
+};
+uint64_t tsdf_extract_scratch_bytes(int64_t n);
+void tsdf_extract_carve(int64_t n, void* scratch, TsdfExtractArgs& a);
+hipError_t launch_tsdf_count(const TsdfExtractArgs& a, uint32_t* d_counts, hipStream_t st);
+hipError_t launch_tsdf_emit(const TsdfExtractArgs& a, uint32_t max_vertices, uint32_t max_triangles, float* vertices, float* vertex_colors,
+                            int32_t* triangles, hipStream_t st);
+// exclusive scan in place of `lists` lists of nb block counts each (compact.hip's scan kernel), the totals to d_counts[lists]
+hipError_t launch_block_counts_scan(uint32_t* block_counts, int nb, int lists, uint32_t* d_counts, hipStream_t st);
 // map-quality evaluation of one frame (loss.hip; the rules: include/gsplat_hip.h, gs_eval_frame).  One plan for the layout call, the launches and
 // the finish kernel: level sizes, workgroup records per pass, offsets of the records (in doubles) and of the pooled images (in bytes)
 struct EvalPlan {

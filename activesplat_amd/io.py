@@ -8,6 +8,7 @@
 * `cut_gaussian_by_height` -- the visualiser's height filter (src/visualizer/visualizer.py:2277-2286), here on the
   library's stream-compaction kernels (gs_compact_index + gs_gather_rows) instead of five boolean-mask gathers.
 * `load_params` -- NEW (the reference has a `load_checkpoint` flag but no loading code).
+* `save_mesh_ply` -- NEW: the extracted surface (volume.py) as a binary PLY, the format the reference's scene meshes come in.
 """
 from __future__ import annotations
 
@@ -90,3 +91,28 @@ def cut_gaussian_by_height(gaussian_params, upper_limit, lower_limit):
     for k in GAUSSIAN_ROW_KEYS:
         gaussian_params[k] = O.gather_rows(gaussian_params[k], index)
     return gaussian_params
+
+
+def save_mesh_ply(mesh, path):
+    """`mesh` (a `sensor.MeshScene`: vertices fp32 [V, 3], triangles int32 [T, 3], vertex_colors uint8 [V, 3]) as a binary little-endian PLY:
+    per vertex x, y, z (float) and red, green, blue (uchar), per face a uchar count of 3 and three int indices.  One copy to the host.  -> path"""
+    v = np.ascontiguousarray(_np(mesh.vertices), dtype="<f4").reshape(-1, 3)
+    t = np.ascontiguousarray(_np(mesh.triangles), dtype="<i4").reshape(-1, 3)
+    c = np.ascontiguousarray(_np(mesh.vertex_colors), dtype=np.uint8).reshape(-1, 3)
+    if len(c) != len(v):
+        raise ValueError(f"{len(v)} vertices but {len(c)} vertex colours")
+    vertex = np.empty(len(v), dtype=[("xyz", "<f4", 3), ("rgb", "u1", 3)])
+    vertex["xyz"], vertex["rgb"] = v, c
+    face = np.empty(len(t), dtype=[("n", "u1"), ("index", "<i4", 3)])
+    face["n"], face["index"] = 3, t
+    header = ("ply\nformat binary_little_endian 1.0\ncomment activesplat_amd TSDF surface\n"
+              f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+              f"element face {len(t)}\nproperty list uchar int vertex_indices\nend_header\n")
+    folder = os.path.dirname(os.path.abspath(path))
+    os.makedirs(folder, exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(vertex.tobytes())
+        f.write(face.tobytes())
+    return path

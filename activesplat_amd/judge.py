@@ -11,6 +11,8 @@ all cores to finish.  Here the same answer is three library calls per frame (inc
                           point set from that one");
 * `CompletionJudge`    -- the running minima, one gs_completion_row per frame into a device table, nothing read back until `rows()`;
 * `map_distances`      -- the same two directions between the Gaussian map's centres and a point set.  NOT a reference quantity.
+* `mesh_distances`     -- the same two directions between samples of a mesh (the map's extracted surface, volume.py) and a point set.  NOT a
+                          reference quantity either.
 
 The back-projection rule restates what Open3D's create_from_rgbd_image documents; it was NOT run against Open3D (not installed, not a
 dependency).  Frames: points, samples and poses must share one frame.  `SplatMapper.judge` feeds poses relative to frame 0's camera, so its
@@ -241,5 +243,32 @@ def map_distances(params, samples, min_opacity=0.5):
     rs = torch.empty(int(lib.gs_completion_row_scratch_bytes()), dtype=torch.uint8, device=s.device)
     _lib.check(lib.gs_completion_row(int(s.shape[0]), R._ptr(d), int(means.shape[0]), R._ptr(acc) if means.shape[0] else None, R._ptr(keep), 0.0,
                                      R._ptr(row), R._ptr(rs), _lib.stream_ptr(s.device)))
+    r = row.cpu().numpy()
+    return float(r[2]), float(r[3]), float(r[5])
+
+
+@torch.no_grad()
+def mesh_distances(mesh, samples, n=200000, uniforms=None):
+    """How far a mesh is from a point set: `sensor.sample_surface(mesh, n, uniforms)` and one `nearest_distances`-style launch in each direction
+    between `samples` [N, 3] and those `n` points -> (completion: mean distance from a sample to its nearest mesh point, share of the samples
+    within 0.05, accuracy: mean distance from a mesh point to its nearest sample) as floats (one small copy).  `mesh`: a `sensor.MeshScene` with
+    at least one triangle, e.g. `TsdfVolume.extract_mesh()` or `SplatMapper.extract_mesh(...)`, in the frame of `samples`.  Mirrors
+    `map_distances` with a surface in place of the Gaussians' centres.  THIS BUILD'S quantity: the reference judges the sensor frames, never the map."""
+    from .sensor import sample_surface
+    s = _cloud(samples, "samples")
+    if s.shape[0] == 0:
+        raise ValueError("samples must hold at least one point")
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be at least 1")
+    pts = _cloud(sample_surface(mesh, n, uniforms=uniforms), "mesh samples", s.device)
+    lib = _lib.get()
+    d = torch.full((s.shape[0],), float("inf"), dtype=torch.float32, device=s.device)
+    acc = torch.empty(n, dtype=torch.float32, device=s.device)
+    scratch = _nearest(s, None, pts, None, NEAREST_ROOT, d)
+    _nearest(pts, None, s, None, NEAREST_ROOT, acc, scratch)
+    row = torch.zeros(6, dtype=torch.float64, device=s.device)
+    rs = torch.empty(int(lib.gs_completion_row_scratch_bytes()), dtype=torch.uint8, device=s.device)
+    _lib.check(lib.gs_completion_row(int(s.shape[0]), R._ptr(d), n, R._ptr(acc), None, 0.0, R._ptr(row), R._ptr(rs), _lib.stream_ptr(s.device)))
     r = row.cpu().numpy()
     return float(r[2]), float(r[3]), float(r[5])

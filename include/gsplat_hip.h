@@ -205,7 +205,7 @@ const char* gs_version(void);
 /* Integer version of THIS binary interface: bumped whenever an entry point's argument list or a published record layout changes (e.g.
  * the seed argument of gs_densify_children, the 40-byte SH Jacobian record).  A host binding compares it with the GS_ABI_VERSION it was
  * written against before the first call, so that a stale prebuilt library fails at load time instead of misreading its arguments. */
-#define GS_ABI_VERSION 24
+#define GS_ABI_VERSION 25
 int32_t gs_abi_version(void);
 
 /* Optional per-stage timing (hipEvents recorded on the caller's stream around each stage's launches).
@@ -983,6 +983,68 @@ typedef struct GsEvalLayout {
 int gs_eval_frame_layout(int32_t width, int32_t height, int32_t flags, GsEvalLayout* layout);
 int gs_eval_frame(int32_t width, int32_t height, const float* im, const float* depth, const float* silhouette, const float* gt_im,
                   const float* gt_depth, float sil_thres, int32_t flags, double* row, void* scratch, gs_stream_t stream);
+
+/* ---- TSDF fusion and surface extraction: from depth frames to an indexed triangle mesh ----
+ * A NEW CAPABILITY: the reference has no counterpart (its family fuses rendered depth with Open3D, offline).  The arithmetic below is this
+ * build's own and is pinned to restatements kept with the tests (tests/volume_cases.py), not to the reference.
+ *
+ * The volume: nx * ny * nz grid points, x fastest (point (i, j, k) at index (k * ny + j) * nx + i), DEVICE, fp32:
+ *   tsdf [n] (a fresh volume holds 1), weight [n] (0), color [n, 3] (0).  Grid point (i, j, k) is the voxel centre
+ *   origin + (i + 0.5, j + 0.5, k + 0.5) * voxel_size, each coordinate formed as o + ((float)i + 0.5f) * voxel_size.
+ *
+ * gs_tsdf_integrate folds n_frames frames into the volume, in frame order.  depth [n_frames, height, width], frame_color [n_frames, 3, height, width]
+ * (planar, the rasteriser's layout; nullable: the volume's colour is then neither read nor written and `color` may be null), silhouette
+ * [n_frames, height, width] (nullable): fp32, DEVICE.  h_intrinsics4 = HOST {fx, fy, cx, cy}, shared by the frames; h_w2c12 = HOST n_frames row-major
+ * 3x4 [R|t] world-to-camera.  Per grid point p and frame, all in fp32, every operation rounded on its own (no fused multiply-add):
+ *   1. c = R p + t (each row as r0 * px + r1 * py + r2 * pz + t).  Skipped unless c.z > 0.
+ *   2. u = fx * c.x / c.z + cx, v = fy * c.y / c.z + cy.  Pixel centres sit at integer coordinates (gs_depth_cloud's convention).  The pixel is
+ *      (floor(u + 0.5), floor(v + 0.5)); skipped when outside the image.
+ *   3. d = depth[pixel].  With a silhouette: skipped unless silhouette[pixel] > sil_thres, and d = depth / silhouette (the rasteriser's depth
+ *      image is sum z alpha T, not normalised).  Skipped unless 0 < d <= depth_max (infinity: no limit).  A NaN is skipped.
+ *   4. sdf = d - c.z.  Skipped when sdf < -trunc.  s = min(1, sdf / trunc).
+ *   5. tsdf = (tsdf * w + s) / (w + 1); each colour channel likewise with the frame's colour at the pixel; then w = min(w + 1, max_weight).
+ * One thread owns four consecutive grid points for the whole call and keeps their state in registers across the frames: the volume is read
+ * and written once per call (16-byte accesses), and a batch gives the bits of the same frames integrated one call at a time.  No atomics; two
+ * calls on the same inputs give the same bytes.  At most 16 frames per call (the poses travel in the kernel arguments); a host loops for more.
+ * Refused with GS_EINVAL before any launch: a null pointer (color only with frame_color null); tsdf / weight / color not 16-byte aligned, an
+ * image not 4-byte aligned; a dimension below 1 or nx * ny * nz >= 2^31; voxel_size, trunc, fx or fy not positive and finite; an origin, cx, cy
+ * or pose entry that is not finite; max_weight below 1 or not finite; n_frames outside 0 .. 16; width or height outside 1 .. 16384 (the range of
+ * gs_depth_cloud); depth_max not positive; a NaN sil_thres.
+ *
+ * Extraction is marching tetrahedra on Kuhn's split of every cell (a cell = eight neighbouring grid points, named by its lowest one): for each
+ * permutation (a, b, c) of the axes, in lexicographic order, one tetrahedron with the corners 0 -> e_a -> e_a + e_b -> (1, 1, 1).  The split
+ * is the same in every cell, so neighbours agree on the diagonals of their shared faces and the surface is watertight without a matching
+ * pass.  The 16-case table of a tetrahedron is derived by the library (from which corners are inside and the geometry of a reference
+ * tetrahedron), not typed in.
+ *   validity     a grid point is valid when weight >= min_weight, inside when tsdf < 0.  A cell emits only when all eight corners are valid.
+ *   vertices     live on edges.  A grid point owns seven edges, towards +x, +y, +z, +xy, +xz, +yz, +xyz (slots 0 .. 6).  An owned edge gets a
+ *                vertex when its ends differ in sign and a valid cell contains it.  With a the value at the owner (the lower index), b at the
+ *                other end: t = a / (a - b), position p_a + t * (p_b - p_a), colour c_a + t * (c_b - c_a), each operation rounded on its own.
+ *                Every cell that touches the edge refers to that one vertex: the mesh is welded.
+ *   triangles    with q0 .. q3 the corners of a tetrahedron in the order above: a lone corner q (the only one inside, or the only one outside)
+ *                with the others r0 < r1 < r2 gives the triangle (q r0, q r1, q r2); two inside p0 < p1 against two outside o0 < o1 give the
+ *                quad (p0 o0, p0 o1, p1 o1, p1 o0), split into its corners (0, 1, 2) and (0, 2, 3).  The last two corners of every triangle of a
+ *                case change places where the right-hand normal would otherwise point towards the inside corners: the normal points from
+ *                negative to positive tsdf, towards free space.  A triangle with a vertex at t == 0 has no area; it is KEPT, so that the
+ *                topology stays a manifold.
+ *   order        vertices in (grid point, slot) order, triangles in (cell, tetrahedron, triangle) order: exclusive scans, no atomics, the same
+ *                bytes every run.
+ * gs_tsdf_count writes the per-point edge masks, per-cell triangle counts and their scanned block sums into scratch and the two totals to the
+ * DEVICE words d_counts[0] = vertices, d_counts[1] = triangles; the host copies those 8 bytes, allocates, and calls gs_tsdf_emit with the SAME
+ * scratch, dimensions and tsdf.  gs_tsdf_emit writes vertices fp32 [V, 3], vertex_colors fp32 [V, 3] (only with color) and triangles int32
+ * [T, 3]; nothing is written at or beyond max_vertices / max_triangles rows.  A volume with a dimension of 1, or without a valid cell, gives 0 and
+ * 0.  scratch: DEVICE, gs_tsdf_extract_scratch_bytes(nx, ny, nz) bytes (0 for a shape that is refused), 16-byte aligned.
+ * Refused with GS_EINVAL before any launch: a null pointer (color may be null; an output may be null when its maximum is 0), a misaligned
+ * one, a dimension below 1, nx * ny * nz >= 2^31 or 7 * nx * ny * nz >= 2^31 (vertex indices are int32), a NaN min_weight, an origin or
+ * voxel_size as above, a negative maximum. */
+int gs_tsdf_integrate(int32_t nx, int32_t ny, int32_t nz, const float* h_origin3, float voxel_size, float trunc, float max_weight, float* tsdf,
+                      float* weight, float* color, int32_t n_frames, int32_t width, int32_t height, const float* depth, const float* frame_color,
+                      const float* silhouette, const float* h_intrinsics4, const float* h_w2c12, float sil_thres, float depth_max, gs_stream_t stream);
+uint64_t gs_tsdf_extract_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);
+int gs_tsdf_count(int32_t nx, int32_t ny, int32_t nz, const float* tsdf, const float* weight, float min_weight, void* scratch, uint32_t* d_counts,
+                  gs_stream_t stream);
+int gs_tsdf_emit(int32_t nx, int32_t ny, int32_t nz, const float* h_origin3, float voxel_size, const float* tsdf, const float* color, void* scratch,
+                 int32_t max_vertices, int32_t max_triangles, float* vertices, float* vertex_colors, int32_t* triangles, gs_stream_t stream);
 
 #ifdef __cplusplus
 }
