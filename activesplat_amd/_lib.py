@@ -84,7 +84,7 @@ SORT_AUTO, SORT_TILE_LDS, SORT_RADIX = 0, 1, 2
 
 
 #: the GS_ABI_VERSION of include/gsplat_hip.h this binding was written against (checked when a library is bound)
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 vp, i32, u32, i64, u64, f32, f64, cint = C.c_void_p, C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_int
 
@@ -282,6 +282,22 @@ BINDINGS = {
     "gs_tsdf_count": (cint, [i32, i32, i32, vp, vp, f32, vp, vp, vp]),
     # (nx, ny, nz, h_origin3, voxel_size, tsdf, color, scratch, max_vertices, max_triangles, vertices, vertex_colors, triangles, stream)
     "gs_tsdf_emit": (cint, [i32, i32, i32, C.POINTER(f32), f32, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    # (H, W)
+    "gs_roadmap_scratch_bytes": (u64, [i32, i32]),
+    # (H, W, free_map, unseen, agent_r, agent_c, open_size, dilate, trav, scratch, d_status, stream)
+    "gs_traversable_map": (cint, [i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    # (H, W, trav, dist2, feature, scratch, stream)
+    "gs_clearance_field": (cint, [i32, i32, vp, vp, vp, vp, vp]),
+    # (H, W, trav, dist2, feature, min_dist2, gamma2, roadmap, stream)
+    "gs_voronoi_roadmap": (cint, [i32, i32, vp, vp, vp, i32, i32, vp, vp]),
+    # (H, W, mask, seed_r, seed_c, d_seed_rc, field, scratch, d_status, h_rounds, stream)
+    "gs_grid_geodesic": (cint, [i32, i32, vp, i32, i32, vp, vp, vp, vp, C.POINTER(i32), vp]),
+    # (H, W, roadmap, field, d_entry4, scratch, stream)
+    "gs_roadmap_entry": (cint, [i32, i32, vp, vp, vp, vp, vp]),
+    # (H, W, roadmap, dist2, field, cell, node_rc, node_dist2, node_field, d_count, scratch, stream)
+    "gs_roadmap_nodes": (cint, [i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+    # (H, W, mask, field, target_r, target_c, d_target_rc, capacity, path_rc, d_count2, stream)
+    "gs_trace_path": (cint, [i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp]),
 }
 
 SYMBOLS = tuple(BINDINGS)

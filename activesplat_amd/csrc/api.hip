@@ -1654,4 +1654,132 @@ int gs_eval_frame(int32_t width, int32_t height, const float* im, const float* d
     return launched("gs_eval_frame", "", gs::launch_eval_frame(p, im, depth, silhouette, gt_im, gt_depth, sil_thres, flags, row, scratch, (hipStream_t)stream));
 }
 
+// ---- planner roadmap (stats.hip) ----
+static int road_grid_checked(const char* who, int32_t H, int32_t W, gs::RoadGrid& g)
+{
+    if (H < 1 || W < 1 || H > gs::kRoadMaxSide || W > gs::kRoadMaxSide) return fail(GS_EINVAL, "%s: map size out of range (1 <= H, W <= 4096)", who);
+    g.H = H; g.W = W; g.npix = H * W;
+    return GS_OK;
+}
+
+uint64_t gs_roadmap_scratch_bytes(int32_t H, int32_t W)
+{
+    gs::RoadGrid g;
+    if (road_grid_checked("gs_roadmap_scratch_bytes", H, W, g) != GS_OK) return 0;
+    return 2 * align_up((uint64_t)g.npix) + align_up(4 * (uint64_t)g.npix) + 256;      // two byte maps, one int32 map, the relaxation's four words
+}
+
+int gs_traversable_map(int32_t H, int32_t W, const uint8_t* free_map, const uint8_t* unseen, int32_t agent_r, int32_t agent_c, int32_t open_size,
+                       int32_t dilate, uint8_t* trav, void* scratch, uint32_t* d_status, gs_stream_t stream)
+{
+    gs::TravArgs a;
+    const int rc = road_grid_checked("gs_traversable_map", H, W, a.g);
+    if (rc != GS_OK) return rc;
+    if (!free_map || !unseen || !trav || !scratch || !d_status || ((uintptr_t)scratch & 15) || ((uintptr_t)d_status & 3))
+        return fail(GS_EINVAL, "gs_traversable_map: null pointer, scratch not 16-byte aligned or d_status not 4-byte aligned");
+    if (agent_r < 0 || agent_r >= H || agent_c < 0 || agent_c >= W) return fail(GS_EINVAL, "gs_traversable_map: the agent's pixel must lie in the image");
+    if (open_size < 1 || open_size > 16) return fail(GS_EINVAL, "gs_traversable_map: 1 <= open_size <= 16");
+    if (dilate < 1 || dilate > 15 || !(dilate & 1)) return fail(GS_EINVAL, "gs_traversable_map: dilate must be odd, 1 <= dilate <= 15");
+    const uint64_t map_bytes = align_up((uint64_t)a.g.npix);
+    a.free_map = free_map; a.unseen = unseen; a.agent = agent_r * W + agent_c; a.open_size = open_size; a.dilate = dilate;
+    a.map_a = (uint8_t*)scratch; a.map_b = a.map_a + map_bytes; a.parent = (uint32_t*)(a.map_a + 2 * map_bytes);
+    a.out = trav; a.status = d_status;
+    return launched("gs_traversable_map", "", gs::launch_traversable_map(a, (hipStream_t)stream));
+}
+
+int gs_clearance_field(int32_t H, int32_t W, const uint8_t* trav, int32_t* dist2, int16_t* feature, void* scratch, gs_stream_t stream)
+{
+    gs::RoadGrid g;
+    const int rc = road_grid_checked("gs_clearance_field", H, W, g);
+    if (rc != GS_OK) return rc;
+    if (!trav || !dist2 || !feature || !scratch || ((uintptr_t)scratch & 15) || ((uintptr_t)dist2 & 3) || ((uintptr_t)feature & 1))
+        return fail(GS_EINVAL, "gs_clearance_field: null pointer, scratch not 16-byte aligned, dist2 not 4-byte or feature not 2-byte aligned");
+    return launched("gs_clearance_field", "", gs::launch_clearance_field(g, trav, (int32_t*)scratch, dist2, feature, (hipStream_t)stream));
+}
+
+int gs_voronoi_roadmap(int32_t H, int32_t W, const uint8_t* trav, const int32_t* dist2, const int16_t* feature, int32_t min_dist2, int32_t gamma2,
+                       uint8_t* roadmap, gs_stream_t stream)
+{
+    gs::RoadGrid g;
+    const int rc = road_grid_checked("gs_voronoi_roadmap", H, W, g);
+    if (rc != GS_OK) return rc;
+    if (!trav || !dist2 || !feature || !roadmap || ((uintptr_t)dist2 & 3) || ((uintptr_t)feature & 1))
+        return fail(GS_EINVAL, "gs_voronoi_roadmap: null pointer, dist2 not 4-byte or feature not 2-byte aligned");
+    if (min_dist2 < 0 || gamma2 < 0) return fail(GS_EINVAL, "gs_voronoi_roadmap: min_dist2 and gamma2 must not be negative");
+    return launched("gs_voronoi_roadmap", "", gs::launch_voronoi_roadmap(g, trav, dist2, feature, min_dist2, gamma2, roadmap, (hipStream_t)stream));
+}
+
+int gs_grid_geodesic(int32_t H, int32_t W, const uint8_t* mask, int32_t seed_r, int32_t seed_c, const int32_t* d_seed_rc, int32_t* field,
+                     void* scratch, uint32_t* d_status, int32_t* h_rounds, gs_stream_t stream)
+{
+    gs::RoadGrid g;
+    const hipStream_t st = (hipStream_t)stream;
+    const int rc = road_grid_checked("gs_grid_geodesic", H, W, g);
+    if (rc != GS_OK) return rc;
+    if (!mask || !field || !scratch || !d_status || !h_rounds || ((uintptr_t)scratch & 15) || (((uintptr_t)field | (uintptr_t)d_status | (uintptr_t)d_seed_rc) & 3))
+        return fail(GS_EINVAL, "gs_grid_geodesic: null pointer (d_seed_rc may be null), scratch not 16-byte aligned or an array not 4-byte aligned");
+    int32_t* other = (int32_t*)scratch;
+    uint32_t* words = (uint32_t*)((uint8_t*)scratch + align_up(4 * (uint64_t)g.npix));
+    uint32_t h_words[4] = {0, 0, 0, 0};
+    *h_rounds = 0;
+    if (int e = launched("gs_grid_geodesic", "init", gs::launch_geodesic_init(g, mask, seed_r, seed_c, d_seed_rc, field, words, d_status, st))) return e;
+    if (int e = launched("gs_grid_geodesic", "D2H", hipMemcpyAsync(h_words, words, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st))) return e;
+    if (int e = launched("gs_grid_geodesic", "sync", hipStreamSynchronize(st))) return e;
+    if (!h_words[2]) return GS_OK;                                       // seed outside the mask: all unreachable, status bit 1 raised
+    const int64_t mask_pixels = h_words[1];
+    // a round that changes something fixes the final value of at least one more mask pixel (the unfinished pixel nearest to the seed has a
+    // finished neighbour on its shortest path, in its tile or in the halo), and the seed is final from the start: fewer than mask_pixels
+    // rounds change anything.  The round that changes nothing ends the loop and is not counted; both buffers then hold the field.
+    int32_t *src = field, *dst = other;
+    for (int64_t rounds = 0;; rounds++) {
+        if (rounds >= mask_pixels) return fail(GS_ECAPACITY, "gs_grid_geodesic: the relaxation did not settle within as many rounds as the mask has pixels");
+        if (int e = launched("gs_grid_geodesic", "round", gs::launch_geodesic_round(g, mask, src, dst, words, st))) return e;
+        if (int e = launched("gs_grid_geodesic", "D2H", hipMemcpyAsync(h_words, words, sizeof(uint32_t), hipMemcpyDeviceToHost, st))) return e;
+        if (int e = launched("gs_grid_geodesic", "sync", hipStreamSynchronize(st))) return e;
+        if (!h_words[0]) break;
+        *h_rounds = (int32_t)(rounds + 1);
+        int32_t* t = src; src = dst; dst = t;
+    }
+    return GS_OK;
+}
+
+int gs_roadmap_entry(int32_t H, int32_t W, const uint8_t* roadmap, const int32_t* field, int32_t* d_entry4, void* scratch, gs_stream_t stream)
+{
+    gs::RoadGrid g;
+    const int rc = road_grid_checked("gs_roadmap_entry", H, W, g);
+    if (rc != GS_OK) return rc;
+    if (!roadmap || !field || !d_entry4 || !scratch || ((uintptr_t)scratch & 15) || (((uintptr_t)field | (uintptr_t)d_entry4) & 3))
+        return fail(GS_EINVAL, "gs_roadmap_entry: null pointer, scratch not 16-byte aligned or an array not 4-byte aligned");
+    return launched("gs_roadmap_entry", "", gs::launch_roadmap_entry(g, roadmap, field, scratch, d_entry4, (hipStream_t)stream));
+}
+
+int gs_roadmap_nodes(int32_t H, int32_t W, const uint8_t* roadmap, const int32_t* dist2, const int32_t* field, int32_t cell, int32_t* node_rc,
+                     int32_t* node_dist2, int32_t* node_field, int32_t* d_count, void* scratch, gs_stream_t stream)
+{
+    gs::NodeArgs a;
+    const int rc = road_grid_checked("gs_roadmap_nodes", H, W, a.g);
+    if (rc != GS_OK) return rc;
+    if (!roadmap || !dist2 || !field || !node_rc || !node_dist2 || !node_field || !d_count || !scratch || ((uintptr_t)scratch & 15) ||
+        (((uintptr_t)dist2 | (uintptr_t)field | (uintptr_t)node_rc | (uintptr_t)node_dist2 | (uintptr_t)node_field | (uintptr_t)d_count) & 3))
+        return fail(GS_EINVAL, "gs_roadmap_nodes: null pointer, scratch not 16-byte aligned or an array not 4-byte aligned");
+    if (cell < 1 || cell > 64) return fail(GS_EINVAL, "gs_roadmap_nodes: 1 <= cell <= 64");
+    a.roadmap = roadmap; a.dist2 = dist2; a.field = field; a.cell = cell;
+    a.cells_y = (H + cell - 1) / cell; a.cells_x = (W + cell - 1) / cell;
+    a.pick = (int32_t*)scratch;
+    a.node_rc = node_rc; a.node_dist2 = node_dist2; a.node_field = node_field; a.count = d_count;
+    return launched("gs_roadmap_nodes", "", gs::launch_roadmap_nodes(a, (hipStream_t)stream));
+}
+
+int gs_trace_path(int32_t H, int32_t W, const uint8_t* mask, const int32_t* field, int32_t target_r, int32_t target_c, const int32_t* d_target_rc,
+                  int32_t capacity, int32_t* path_rc, int32_t* d_count2, gs_stream_t stream)
+{
+    gs::RoadGrid g;
+    const int rc = road_grid_checked("gs_trace_path", H, W, g);
+    if (rc != GS_OK) return rc;
+    if (capacity < 0) return fail(GS_EINVAL, "gs_trace_path: capacity must not be negative");
+    if (!mask || !field || !d_count2 || (capacity > 0 && !path_rc) || (((uintptr_t)field | (uintptr_t)d_target_rc | (uintptr_t)path_rc | (uintptr_t)d_count2) & 3))
+        return fail(GS_EINVAL, "gs_trace_path: null pointer (d_target_rc may be null; path_rc when capacity is 0) or an array not 4-byte aligned");
+    return launched("gs_trace_path", "", gs::launch_trace_path(g, mask, field, target_r, target_c, d_target_rc, capacity, path_rc, d_count2, (hipStream_t)stream));
+}
+
 }  // extern "C"

@@ -947,6 +947,37 @@ struct HighLossArgs {
     float* grid;                                                       // [gh * gw]
 };
 hipError_t launch_high_loss_grid(const HighLossArgs& a, hipStream_t st);
+// planner roadmap (stats.hip; the rules: include/gsplat_hip.h, gs_traversable_map .. gs_trace_path).  Maps are uint8 [H, W], pixel (r, c) at r W + c.
+constexpr int kRoadMaxSide = 4096;          // H, W <= 4096: a clearance row fits the LDS, 17 H W < 2^31, a coordinate (frame included) an int16
+constexpr int kGeoTile = 32;                // a relaxation workgroup's tile (plus a one-pixel halo), four pixels per thread
+struct RoadGrid { int H, W, npix; };
+struct TravArgs {
+    RoadGrid g;
+    const uint8_t *free_map, *unseen;
+    int agent, open_size, dilate;                                      // agent: linear index
+    uint8_t *map_a, *map_b;                                            // scratch [npix] each
+    uint32_t* parent;                                                  // scratch [npix], complemented (grid_dbscan's forest)
+    uint8_t* out; uint32_t* status;
+};
+hipError_t launch_traversable_map(const TravArgs& a, hipStream_t st);
+hipError_t launch_clearance_field(const RoadGrid& g, const uint8_t* trav, int32_t* near_row, int32_t* dist2, int16_t* feature, hipStream_t st);
+hipError_t launch_voronoi_roadmap(const RoadGrid& g, const uint8_t* trav, const int32_t* dist2, const int16_t* feature, int min_dist2, int gamma2,
+                                  uint8_t* out, hipStream_t st);
+// words[4]: changed | mask pixels | seed in the mask | spare
+hipError_t launch_geodesic_init(const RoadGrid& g, const uint8_t* mask, int seed_r, int seed_c, const int32_t* d_seed_rc, int32_t* field,
+                                uint32_t* words, uint32_t* status, hipStream_t st);
+hipError_t launch_geodesic_round(const RoadGrid& g, const uint8_t* mask, const int32_t* src, int32_t* dst, uint32_t* changed, hipStream_t st);
+hipError_t launch_roadmap_entry(const RoadGrid& g, const uint8_t* roadmap, const int32_t* field, void* scratch, int32_t* entry, hipStream_t st);
+struct NodeArgs {
+    RoadGrid g;
+    const uint8_t* roadmap; const int32_t *dist2, *field;
+    int cell, cells_y, cells_x;
+    int32_t* pick;                                                     // scratch [cells_y * cells_x]
+    int32_t *node_rc, *node_dist2, *node_field, *count;
+};
+hipError_t launch_roadmap_nodes(const NodeArgs& a, hipStream_t st);
+hipError_t launch_trace_path(const RoadGrid& g, const uint8_t* mask, const int32_t* field, int target_r, int target_c, const int32_t* d_target_rc,
+                             int capacity, int32_t* path_rc, int32_t* count2, hipStream_t st);
 uint64_t grow_scratch_bytes(int64_t npix);
 hipError_t launch_grow(int W, int H, const float* rd, const float* sil, const float* gt, const float* color, const float* k4,
                        const float* c2w12, float sil_thres, int isotropic, float* means3D, float* rgb, float* rot, float* logit,

@@ -18,6 +18,9 @@
 //
 //  high_loss_grid   : the mask of get_high_loss_samples (src/mapper/splatam/__init__.py:212-215) and its cv2.resize to one pixel per degree
 //                     (:218) in integers, one launch; the grid is what grid_dbscan reads next.  Rules: include/gsplat_hip.h.
+//
+//  planner roadmap  : traversable map, clearance field, integer medial axis, geodesic fields, nodes and paths on the planner's top-down maps
+//                     (a grid formulation of src/planner/planner.py:111-370, at the end of this file).  Rules: include/gsplat_hip.h.
 #include "gs_common.h"
 
 namespace gs {
@@ -699,6 +702,414 @@ hipError_t launch_high_loss_grid(const HighLossArgs& a, hipStream_t st)
 {
     const int npix = a.mask_full ? a.W * a.H : 0, ngrid = a.gw * a.gh, n = npix > ngrid ? npix : ngrid;
     hipLaunchKernelGGL(high_loss_grid_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
+    return hipGetLastError();
+}
+
+// ---- planner roadmap: traversable map, clearance field, Voronoi skeleton, geodesic fields, nodes, paths ------------------------------------------
+// (a grid formulation of src/planner/planner.py:111-370; every rule is stated in include/gsplat_hip.h, gs_traversable_map .. gs_trace_path).
+// Maps are bytes, one pixel per thread, all arithmetic in integers; nothing depends on the schedule: the labelling reuses grid_dbscan's union by
+// atomic minimum (the root of a component is its smallest pixel whatever the order), the fields are relaxed between two buffers (a round is a
+// function of the previous round), everything else is a gather.
+
+__device__ __forceinline__ bool road_pixel(const RoadGrid& g, int& r, int& c)
+{
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= g.npix) return false;
+    r = p / g.W; c = p - r * g.W;
+    return true;
+}
+
+// step 1 and the erosion half of step 2: e(r, c) = the open_size x open_size square whose top-left pixel is (r, c) lies in the image and in m0
+__global__ __launch_bounds__(kBlock) void trav_erode_kernel(TravArgs a)
+{
+    int r, c;
+    if (!road_pixel(a.g, r, c)) return;
+    const int s = a.open_size, W = a.g.W;
+    bool all = r + s <= a.g.H && c + s <= W;
+    for (int i = 0; all && i < s; i++)
+        for (int j = 0; all && j < s; j++) {
+            const int q = (r + i) * W + c + j;
+            all = a.free_map[q] != 0 && a.unseen[q] == 0;
+        }
+    a.map_a[r * W + c] = all ? 1 : 0;
+}
+
+// the other half of step 2: a pixel is in the opening iff one of the squares that cover it is whole
+__global__ __launch_bounds__(kBlock) void trav_open_kernel(TravArgs a)
+{
+    int r, c;
+    if (!road_pixel(a.g, r, c)) return;
+    const int s = a.open_size, W = a.g.W;
+    bool any = false;
+    for (int i = 0; !any && i < s && i <= r; i++)
+        for (int j = 0; !any && j < s && j <= c; j++) any = a.map_a[(r - i) * W + c - j] != 0;
+    a.map_b[r * W + c] = any ? 1 : 0;
+}
+
+// step 3, and every pixel starts as its own root (parents complemented, as grid_dbscan's)
+__global__ __launch_bounds__(kBlock) void trav_dilate_kernel(TravArgs a)
+{
+    int r, c;
+    if (!road_pixel(a.g, r, c)) return;
+    const int h = a.dilate / 2, W = a.g.W;
+    const int r0 = r - h < 0 ? 0 : r - h, r1 = r + h >= a.g.H ? a.g.H - 1 : r + h, c0 = c - h < 0 ? 0 : c - h, c1 = c + h >= W ? W - 1 : c + h;
+    bool any = false;
+    for (int i = r0; !any && i <= r1; i++)
+        for (int j = c0; !any && j <= c1; j++) any = a.map_b[i * W + j] != 0;
+    a.map_a[r * W + c] = any ? 1 : 0;
+    a.parent[r * W + c] = ~(uint32_t)(r * W + c);
+}
+
+// step 4: one union per set forward neighbour (right, below-left, below, below-right); dbscan_union's loops carry their own bounds
+__global__ __launch_bounds__(kBlock) void trav_union_kernel(TravArgs a)
+{
+    int r, c;
+    if (!road_pixel(a.g, r, c)) return;
+    const int W = a.g.W, p = r * W + c;
+    if (!a.map_a[p]) return;
+    if (c + 1 < W && a.map_a[p + 1]) dbscan_union(a.parent, (uint32_t)p, (uint32_t)(p + 1), a.g.npix);
+    if (r + 1 < a.g.H)
+        for (int dc = -1; dc <= 1; dc++)
+            if (c + dc >= 0 && c + dc < W && a.map_a[p + W + dc]) dbscan_union(a.parent, (uint32_t)p, (uint32_t)(p + W + dc), a.g.npix);
+}
+
+// steps 4 and 5: keep the pixels whose root is the agent's (the union pass is over: the forest only gets read)
+__global__ __launch_bounds__(kBlock) void trav_keep_kernel(TravArgs a)
+{
+    int r, c;
+    if (!road_pixel(a.g, r, c)) return;
+    const int p = r * a.g.W + c;
+    const bool agent_set = a.map_a[a.agent] != 0;
+    if (p == 0 && !agent_set) atomicOr(a.status, 1u);
+    bool keep = false;
+    if (agent_set && a.map_a[p])
+        keep = dbscan_find(a.parent, (uint32_t)p, a.g.npix, false) == dbscan_find(a.parent, (uint32_t)a.agent, a.g.npix, false);
+    a.out[p] = keep ? 1 : 0;
+}
+
+hipError_t launch_traversable_map(const TravArgs& a, hipStream_t st)
+{
+    const dim3 grid((a.g.npix + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(trav_erode_kernel, grid, dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(trav_open_kernel, grid, dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(trav_dilate_kernel, grid, dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(trav_union_kernel, grid, dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(trav_keep_kernel, grid, dim3(kBlock), 0, st, a);
+    return hipGetLastError();
+}
+
+// clearance, pass 1: a thread owns a column and sweeps it down (the nearest obstacle row at or above, -1: the frame) and up (at or below, H: the
+// frame); the nearer of the two stays, the one above on a tie.  An obstacle pixel names itself.
+__global__ __launch_bounds__(kBlock) void clearance_columns_kernel(RoadGrid g, const uint8_t* __restrict__ trav, int32_t* __restrict__ near_row)
+{
+    const int c = blockIdx.x * kBlock + threadIdx.x;
+    if (c >= g.W) return;
+    int last = -1;
+    for (int r = 0; r < g.H; r++) {
+        if (!trav[r * g.W + c]) last = r;
+        near_row[r * g.W + c] = last;
+    }
+    last = g.H;
+    for (int r = g.H - 1; r >= 0; r--) {
+        if (!trav[r * g.W + c]) last = r;
+        const int above = near_row[r * g.W + c];
+        near_row[r * g.W + c] = r - above <= last - r ? above : last;
+    }
+}
+
+// clearance, pass 2: a workgroup owns a row; the per-column picks of the row (and of the frame's columns -1 and W, which hold an obstacle in the
+// row itself) sit in LDS and a thread scans outwards from its column until the column offset alone exceeds the best distance: at most W + 2 steps
+__global__ __launch_bounds__(kBlock) void clearance_rows_kernel(RoadGrid g, const int32_t* __restrict__ near_row, int32_t* __restrict__ dist2,
+                                                                int16_t* __restrict__ feature)
+{
+    __shared__ int32_t s_row[kRoadMaxSide + 2];
+    const int r = blockIdx.x, W = g.W;
+    for (int i = threadIdx.x; i < W + 2; i += kBlock) s_row[i] = i == 0 || i == W + 1 ? r : near_row[r * W + i - 1];
+    __syncthreads();
+    for (int c = threadIdx.x; c < W; c += kBlock) {
+        int best = 0x7fffffff, br = 0, bc = 0;
+        for (int k = 0; k <= W + 1; k++) {
+            if (k * k > best) break;
+            for (int side = 0; side < (k ? 2 : 1); side++) {
+                const int cc = side ? c + k : c - k;
+                if (cc < -1 || cc > W) continue;
+                const int fr = s_row[cc + 1], d = k * k + (r - fr) * (r - fr);
+                if (d < best || (d == best && (fr < br || (fr == br && cc < bc)))) { best = d; br = fr; bc = cc; }
+            }
+        }
+        dist2[r * W + c] = best;
+        feature[2 * (r * W + c)] = (int16_t)br;
+        feature[2 * (r * W + c) + 1] = (int16_t)bc;
+    }
+}
+
+hipError_t launch_clearance_field(const RoadGrid& g, const uint8_t* trav, int32_t* near_row, int32_t* dist2, int16_t* feature, hipStream_t st)
+{
+    hipLaunchKernelGGL(clearance_columns_kernel, dim3((g.W + kBlock - 1) / kBlock), dim3(kBlock), 0, st, g, trav, near_row);
+    hipLaunchKernelGGL(clearance_rows_kernel, dim3(g.H), dim3(kBlock), 0, st, g, near_row, dist2, feature);
+    return hipGetLastError();
+}
+
+// the integer medial axis, as a gather: a pixel looks at its four neighbours and decides about itself alone
+__global__ __launch_bounds__(kBlock) void voronoi_roadmap_kernel(RoadGrid g, const uint8_t* __restrict__ trav, const int32_t* __restrict__ dist2,
+                                                                 const int16_t* __restrict__ feature, int min_dist2, int gamma2, uint8_t* __restrict__ out)
+{
+    int r, c;
+    if (!road_pixel(g, r, c)) return;
+    const int p = r * g.W + c;
+    bool marked = false;
+    if (trav[p] && dist2[p] >= min_dist2) {
+        const int fr = feature[2 * p], fc = feature[2 * p + 1];
+        const int dr[4] = {-1, 0, 0, 1}, dc[4] = {0, -1, 1, 0};
+        for (int k = 0; k < 4; k++) {
+            const int qr = r + dr[k], qc = c + dc[k];
+            if (qr < 0 || qr >= g.H || qc < 0 || qc >= g.W || !trav[qr * g.W + qc]) continue;
+            const int q = qr * g.W + qc, gr = feature[2 * q], gc = feature[2 * q + 1];
+            if ((fr - gr) * (fr - gr) + (fc - gc) * (fc - gc) <= gamma2) continue;
+            const int sr = r + qr, sc = c + qc;
+            const int ap = (sr - 2 * fr) * (sr - 2 * fr) + (sc - 2 * fc) * (sc - 2 * fc), aq = (sr - 2 * gr) * (sr - 2 * gr) + (sc - 2 * gc) * (sc - 2 * gc);
+            marked = marked || aq <= ap;
+        }
+    }
+    out[p] = marked ? 1 : 0;
+}
+
+hipError_t launch_voronoi_roadmap(const RoadGrid& g, const uint8_t* trav, const int32_t* dist2, const int16_t* feature, int min_dist2, int gamma2,
+                                  uint8_t* out, hipStream_t st)
+{
+    hipLaunchKernelGGL(voronoi_roadmap_kernel, dim3((g.npix + kBlock - 1) / kBlock), dim3(kBlock), 0, st, g, trav, dist2, feature, min_dist2, gamma2, out);
+    return hipGetLastError();
+}
+
+constexpr int32_t kGeoInf = 0x7fffffff;
+constexpr int kGeoSide = kGeoTile + 2, kGeoCells = kGeoSide * kGeoSide;
+
+// field = unreachable everywhere but the seed; words[1] = the number of mask pixels, words[2] = 1 when the seed is in the image and in the mask
+// (status bit 1 otherwise).  The seed comes from the arguments, or from a device pair (r, c) when d_seed_rc is given.
+__global__ __launch_bounds__(kBlock) void geodesic_init_kernel(RoadGrid g, const uint8_t* __restrict__ mask, int seed_r, int seed_c,
+                                                               const int32_t* __restrict__ d_seed_rc, int32_t* __restrict__ field,
+                                                               uint32_t* __restrict__ words, uint32_t* __restrict__ status)
+{
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (d_seed_rc) { seed_r = d_seed_rc[0]; seed_c = d_seed_rc[1]; }
+    const bool seed_in = seed_r >= 0 && seed_r < g.H && seed_c >= 0 && seed_c < g.W && mask[seed_r * g.W + seed_c] != 0;
+    const bool m = p < g.npix && mask[p] != 0;
+    if (p < g.npix) field[p] = seed_in && p == seed_r * g.W + seed_c ? 0 : kGeoInf;
+    const uint64_t bits = __ballot(m);
+    if ((threadIdx.x & 63) == 0 && bits) atomicAdd(&words[1], (uint32_t)__popcll(bits));
+    if (p == 0) {
+        if (seed_in) words[2] = 1u;
+        else atomicOr(status, 2u);
+    }
+}
+
+// One round: a workgroup loads its 32 x 32 tile and a one-pixel halo from src, relaxes the tile to local convergence in LDS -- Jacobi sweeps
+// between barriers, so that the round is a function of src alone; a sweep that changes nothing ends the loop, and a sweep that changes
+// something fixes the final value of one more pixel of the tile, hence the written bound of kGeoTile^2 sweeps -- and writes the tile to dst.
+// It waits for no other workgroup: what the neighbours find this round arrives through src in the next one.
+__global__ __launch_bounds__(kBlock) void geodesic_round_kernel(RoadGrid g, const uint8_t* __restrict__ mask, const int32_t* __restrict__ src,
+                                                                int32_t* __restrict__ dst, uint32_t* __restrict__ changed)
+{
+    __shared__ int32_t s_f[kGeoCells];
+    __shared__ uint8_t s_m[kGeoCells];
+    const int t = threadIdx.x, r0 = blockIdx.y * kGeoTile - 1, c0 = blockIdx.x * kGeoTile - 1;
+    bool finite = false;
+    for (int i = t; i < kGeoCells; i += kBlock) {
+        const int ly = i / kGeoSide, r = r0 + ly, c = c0 + i - ly * kGeoSide;
+        const bool in = r >= 0 && r < g.H && c >= 0 && c < g.W && mask[r * g.W + c] != 0;
+        const int32_t v = in ? src[r * g.W + c] : kGeoInf;
+        s_f[i] = v; s_m[i] = in ? 1 : 0;
+        finite = finite || v != kGeoInf;
+    }
+    const int lx = (t & (kGeoTile - 1)) + 1, ly0 = (t / kGeoTile) * 4 + 1;       // four pixels of one column per thread
+    bool ever = false;
+    if (__syncthreads_or(finite)) {
+        for (int sweep = 0; sweep < kGeoTile * kGeoTile; sweep++) {
+            int32_t nv[4];
+            bool ch = false;
+            for (int k = 0; k < 4; k++) {
+                const int i = (ly0 + k) * kGeoSide + lx;
+                int32_t v = s_f[i];
+                if (s_m[i])
+                    for (int dy = -1; dy <= 1; dy++)
+                        for (int dx = -1; dx <= 1; dx++) {
+                            const int32_t n = s_f[i + dy * kGeoSide + dx];
+                            const int32_t cand = n == kGeoInf ? kGeoInf : n + (dx && dy ? 17 : 12);   // (the centre never wins: n + 12 > n)
+                            v = cand < v ? cand : v;
+                        }
+                nv[k] = v;
+                ch = ch || v != s_f[i];
+            }
+            __syncthreads();
+            for (int k = 0; k < 4; k++) s_f[(ly0 + k) * kGeoSide + lx] = nv[k];
+            ever = ever || ch;
+            if (!__syncthreads_or(ch)) break;
+        }
+    }
+    for (int k = 0; k < 4; k++) {
+        const int r = r0 + ly0 + k, c = c0 + lx;
+        if (r < g.H && c < g.W) dst[r * g.W + c] = s_f[(ly0 + k) * kGeoSide + lx];
+    }
+    if (__any(ever) && (t & 63) == 0) atomicOr(changed, 1u);
+}
+
+hipError_t launch_geodesic_init(const RoadGrid& g, const uint8_t* mask, int seed_r, int seed_c, const int32_t* d_seed_rc, int32_t* field,
+                                uint32_t* words, uint32_t* status, hipStream_t st)
+{
+    hipError_t e = hipMemsetAsync(words, 0, 4 * sizeof(uint32_t), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(geodesic_init_kernel, dim3((g.npix + kBlock - 1) / kBlock), dim3(kBlock), 0, st, g, mask, seed_r, seed_c, d_seed_rc, field, words, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_geodesic_round(const RoadGrid& g, const uint8_t* mask, const int32_t* src, int32_t* dst, uint32_t* changed, hipStream_t st)
+{
+    hipError_t e = hipMemsetAsync(changed, 0, sizeof(uint32_t), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(geodesic_round_kernel, dim3((g.W + kGeoTile - 1) / kGeoTile, (g.H + kGeoTile - 1) / kGeoTile), dim3(kBlock), 0, st, g, mask, src, dst, changed);
+    return hipGetLastError();
+}
+
+// the roadmap pixel with the smallest finite field value, the smallest index on a tie, as the minimum of the keys (field << 32 | index):
+// workgroup b of the first launch sweeps pixels [b kEntryChunk, (b + 1) kEntryChunk) and leaves its minimum in partial[b]; one workgroup of
+// the second launch takes the minimum of those.  entry = (r, c, field, index), or (-1, -1, unreachable, -1).
+constexpr int kEntryChunk = 16 * kBlock;
+constexpr unsigned long long kEntryNone = ~0ull;
+
+__device__ __forceinline__ unsigned long long entry_block_min(unsigned long long key)
+{
+    __shared__ unsigned long long s_key[kBlock / kWave];
+    for (int m = 1; m < kWave; m <<= 1) { const unsigned long long o = __shfl_xor(key, m); key = o < key ? o : key; }
+    if ((threadIdx.x & 63) == 0) s_key[threadIdx.x >> 6] = key;
+    __syncthreads();
+    for (int w = 0; w < kBlock / kWave; w++) key = s_key[w] < key ? s_key[w] : key;
+    return key;
+}
+
+__global__ __launch_bounds__(kBlock) void roadmap_entry_partial_kernel(RoadGrid g, const uint8_t* __restrict__ roadmap, const int32_t* __restrict__ field,
+                                                                       unsigned long long* __restrict__ partial)
+{
+    unsigned long long key = kEntryNone;
+    const int p0 = blockIdx.x * kEntryChunk, p1 = p0 + kEntryChunk < g.npix ? p0 + kEntryChunk : g.npix;
+    for (int p = p0 + threadIdx.x; p < p1; p += kBlock)
+        if (roadmap[p] && field[p] != kGeoInf) {
+            const unsigned long long k = ((unsigned long long)(uint32_t)field[p] << 32) | (uint32_t)p;
+            key = k < key ? k : key;
+        }
+    key = entry_block_min(key);
+    if (threadIdx.x == 0) partial[blockIdx.x] = key;
+}
+
+__global__ __launch_bounds__(kBlock) void roadmap_entry_final_kernel(RoadGrid g, const unsigned long long* __restrict__ partial, int nb,
+                                                                     int32_t* __restrict__ entry)
+{
+    unsigned long long key = kEntryNone;
+    for (int b = threadIdx.x; b < nb; b += kBlock) key = partial[b] < key ? partial[b] : key;
+    key = entry_block_min(key);
+    if (threadIdx.x == 0) {
+        const int p = key == kEntryNone ? -1 : (int)(uint32_t)key;
+        entry[0] = p < 0 ? -1 : p / g.W; entry[1] = p < 0 ? -1 : p % g.W;
+        entry[2] = p < 0 ? kGeoInf : (int32_t)(key >> 32); entry[3] = p;
+    }
+}
+
+hipError_t launch_roadmap_entry(const RoadGrid& g, const uint8_t* roadmap, const int32_t* field, void* scratch, int32_t* entry, hipStream_t st)
+{
+    const int nb = (g.npix + kEntryChunk - 1) / kEntryChunk;             // at most 4096: 32 KiB of the scratch
+    unsigned long long* partial = (unsigned long long*)scratch;
+    hipLaunchKernelGGL(roadmap_entry_partial_kernel, dim3(nb), dim3(kBlock), 0, st, g, roadmap, field, partial);
+    hipLaunchKernelGGL(roadmap_entry_final_kernel, dim3(1), dim3(kBlock), 0, st, g, partial, nb, entry);
+    return hipGetLastError();
+}
+
+// nodes, count: a wavefront owns a cell; its lanes stride over the cell's pixels in row-major order and keep the largest key
+// (dist2 << 32 | ~index) among the roadmap pixels with a finite field: the largest clearance, the smallest index on a tie; pick = index or -1
+__global__ __launch_bounds__(kBlock) void nodes_pick_kernel(NodeArgs a)
+{
+    const int cell = blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (cell >= a.cells_y * a.cells_x) return;                          // (whole wavefronts: the shuffles below see every lane)
+    const int cy = cell / a.cells_x, cx = cell - cy * a.cells_x, W = a.g.W, r0 = cy * a.cell, c0 = cx * a.cell;
+    const int h = r0 + a.cell < a.g.H ? a.cell : a.g.H - r0, w = c0 + a.cell < W ? a.cell : W - c0;
+    unsigned long long key = 0ull;                                      // (no pixel has index 2^32 - 1: 0 is "none")
+    for (int i = lane; i < h * w; i += kWave) {
+        const int p = (r0 + i / w) * W + c0 + i % w;
+        if (a.roadmap[p] && a.field[p] != kGeoInf) {
+            const unsigned long long k = ((unsigned long long)(uint32_t)a.dist2[p] << 32) | (uint32_t)~(uint32_t)p;
+            key = k > key ? k : key;
+        }
+    }
+    for (int m = 1; m < kWave; m <<= 1) { const unsigned long long o = __shfl_xor(key, m); key = o > key ? o : key; }
+    if (lane == 0) a.pick[cell] = key ? (int32_t)~(uint32_t)key : -1;
+}
+
+// nodes, scan and emit: one workgroup; a thread counts the picks of its run of cells, thread 0 scans the 256 counts, and every thread writes
+// its run's nodes behind its offset: row-major cell order, no atomics.  The count stays on the device.
+__global__ __launch_bounds__(kBlock) void nodes_emit_kernel(NodeArgs a)
+{
+    __shared__ int32_t s_sum[kBlock];
+    const int t = threadIdx.x, n = a.cells_y * a.cells_x, per = (n + kBlock - 1) / kBlock;
+    const int i0 = t * per < n ? t * per : n, i1 = i0 + per < n ? i0 + per : n;
+    int32_t s = 0;
+    for (int i = i0; i < i1; i++) s += a.pick[i] >= 0;
+    s_sum[t] = s;
+    __syncthreads();
+    if (t == 0) {
+        int32_t run = 0;
+        for (int i = 0; i < kBlock; i++) { const int32_t v = s_sum[i]; s_sum[i] = run; run += v; }
+        a.count[0] = run;
+    }
+    __syncthreads();
+    int32_t k = s_sum[t];
+    for (int i = i0; i < i1; i++) {
+        const int p = a.pick[i];
+        if (p < 0) continue;
+        a.node_rc[2 * k] = p / a.g.W; a.node_rc[2 * k + 1] = p % a.g.W;
+        a.node_dist2[k] = a.dist2[p]; a.node_field[k] = a.field[p];
+        k++;
+    }
+}
+
+hipError_t launch_roadmap_nodes(const NodeArgs& a, hipStream_t st)
+{
+    const int n = a.cells_y * a.cells_x;
+    hipLaunchKernelGGL(nodes_pick_kernel, dim3((n + kBlock / kWave - 1) / (kBlock / kWave)), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(nodes_emit_kernel, dim3(1), dim3(kBlock), 0, st, a);
+    return hipGetLastError();
+}
+
+// the walk down a field: one wavefront; lanes 0..7 test one neighbour each, in the stated order, and the lowest lane that qualifies is the
+// step.  `capacity` bounds the loop.  count2 = (pixels written, 0 done | 1 target outside the mask or unreachable | 2 capacity reached |
+// 3 no neighbour qualifies: not a field of this mask)
+__global__ __launch_bounds__(kWave) void trace_path_kernel(RoadGrid g, const uint8_t* __restrict__ mask, const int32_t* __restrict__ field, int r, int c,
+                                                           const int32_t* __restrict__ d_target_rc, int capacity, int32_t* __restrict__ path_rc,
+                                                           int32_t* __restrict__ count2)
+{
+    const int lane = threadIdx.x, k = lane < 4 ? lane : lane + 1;                 // 3 x 3 window without its centre
+    const int dr = k / 3 - 1, dc = k % 3 - 1, w = dr && dc ? 17 : 12;
+    if (d_target_rc) { r = d_target_rc[0]; c = d_target_rc[1]; }
+    int count = 0, status = 2;
+    if (r < 0 || r >= g.H || c < 0 || c >= g.W || !mask[r * g.W + c] || field[r * g.W + c] == kGeoInf) status = 1;
+    else
+        for (int step = 0; step < capacity; step++) {
+            if (lane == 0) { path_rc[2 * count] = r; path_rc[2 * count + 1] = c; }
+            count++;
+            const int32_t f = field[r * g.W + c];
+            if (f == 0) { status = 0; break; }
+            const int nr = r + dr, nc = c + dc;
+            bool ok = lane < 8 && nr >= 0 && nr < g.H && nc >= 0 && nc < g.W && mask[nr * g.W + nc] != 0;
+            if (ok) { const int32_t fn = field[nr * g.W + nc]; ok = fn != kGeoInf && fn + w == f; }
+            const uint64_t hits = __ballot(ok);
+            if (!hits) { status = 3; break; }
+            const int j = __ffsll((unsigned long long)hits) - 1, kk = j < 4 ? j : j + 1;
+            r += kk / 3 - 1; c += kk % 3 - 1;
+        }
+    if (lane == 0) { count2[0] = count; count2[1] = status; }
+}
+
+hipError_t launch_trace_path(const RoadGrid& g, const uint8_t* mask, const int32_t* field, int target_r, int target_c, const int32_t* d_target_rc,
+                             int capacity, int32_t* path_rc, int32_t* count2, hipStream_t st)
+{
+    hipLaunchKernelGGL(trace_path_kernel, dim3(1), dim3(kWave), 0, st, g, mask, field, target_r, target_c, d_target_rc, capacity, path_rc, count2);
     return hipGetLastError();
 }
 

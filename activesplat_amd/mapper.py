@@ -533,6 +533,56 @@ class SplatMapper:
         return TD.topdown_maps(self.params, cam, upper, lower, scale_modifier=scale_modifier)
 
     @torch.no_grad()
+    def roadmap(self, world_center, world_shape, grid_shape, upper, lower, agent_xz, agent_radius, node_spacing, node_y=0.0, height=1000.0,
+                scale_modifier=0.01):
+        """From the current map to the planner's candidate viewpoints without a map leaving the device (roadmap.py; a grid formulation of
+        src/planner/planner.py:111-370, NOT its contour / scipy Voronoi / networkx chain): `topdown_maps(...)`, then `plan_roadmap` with the
+        agent at the pixel that shows `agent_xz` = world (x, z), `agent_radius` and `node_spacing` in metres (converted with the finer of the
+        two pixel scales; the spacing to a whole number of pixels, at least 1).  -> (Roadmap, positions float64 [K, 3] on the HOST: the
+        nodes' world (x, node_y, z) -- what `global_invisibility_scores` takes; a second small copy, of the K pixel pairs)."""
+        from . import roadmap as RM
+        maps = self.topdown_maps(world_center, world_shape, grid_shape, upper, lower, height, scale_modifier)
+        W, H = int(grid_shape[0]), int(grid_shape[1])
+        px_per_m = max(W / float(world_shape[0]), H / float(world_shape[1]))
+        r, c = (int(v) for v in np.rint(RM.world_to_pixel(agent_xz, world_center, world_shape, grid_shape, height)))
+        if not (0 <= r < H and 0 <= c < W):
+            raise ValueError(f"agent_xz {tuple(float(v) for v in agent_xz)} projects to pixel {(r, c)}, outside the {H} x {W} map")
+        cell = min(RM.MAX_CELL, max(1, int(round(float(node_spacing) * px_per_m))))
+        rm = RM.plan_roadmap(maps, (r, c), float(agent_radius) * px_per_m, cell)
+        rm.world = dict(world_center=tuple(float(v) for v in world_center), world_shape=tuple(float(v) for v in world_shape), grid_shape=(W, H),
+                        height=float(height))
+        xz = RM.pixel_to_world(rm.node_rc.cpu().numpy(), **rm.world)     # (K pixel pairs to the host: the scores take host positions)
+        positions = np.stack([xz[:, 0], np.full(rm.K, float(node_y)), xz[:, 1]], 1)
+        return rm, positions
+
+    @torch.no_grad()
+    def plan_step(self, view_c2w, world_center, world_shape, grid_shape, upper, lower, agent_radius, node_spacing, height=1000.0,
+                  scale_modifier=0.01, max_clusters=256):
+        """One planning step: `roadmap(...)` with the agent at `view_c2w`'s position (nodes at its height), `global_invisibility_scores` of the
+        nodes, and the node with the largest invisibility -- ties go to the smaller path length, then to the lower index (every node of a
+        Roadmap is reachable: nodes are picked among the pixels its geodesic field reaches).  This greedy choice is NOT the reference's
+        stateful subregion policy (no subregion clustering, no escape plans, no path smoothing).
+        -> dict(roadmap, positions [K, 3], invisibility [K], volume [K], node, path_rc int32 [n, 2] (device), waypoints fp32 [n, 3] (device;
+        world, agent to node, at the agent's height)); node = -1 and empty paths when there is no node."""
+        from . import roadmap as RM
+        c2w = np.asarray(view_c2w.detach().cpu().numpy() if torch.is_tensor(view_c2w) else view_c2w, dtype=np.float64)
+        agent_xz, node_y = (c2w[0, 3], c2w[2, 3]), float(c2w[1, 3])
+        rm, positions = self.roadmap(world_center, world_shape, grid_shape, upper, lower, agent_xz, agent_radius, node_spacing, node_y, height,
+                                     scale_modifier)
+        out = dict(roadmap=rm, positions=positions, invisibility=np.zeros(0), volume=np.zeros(0), node=-1,
+                   path_rc=torch.zeros(0, 2, dtype=torch.int32, device=self.device), waypoints=torch.zeros(0, 3, device=self.device))
+        if rm.K == 0:
+            return out
+        inv, vol = self.global_invisibility_scores(view_c2w, positions, max_clusters=max_clusters)
+        length = rm.node_path_length().cpu().numpy()
+        node = int(np.lexsort((np.arange(rm.K), length, -inv))[0])
+        path = rm.path_to(node)
+        xz = RM.pixel_to_world(path, **rm.world)
+        out.update(invisibility=inv, volume=vol, node=node, path_rc=path,
+                   waypoints=torch.stack([xz[:, 0], torch.full_like(xz[:, 0], node_y), xz[:, 1]], 1))
+        return out
+
+    @torch.no_grad()
     def invisibility(self, w2c, width=120, height=150, intrinsics=None):
         """1 - opacity, the quantity the planner scores view points with (__init__.py:739,795)."""
         _, _, opacity = self.render_rgbd(w2c, width=width, height=height, intrinsics=intrinsics)

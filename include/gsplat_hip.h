@@ -205,7 +205,7 @@ const char* gs_version(void);
 /* Integer version of THIS binary interface: bumped whenever an entry point's argument list or a published record layout changes (e.g.
  * the seed argument of gs_densify_children, the 40-byte SH Jacobian record).  A host binding compares it with the GS_ABI_VERSION it was
  * written against before the first call, so that a stale prebuilt library fails at load time instead of misreading its arguments. */
-#define GS_ABI_VERSION 25
+#define GS_ABI_VERSION 26
 int32_t gs_abi_version(void);
 
 /* Optional per-stage timing (hipEvents recorded on the caller's stream around each stage's launches).
@@ -1045,6 +1045,68 @@ int gs_tsdf_count(int32_t nx, int32_t ny, int32_t nz, const float* tsdf, const f
                   gs_stream_t stream);
 int gs_tsdf_emit(int32_t nx, int32_t ny, int32_t nz, const float* h_origin3, float voxel_size, const float* tsdf, const float* color, void* scratch,
                  int32_t max_vertices, int32_t max_triangles, float* vertices, float* vertex_colors, int32_t* triangles, gs_stream_t stream);
+
+/* Planner roadmap on the device (stats.hip): from the planner's top-down maps to candidate viewpoints and the paths to them.  A grid
+ * formulation of the reference's host chain (src/planner/planner.py:111-370: contours, scipy.spatial.Voronoi of sampled contour points, networkx
+ * Dijkstra) -- a medial axis of free space, candidate nodes on it, shortest paths along it -- in exact integers; NOT a bit-for-bit restatement
+ * of that chain.  Maps are uint8 [H, W] DEVICE arrays (0 = clear, anything else = set), a pixel is (r, c) with linear index r * W + c, and every
+ * output is the same bytes from run to run.  Supported: 1 <= H, W <= 4096.  scratch: DEVICE, gs_roadmap_scratch_bytes(H, W) bytes (0 for a shape
+ * that is refused), 16-byte aligned; one scratch serves all the calls below, one after the other.  Refused with GS_EINVAL before any launch:
+ * a null or misaligned pointer, a shape out of range, and what each call names.
+ *
+ * gs_traversable_map   free_map, unseen: gs_render_forward_topdown's free_map_binary and visible_map_binary (1 = never seen).
+ *   1  m0 = free_map != 0 and unseen == 0;
+ *   2  opening: the union of all open_size x open_size squares that lie wholly inside the image and inside m0 (the reference's 4 x 4 MORPH_OPEN);
+ *   3  dilation: a pixel is set if any pixel of the dilate x dilate window centred on it, clipped to the image, is set (its 3 x 3 dilate);
+ *   4  of the result, the 8-connected component that holds the agent's pixel (agent_r, agent_c) is kept;
+ *   5  if that pixel is not set, trav is all 0 and bit 0 of *d_status is raised (OR-ed in: the caller clears the word).
+ *   The reference's contour fill and approxPolyDP are deliberately replaced by the component rule of step 4.
+ *   1 <= open_size <= 16; dilate odd, 1 <= dilate <= 15; the agent's pixel inside the image.
+ *
+ * gs_clearance_field   obstacles are the pixels with trav == 0 plus a one-pixel frame around the image (rows -1 and H, columns -1 and W).
+ *   dist2 [H, W] int32: the squared distance to the nearest obstacle, 0 on obstacles.  feature [H, W, 2] int16: that obstacle (r, c); among
+ *   equidistant obstacles the one with the smallest (r, c) in lexicographic order.  Two passes: per column the nearest obstacle above or below
+ *   (above on a tie), then per row the minimum of (c - c')^2 + g(c')^2 over the columns' picks (the frame's columns included).
+ *
+ * gs_voronoi_roadmap   the integer medial axis.  For every pair of 4-adjacent pixels p, q with trav set and |f(p) - f(q)|^2 > gamma2 (f: feature):
+ *   ap = |p + q - 2 f(p)|^2, aq = |p + q - 2 f(q)|^2; p is marked if aq <= ap, q is marked if ap <= aq (both on equality).  roadmap = marked
+ *   and dist2 >= min_dist2 (the caller passes ceil(radius_px^2)).  min_dist2, gamma2 >= 0.
+ *
+ * gs_grid_geodesic     field [H, W] int32: the shortest path length from the seed over the 8-connected pixels of mask, a straight step weighing
+ *   12 and a diagonal step 17; a diagonal step needs only its two end pixels in the mask.  Unreachable pixels (and pixels outside the mask)
+ *   hold INT32_MAX.  The seed is (seed_r, seed_c), or the DEVICE pair d_seed_rc[0..1] when d_seed_rc is not null; a seed outside the image
+ *   or outside the mask gives an all-unreachable field and raises bit 1 of *d_status.  The call repeats a relaxation launch (a workgroup
+ *   relaxes a 32 x 32 tile plus halo to local convergence; no workgroup waits for another) while a changed word is set, reading 4 bytes per
+ *   round (and 12 once, before the first): it WAITS for the stream.  *h_rounds (HOST): the number of rounds that changed something -- fewer than
+ *   the mask has pixels, else GS_ECAPACITY.
+ *
+ * gs_roadmap_entry     d_entry4 (DEVICE int32[4]) = (r, c, field value, linear index) of the roadmap pixel with the smallest finite field value,
+ *   the smallest index on a tie; (-1, -1, INT32_MAX, -1) when there is none.  Per-workgroup minima of the keys (field << 32 | index) go through
+ *   scratch, one workgroup takes their minimum: no atomics.
+ *
+ * gs_roadmap_nodes     cells of cell x cell pixels anchored at (0, 0) (the last row and column of cells may be cut by the image).  Per cell the
+ *   roadmap pixel with a finite field value and the largest dist2, the smallest index on a tie; the picks in row-major cell order (count, scan,
+ *   emit: no atomics) as node_rc [K, 2], node_dist2 [K], node_field [K] int32, each with room for ceil(H / cell) * ceil(W / cell) rows;
+ *   d_count[0] = K stays on the DEVICE.  1 <= cell <= 64.
+ *
+ * gs_trace_path        from the target (target_r, target_c) -- or the DEVICE pair d_target_rc -- step to a neighbour n in the mask with
+ *   field[n] + w == field[current] (w = 12 or 17), trying (-1,-1), (-1,0), (-1,1), (0,-1), (0,1), (1,-1), (1,0), (1,1) in this order and taking the
+ *   first that qualifies, until the field reads 0.  One wavefront walks; at most `capacity` pixels are written.  path_rc [capacity, 2] int32: the
+ *   pixels from the target to the seed, both included; d_count2 (DEVICE int32[2]) = (pixels written, 0 done | 1 target outside the image or the
+ *   mask, or unreachable | 2 capacity reached first | 3 no neighbour qualifies: not a field of this mask). */
+uint64_t gs_roadmap_scratch_bytes(int32_t H, int32_t W);
+int gs_traversable_map(int32_t H, int32_t W, const uint8_t* free_map, const uint8_t* unseen, int32_t agent_r, int32_t agent_c, int32_t open_size,
+                       int32_t dilate, uint8_t* trav, void* scratch, uint32_t* d_status, gs_stream_t stream);
+int gs_clearance_field(int32_t H, int32_t W, const uint8_t* trav, int32_t* dist2, int16_t* feature, void* scratch, gs_stream_t stream);
+int gs_voronoi_roadmap(int32_t H, int32_t W, const uint8_t* trav, const int32_t* dist2, const int16_t* feature, int32_t min_dist2, int32_t gamma2,
+                       uint8_t* roadmap, gs_stream_t stream);
+int gs_grid_geodesic(int32_t H, int32_t W, const uint8_t* mask, int32_t seed_r, int32_t seed_c, const int32_t* d_seed_rc, int32_t* field,
+                     void* scratch, uint32_t* d_status, int32_t* h_rounds, gs_stream_t stream);
+int gs_roadmap_entry(int32_t H, int32_t W, const uint8_t* roadmap, const int32_t* field, int32_t* d_entry4, void* scratch, gs_stream_t stream);
+int gs_roadmap_nodes(int32_t H, int32_t W, const uint8_t* roadmap, const int32_t* dist2, const int32_t* field, int32_t cell, int32_t* node_rc,
+                     int32_t* node_dist2, int32_t* node_field, int32_t* d_count, void* scratch, gs_stream_t stream);
+int gs_trace_path(int32_t H, int32_t W, const uint8_t* mask, const int32_t* field, int32_t target_r, int32_t target_c, const int32_t* d_target_rc,
+                  int32_t capacity, int32_t* path_rc, int32_t* d_count2, gs_stream_t stream);
 
 #ifdef __cplusplus
 }
