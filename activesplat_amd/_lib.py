@@ -84,7 +84,7 @@ SORT_AUTO, SORT_TILE_LDS, SORT_RADIX = 0, 1, 2
 
 
 #: the GS_ABI_VERSION of include/gsplat_hip.h this binding was written against (checked when a library is bound)
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 vp, i32, u32, i64, u64, f32, f64, cint = C.c_void_p, C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_int
 
@@ -298,6 +298,18 @@ BINDINGS = {
     "gs_roadmap_nodes": (cint, [i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
     # (H, W, mask, field, target_r, target_c, d_target_rc, capacity, path_rc, d_count2, stream)
     "gs_trace_path": (cint, [i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp]),
+    # (path)
+    "gs_set_node_distance_path": (cint, [i32]),
+    # (H, W)
+    "gs_node_distances_scratch_bytes": (u64, [i32, i32]),
+    # (H, W, roadmap, K, node_rc, D, scratch, stream)
+    "gs_node_distances": (cint, [i32, i32, vp, i32, vp, vp, vp, vp]),
+    # (H, W, dist2, n, segments, clearance, stream)
+    "gs_segment_clearance": (cint, [i32, i32, vp, i32, vp, vp, vp]),
+    # (K)
+    "gs_subregions_scratch_bytes": (u64, [i32]),
+    # (K, node_rc, D, path_weight, coord_weight, threshold, labels, d_count, heights, scratch, stream)
+    "gs_subregions": (cint, [i32, vp, vp, f64, f64, f64, vp, vp, vp, vp, vp]),
 }
 
 SYMBOLS = tuple(BINDINGS)

@@ -1782,4 +1782,69 @@ int gs_trace_path(int32_t H, int32_t W, const uint8_t* mask, const int32_t* fiel
     return launched("gs_trace_path", "", gs::launch_trace_path(g, mask, field, target_r, target_c, d_target_rc, capacity, path_rc, d_count2, (hipStream_t)stream));
 }
 
+// ---- roadmap subregions (stats.hip) ----
+static std::atomic<int> g_node_distance_path{GS_NODE_DISTANCES_AUTO};
+
+int gs_set_node_distance_path(int32_t path)
+{
+    if (path < GS_NODE_DISTANCES_AUTO || path > GS_NODE_DISTANCES_GLOBAL) return fail(GS_EINVAL, "gs_set_node_distance_path: bad path");
+    g_node_distance_path = path;
+    return GS_OK;
+}
+
+uint64_t gs_node_distances_scratch_bytes(int32_t H, int32_t W)
+{
+    gs::RoadGrid g;
+    if (road_grid_checked("gs_node_distances_scratch_bytes", H, W, g) != GS_OK) return 0;
+    return gs::node_distances_scratch_bytes(g);
+}
+
+int gs_node_distances(int32_t H, int32_t W, const uint8_t* roadmap, int32_t K, const int32_t* node_rc, int32_t* D, void* scratch, gs_stream_t stream)
+{
+    gs::NodeDistArgs a;
+    const int rc = road_grid_checked("gs_node_distances", H, W, a.g);
+    if (rc != GS_OK) return rc;
+    if (K < 0 || K > gs::kMaxNodes) return fail(GS_EINVAL, "gs_node_distances: node count out of range (0 <= K <= 1024)");
+    if (!roadmap || !scratch || (K > 0 && (!node_rc || !D)) || ((uintptr_t)scratch & 15) || (((uintptr_t)node_rc | (uintptr_t)D) & 3))
+        return fail(GS_EINVAL, "gs_node_distances: null pointer (node_rc and D when K is 0), scratch not 16-byte aligned or an array not 4-byte aligned");
+    a.mask = roadmap; a.K = K; a.path = g_node_distance_path; a.node_rc = node_rc; a.D = D;
+    gs::node_distances_carve(scratch, a);
+    return launched("gs_node_distances", "", gs::launch_node_distances(a, (hipStream_t)stream));
+}
+
+int gs_segment_clearance(int32_t H, int32_t W, const int32_t* dist2, int32_t n, const int32_t* segments, int32_t* clearance, gs_stream_t stream)
+{
+    gs::RoadGrid g;
+    const int rc = road_grid_checked("gs_segment_clearance", H, W, g);
+    if (rc != GS_OK) return rc;
+    if (n < 0 || n > (1 << 24)) return fail(GS_EINVAL, "gs_segment_clearance: segment count out of range (0 <= n <= 2^24)");
+    if (!dist2 || (n > 0 && (!segments || !clearance)) || (((uintptr_t)dist2 | (uintptr_t)segments | (uintptr_t)clearance) & 3))
+        return fail(GS_EINVAL, "gs_segment_clearance: null pointer (segments and clearance when n is 0) or an array not 4-byte aligned");
+    return launched("gs_segment_clearance", "", gs::launch_segment_clearance(g, dist2, n, segments, clearance, (hipStream_t)stream));
+}
+
+uint64_t gs_subregions_scratch_bytes(int32_t K)
+{
+    if (K < 0 || K > gs::kMaxNodes) { fail(GS_EINVAL, "gs_subregions_scratch_bytes: node count out of range (0 <= K <= 1024)"); return 0; }
+    return gs::subregions_scratch_bytes(K);
+}
+
+int gs_subregions(int32_t K, const int32_t* node_rc, const int32_t* D, double path_weight, double coord_weight, double threshold, int32_t* labels,
+                  int32_t* d_count, double* heights, void* scratch, gs_stream_t stream)
+{
+    gs::SubregionArgs a;
+    if (K < 0 || K > gs::kMaxNodes) return fail(GS_EINVAL, "gs_subregions: node count out of range (0 <= K <= 1024)");
+    // (written so that a NaN fails them)
+    if (!(path_weight >= 0.0 && path_weight <= 1.7976931348623157e308) || !(coord_weight >= 0.0 && coord_weight <= 1.7976931348623157e308) || !(threshold >= 0.0))
+        return fail(GS_EINVAL, "gs_subregions: the weights must be finite and not negative, the threshold not negative");
+    if (!d_count || !scratch || (K > 0 && (!node_rc || !D || !labels)) || (K > 1 && !heights) || (((uintptr_t)scratch | (uintptr_t)heights) & 7) ||
+        (((uintptr_t)node_rc | (uintptr_t)D | (uintptr_t)labels | (uintptr_t)d_count) & 3))
+        return fail(GS_EINVAL, "gs_subregions: null pointer (the arrays a K of 0 or 1 leaves empty may be null), scratch or heights not 8-byte aligned or an "
+                               "array not 4-byte aligned");
+    a.K = K; a.node_rc = node_rc; a.D = D; a.path_weight = path_weight; a.coord_weight = coord_weight; a.threshold = threshold;
+    a.labels = labels; a.count = d_count; a.heights = heights;
+    gs::subregions_carve(scratch, a);
+    return launched("gs_subregions", "", gs::launch_subregions(a, (hipStream_t)stream));
+}
+
 }  // extern "C"

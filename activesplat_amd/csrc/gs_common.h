@@ -978,6 +978,36 @@ struct NodeArgs {
 hipError_t launch_roadmap_nodes(const NodeArgs& a, hipStream_t st);
 hipError_t launch_trace_path(const RoadGrid& g, const uint8_t* mask, const int32_t* field, int target_r, int target_c, const int32_t* d_target_rc,
                              int capacity, int32_t* path_rc, int32_t* count2, hipStream_t st);
+// roadmap subregions (stats.hip; the rules: include/gsplat_hip.h, gs_node_distances .. gs_subregions)
+constexpr int kMaxNodes = GS_MAX_NODES;     // K <= 1024: one workgroup clusters with the per-cluster caches in LDS, the pair sums take 8 K^2 bytes
+constexpr int kNodeLdsCap = 32768;          // skeleton pixels whose distances fit the LDS of one workgroup (128 of the 160 KiB)
+constexpr int kSkelChunk = 4096;            // pixels per workgroup of the skeleton's count and emit launches (16 consecutive pixels per thread)
+struct NodeDistArgs {
+    RoadGrid g;
+    const uint8_t* mask;
+    int K, path;                                                       // path: 0 by size, 1 LDS (where it fits), 2 global
+    const int32_t* node_rc;
+    int32_t *index, *pixel;                                            // scratch [npix] each: pixel -> skeleton entry or -1; entry -> pixel (24 bits) | its
+                                                                       // eight neighbours in the mask << 24 (3 x 3 window in row-major order, the centre left out)
+    uint32_t *block_counts, *words;                                    // scratch [ceil(npix / kSkelChunk)], [4]: words[0] = skeleton entries
+    int32_t* dist; int64_t dist_cap;                                   // scratch: the global path's distance arrays, dist_cap int32 in all
+    int32_t* D;
+};
+uint64_t node_distances_scratch_bytes(const RoadGrid& g);
+void node_distances_carve(void* scratch, NodeDistArgs& a);
+hipError_t launch_node_distances(const NodeDistArgs& a, hipStream_t st);
+hipError_t launch_segment_clearance(const RoadGrid& g, const int32_t* dist2, int n, const int32_t* segments, int32_t* clearance, hipStream_t st);
+struct SubregionArgs {
+    int K;
+    const int32_t *node_rc, *D;
+    double path_weight, coord_weight, threshold;
+    double *sums, *partial;                                            // scratch [K, K], [ceil(K K / kBlock)]
+    int32_t* member;                                                   // scratch [K]: the cluster (its smallest member) of a node
+    int32_t *labels, *count; double* heights;
+};
+uint64_t subregions_scratch_bytes(int K);
+void subregions_carve(void* scratch, SubregionArgs& a);
+hipError_t launch_subregions(const SubregionArgs& a, hipStream_t st);
 uint64_t grow_scratch_bytes(int64_t npix);
 hipError_t launch_grow(int W, int H, const float* rd, const float* sil, const float* gt, const float* color, const float* k4,
                        const float* c2w12, float sil_thres, int isotropic, float* means3D, float* rgb, float* rot, float* logit,

@@ -1113,4 +1113,339 @@ hipError_t launch_trace_path(const RoadGrid& g, const uint8_t* mask, const int32
     return hipGetLastError();
 }
 
+// ---- roadmap subregions: all-pairs node distances, segment clearance, average-linkage clustering -------------------------------------------------
+// (src/planner/planner.py:473-574 on the grid roadmap; the rules: include/gsplat_hip.h, gs_node_distances .. gs_subregions)
+
+// The skeleton (the mask's pixels) as a list, in row-major order: count, scan, emit, no atomics.  A thread owns 16 consecutive pixels of its
+// workgroup's kSkelChunk; thread 0 scans the 256 counts.  emit = false: block_counts[b] = the chunk's count; emit = true: block_counts[b] is
+// the chunk's offset, index[p] = the entry of pixel p or -1, pixel[entry] = p.
+__global__ __launch_bounds__(kBlock) void skeleton_list_kernel(NodeDistArgs a, bool emit)
+{
+    __shared__ int32_t s_sum[kBlock];
+    constexpr int per = kSkelChunk / kBlock;
+    const int t = threadIdx.x, p0 = blockIdx.x * kSkelChunk + t * per, p1 = p0 + per < a.g.npix ? p0 + per : a.g.npix;
+    int32_t s = 0;
+    for (int p = p0; p < p1; p++) s += a.mask[p] != 0;
+    s_sum[t] = s;
+    __syncthreads();
+    if (t == 0) {
+        int32_t run = 0;
+        for (int i = 0; i < kBlock; i++) { const int32_t v = s_sum[i]; s_sum[i] = run; run += v; }
+        if (!emit) a.block_counts[blockIdx.x] = (uint32_t)run;
+    }
+    if (!emit) return;
+    __syncthreads();
+    int32_t e = (int32_t)a.block_counts[blockIdx.x] + s_sum[t];
+    for (int p = p0; p < p1; p++) {
+        const bool m = a.mask[p] != 0;
+        a.index[p] = m ? e : -1;
+        if (!m) continue;
+        const int r = p / a.g.W, c = p - r * a.g.W;
+        uint32_t nb = 0;                                               // bit k: neighbour k of the 3 x 3 window (row-major, 4 = the centre) is in the mask
+        for (int k = 0; k < 9; k++) {
+            const int nr = r + k / 3 - 1, nc = c + k % 3 - 1;
+            if (k != 4 && nr >= 0 && nr < a.g.H && nc >= 0 && nc < a.g.W && a.mask[nr * a.g.W + nc]) nb |= 1u << k;
+        }
+        a.pixel[e++] = (int32_t)((uint32_t)p | (nb & 15u) << 24 | (nb >> 5) << 28);       // (p < 2^24: the top byte holds the eight bits)
+    }
+}
+
+// exclusive scan of the chunk counts in place (at most 4096 of them: a run per thread, thread 0 scans the 256 run sums); words[0] = the total
+__global__ __launch_bounds__(kBlock) void skeleton_scan_kernel(NodeDistArgs a, int nb)
+{
+    __shared__ uint32_t s_sum[kBlock];
+    const int t = threadIdx.x, per = (nb + kBlock - 1) / kBlock;
+    const int i0 = t * per < nb ? t * per : nb, i1 = i0 + per < nb ? i0 + per : nb;
+    uint32_t s = 0;
+    for (int i = i0; i < i1; i++) s += a.block_counts[i];
+    s_sum[t] = s;
+    __syncthreads();
+    if (t == 0) {
+        uint32_t run = 0;
+        for (int i = 0; i < kBlock; i++) { const uint32_t v = s_sum[i]; s_sum[i] = run; run += v; }
+        a.words[0] = run;
+    }
+    __syncthreads();
+    uint32_t run = s_sum[t];
+    for (int i = i0; i < i1; i++) { const uint32_t v = a.block_counts[i]; a.block_counts[i] = run; run += v; }
+}
+
+__device__ __forceinline__ int32_t node_entry(const NodeDistArgs& a, int k)
+{
+    const int r = a.node_rc[2 * k], c = a.node_rc[2 * k + 1];
+    return r >= 0 && r < a.g.H && c >= 0 && c < a.g.W ? a.index[r * a.g.W + c] : -1;
+}
+
+// One seed node: d (M entries, LDS or global, this workgroup's alone) = unreachable but 0 at the seed, then relaxed IN PLACE until a sweep
+// changes nothing.  A thread writes only the entries it owns (t, t + 256, ..) and reads its neighbours' as they are, old or new: every value
+// is the length of a real path, values only fall, and the sweep that changes nothing has read only final values, so the fixed point -- the
+// shortest distances -- is reached whatever the schedule.  A sweep that changes something makes final the unfinished entry nearest the seed
+// (its predecessor was final before the sweep): at most M changing sweeps.  Row `seed` of D = d at the nodes' entries.
+__device__ __forceinline__ void node_dist_seed(const NodeDistArgs& a, int M, int seed, int32_t* d)
+{
+    const int t = threadIdx.x, W = a.g.W;
+    const int32_t se = node_entry(a, seed);
+    for (int e = t; e < M; e += kBlock) d[e] = e == se ? 0 : kGeoInf;
+    __syncthreads();
+    if (se >= 0)
+        for (int sweep = 0; sweep <= M; sweep++) {
+            bool ch = false;
+            for (int e = t; e < M; e += kBlock) {
+                const uint32_t word = (uint32_t)a.pixel[e];
+                const int p = (int)(word & 0xffffffu);
+                const int32_t v = d[e];
+                int32_t best = v;
+                for (uint32_t nb = word >> 24; nb; nb &= nb - 1) {      // the neighbours in the mask alone (two or three on a skeleton): in the image, listed
+                    const int bit = __ffs(nb) - 1, k = bit < 4 ? bit : bit + 1, dr = k / 3 - 1, dc = k % 3 - 1;
+                    const int32_t n = d[a.index[p + dr * W + dc]];
+                    const int32_t cand = n == kGeoInf ? kGeoInf : n + (dr && dc ? 17 : 12);
+                    best = cand < best ? cand : best;
+                }
+                if (best < v) { d[e] = best; ch = true; }
+            }
+            if (!__syncthreads_or(ch)) break;
+        }
+    for (int j = t; j < a.K; j += kBlock) {
+        const int32_t e = node_entry(a, j);
+        a.D[(int64_t)seed * a.K + j] = se >= 0 && e >= 0 ? d[e] : kGeoInf;
+    }
+    __syncthreads();                                                   // (the next seed of this workgroup starts on the same array)
+}
+
+// A workgroup per seed while the skeleton's distances fit the LDS; else the first G workgroups take the seeds G apart, each on its own M
+// entries of the global array (G = as many arrays as fit dist_cap, at least one: dist_cap >= npix >= M), and the others leave.
+__global__ __launch_bounds__(kBlock) void node_dist_kernel(NodeDistArgs a)
+{
+    __shared__ int32_t s_d[kNodeLdsCap];
+    const int M = (int)a.words[0];
+    if (M == 0 || (a.path != 2 && M <= kNodeLdsCap)) { node_dist_seed(a, M, blockIdx.x, s_d); return; }
+    const int64_t fit = a.dist_cap / M;
+    const int G = fit < (int64_t)gridDim.x ? (int)fit : (int)gridDim.x;
+    if ((int)blockIdx.x >= G) return;
+    for (int seed = blockIdx.x; seed < a.K; seed += G) node_dist_seed(a, M, seed, a.dist + (int64_t)blockIdx.x * M);
+}
+
+uint64_t node_distances_scratch_bytes(const RoadGrid& g)
+{
+    const uint64_t n = (uint64_t)g.npix, nb = (n + kSkelChunk - 1) / kSkelChunk;
+    return 4 * ((4 * n + 255) / 256 * 256) + (4 * nb + 255) / 256 * 256 + 256;          // index, pixel, two maps of distances; chunk counts; words
+}
+
+void node_distances_carve(void* scratch, NodeDistArgs& a)
+{
+    const uint64_t map = (4 * (uint64_t)a.g.npix + 255) / 256 * 256, nb = ((uint64_t)a.g.npix + kSkelChunk - 1) / kSkelChunk;
+    uint8_t* p = (uint8_t*)scratch;
+    a.index = (int32_t*)p; p += map;
+    a.pixel = (int32_t*)p; p += map;
+    a.dist = (int32_t*)p; p += 2 * map;
+    a.dist_cap = (int64_t)(2 * map / 4);
+    a.block_counts = (uint32_t*)p; p += (4 * nb + 255) / 256 * 256;
+    a.words = (uint32_t*)p;
+}
+
+hipError_t launch_node_distances(const NodeDistArgs& a, hipStream_t st)
+{
+    if (a.K == 0) return hipSuccess;
+    const int nb = (a.g.npix + kSkelChunk - 1) / kSkelChunk;
+    hipLaunchKernelGGL(skeleton_list_kernel, dim3(nb), dim3(kBlock), 0, st, a, false);
+    hipLaunchKernelGGL(skeleton_scan_kernel, dim3(1), dim3(kBlock), 0, st, a, nb);
+    hipLaunchKernelGGL(skeleton_list_kernel, dim3(nb), dim3(kBlock), 0, st, a, true);
+    hipLaunchKernelGGL(node_dist_kernel, dim3(a.K), dim3(kBlock), 0, st, a);
+    return hipGetLastError();
+}
+
+// floor((2 a + N) / (2 N)) for N > 0 in exact integers (C's division truncates: the negative numerators go through the positive quotient)
+__device__ __forceinline__ int line_round(int a, int N)
+{
+    const int x = 2 * a + N, y = 2 * N;
+    return x >= 0 ? x / y : -((-x + y - 1) / y);
+}
+
+// a wavefront per segment: lane l takes the line's pixels l, l + 64, ..; the minimum over the lanes by shuffles.  An end point outside the
+// image is a pixel outside the image (i = 0 and i = N give the end points themselves): 0 without a walk; with both inside every pixel of the
+// line is inside (each coordinate stays between its ends), N <= 4095 and 2 i |dr| + N stays below 2^31.
+__global__ __launch_bounds__(kBlock) void segment_clearance_kernel(RoadGrid g, const int32_t* __restrict__ dist2, int n, const int32_t* __restrict__ seg,
+                                                                   int32_t* __restrict__ out)
+{
+    const int s = blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (s >= n) return;                                                 // (whole wavefronts)
+    const int r0 = seg[4 * s], c0 = seg[4 * s + 1], r1 = seg[4 * s + 2], c1 = seg[4 * s + 3];
+    int32_t best = 0;
+    if (r0 >= 0 && r0 < g.H && c0 >= 0 && c0 < g.W && r1 >= 0 && r1 < g.H && c1 >= 0 && c1 < g.W) {
+        const int dr = r1 - r0, dc = c1 - c0, ar = dr < 0 ? -dr : dr, ac = dc < 0 ? -dc : dc, N = ar > ac ? ar : ac;
+        best = kGeoInf;
+        for (int i = lane; i <= N; i += kWave) {
+            const int r = N ? r0 + line_round(i * dr, N) : r0, c = N ? c0 + line_round(i * dc, N) : c0;
+            const int32_t v = r >= 0 && r < g.H && c >= 0 && c < g.W ? dist2[r * g.W + c] : 0;
+            best = v < best ? v : best;
+        }
+    }
+    for (int m = 1; m < kWave; m <<= 1) { const int32_t o = __shfl_xor(best, m); best = o < best ? o : best; }
+    if (lane == 0) out[s] = best;
+}
+
+hipError_t launch_segment_clearance(const RoadGrid& g, const int32_t* dist2, int n, const int32_t* segments, int32_t* clearance, hipStream_t st)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(segment_clearance_kernel, dim3((n + kBlock / kWave - 1) / (kBlock / kWave)), dim3(kBlock), 0, st, g, dist2, n, segments, clearance);
+    return hipGetLastError();
+}
+
+// C of the pair (i, j) from D above the diagonal, +inf where D says unreachable (filled in by the clustering launch): two products and one
+// sum, none fused
+__device__ __forceinline__ double subregion_pair(const SubregionArgs& a, int i, int j)
+{
+#pragma clang fp contract(off)
+    if (i == j) return 0.0;
+    const int lo = i < j ? i : j, hi = i < j ? j : i;
+    const int32_t d = a.D[(int64_t)lo * a.K + hi];
+    if (d == kGeoInf) return INFINITY;
+    const int64_t dr = (int64_t)a.node_rc[2 * lo] - a.node_rc[2 * hi], dc = (int64_t)a.node_rc[2 * lo + 1] - a.node_rc[2 * hi + 1];
+    const double path = a.path_weight * ((double)d / 12.0), coord = a.coord_weight * sqrt((double)(dr * dr + dc * dc));
+    return path + coord;
+}
+
+// sums = C, and per workgroup the largest finite C of its 256 pairs (a maximum does not depend on the order; no atomics)
+__global__ __launch_bounds__(kBlock) void subregion_matrix_kernel(SubregionArgs a)
+{
+    __shared__ double s_max[kBlock / kWave];
+    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x, n = (int64_t)a.K * a.K;
+    double v = 0.0;
+    if (q < n) {
+        const double c = subregion_pair(a, (int)(q / a.K), (int)(q % a.K));
+        a.sums[q] = c;
+        v = c == INFINITY ? 0.0 : c;
+    }
+    for (int m = 1; m < kWave; m <<= 1) { const double o = __shfl_xor(v, m); v = o > v ? o : v; }
+    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kBlock / kWave; w++) v = s_max[w] > v ? s_max[w] : v;
+        a.partial[blockIdx.x] = v;
+    }
+}
+
+// the smallest (value, index) of the workgroup, the smaller index on equal values, to every thread; (+inf, -1) when no thread has a candidate
+struct SubMin { double v; int i; };
+__device__ __forceinline__ SubMin subregion_block_min(double v, int i)
+{
+    __shared__ double s_v[kBlock / kWave];
+    __shared__ int s_i[kBlock / kWave];
+    for (int m = 1; m < kWave; m <<= 1) {
+        const double ov = __shfl_xor(v, m);
+        const int oi = __shfl_xor(i, m);
+        if (oi >= 0 && (i < 0 || ov < v || (ov == v && oi < i))) { v = ov; i = oi; }
+    }
+    __syncthreads();                                                   // (the previous call's readers are done)
+    if ((threadIdx.x & 63) == 0) { s_v[threadIdx.x >> 6] = v; s_i[threadIdx.x >> 6] = i; }
+    __syncthreads();
+    SubMin r = {INFINITY, -1};
+    for (int w = 0; w < kBlock / kWave; w++)
+        if (s_i[w] >= 0 && (r.i < 0 || s_v[w] < r.v || (s_v[w] == r.v && s_i[w] < r.i))) { r.v = s_v[w]; r.i = s_i[w]; }
+    return r;
+}
+
+// Average linkage by one workgroup.  A cluster is named by its smallest member; sums[x][y] = the sum of C over the member pairs of clusters
+// x and y, the average = sums / (|x| |y|).  near[x] = the cluster y > x with the smallest average (the smallest y on equal averages) and
+// near_v[x] that average: the pair to merge is the smallest (near_v[a], a) -- the lexicographically smallest (a, b) among the closest pairs.
+// After a merge of a < b: row and column a of sums take the sums with b added; a cluster that pointed at a or b, and a itself, look again
+// (the whole workgroup scans one row); a cluster x < a that pointed elsewhere compares its new average with a (it cannot have fallen below
+// near_v[x] -- the linkage is reducible -- but it can tie with a smaller name).
+__global__ __launch_bounds__(kBlock) void subregion_cluster_kernel(SubregionArgs a, int nparts)
+{
+    __shared__ double s_near_v[kMaxNodes];
+    __shared__ int32_t s_near[kMaxNodes], s_size[kMaxNodes];
+    __shared__ uint8_t s_live[kMaxNodes], s_again[kMaxNodes];
+    __shared__ int32_t s_rank[kMaxNodes];
+    const int t = threadIdx.x, K = a.K;
+    // the largest finite C; unreachable pairs take it plus one
+    double mx = 0.0;
+    for (int i = t; i < nparts; i += kBlock) mx = a.partial[i] > mx ? a.partial[i] : mx;
+    mx = -subregion_block_min(-mx, 0).v;
+    const double fill = mx + 1.0;
+    for (int64_t q = t; q < (int64_t)K * K; q += kBlock)
+        if (a.sums[q] == INFINITY) a.sums[q] = fill;
+    for (int x = t; x < K; x += kBlock) { s_size[x] = 1; s_live[x] = 1; a.member[x] = x; }
+    __syncthreads();
+    auto look = [&](int x) {                                           // near[x], by the whole workgroup
+        double bv = INFINITY; int bi = -1;
+        for (int y = x + 1 + t; y < K; y += kBlock)
+            if (s_live[y]) {
+                const double v = a.sums[(int64_t)x * K + y] / (double)(s_size[x] * s_size[y]);
+                if (bi < 0 || v < bv) { bv = v; bi = y; }             // (ascending y: the first of equal averages stays)
+            }
+        const SubMin r = subregion_block_min(bv, bi);
+        if (t == 0) { s_near[x] = r.i; s_near_v[x] = r.v; }
+    };
+    for (int x = 0; x < K; x++) look(x);
+    __syncthreads();
+    int step = 0;
+    for (; step < K - 1; step++) {
+        double bv = INFINITY; int bi = -1;
+        for (int x = t; x < K; x += kBlock)
+            if (s_live[x] && s_near[x] >= 0 && (bi < 0 || s_near_v[x] < bv)) { bv = s_near_v[x]; bi = x; }
+        const SubMin pick = subregion_block_min(bv, bi);
+        if (pick.i < 0 || pick.v > a.threshold) break;
+        const int ca = pick.i, cb = s_near[ca];
+        __syncthreads();                                               // (everyone has read near[ca] before thread 0 writes near again)
+        if (t == 0) a.heights[step] = pick.v;
+        for (int x = t; x < K; x += kBlock) {
+            if (a.member[x] == cb) a.member[x] = ca;
+            bool again = false;
+            if (s_live[x] && x != cb) {
+                if (x != ca) {
+                    const double s = a.sums[(int64_t)ca * K + x] + a.sums[(int64_t)cb * K + x];
+                    a.sums[(int64_t)ca * K + x] = s; a.sums[(int64_t)x * K + ca] = s;
+                }
+                again = x == ca || s_near[x] == ca || s_near[x] == cb;
+            }
+            s_again[x] = again ? 1 : 0;
+        }
+        __syncthreads();
+        if (t == 0) { s_size[ca] += s_size[cb]; s_live[cb] = 0; }
+        __syncthreads();
+        for (int x = t; x < ca; x += kBlock)
+            if (s_live[x] && !s_again[x]) {
+                const double v = a.sums[(int64_t)x * K + ca] / (double)(s_size[x] * s_size[ca]);
+                if (v < s_near_v[x] || (v == s_near_v[x] && ca < s_near[x])) { s_near_v[x] = v; s_near[x] = ca; }
+            }
+        for (int x = 0; x < cb; x++)                                   // (uniform: s_again is read by every thread alike)
+            if (s_again[x]) look(x);
+        __syncthreads();
+    }
+    for (int k = step + t; k < K - 1; k += kBlock) a.heights[k] = INFINITY;
+    __syncthreads();
+    if (t == 0) {
+        int32_t run = 0;
+        for (int x = 0; x < K; x++) { s_rank[x] = run; run += s_live[x]; }
+        a.count[0] = run;
+    }
+    __syncthreads();
+    for (int x = t; x < K; x += kBlock) a.labels[x] = s_rank[a.member[x]];
+}
+
+uint64_t subregions_scratch_bytes(int K)
+{
+    const uint64_t n = (uint64_t)K * K;
+    return (8 * n + 255) / 256 * 256 + (8 * ((n + kBlock - 1) / kBlock) + 255) / 256 * 256 + (4 * (uint64_t)K + 255) / 256 * 256 + 256;
+}
+
+void subregions_carve(void* scratch, SubregionArgs& a)
+{
+    const uint64_t n = (uint64_t)a.K * a.K;
+    uint8_t* p = (uint8_t*)scratch;
+    a.sums = (double*)p; p += (8 * n + 255) / 256 * 256;
+    a.partial = (double*)p; p += (8 * ((n + kBlock - 1) / kBlock) + 255) / 256 * 256;
+    a.member = (int32_t*)p;
+}
+
+hipError_t launch_subregions(const SubregionArgs& a, hipStream_t st)
+{
+    if (a.K == 0) return hipMemsetAsync(a.count, 0, sizeof(int32_t), st);
+    const int nparts = (int)(((int64_t)a.K * a.K + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(subregion_matrix_kernel, dim3(nparts), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(subregion_cluster_kernel, dim3(1), dim3(kBlock), 0, st, a, nparts);
+    return hipGetLastError();
+}
+
 }  // namespace gs

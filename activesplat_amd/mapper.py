@@ -551,19 +551,29 @@ class SplatMapper:
         rm = RM.plan_roadmap(maps, (r, c), float(agent_radius) * px_per_m, cell)
         rm.world = dict(world_center=tuple(float(v) for v in world_center), world_shape=tuple(float(v) for v in world_shape), grid_shape=(W, H),
                         height=float(height))
+        rm.px_per_m, rm.radius_px = px_per_m, float(agent_radius) * px_per_m
         xz = RM.pixel_to_world(rm.node_rc.cpu().numpy(), **rm.world)     # (K pixel pairs to the host: the scores take host positions)
         positions = np.stack([xz[:, 0], np.full(rm.K, float(node_y)), xz[:, 1]], 1)
         return rm, positions
 
     @torch.no_grad()
     def plan_step(self, view_c2w, world_center, world_shape, grid_shape, upper, lower, agent_radius, node_spacing, height=1000.0,
-                  scale_modifier=0.01, max_clusters=256):
+                  scale_modifier=0.01, max_clusters=256, policy=None):
         """One planning step: `roadmap(...)` with the agent at `view_c2w`'s position (nodes at its height), `global_invisibility_scores` of the
         nodes, and the node with the largest invisibility -- ties go to the smaller path length, then to the lower index (every node of a
-        Roadmap is reachable: nodes are picked among the pixels its geodesic field reaches).  This greedy choice is NOT the reference's
-        stateful subregion policy (no subregion clustering, no escape plans, no path smoothing).
+        Roadmap is reachable: nodes are picked among the pixels its geodesic field reaches).  This greedy choice (policy=None, the default)
+        is NOT the reference's stateful subregion policy.
         -> dict(roadmap, positions [K, 3], invisibility [K], volume [K], node, path_rc int32 [n, 2] (device), waypoints fp32 [n, 3] (device;
-        world, agent to node, at the agent's height)); node = -1 and empty paths when there is no node."""
+        world, agent to node, at the agent's height)); node = -1 and empty paths when there is no node.
+
+        policy: a `policy.SubregionPolicy` makes the reference's hierarchical choice instead (planner_node.py:249-463; what of it is not
+        restated -- the reweighting after exhaustion, escape plans, spline smoothing -- is listed in policy.py): roadmap -> `node_distances`
+        -> `subregions` -> `nodes_in_horizon` -> `global_invisibility_scores` -> `node_scores` -> `policy.choose` -> `path_to` ->
+        `shortcut_path`.  The agent's pixel is recorded as visited; `policy.arrive` / `policy.fail` are the caller's to call as the agent
+        moves.  The way to a node is measured along the roadmap (`node_path_length` / 12 pixels).  The dict gains subregions (labels int32
+        [K], host), scores (int32 [K], host), distances (D, device), shortcut_rc (int32 [m, 2], device: the agent's pixel, then the path
+        from the farthest pixel a straight line reaches with 1.5 radii of clearance), safe (0-dim uint8, device), and waypoints follow
+        shortcut_rc; path_rc stays the whole pixel path."""
         from . import roadmap as RM
         c2w = np.asarray(view_c2w.detach().cpu().numpy() if torch.is_tensor(view_c2w) else view_c2w, dtype=np.float64)
         agent_xz, node_y = (c2w[0, 3], c2w[2, 3]), float(c2w[1, 3])
@@ -573,6 +583,8 @@ class SplatMapper:
                    path_rc=torch.zeros(0, 2, dtype=torch.int32, device=self.device), waypoints=torch.zeros(0, 3, device=self.device))
         if rm.K == 0:
             return out
+        if policy is not None:
+            return self._plan_step_policy(out, policy, view_c2w, node_y, max_clusters)
         inv, vol = self.global_invisibility_scores(view_c2w, positions, max_clusters=max_clusters)
         length = rm.node_path_length().cpu().numpy()
         node = int(np.lexsort((np.arange(rm.K), length, -inv))[0])
@@ -580,6 +592,17 @@ class SplatMapper:
         xz = RM.pixel_to_world(path, **rm.world)
         out.update(invisibility=inv, volume=vol, node=node, path_rc=path,
                    waypoints=torch.stack([xz[:, 0], torch.full_like(xz[:, 0], node_y), xz[:, 1]], 1))
+        return out
+
+    def _plan_step_policy(self, out, policy, view_c2w, node_y, max_clusters):
+        """plan_step's second half under a SubregionPolicy (the roadmap has nodes)"""
+        from . import policy as PL
+        from . import roadmap as RM
+        rm, positions = out["roadmap"], out["positions"]
+        out.update(PL.plan(rm, policy, lambda: self.global_invisibility_scores(view_c2w, positions, max_clusters=max_clusters), rm.px_per_m, rm.radius_px))
+        if out["node"] >= 0:
+            xz = RM.pixel_to_world(out["shortcut_rc"], **rm.world)
+            out["waypoints"] = torch.stack([xz[:, 0], torch.full_like(xz[:, 0], node_y), xz[:, 1]], 1)
         return out
 
     @torch.no_grad()

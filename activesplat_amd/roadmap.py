@@ -275,6 +275,142 @@ def plan_roadmap(maps, agent_rc, radius_px, cell, open_size=4, dilate=3, gamma2=
                    cell=int(cell), min_dist2=min_dist2)
 
 
+# ---- subregions, line tests --------------------------------------------------------------------------------------------------------------------
+# What the reference's hierarchical target choice (scripts/nodes/planner_node.py:249-463, activesplat_amd/policy.py) needs on top of a Roadmap:
+# the all-pairs node distances, the clustering of the nodes into subregions (src/planner/planner.py:530-574) and the line tests of
+# planner.py:473-528 and planner_node.py:1173-1200, here on the clearance field.  The rules: include/gsplat_hip.h, gs_node_distances ..
+# gs_subregions.  The calls enqueue work and wait for nothing; there is no CPU fallback.
+
+MAX_NODES = 1024                       # GS_MAX_NODES: the node count gs_node_distances and gs_subregions take
+NODE_DISTANCE_PATHS = {"auto": 0, "lds": 1, "global": 2}
+
+
+def set_node_distance_path(path):
+    """test knob: where `node_distances` keeps a seed's distances -- "lds" (only where the skeleton fits), "global", or "auto" by size"""
+    _lib.check(_lib.get().gs_set_node_distance_path(NODE_DISTANCE_PATHS[path]))
+
+
+def _nodes(node_rc, device, name="node_rc"):
+    if not torch.is_tensor(node_rc):
+        raise TypeError(f"{name} must be a torch tensor, got {type(node_rc).__name__}")
+    if node_rc.dtype != torch.int32 or node_rc.dim() != 2 or node_rc.shape[1] != 2 or not node_rc.is_contiguous() or node_rc.device != device:
+        raise ValueError(f"{name} must be a contiguous int32 [K, 2] tensor on {device}")
+    K = int(node_rc.shape[0])
+    if K > MAX_NODES:
+        raise ValueError(f"{name}: {K} nodes, at most {MAX_NODES} are taken")
+    return node_rc.detach(), K
+
+
+@torch.no_grad()
+def node_distances(rm, node_rc=None, scratch=None):
+    """D int32 [K, K] on the device: D[i][j] = the shortest path length from node i to node j along the roadmap, in `grid_geodesic`'s weights
+    (exactly `grid_geodesic(rm.roadmap, node_rc[i])[node_rc[j]]`: symmetric, 0 on the diagonal, UNREACHABLE where no path exists).  One call:
+    no per-seed host loop, nothing is read back.  `rm`: a Roadmap, or a uint8 [H, W] mask together with `node_rc` (int32 [K, 2] on the device;
+    default: the Roadmap's nodes).  K <= MAX_NODES."""
+    mask = rm.roadmap if isinstance(rm, Roadmap) else rm
+    mask, H, W = _map(mask, "roadmap")
+    node_rc, K = _nodes(rm.node_rc if node_rc is None else node_rc, mask.device)
+    lib, dev = _lib.get(), mask.device
+    need = int(lib.gs_node_distances_scratch_bytes(H, W))
+    if scratch is None or scratch.numel() < need or scratch.device != dev:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    D = torch.empty(K, K, dtype=torch.int32, device=dev)
+    _lib.check(lib.gs_node_distances(H, W, R._ptr(mask), K, R._ptr(node_rc) if K else None, R._ptr(D) if K else None, R._ptr(scratch), _lib.stream_ptr(dev)))
+    return D
+
+
+@torch.no_grad()
+def segment_clearance(dist2, segments):
+    """`segments`: int32 [n, 4] = (r0, c0, r1, c1) on the device, end points outside the image allowed.  -> int32 [n]: the minimum of `dist2`
+    over the pixels of the integer line (pixel i of N = max(|dr|, |dc|) is (r0 + floor((2 i dr + N) / (2 N)), c0 + likewise)); a pixel outside
+    the image counts as an obstacle (0).  A segment is clear for a radius rho when its clearance >= ceil(rho^2)."""
+    dist2, H, W = _map(dist2, "dist2", torch.int32)
+    if not torch.is_tensor(segments):
+        raise TypeError(f"segments must be a torch tensor, got {type(segments).__name__}")
+    if segments.dtype != torch.int32 or segments.dim() != 2 or segments.shape[1] != 4 or not segments.is_contiguous() or segments.device != dist2.device:
+        raise ValueError(f"segments must be a contiguous int32 [n, 4] tensor on {dist2.device}")
+    n = int(segments.shape[0])
+    out = torch.empty(n, dtype=torch.int32, device=dist2.device)
+    _lib.check(_lib.get().gs_segment_clearance(H, W, R._ptr(dist2), n, R._ptr(segments) if n else None, R._ptr(out) if n else None,
+                                               _lib.stream_ptr(dist2.device)))
+    return out
+
+
+def _from_agent(rm, rc):
+    """segments agent -> each of `rc` (int32 [n, 2] on the device)"""
+    agent = torch.tensor(rm.agent_rc, dtype=torch.int32, device=rc.device).expand(rc.shape[0], 2)          # (the one small copy: 8 bytes up)
+    return torch.cat([agent, rc], 1).contiguous()
+
+
+@torch.no_grad()
+def nodes_in_horizon(rm):
+    """uint8 [K] on the device: 1 where the integer line from the agent's pixel to the node runs wholly on `rm.trav` (its clearance >= 1).
+    The reference's IN_HORIZON flag (planner_node.py:1173-1200) is a 1-pixel `cv2.line` on its free map, with the agent's own disc masked
+    out of the test; this is the grid rule of `segment_clearance` instead, and the agent's disc is NOT masked out."""
+    return (segment_clearance(rm.dist2, _from_agent(rm, rm.node_rc)) >= 1).to(torch.uint8)
+
+
+def path_length_px(path_rc):
+    """the Euclidean sum over the vertices of a pixel path [n, 2], in fp64 on the device -> 0-dim tensor"""
+    d = (path_rc[1:] - path_rc[:-1]).to(torch.float64)
+    return torch.sqrt((d * d).sum(1)).sum()
+
+
+@torch.no_grad()
+def shortcut_path(rm, path_rc, radius_px, ratio=1.5):
+    """The reference's "fast forward" and safe-path tests (planner.py:473-528) on the clearance field.  `path_rc`: the agent-to-node pixel
+    path of `rm.path_to` (int32 [n, 2], n >= 1, its first pixel the agent's).  k = the LARGEST index whose segment from the agent is clear for
+    the radius `ratio * radius_px` (clearance >= ceil((ratio radius_px)^2); k = 0, the agent's own pixel, always qualifies).  The reference
+    walks back from the far end and also stops early once the distance to the agent starts to grow again; that early break is deliberately
+    dropped.  -> (path int32 [n - k + 1, 2]: the agent's pixel followed by path_rc[k:], k: 0-dim int64, safe: 0-dim uint8 -- the clearance of
+    the agent -> path_rc[k] segment >= ceil(radius_px^2); the pixels behind it are roadmap pixels (or the traversable way to the entry)
+    and keep dist2 >= min_dist2), all on the device.  One 8-byte copy (k sizes the result)."""
+    if not torch.is_tensor(path_rc) or path_rc.dtype != torch.int32 or path_rc.dim() != 2 or path_rc.shape[1] != 2 or path_rc.shape[0] < 1:
+        raise ValueError("path_rc must be an int32 [n, 2] tensor with n >= 1")
+    radius_px, ratio = float(radius_px), float(ratio)
+    if not (0.0 <= radius_px < math.inf and 0.0 <= ratio < math.inf):
+        raise ValueError("radius_px and ratio must be finite and not negative")
+    path_rc = path_rc.contiguous()
+    clear = segment_clearance(rm.dist2, _from_agent(rm, path_rc))
+    ok = clear >= int(math.ceil((ratio * radius_px) ** 2))
+    ok[0] = True
+    index = torch.arange(path_rc.shape[0], device=path_rc.device)
+    k = torch.where(ok, index, torch.zeros_like(index)).max()
+    safe = (clear[k] >= int(math.ceil(radius_px * radius_px))).to(torch.uint8)
+    agent = torch.tensor([rm.agent_rc], dtype=torch.int32, device=path_rc.device)
+    return torch.cat([agent, path_rc[int(k.item()):]]), k, safe
+
+
+@torch.no_grad()
+def subregions(rm, D, px_per_m, path_weight=0.5, coord_weight=0.5, scope_m=2.0, node_rc=None, scratch=None):
+    """The reference's `get_subregions` (planner.py:530-574) on the device, in fp64: C[i][j] = path_weight D[i][j] / 12 + coord_weight
+    |node_i - node_j| (pixels; the largest finite C + 1 where D is UNREACHABLE), average linkage -- merge the two clusters with the smallest
+    average pairwise C, on a tie the pair whose smallest members are lexicographically smallest -- until that minimum exceeds
+    scope_m * px_per_m: `fcluster(linkage(C, 'average'), t, 'distance')`.  `rm`: a Roadmap (or None with `node_rc` given).
+    -> (labels int32 [K]: clusters numbered 0, 1, .. by their smallest member; count int32 [1]; heights fp64 [K - 1]: the merge heights in
+    merge order, +inf from the first merge not made), all on the device."""
+    if not torch.is_tensor(D):
+        raise TypeError(f"D must be a torch tensor, got {type(D).__name__}")
+    node_rc, K = _nodes(rm.node_rc if node_rc is None else node_rc, D.device)
+    if D.dtype != torch.int32 or tuple(D.shape) != (K, K) or not D.is_contiguous():
+        raise ValueError(f"D must be a contiguous int32 [{K}, {K}] tensor, got {D.dtype} {list(D.shape)}")
+    R._require_rocm(D.device)
+    t = float(scope_m) * float(px_per_m)
+    path_weight, coord_weight = float(path_weight), float(coord_weight)
+    if not (0.0 <= path_weight < math.inf and 0.0 <= coord_weight < math.inf and t >= 0.0):
+        raise ValueError("path_weight and coord_weight must be finite and not negative, scope_m * px_per_m not negative")
+    lib, dev = _lib.get(), D.device
+    need = int(lib.gs_subregions_scratch_bytes(K))
+    if scratch is None or scratch.numel() < need or scratch.device != dev:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    labels = torch.empty(K, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    heights = torch.empty(max(K - 1, 0), dtype=torch.float64, device=dev)
+    _lib.check(lib.gs_subregions(K, R._ptr(node_rc) if K else None, R._ptr(D) if K else None, path_weight, coord_weight, t, R._ptr(labels) if K else None,
+                                 R._ptr(count), R._ptr(heights) if K > 1 else None, R._ptr(scratch), _lib.stream_ptr(dev)))
+    return labels, count, heights
+
+
 # ---- pixels and the world ------------------------------------------------------------------------------------------------------------------------
 # `topdown.topdown_camera` looks down the +y axis from `height` metres above `world_center` = (x, z): camera x = world x, camera y = -world z,
 # depth = world y + height, fx = W height / world_width, fy = H height / world_height, principal point (W // 2, H // 2).  The rasteriser samples

@@ -21,7 +21,7 @@
  *   - return value 0 = success, otherwise a GS_E* code; gs_last_error() gives the message;
  *   - no torch types.  Process-wide state: the last-error string (thread-local), the host-mapped status word (gs_async_status_word) and the
  *     development knobs gs_set_sort_path, gs_set_forward_segments, gs_set_half_quadrants, gs_set_backward_chain[_tickets|_polls],
- *     gs_set_backward_segments, gs_set_forward_priority (defaults: automatic path choice, segments on, few-tile kernels up to 256 tiles, three chained pieces above 768 tiles).
+ *     gs_set_backward_segments, gs_set_forward_priority, gs_set_node_distance_path (defaults: automatic path choice, segments on, few-tile kernels up to 256 tiles, three chained pieces above 768 tiles).
  *     The knobs are atomics that every launch reads ONCE: set from another thread (the reference runs a visualiser thread next to the mapper) a
  *     new value takes effect at a launch boundary of the other threads, never inside one launch's decisions; a forward and the backward that
  *     consumes its state tolerate a change in between (the forward clears the hand-over flags and records its "recorded" word whatever the
@@ -205,7 +205,7 @@ const char* gs_version(void);
 /* Integer version of THIS binary interface: bumped whenever an entry point's argument list or a published record layout changes (e.g.
  * the seed argument of gs_densify_children, the 40-byte SH Jacobian record).  A host binding compares it with the GS_ABI_VERSION it was
  * written against before the first call, so that a stale prebuilt library fails at load time instead of misreading its arguments. */
-#define GS_ABI_VERSION 26
+#define GS_ABI_VERSION 27
 int32_t gs_abi_version(void);
 
 /* Optional per-stage timing (hipEvents recorded on the caller's stream around each stage's launches).
@@ -1107,6 +1107,53 @@ int gs_roadmap_nodes(int32_t H, int32_t W, const uint8_t* roadmap, const int32_t
                      int32_t* node_dist2, int32_t* node_field, int32_t* d_count, void* scratch, gs_stream_t stream);
 int gs_trace_path(int32_t H, int32_t W, const uint8_t* mask, const int32_t* field, int32_t target_r, int32_t target_c, const int32_t* d_target_rc,
                   int32_t capacity, int32_t* path_rc, int32_t* d_count2, gs_stream_t stream);
+
+/* Roadmap subregions (stats.hip): what the reference's hierarchical target choice needs on top of the roadmap above -- the all-pairs path
+ * lengths between the nodes, line tests on the clearance field, and the average-linkage clustering of src/planner/planner.py:530-574
+ * (get_subregions) -- as three calls that only enqueue work: no host read, no wait.  Integers wherever the rule is integer, no float atomics,
+ * the same bytes from run to run.  Refused with GS_EINVAL before any launch: a null or misaligned pointer, a shape or count out of range.
+ * GS_MAX_NODES bounds the node count of gs_node_distances and gs_subregions (the clustering workgroup keeps its per-cluster caches in LDS and
+ * 8 K^2 bytes of pair sums in scratch).
+ *
+ * gs_node_distances    D [K, K] int32: D[i][j] = the shortest path length from node i to node j over the 8-connected pixels of roadmap, with
+ *   gs_grid_geodesic's weights (straight step 12, diagonal step 17, a diagonal step needs only its two end pixels): D[i][j] is exactly what
+ *   gs_grid_geodesic seeded at node i holds at node j, so D is symmetric, D[i][i] = 0 and D[i][j] = INT32_MAX where no path exists; a node
+ *   outside the image or off the roadmap has INT32_MAX in its whole row and column (its own diagonal entry included), as that field has.
+ *   node_rc [K, 2] int32 (r, c).  The roadmap's pixels are listed in row-major order (count, scan, emit); one workgroup per seed node relaxes
+ *   the list's distances in place until a sweep changes nothing and writes the K values at the node pixels.  While the list has at most 32768
+ *   pixels the distances sit in LDS; beyond, workgroups share scratch arrays, as many as fit, and take the seeds in turns.  scratch: DEVICE,
+ *   gs_node_distances_scratch_bytes(H, W) bytes (16 H W and some: it does not grow with K), 16-byte aligned.  0 <= K <= GS_MAX_NODES.
+ *   gs_set_node_distance_path forces a path (GS_NODE_DISTANCES_*; LDS only where the list fits): a test knob, the results are the same.
+ *
+ * gs_segment_clearance clearance [n] int32: the minimum of dist2 over the pixels of the integer line of segment s = (r0, c0, r1, c1)
+ *   (segments [n, 4] int32).  N = max(|r1 - r0|, |c1 - c0|); for i = 0..N the pixel is (r0 + rnd(i (r1 - r0), N), c0 + rnd(i (c1 - c0), N)) with
+ *   rnd(a, N) = floor((2 a + N) / (2 N)) in exact integers (floor division also for negative a: a half rounds towards +infinity); N = 0: the
+ *   single pixel.  A pixel outside the image counts as an obstacle: the minimum is 0 -- so a segment with an end point outside the image has
+ *   clearance 0, whatever its coordinates.  A segment is "clear for radius rho" when its clearance >= ceil(rho^2).  One wavefront per
+ *   segment, a minimum over its lanes; no atomics.  0 <= n <= 2^24.
+ *
+ * gs_subregions        average-linkage clustering of the K nodes in fp64, cut at `threshold` (the caller passes scope_m * px_per_m).
+ *   C[i][j] = path_weight * (D[i][j] / 12) + coord_weight * |node_i - node_j| (pixels; two products and one sum, none fused; D is read
+ *   above the diagonal, i < j, and taken as symmetric); where D is INT32_MAX, C = (the largest finite C, 0 without one) + 1 (planner.py:553-555).
+ *   Every node starts as a cluster.  The distance of two clusters A, B is (the sum of C over their member pairs) / (|A| |B|); the sums are kept
+ *   per cluster pair and added when clusters merge: sum(A u B, X) = sum(A, X) + sum(B, X).  Repeatedly the two clusters with the smallest
+ *   distance are merged -- among equal distances the pair whose smallest members (a, b), a < b, are lexicographically smallest -- until the
+ *   smallest distance exceeds threshold or one cluster is left.  For a reducible linkage such as this one that is
+ *   fcluster(linkage(C, 'average'), threshold, 'distance').  labels [K] int32: clusters numbered 0, 1, .. by their smallest member;
+ *   d_count[0] (DEVICE) = their number; heights [K - 1] fp64: the merge distances in merge order, +inf from the first merge not made.
+ *   One workgroup merges; each cluster caches its nearest later cluster.  scratch: DEVICE, gs_subregions_scratch_bytes(K) bytes, 8-byte
+ *   aligned.  0 <= K <= GS_MAX_NODES; weights finite and >= 0, threshold >= 0 (+inf: merge everything). */
+#define GS_MAX_NODES 1024
+#define GS_NODE_DISTANCES_AUTO 0
+#define GS_NODE_DISTANCES_LDS 1
+#define GS_NODE_DISTANCES_GLOBAL 2
+int gs_set_node_distance_path(int32_t path);
+uint64_t gs_node_distances_scratch_bytes(int32_t H, int32_t W);
+int gs_node_distances(int32_t H, int32_t W, const uint8_t* roadmap, int32_t K, const int32_t* node_rc, int32_t* D, void* scratch, gs_stream_t stream);
+int gs_segment_clearance(int32_t H, int32_t W, const int32_t* dist2, int32_t n, const int32_t* segments, int32_t* clearance, gs_stream_t stream);
+uint64_t gs_subregions_scratch_bytes(int32_t K);
+int gs_subregions(int32_t K, const int32_t* node_rc, const int32_t* D, double path_weight, double coord_weight, double threshold, int32_t* labels,
+                  int32_t* d_count, double* heights, void* scratch, gs_stream_t stream);
 
 #ifdef __cplusplus
 }
