@@ -84,7 +84,7 @@ SORT_AUTO, SORT_TILE_LDS, SORT_RADIX = 0, 1, 2
 
 
 #: the GS_ABI_VERSION of include/gsplat_hip.h this binding was written against (checked when a library is bound)
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 vp, i32, u32, i64, u64, f32, f64, cint = C.c_void_p, C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_int
 
@@ -260,6 +260,10 @@ BINDINGS = {
     # (num_vertices, vertices, num_triangles, triangles, vertex_colors, h_intrinsics4, h_w2c12, near_z, width, height, scratch, capacity, depth, tri_id, color, d_counts, uvs, tri_texture, num_textures, h_textures, textures, pool, pool_texels, stream)
     "gs_mesh_render_textured": (cint, [i32, vp, i32, vp, vp, C.POINTER(f32), C.POINTER(f32), f32, i32, i32, vp, u32, vp, vp, vp, vp, vp, vp, i32,
                                        C.POINTER(GsTextureDesc), vp, vp, u64, vp]),
+    # (num_triangles, grid_width, grid_height, capacity, layout)
+    "gs_mesh_navgrid_layout": (cint, [i32, i32, i32, u32, C.POINTER(GsMeshLayout)]),
+    # (num_vertices, vertices, num_triangles, triangles, x0, z0, cell, floor_y, max_climb, agent_height, grid_width, grid_height, scratch, capacity, grid, d_counts, stream)
+    "gs_mesh_navgrid": (cint, [i32, vp, i32, vp, f64, f64, f64, f64, f64, f64, i32, i32, vp, u32, vp, vp, vp]),
     # (width, height, depth, h_intrinsics4, h_c2w12, points, valid, stream)
     "gs_depth_cloud": (cint, [i32, i32, vp, C.POINTER(f32), C.POINTER(f32), vp, vp, vp]),
     # (n_query, n_points)

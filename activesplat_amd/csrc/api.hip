@@ -1503,6 +1503,59 @@ int gs_mesh_render(int32_t num_vertices, const float* vertices, int32_t num_tria
     return launched("gs_mesh_render", "", gs::launch_mesh_render(a, (hipStream_t)stream));
 }
 
+// gs_mesh_navgrid's scratch: gs_mesh_render's regions, with 48-byte records
+static int navgrid_layout_checked(const char* who, int32_t num_triangles, int32_t grid_width, int32_t grid_height, uint32_t capacity, GsMeshLayout& L)
+{
+    if (num_triangles < 0) return fail(GS_EINVAL, "%s: num_triangles must not be negative", who);
+    if (grid_width < 1 || grid_height < 1 || grid_width > 16384 || grid_height > 16384)
+        return fail(GS_EINVAL, "%s: grid size out of range (1 <= grid_width, grid_height <= 16384)", who);
+    const uint64_t tiles = tiles_of(grid_width, grid_height);
+    uint64_t at = 0;
+    L.total = at;       at += 256;
+    L.records = at;     at += align_up((uint64_t)num_triangles * 48u);
+    L.rects = at;       at += align_up((uint64_t)num_triangles * 8u);
+    L.tile_count = at;  at += align_up((tiles + 1) * 4u);
+    L.tile_offset = at; at += align_up((tiles + 1) * 4u);
+    L.list = at;        at += align_up((uint64_t)capacity * 4u);
+    L.total_bytes = at;
+    return GS_OK;
+}
+
+int gs_mesh_navgrid_layout(int32_t num_triangles, int32_t grid_width, int32_t grid_height, uint32_t capacity, GsMeshLayout* layout)
+{
+    if (!layout) return fail(GS_EINVAL, "gs_mesh_navgrid_layout: null pointer");
+    return navgrid_layout_checked("gs_mesh_navgrid_layout", num_triangles, grid_width, grid_height, capacity, *layout);
+}
+
+int gs_mesh_navgrid(int32_t num_vertices, const float* vertices, int32_t num_triangles, const int32_t* triangles, double x0, double z0, double cell,
+                    double floor_y, double max_climb, double agent_height, int32_t grid_width, int32_t grid_height, void* scratch, uint32_t capacity,
+                    uint8_t* grid, uint32_t* d_counts, gs_stream_t stream)
+{
+    const char* who = "gs_mesh_navgrid";
+    GsMeshLayout L;
+    const int rc = navgrid_layout_checked(who, num_triangles, grid_width, grid_height, capacity, L);
+    if (rc != GS_OK) return rc;
+    if (num_vertices < 0) return fail(GS_EINVAL, "%s: num_vertices must not be negative", who);
+    if (!scratch || !grid || !d_counts || (num_triangles > 0 && (!vertices || !triangles)) || ((uintptr_t)scratch & 15))
+        return fail(GS_EINVAL, "%s: null pointer (the mesh arrays may be null only with num_triangles == 0) or scratch not 16-byte aligned", who);
+    // (written so that a NaN fails them)
+    const double big = 1.7976931348623157e308;
+    if (!(fabs(x0) <= big) || !(fabs(z0) <= big) || !(fabs(floor_y) <= big) || !(fabs(max_climb) <= big) || !(fabs(agent_height) <= big))
+        return fail(GS_EINVAL, "%s: x0, z0, floor_y, max_climb and agent_height must be finite", who);
+    if (!(cell > 0.0 && cell <= big)) return fail(GS_EINVAL, "%s: cell must be positive and finite", who);
+    if (!(max_climb >= 0.0)) return fail(GS_EINVAL, "%s: max_climb must not be negative", who);
+    if (!(agent_height > max_climb)) return fail(GS_EINVAL, "%s: agent_height must exceed max_climb", who);
+    gs::NavGridArgs a;
+    a.V = num_vertices; a.T = num_triangles; a.vertices = vertices; a.triangles = triangles;
+    a.x0 = x0; a.z0 = z0; a.cell = cell; a.floor_y = floor_y; a.max_climb = max_climb; a.agent_height = agent_height;
+    a.W = grid_width; a.H = grid_height;
+    char* b = (char*)scratch;
+    a.total = (uint64_t*)(b + L.total); a.records = (float4*)(b + L.records); a.rects = (uint2*)(b + L.rects);
+    a.tile_count = (uint32_t*)(b + L.tile_count); a.tile_offset = (uint32_t*)(b + L.tile_offset); a.list = (uint32_t*)(b + L.list);
+    a.capacity = capacity; a.grid = grid; a.d_counts = d_counts;
+    return launched(who, "", gs::launch_mesh_navgrid(a, (hipStream_t)stream));
+}
+
 // levels and offsets of one texture after `at` texels; false: a size out of range
 static bool texture_plan(int32_t width, int32_t height, uint64_t& at, int32_t& levels, uint64_t (&offset)[GS_TEXTURE_MAX_LEVELS])
 {

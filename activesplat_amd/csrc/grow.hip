@@ -889,6 +889,242 @@ hipError_t launch_mesh_render_textured(const MeshArgs& a, const float* uvs, cons
     return hipGetLastError();
 }
 
+// ---- navigable grid of a storey from the triangle mesh (what the reference takes from Habitat-sim's navmesh, src/dataloader/dataloader.py:237-272;
+// the rule: include/gsplat_hip.h, gs_mesh_navgrid) ---------------------------------------------------------------------------------------------
+// A top-down, conservative classification of H x W square cells: every triangle is clipped against every cell it can reach, in fp64, and the y
+// range of what is left sets the cell's floor and obstacle bits.  The launches are gs_mesh_render's:
+//   setup  one thread per triangle: the nine fp32 coordinates as a 48-byte record, the per-triangle height pre-test, a conservative rectangle of
+//          16 x 16-cell tiles around its xz bounding box and the tile counts;
+//   scan, fill   mesh_scan_kernel and mesh_fill_kernel as they are;
+//   tile   one workgroup per tile, one cell per thread, a wavefront per 8 x 8 quadrant: the tile's records staged through LDS in chunks of
+//          kNavChunk, every lane reads each of them once (broadcast reads), rejects by bounding box, clips, and ORs two bits into a register;
+//          one byte store per cell.
+// The clip is Sutherland-Hodgman in its re-entrant form: a vertex a stage emits is fed to the next stage at once, and each stage keeps only its
+// first and its previous vertex, so the polygon (up to 7 vertices of 3 doubles) is never stored -- no array indexed at run time, no scratch
+// memory.  The vertices reach the last stage in the order, and from the operands, of the stage-after-stage formulation in the header: stage k
+// sees a0 [if inside], I(a0, a1), a1 [if inside], .., I(a_n-1, a0), which is that formulation's output list.
+// What the rectangle and the bounding-box rejection may skip (both only skip work whose result the rule fixes as "empty polygon"):
+//   x  the first two half-spaces test the triangle's own x: all three below xa, or all three above xb, leave nothing (exact comparisons);
+//   z  the last two test z of vertices that the x stages may have interpolated, p = a + t (b - a) with 0 <= t <= 1 (the quotient of two
+//      correctly rounded differences of which the first is not the larger).  Its three roundings keep p.z within a few units of 2^-52 max|z|
+//      of [min z, max z], twice over for a point interpolated from interpolated points; the box is padded by 2^-30 max|z|, far beyond that;
+//   the rectangle's cell range comes from a division and is widened by one cell plus 2^-50 (|origin| / cell + 32768) cells, which covers
+//   the rounding of the quotient and of the cell borders x0 + c cell; the borders are monotonic in c, so cells outside the range are
+//   rejected by the exact test as well.  Listing a triangle in a tile it cannot reach costs time and changes nothing.
+constexpr int kNavChunk = 256;              // records per pass: 256 x 48 B = 12 KiB of LDS per workgroup
+
+// y_floor = floor_y - max_climb, y_step = floor_y + max_climb, y_head = floor_y + agent_height (fp64 sums of the host)
+struct NavGridCam { double x0, z0, cell, y_floor, y_step, y_head; int W, H, gx, gy; };
+
+__device__ __forceinline__ uint32_t nav_bits(const NavGridCam& c, double lo, double hi)
+{
+    return (hi >= c.y_floor && lo <= c.y_step ? 1u : 0u) | (hi > c.y_step && lo < c.y_head ? 2u : 0u);
+}
+
+__device__ __forceinline__ double nav_z_pad(double zmin, double zmax)
+{
+    const double m = fabs(zmin) > fabs(zmax) ? fabs(zmin) : fabs(zmax);
+    return m * (1.0 / 1073741824.0);
+}
+
+// cells lo .. hi (clamped to 0 .. n - 1; lo > hi: none) that the interval [vmin, vmax] can reach along one axis
+__device__ __forceinline__ bool nav_cell_range(double vmin, double vmax, double origin, double cell, int n, int& lo, int& hi)
+{
+#pragma clang fp contract(off)
+    const double slack = 1.0 + (fabs(origin) / cell + 32768.0) * (1.0 / 1125899906842624.0);
+    const double a = floor((vmin - origin) / cell - slack), b = floor((vmax - origin) / cell + slack);
+    if (b < 0.0 || a > (double)(n - 1)) return false;
+    lo = !(a > 0.0) ? 0 : (int)a;                                           // (written so that a NaN -- inf - inf at an absurd cell size -- lists every cell)
+    hi = !(b < (double)(n - 1)) ? n - 1 : (int)b;
+    return true;
+}
+
+__global__ __launch_bounds__(kBlock) void navgrid_setup_kernel(NavGridCam c, int T, int V, const float* __restrict__ verts, const int32_t* __restrict__ tris,
+                                                                float4* __restrict__ records, uint2* __restrict__ rects, uint32_t* __restrict__ tile_count)
+{
+    __shared__ uint2 s_rect[kBlock];
+    __shared__ int s_big[kBlock], s_nbig;
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool live = t < T;
+    const int idx[3] = {live ? tris[3 * t] : -1, live ? tris[3 * t + 1] : -1, live ? tris[3 * t + 2] : -1};
+    uint2 rect = make_uint2(1u, 0u);
+    // (a triangle with an index outside the vertex array is dropped, not read)
+    if ((unsigned)idx[0] < (unsigned)V && (unsigned)idx[1] < (unsigned)V && (unsigned)idx[2] < (unsigned)V) {
+        float p[3][3];
+        bool finite = true;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float* v = verts + 3 * (int64_t)idx[k];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                p[k][j] = v[j];
+                finite = finite && fabsf(p[k][j]) <= 3.402823466e38f;
+            }
+        }
+        if (finite) {
+            float lo[3], hi[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                lo[j] = fminf(p[0][j], fminf(p[1][j], p[2][j]));
+                hi[j] = fmaxf(p[0][j], fmaxf(p[1][j], p[2][j]));
+            }
+            // the height pre-test on the triangle's own y range: a triangle that sets neither bit is never listed
+            if (nav_bits(c, (double)lo[1], (double)hi[1]) != 0u) {
+                const double pad = nav_z_pad((double)lo[2], (double)hi[2]);
+                int c0, c1, r0, r1;
+                if (nav_cell_range((double)lo[0], (double)hi[0], c.x0, c.cell, c.W, c0, c1) &&
+                    nav_cell_range((double)lo[2] - pad, (double)hi[2] + pad, c.z0, c.cell, c.H, r0, r1)) {
+                    records[3 * t + 0] = make_float4(p[0][0], p[0][1], p[0][2], p[1][0]);
+                    records[3 * t + 1] = make_float4(p[1][1], p[1][2], p[2][0], p[2][1]);
+                    records[3 * t + 2] = make_float4(p[2][2], 0.0f, 0.0f, 0.0f);
+                    rect = make_uint2((uint32_t)(c0 / kTile) | ((uint32_t)(c1 / kTile) << 16), (uint32_t)(r0 / kTile) | ((uint32_t)(r1 / kTile) << 16));
+                }
+            }
+        }
+    }
+    if (live) rects[t] = rect;
+    mesh_for_tiles(rect, live, c.gx, s_rect, s_big, &s_nbig, [&](int tile, int) { atomicAdd(tile_count + tile, 1u); });
+}
+
+// The four clip stages (x >= xa, x <= xb, z >= za, z <= zb).  Every member is addressed with a compile-time stage number, so the whole state
+// lives in registers.
+struct NavClip {
+    double bound[4];
+    double fx[4], fy[4], fz[4];             // the first vertex a stage received
+    double sx[4], sy[4], sz[4];             // the vertex it received last
+    bool have[4];
+    double lo, hi;                          // y range of what left the last stage
+    bool any;
+};
+
+template <int K>
+__device__ __forceinline__ bool nav_inside(const NavClip& s, double x, double z)
+{
+    return K == 0 ? x >= s.bound[0] : (K == 1 ? x <= s.bound[1] : (K == 2 ? z >= s.bound[2] : z <= s.bound[3]));
+}
+
+template <int K>
+__device__ __forceinline__ void nav_feed(NavClip& s, double x, double y, double z);
+
+// the two things an edge (a, b) can hand to the next stage, in the rule's order: the crossing point, then b itself
+template <int K>
+__device__ __forceinline__ void nav_edge(NavClip& s, bool crossing, double ax, double ay, double az, double bx, double by, double bz, bool emit_b)
+{
+#pragma clang fp contract(off)
+    const double bound = s.bound[K];
+    const double ak = K < 2 ? ax : az, bk = K < 2 ? bx : bz;
+    const double t = (bound - ak) / (bk - ak);                                 // (used only where the edge crosses: ak != bk)
+    const double qx = ax + t * (bx - ax), qy = ay + t * (by - ay), qz = az + t * (bz - az);
+    const double px = K < 2 ? bound : qx, pz = K < 2 ? qz : bound;
+    // one call site for both, so that the next stage's code exists once and lanes that emit either walk it together
+#pragma unroll 1
+    for (int j = 0; j < 2; ++j) {
+        const bool first = j == 0;
+        if (first ? crossing : emit_b) nav_feed<K + 1>(s, first ? px : bx, first ? qy : by, first ? pz : bz);
+    }
+}
+
+template <int K>
+__device__ __forceinline__ void nav_feed(NavClip& s, double x, double y, double z)
+{
+    if constexpr (K == 4) {
+        s.lo = y < s.lo ? y : s.lo;
+        s.hi = y > s.hi ? y : s.hi;
+        s.any = true;
+    } else {
+        const bool in = nav_inside<K>(s, x, z);
+        const bool had = s.have[K];
+        const double ax = s.sx[K], ay = s.sy[K], az = s.sz[K];
+        if (!had) { s.fx[K] = x; s.fy[K] = y; s.fz[K] = z; s.have[K] = true; }
+        s.sx[K] = x; s.sy[K] = y; s.sz[K] = z;
+        nav_edge<K>(s, had && nav_inside<K>(s, ax, az) != in, ax, ay, az, x, y, z, in);
+    }
+}
+
+// the closing edge (last vertex, first vertex) of every stage, front to back
+template <int K>
+__device__ __forceinline__ void nav_close(NavClip& s)
+{
+    if constexpr (K < 4) {
+        const double ax = s.sx[K], ay = s.sy[K], az = s.sz[K], bx = s.fx[K], by = s.fy[K], bz = s.fz[K];
+        nav_edge<K>(s, s.have[K] && nav_inside<K>(s, ax, az) != nav_inside<K>(s, bx, bz), ax, ay, az, bx, by, bz, false);
+        nav_close<K + 1>(s);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void navgrid_tile_kernel(NavGridCam c, const float4* __restrict__ records, const uint32_t* __restrict__ tile_offset,
+                                                               const uint32_t* __restrict__ list, const uint64_t* __restrict__ total, uint32_t capacity,
+                                                               uint8_t* __restrict__ grid)
+{
+#pragma clang fp contract(off)
+    __shared__ float4 s_rec[3 * kNavChunk];
+    const float* s_v = (const float*)s_rec;
+    const int tile = blockIdx.y * c.gx + blockIdx.x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int col = blockIdx.x * kTile + (wave & 1) * kQuad + (lane & 7);
+    const int row = blockIdx.y * kTile + (wave >> 1) * kQuad + (lane >> 3);
+    const bool listed = *total <= (uint64_t)capacity;
+    const uint32_t begin = listed ? tile_offset[tile] : 0u, end = listed ? tile_offset[tile + 1] : 0u;
+    // the cell's borders, exactly as the rule writes them
+    const double xa = c.x0 + (double)col * c.cell, xb = c.x0 + (double)(col + 1) * c.cell;
+    const double za = c.z0 + (double)row * c.cell, zb = c.z0 + (double)(row + 1) * c.cell;
+    const double inf = (double)__uint_as_float(0x7f800000u);
+    uint32_t bits = 0u;
+    for (uint32_t base = begin; base < end; base += kNavChunk) {
+        const int n = end - base < (uint32_t)kNavChunk ? (int)(end - base) : kNavChunk;
+        __syncthreads();                                        // the chunk before this one has been read by every wavefront
+        if ((int)threadIdx.x < n) {
+            const float4* r = records + 3 * (int64_t)list[base + threadIdx.x];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) s_rec[3 * threadIdx.x + j] = r[j];
+        }
+        __syncthreads();
+        for (int k = 0; k < n && bits != 3u; ++k) {             // (both bits set: no triangle can add to them)
+            const float* v = s_v + 12 * k;
+            const float x0 = v[0], x1 = v[3], x2 = v[6], z0 = v[2], z1 = v[5], z2 = v[8];
+            const double xmin = (double)fminf(x0, fminf(x1, x2)), xmax = (double)fmaxf(x0, fmaxf(x1, x2));
+            if (xmax < xa || xmin > xb) continue;
+            const double zmin = (double)fminf(z0, fminf(z1, z2)), zmax = (double)fmaxf(z0, fmaxf(z1, z2));
+            const double pad = nav_z_pad(zmin, zmax);
+            if (zmax + pad < za || zmin - pad > zb) continue;
+            NavClip s;
+            s.bound[0] = xa; s.bound[1] = xb; s.bound[2] = za; s.bound[3] = zb;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                s.have[q] = false;
+                s.fx[q] = s.fy[q] = s.fz[q] = s.sx[q] = s.sy[q] = s.sz[q] = 0.0;
+            }
+            s.lo = inf; s.hi = -inf; s.any = false;
+#pragma unroll 1
+            for (int i = 0; i < 3; ++i) nav_feed<0>(s, (double)v[3 * i], (double)v[3 * i + 1], (double)v[3 * i + 2]);
+            nav_close<0>(s);
+            if (s.any) bits |= nav_bits(c, s.lo, s.hi);
+        }
+    }
+    if (col < c.W && row < c.H) grid[(int64_t)row * c.W + col] = (uint8_t)bits;
+}
+
+hipError_t launch_mesh_navgrid(const NavGridArgs& a, hipStream_t st)
+{
+    NavGridCam c;
+    c.x0 = a.x0; c.z0 = a.z0; c.cell = a.cell;
+    c.y_floor = a.floor_y - a.max_climb; c.y_step = a.floor_y + a.max_climb; c.y_head = a.floor_y + a.agent_height;
+    c.W = a.W; c.H = a.H; c.gx = (a.W + kTile - 1) / kTile; c.gy = (a.H + kTile - 1) / kTile;
+    const int tiles = c.gx * c.gy;
+    hipError_t e = hipMemsetAsync(a.tile_count, 0, (size_t)(tiles + 1) * 4, st);
+    if (e != hipSuccess) return e;
+    const unsigned tb = (unsigned)(((int64_t)a.T + kBlock - 1) / kBlock);
+    if (a.T > 0)
+        hipLaunchKernelGGL(navgrid_setup_kernel, dim3(tb), dim3(kBlock), 0, st, c, a.T, a.V, a.vertices, a.triangles, a.records, a.rects, a.tile_count);
+    hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(kBlock), 0, st, tiles, a.tile_count, a.tile_offset, a.total, a.d_counts);
+    if (a.T > 0)
+        hipLaunchKernelGGL(mesh_fill_kernel, dim3(tb), dim3(kBlock), 0, st, a.T, c.gx, (const uint2*)a.rects, (const uint32_t*)a.tile_offset, a.tile_count,
+                           (const uint64_t*)a.total, a.capacity, a.list);
+    hipLaunchKernelGGL(navgrid_tile_kernel, dim3(c.gx, c.gy), dim3(kBlock), 0, st, c, (const float4*)a.records, (const uint32_t*)a.tile_offset,
+                       (const uint32_t*)a.list, (const uint64_t*)a.total, a.capacity, a.grid);
+    return hipGetLastError();
+}
+
 // ---- TSDF fusion and surface extraction (a NEW capability: the reference has no counterpart; the rules: include/gsplat_hip.h,
 // gs_tsdf_integrate / gs_tsdf_count / gs_tsdf_emit) --------------------------------------------------------------------------------------
 // Integration: a thread owns a run of four voxels along the flat index (x fastest) for the whole call and keeps their tsdf, weight and colour

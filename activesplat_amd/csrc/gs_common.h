@@ -1047,6 +1047,23 @@ hipError_t launch_mesh_render(const MeshArgs& a, hipStream_t st);
 hipError_t launch_texture_mips(int num_textures, const GsTextureDesc* h_table, const GsTextureDesc* table, uint32_t* pool, hipStream_t st);
 hipError_t launch_mesh_render_textured(const MeshArgs& a, const float* uvs, const int32_t* tri_texture, int num_textures, const GsTextureDesc* table,
                                        const uint32_t* pool, hipStream_t st);
+// the navigable grid of a storey from the mesh (grow.hip; the rule: include/gsplat_hip.h, gs_mesh_navgrid).  Scratch pointers as carved by the
+// layout call; the scan and the fill of the tile lists are the mesh sensor's kernels.
+struct NavGridArgs {
+    int V, T;
+    const float* vertices;                                             // [V, 3] simulator world frame, y up
+    const int32_t* triangles;                                          // [T, 3]
+    double x0, z0, cell, floor_y, max_climb, agent_height;
+    int W, H;                                                          // cells along x, along z
+    uint64_t* total;                                                   // scratch: the needed list length, 64 bits
+    float4* records;                                                   // scratch: [T] x 3 (the nine coordinates, three unused floats)
+    uint2* rects;                                                      // scratch: [T] tile rectangles, as MeshArgs
+    uint32_t *tile_count, *tile_offset, *list;                         // scratch: [tiles + 1], [tiles + 1], [capacity]
+    uint32_t capacity;
+    uint8_t* grid;                                                     // [H, W]
+    uint32_t* d_counts;                                                // [2]: needed list length (saturating), longest tile list
+};
+hipError_t launch_mesh_navgrid(const NavGridArgs& a, hipStream_t st);
 // TSDF fusion and surface extraction (grow.hip; the rules: include/gsplat_hip.h, gs_tsdf_integrate / gs_tsdf_count / gs_tsdf_emit).  A new
 // capability: the reference has no counterpart.  One argument block for the integration kernel (poses and intrinsics travel in it), one for the
 // extraction's kernels, with the scratch carved as tsdf_extract_scratch_bytes lays it out.

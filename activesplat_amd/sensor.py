@@ -18,7 +18,8 @@ that decided the hit, a level of detail from the footprint of one pixel step, tr
 exact integers, REPEAT / CLAMP / MIRROR wrapping.  Texels are used as stored.  Not modelled: sRGB decoding (filtering happens in stored space),
 base-colour factors, vertex-colour modulation, alpha, anisotropic filtering.
 
-Only the depth / colour sensor of the simulator is here: no sensor noise, no far plane, no semantic ids, no actions, physics or navmesh.  The rule is two-sided; whether Habitat's renderer culls back faces was not established (no Habitat here),
+Only the depth / colour sensor of the simulator is here: no sensor noise, no far plane, no semantic ids.  The agent that carries the sensor -- the
+navigable area computed from this mesh, the discrete actions, the episode loop -- is in agent.py and explore.py.  The rule is two-sided; whether Habitat's renderer culls back faces was not established (no Habitat here),
 so a mesh seen from behind differs if it does.  Nothing was run against Habitat-sim.
 
 There is no CPU fallback.

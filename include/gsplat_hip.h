@@ -205,7 +205,7 @@ const char* gs_version(void);
 /* Integer version of THIS binary interface: bumped whenever an entry point's argument list or a published record layout changes (e.g.
  * the seed argument of gs_densify_children, the 40-byte SH Jacobian record).  A host binding compares it with the GS_ABI_VERSION it was
  * written against before the first call, so that a stale prebuilt library fails at load time instead of misreading its arguments. */
-#define GS_ABI_VERSION 27
+#define GS_ABI_VERSION 28
 int32_t gs_abi_version(void);
 
 /* Optional per-stage timing (hipEvents recorded on the caller's stream around each stage's launches).
@@ -898,6 +898,52 @@ int gs_mesh_render_textured(int32_t num_vertices, const float* vertices, int32_t
                             uint32_t capacity, float* depth, int32_t* tri_id, uint8_t* color, uint32_t* d_counts, const float* uvs,
                             const int32_t* tri_texture, int32_t num_textures, const GsTextureDesc* h_textures, const GsTextureDesc* textures,
                             const uint32_t* pool, uint64_t pool_texels, gs_stream_t stream);
+
+/* ---- Navigable grid of a storey from the mesh (the reference moves its agent with Habitat-sim's sim.step on a navmesh,
+ * src/dataloader/dataloader.py:237-272) ----
+ * A top-down, CONSERVATIVE classification of grid_height x grid_width square cells.  This is a grid rule of this project, NOT Recast and NOT
+ * Habitat's navmesh; it was not run against Habitat-sim.  Stairs are not modelled: one floor height per call.
+ * vertices fp32 [num_vertices, 3] in the simulator's world frame, y UP, triangles int32 [num_triangles, 3]: DEVICE (MeshScene's arrays).
+ * x0, z0, cell, floor_y, max_climb, agent_height: HOST scalars, fp64.
+ * THE GRID.  Cell (r, c), 0 <= r < grid_height, 0 <= c < grid_width, is the CLOSED square
+ *   [xa, xb] x [za, zb] = [x0 + c * cell, x0 + (c + 1) * cell] x [z0 + r * cell, z0 + (r + 1) * cell],  the borders computed in fp64 exactly
+ * as written (one product, one sum).
+ * THE RULE.  All arithmetic is fp64, every operation rounded on its own (no fused multiply-add), so that a numpy restatement gives the same bits.
+ *   dropped     a triangle with a vertex index outside 0 .. num_vertices - 1 is dropped without being read; so is one with a non-finite vertex.
+ *   pre-test    [Ylo, Yhi] = the y range of the triangle's own three vertices.  If that range sets neither bit (below), the triangle
+ *               contributes nothing to any cell.  Decided first, per triangle.
+ *   clipping    for every other triangle and every cell: the 3-D triangle (vertices widened to fp64) is clipped against the four half-spaces
+ *               x >= xa, x <= xb, z >= za, z <= zb, in this order, by Sutherland-Hodgman: the edges (a, b) of the polygon are walked in order
+ *               (the last edge closes it); a is emitted if it is inside; if exactly one of a, b is inside, p = a + t * (b - a) with
+ *               t = (bound - a.k) / (b.k - a.k) is emitted (k the clipped coordinate; per coordinate one difference, one product, one sum), and
+ *               the clipped coordinate of p is set to `bound` exactly.  "Inside" is the closed comparison.  An empty polygon contributes
+ *               nothing.  A vertical triangle (zero-area projection) and a degenerate one need no special case.
+ *   bits        [lo, hi] = the y range of the clipped polygon's vertices.
+ *               bit 1 (obstacle) iff hi >  floor_y + max_climb  and  lo <  floor_y + agent_height
+ *               bit 0 (floor)    iff hi >= floor_y - max_climb  and  lo <= floor_y + max_climb      (the three sums in fp64)
+ *   output      grid uint8 [grid_height * grid_width], row r, column c: the OR of the bits over all triangles.  1 = navigable floor, 0 = void,
+ *               2 and 3 = blocked.  The result depends on the order of no list; two calls on the same inputs give the same bytes.
+ * Four launches on `stream`, gs_mesh_render's structure: per-triangle setup (a 48-byte record of the nine coordinates, the pre-test, a
+ * conservative rectangle of 16 x 16-cell tiles around the xz bounding box, the tile counts), gs_mesh_render's scan and fill of the tile lists,
+ * and one 256-thread workgroup per tile in which a thread owns one cell, keeps its byte in a register and stores it once; the records are
+ * staged through LDS in chunks.  Integer atomics only, and only for the list fill.  The clip runs in registers (no scratch memory): each stage
+ * hands a vertex to the next as it emits it, which gives the vertices, and the operands of every interpolation, of the formulation above.
+ * Shortcuts taken, each of which only skips a (triangle, cell) pair whose polygon the rule makes empty: the tile rectangle, and a per-cell
+ * rejection by the triangle's exact x range and its z range padded by 2^-30 max|z| (the x stages can move an interpolated z by a few units of
+ * 2^-52 max|z| beyond the triangle's own range).  A cell whose bits are both set skips the remaining triangles.  No other shortcut: in
+ * particular no "cell inside the triangle" path that evaluates the plane at the corners, which is different arithmetic.
+ * CAPACITY, as gs_mesh_render: d_counts[0] (DEVICE) receives the total length D of the tile lists (0xffffffff when it does not fit 32 bits),
+ * d_counts[1] the longest list.  When D > capacity nothing is written to the lists and the grid is CLEARED (0): read d_counts[0] and call
+ * again with capacity >= D.  The scan over the tiles is one workgroup (gs_mesh_render's known limit (2)).
+ * scratch: DEVICE, gs_mesh_navgrid_layout(num_triangles, grid_width, grid_height, capacity).total_bytes bytes, 16-byte aligned; the offsets
+ * are published for tests in a GsMeshLayout whose records are 48 bytes here (nine fp32 coordinates, three unused floats).
+ * Refused with GS_EINVAL before any launch: a null pointer (the two mesh arrays may be null when num_triangles is 0, which is valid and clears
+ * the grid), grid_width or grid_height outside 1 .. 16384, num_triangles < 0, num_vertices < 0, cell not positive and finite, a non-finite
+ * scalar, max_climb < 0, agent_height <= max_climb. */
+int gs_mesh_navgrid_layout(int32_t num_triangles, int32_t grid_width, int32_t grid_height, uint32_t capacity, GsMeshLayout* layout);
+int gs_mesh_navgrid(int32_t num_vertices, const float* vertices, int32_t num_triangles, const int32_t* triangles, double x0, double z0, double cell,
+                    double floor_y, double max_climb, double agent_height, int32_t grid_width, int32_t grid_height, void* scratch, uint32_t capacity,
+                    uint8_t* grid, uint32_t* d_counts, gs_stream_t stream);
 
 /* ---- Completion / accuracy judge (ActiveSplat's own figure: scripts/judges/eval_actions.py:33-40,139-152) ----
  * Per frame the reference back-projects the sensor depth (rgbd_to_pointcloud, src/utils/gui_utils.py:96-125, called with depth scale 1000 and
